@@ -11,12 +11,15 @@ N>1: one process per GPU, every rank encodes its own share of the batch (images 
 weak scaling, no collective on the data path; c4 shards its 1024 frames: strong scaling).
 `python bench.py --gpus N` WITHOUT a launcher starts the N ranks itself (re-executes under
 torch.distributed.run on 127.0.0.1) and fails loudly when fewer than N devices are visible; under a
-launcher (WORLD_SIZE set) --gpus must agree with it.  At N>1 the line also carries `host_inclusive`
+launcher (WORLD_SIZE set) --gpus must agree with it.  With --full at N>1 the line also carries `host_inclusive`
 measured on EVERY rank at the same time (sum, per-rank min/max, total input GB/s: the PCIe side is
 what can fail to scale) and `pool_host` (ONE process driving all N devices, mjh_pool_encode_host).
 
 Prints ONE JSON line (rank 0).  `value` is the DEVICE-RESIDENT rate (frames already in HBM when the
-timed region starts, complete JPEG files left in HBM), as the contract defines it.  Extra objects:
+timed region starts, complete JPEG files left in HBM), as the contract defines it.  A plain run does only what
+that figure needs: set-up, --warmup untimed steps, --steps timed steps back to back, the line; with
+--dump-outputs DIR it also writes the files of the last timed step as .npy arrays (dump_outputs below).
+--full adds every other measurement and check, as extra objects of the same line:
   host_inclusive -- the wall the reference's own definition asks for: pixels in pinned host
                   memory -> JPEG files in host memory, H2D and D2H included, >= 3 s of back-to-back batches through the
                   asynchronous double-buffered mjh_encode_host / mjh_collect path.  Never `value`.
@@ -26,6 +29,7 @@ timed region starts, complete JPEG files left in HBM), as the contract defines i
                   stream), algorithmic bytes = input samples + JPEG bytes of one batch, peak = 8 TB/s HBM.
   cpu_baseline  -- the reference mozjpeg (oracle/_ref, C build) or, if that binary is absent, the C port in oracle/,
                   timed on this box's host cores on a bounded sample.
+  one_batch_at_a_time, other_configs (N=1, metric), jpeg_bytes_per_frame, bit_exact_vs_reference.
 """
 import argparse
 import concurrent.futures as cf
@@ -417,6 +421,46 @@ def host_inclusive(M, params, frames, hb, device, min_s, ref_jpegs):
                     "the device (mjh_encode_host / mjh_collect, double-buffered); one host thread"}
 
 
+DUMP_SAMPLE_BYTES = 4096              # bytes per file at fixed, seeded positions
+DUMP_WHOLE_FILES_BYTES = 48 << 20     # budget of the float32 copies of whole files (the sample and the checksums add ~2 MB)
+
+
+def dump_outputs(out_dir, jpegs):
+    """What a caller of the timed path receives -- the JPEG files of the last timed encode call -- as float arrays, so that
+    two builds can be compared output for output (same arguments = same seeded frames):
+      jpeg_sizes.npy        float64 [n]           bytes per file
+      jpeg_checksums.npy    float64 [n, 2]        sum of the bytes, sum of (position + 1) * byte (exact below 8 MB a file)
+      jpeg_byte_sample.npy  float32 [n, 4096]     the bytes at fixed positions (seeded fractions of each file's length)
+      jpeg_whole_files.npy  float32 [k, max_len]  k files chosen by a seeded permutation, whole, padded with -1, as many
+                                                  as fit in 48 MB (k = 0 when one file alone is larger)
+      jpeg_whole_file_index.npy float64 [k]       which files those are"""
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = [np.frombuffer(j, np.uint8) for j in jpegs]
+    n = len(arrs)
+    sizes = np.array([a.size for a in arrs], np.float64)
+    pos = np.arange(1, max(1, int(sizes.max())) + 1, dtype=np.float64)
+    sums = np.array([[a.sum(dtype=np.float64), float(np.dot(pos[:a.size], a.astype(np.float64)))] for a in arrs], np.float64)
+    rng = np.random.default_rng(20261016)
+    frac = np.sort(rng.random(DUMP_SAMPLE_BYTES))
+    sample = np.stack([a[np.minimum((frac * a.size).astype(np.int64), a.size - 1)].astype(np.float32) for a in arrs])
+    pick = []
+    for i in rng.permutation(n):
+        width = int(max(sizes[j] for j in pick + [i]))
+        if (len(pick) + 1) * width * 4 > DUMP_WHOLE_FILES_BYTES:
+            break
+        pick.append(int(i))
+    pick.sort()
+    width = int(max([sizes[j] for j in pick], default=0))
+    whole = np.full((len(pick), width), -1.0, np.float32)
+    for r, i in enumerate(pick):
+        whole[r, :arrs[i].size] = arrs[i]
+    np.save(os.path.join(out_dir, "jpeg_sizes.npy"), sizes)
+    np.save(os.path.join(out_dir, "jpeg_checksums.npy"), sums)
+    np.save(os.path.join(out_dir, "jpeg_byte_sample.npy"), sample)
+    np.save(os.path.join(out_dir, "jpeg_whole_files.npy"), whole)
+    np.save(os.path.join(out_dir, "jpeg_whole_file_index.npy"), np.array(pick, np.float64))
+
+
 def _free_port():
     import socket
     sk = socket.socket()
@@ -488,6 +532,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=-1, help="untimed steps before (-1 = a tenth of the steps)")
     ap.add_argument("--config", default="metric", choices=sorted(CONFIGS))
     ap.add_argument("--batch", type=int, default=0, help="frames per encode call per GPU (0 = the config's default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the JPEG files of the last one as DIR/*.npy (dump_outputs; rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the comparison with the reference, the per-kernel and roofline "
+                         "figures, one batch at a time, the other configurations, the host legs, the CPU baseline (the options "
+                         "below apply to it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of host CPU work for the cpu_baseline leg")
     ap.add_argument("--no-host-leg", action="store_true")
@@ -495,7 +545,7 @@ def main():
     ap.add_argument("--host-seconds", type=float, default=3.0)
     ap.add_argument("--host-batch", type=int, default=16)
     ap.add_argument("--verify", default="all", help="frames per batch to compare with the reference: all | N")
-    ap.add_argument("--other-configs", default="auto", help="auto: the default N=1 run of the metric configuration appends a compact line per other BASELINE configuration (c2, c3, c5, c5t) under --other-budget seconds; none: skip")
+    ap.add_argument("--other-configs", default="auto", help="auto: the --full N=1 run of the metric configuration appends a compact line per other BASELINE configuration (c2, c3, c5, c5t) under --other-budget seconds; none: skip")
     ap.add_argument("--other-budget", type=float, default=60.0)
     ap.add_argument("--launch-check", action="store_true",
                     help="only start the ranks, form the process group (gloo) and print n_gpus: no GPU is touched (CPU test of the launch path)")
@@ -582,62 +632,68 @@ def main():
         torch.cuda.synchronize()
         enc.sync()
 
-    # Warm-up: W untimed steps, ordered so that the chip is in the timed region's state when the clock starts (round 6, third
-    # session: the files used to be fetched and compared with the reference BETWEEN the warm-up and the timed region -- seconds of
-    # host work with an idle GPU right in front of a region that lasts 0.1 s at the driver's --steps 20; and no warm-up step ran
-    # with two batches in flight).
-    #   step 1      fetches every file; the comparison with the reference follows at once (outside every timed region)
-    #   nprobe      steps with every kernel bracketed (profiling level 1): the DOMINANT interval of the schedule is measured on
-    #               this workload, not assumed; the timed region then brackets exactly that one (level 2)
-    #   the rest    exactly like the timed steps: back to back, two batches in flight, the dominant interval bracketed
     W = args.warmup
-    nprobe = 2 if W >= 4 else 0            # (the first bracketed step creates the events: two are the least)
     focus, probe = None, {}
     jpegs = []
-    late_probe = nprobe == 0
-    if late_probe:
-        # a warm-up too short for probe steps (configurations whose step takes seconds, or --warmup 0: the one step below is then
-        # an extra untimed one): the file-fetching step is the bracketed one -- its intervals include the creation of the events,
-        # which does not change which one is largest
-        enc.set_profiling(1)
-    step(keep=jpegs)
-    barrier()
-    if late_probe:
-        probe = dict(enc.kernel_times())
-        enc.set_profiling(0)
-    jpeg_bytes = sum(len(j) for j in jpegs)
-    # bit-exactness of EVERY frame against the real reference (outside the timed region)
     bitexact = None
-    if rank == 0:
-        lim = None if args.verify == "all" else int(args.verify)
-        if repeats > 1:     # the distinct frames against the reference, every repeat against the file of its first copy
-            bitexact = verify_frames(frames[:distinct], jpegs[:distinct], w, h, kw, lim)
-            same = all(jpegs[i] == jpegs[i % distinct] for i in range(len(jpegs)))
-            bitexact["repeats_identical_to_first_copy"] = same
-            bitexact["ok"] = bool(bitexact["ok"] and same)
-        else:
-            bitexact = verify_frames(frames, jpegs, w, h, kw, lim)
-    barrier()              # (every rank waits for rank 0's comparison, so that the remaining warm-up steps run right before the clock starts on all of them)
-    if nprobe:
-        enc.set_profiling(1)
-        for i in range(nprobe):
-            if i == 1:
-                enc.set_profiling(1)   # the first bracketed step creates the events: its intervals include that; start over
+    if not args.full:
+        # plain run: W untimed steps exactly like the timed ones (back to back, two batches in flight, nothing bracketed)
+        for _ in range(W):
             step()
-            enc.sync()     # (the encoder tunes itself from what the previous batch reported: let every probe batch finish)
-        probe = dict(enc.kernel_times())
-        enc.set_profiling(0)
-    main_stream = {k: v for k, v in probe.items() if "side stream" not in k and not k.startswith("join(")}
-    if main_stream:
-        focus = max(main_stream, key=main_stream.get)
-    enc.set_profiling(2, focus=focus)
-    for _ in range(max(0, W - 1 - nprobe)):
-        step()
+    else:
+        # Warm-up: W untimed steps, ordered so that the chip is in the timed region's state when the clock starts (round 6, third
+        # session: the files used to be fetched and compared with the reference BETWEEN the warm-up and the timed region -- seconds of
+        # host work with an idle GPU right in front of a region that lasts 0.1 s at --steps 20; and no warm-up step ran
+        # with two batches in flight).
+        #   step 1      fetches every file; the comparison with the reference follows at once (outside every timed region)
+        #   nprobe      steps with every kernel bracketed (profiling level 1): the DOMINANT interval of the schedule is measured on
+        #               this workload, not assumed; the timed region then brackets exactly that one (level 2)
+        #   the rest    exactly like the timed steps: back to back, two batches in flight, the dominant interval bracketed
+        nprobe = 2 if W >= 4 else 0            # (the first bracketed step creates the events: two are the least)
+        late_probe = nprobe == 0
+        if late_probe:
+            # a warm-up too short for probe steps (configurations whose step takes seconds, or --warmup 0: the one step below is then
+            # an extra untimed one): the file-fetching step is the bracketed one -- its intervals include the creation of the events,
+            # which does not change which one is largest
+            enc.set_profiling(1)
+        step(keep=jpegs)
+        barrier()
+        if late_probe:
+            probe = dict(enc.kernel_times())
+            enc.set_profiling(0)
+        jpeg_bytes = sum(len(j) for j in jpegs)
+        # bit-exactness of EVERY frame against the real reference (outside the timed region)
+        if rank == 0:
+            lim = None if args.verify == "all" else int(args.verify)
+            if repeats > 1:     # the distinct frames against the reference, every repeat against the file of its first copy
+                bitexact = verify_frames(frames[:distinct], jpegs[:distinct], w, h, kw, lim)
+                same = all(jpegs[i] == jpegs[i % distinct] for i in range(len(jpegs)))
+                bitexact["repeats_identical_to_first_copy"] = same
+                bitexact["ok"] = bool(bitexact["ok"] and same)
+            else:
+                bitexact = verify_frames(frames, jpegs, w, h, kw, lim)
+        barrier()              # (every rank waits for rank 0's comparison, so that the remaining warm-up steps run right before the clock starts on all of them)
+        if nprobe:
+            enc.set_profiling(1)
+            for i in range(nprobe):
+                if i == 1:
+                    enc.set_profiling(1)   # the first bracketed step creates the events: its intervals include that; start over
+                step()
+                enc.sync()     # (the encoder tunes itself from what the previous batch reported: let every probe batch finish)
+            probe = dict(enc.kernel_times())
+            enc.set_profiling(0)
+        main_stream = {k: v for k, v in probe.items() if "side stream" not in k and not k.startswith("join(")}
+        if main_stream:
+            focus = max(main_stream, key=main_stream.get)
+        enc.set_profiling(2, focus=focus)
+        for _ in range(max(0, W - 1 - nprobe)):
+            step()
 
-    # Timed region: K steps back to back.  HIP events bracket only the dominant kernel here (profiling
+    # Timed region: K steps back to back.  With --full, HIP events bracket only the dominant kernel here (profiling
     # level 2: two events per step on the encoder's stream, read once after the loop), so the event
     # barriers of a full per-kernel breakdown do not slow the measured steps.
-    enc.set_profiling(2, focus=focus)
+    if args.full:
+        enc.set_profiling(2, focus=focus)
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -645,8 +701,42 @@ def main():
     barrier()
     t1 = time.perf_counter()
     elapsed = t1 - t0
-    dom_times = dict(enc.kernel_times())          # average ms per encode call over the timed region
+    dom_times = dict(enc.kernel_times()) if args.full else {}     # average ms per encode call over the timed region
     elapsed = shard.max_over_ranks(elapsed, dist, dev)
+    if args.dump_outputs and rank == 0:
+        # the accessors refer to the most recent encode call: the files of the last timed step (of its last call at c4)
+        dump_outputs(args.dump_outputs, [enc.get_jpeg(i) for i in range(calls[-1][1])])
+
+    frames_per_step_all = total if total else B * world
+    line = {
+        "metric": baseline_metric(),
+        "value": round(float(w) * h * frames_per_step_all * args.steps / elapsed / 1e6, 2), "unit": "Mpixels/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True, "scaling": "strong" if total else "weak", "vs_baseline": None,
+        "dtype": "u16/int16" if twelve else "u8/int16 (+f32 trellis costs)",
+        "data": "synthetic",
+        "value_is": "device-resident rate: frames in HBM when the timed region starts, complete JPEG files left in HBM "
+                    "(the PCIe-inclusive wall is host_inclusive.value, with --full)",
+        "config": {"workload": cfg["name"], "config_key": args.config,
+                   "frames_per_step_per_gpu": nframes, "frames_per_encode_call": int(calls[0][1]),
+                   "distinct_frames": int(nframes // repeats),
+                   "value_definition": "device-resident (this line's `value`); SURVEY 8d / BASELINE.md section 3 define the metric from pinned host "
+                                       "pixels to JPEG bytes in host memory: that number is `value_host_inclusive`",
+                   "batches_in_flight": 2,
+                   "input": "resident in HBM", "output": "complete JPEG files in HBM",
+                   "parallelism": "images sharded, 1 process per GPU, no collective"},
+    }
+    if elapsed < 1.0:
+        line["timed_region_warning"] = ("the timed region is %.2f s (%d steps): one noisy box moves it by percent -- the default run "
+                                        "(no --steps) times 3-5 s" % (elapsed, args.steps))
+    if not args.full:
+        enc.close()
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # Untimed extra pass with every kernel bracketed (level 1) for the per-kernel breakdown, one batch at a time (with two in
     # flight an interval between two events on one stream also holds the other batch's kernels)
@@ -721,8 +811,6 @@ def main():
             dist.barrier()
 
     if rank == 0:
-        frames_per_step_all = total if total else B * world
-        total_px = float(w) * h * frames_per_step_all * args.steps
         dom = max(dom_times, key=dom_times.get) if dom_times else max(ktimes, key=ktimes.get)
         dom_ms = dom_times.get(dom, ktimes.get(dom))
         per_call = float(calls[0][1])
@@ -731,23 +819,8 @@ def main():
         # HBM traffic of the dominant kernel from the committed PMC passes (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE,
         # separate runs, fetch corrected by the factor calibrated on k_color; tools/pmc_traffic.py) -- per launch
         traffic, traffic_src = dominant_traffic(args.config, dom, per_call)
-        out = {
-            "metric": baseline_metric(),
-            "value": round(total_px / elapsed / 1e6, 2), "unit": "Mpixels/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "strong" if total else "weak", "vs_baseline": None,
-            "dtype": "u16/int16" if twelve else "u8/int16 (+f32 trellis costs)",
-            "data": "synthetic",
-            "value_is": "device-resident rate: frames in HBM when the timed region starts, complete JPEG files left in HBM "
-                        "(the PCIe-inclusive wall is host_inclusive.value)",
-            "config": {"workload": cfg["name"], "config_key": args.config,
-                       "frames_per_step_per_gpu": nframes, "frames_per_encode_call": int(per_call),
-                       "distinct_frames": int(nframes // repeats),
-                       "value_definition": "device-resident (this line's `value`); SURVEY 8d / BASELINE.md section 3 define the metric from pinned host "
-                                           "pixels to JPEG bytes in host memory: that number is `value_host_inclusive`",
-                       "batches_in_flight": 2,
-                       "input": "resident in HBM", "output": "complete JPEG files in HBM",
-                       "parallelism": "images sharded, 1 process per GPU, no collective"},
+        out = dict(line)
+        out.update({
             "bit_exact": bitexact,
             "bit_exact_vs_reference": bool(bitexact and bitexact["ok"]),
             "jpeg_bytes_per_frame": int(jpeg_bytes / nframes),
@@ -763,7 +836,7 @@ def main():
                          "whole_step_GBps": round(algo_bytes * len(calls) / (elapsed / args.steps) / 1e9, 1),
                          "kernel_ms_per_call(untimed pass, every kernel bracketed)":
                              {k: round(v, 4) for k, v in sorted(ktimes.items(), key=lambda kv: -kv[1])}},
-        }
+        })
         out["one_batch_at_a_time"] = {"ms_per_step": round(serial_ms, 3), "steps": ksteps, "kernel": dom,
                                       "kernel_ms": round(serial_dom.get(dom, 0.0), 4),
                                       "frac": round(algo_bytes / (serial_dom[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if serial_dom.get(dom) else None,
@@ -771,9 +844,6 @@ def main():
         issue = dominant_issue(args.config, dom, per_call, dom_ms)
         if issue is not None:
             out["roofline"]["valu_issue"] = issue      # (the interval is VALU-issue bound, not HBM bound: this is the ceiling it is near)
-        if elapsed < 1.0:
-            out["timed_region_warning"] = ("the timed region is %.2f s (%d steps): one noisy box moves it by percent -- the default run "
-                                           "(no --steps) times 3-5 s" % (elapsed, args.steps))
         if others is not None:
             out["other_configs"] = others
         if pipelined is not None:

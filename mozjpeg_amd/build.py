@@ -66,11 +66,14 @@ def build(force=False, verbose=False):
 def build_shim(force=False, verbose=False):
     """libjpeg drop-in entry points (jpeg_start_compress / jpeg_write_scanlines /
     jpeg_finish_compress) on top of the batch encoder.  It is compiled against the libjpeg headers
-    of the tree it drops into (struct jpeg_compress_struct is ABI), so it is only built where
-    /root/reference (and the generated config headers under oracle/_ref/include) exist."""
+    of the tree it drops into (struct jpeg_compress_struct is ABI), so it is only built where those
+    headers exist: in the reference tree, or as the copies oracle/Makefile puts next to the config
+    headers it generates under oracle/_ref/include (which travel with the built tree)."""
     src = os.path.join(CSRC, "jpeg_shim.c")
     ref = os.environ.get("MOZJPEG_REFERENCE", "/root/reference")
     cfg = os.path.join(HERE, "..", "oracle", "_ref", "include")
+    if not os.path.exists(os.path.join(ref, "jpeglib.h")):
+        ref = cfg
     if not (os.path.exists(src) and os.path.exists(os.path.join(ref, "jpeglib.h")) and os.path.exists(cfg)):
         if verbose:
             print("shim: reference headers not present, keeping prebuilt", SHIM if os.path.exists(SHIM) else "(none)")

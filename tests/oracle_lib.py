@@ -15,6 +15,18 @@ REF_DIR = os.path.join(ORACLE_DIR, "_ref")
 MAXC, MAXS = 4, 64
 
 
+def set_preload(env, lib=None):
+    """LD_PRELOAD of a child process: `lib` (one of this project's drop-in libraries, or None for none of them) in front of
+    whatever the environment preloads besides this project's libraries -- that part is kept as it is, never dropped."""
+    outer = [p for p in os.environ.get("LD_PRELOAD", "").replace(":", " ").split() if not os.path.abspath(p).startswith(ROOT + os.sep)]
+    libs = ([lib] if lib else []) + outer
+    if libs:
+        env["LD_PRELOAD"] = ":".join(libs)
+    else:
+        env.pop("LD_PRELOAD", None)
+    return env
+
+
 class Scan(C.Structure):
     _fields_ = [("comps_in_scan", C.c_int), ("component_index", C.c_int * MAXC),
                 ("Ss", C.c_int), ("Se", C.c_int), ("Ah", C.c_int), ("Al", C.c_int)]
@@ -318,7 +330,7 @@ def ref_jpegtran(jpeg, switches=(), preload=None):
         open(inp, "wb").write(jpeg)
         env = dict(os.environ)
         if preload:
-            env["LD_PRELOAD"] = preload
+            set_preload(env, preload)
         r = subprocess.run([os.path.join(REF_DIR, "jpegtran")] + list(switches) + ["-outfile", outp, inp], env=env,
                            stdout=subprocess.PIPE, stderr=subprocess.PIPE)
         assert r.returncode == 0, r.stderr.decode()

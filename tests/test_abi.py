@@ -147,7 +147,7 @@ def test_drop_in_without_gpu_fails_loudly_and_writes_nothing(tmp_path):
     if not (os.path.exists(shim) and os.path.exists(cjpeg)):
         pytest.skip("shim or reference cjpeg not built")
     out = str(tmp_path / "o.jpg")
-    env = dict(os.environ, LD_PRELOAD=shim)
+    env = O.set_preload(dict(os.environ), shim)
     env.pop("MOZJPEG_HIP_PASSTHROUGH", None)
     r = subprocess.run([cjpeg, "-quality", "75", "-baseline", "-outfile", out, os.path.join(ROOT, "tests", "golden", "testorig.ppm")],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE)

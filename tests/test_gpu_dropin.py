@@ -60,7 +60,7 @@ CJPEG_CASES = [
 
 def run_cjpeg(args, out, env_extra=None):
     env = dict(os.environ)
-    env["LD_PRELOAD"] = SHIM
+    O.set_preload(env, SHIM)
     if env_extra:
         env.update(env_extra)
     return subprocess.run([CJPEG, "-dct", "int"] + args + ["-outfile", out, PPM], env=env,
@@ -151,7 +151,7 @@ needs_sa = pytest.mark.skipif(not (os.path.exists(os.path.join(STANDALONE_DIR, "
 
 def run_cjpeg_standalone(args, out, inp=PPM):
     env = dict(os.environ)
-    env.pop("LD_PRELOAD", None)
+    O.set_preload(env)
     env["LD_LIBRARY_PATH"] = STANDALONE_DIR
     # prove which library the binary gets: the loader's own trace names every object it maps
     env["LD_DEBUG"] = "libs"
@@ -197,11 +197,11 @@ def test_unchanged_cjpeg_readers_and_one_component_sampling(kind, args, tmp_path
         src = PPM
     ref, gpu, alone = (str(tmp_path / n) for n in ("ref.jpg", "gpu.jpg", "alone.jpg"))
     env = dict(os.environ)
-    env.pop("LD_PRELOAD", None)
+    O.set_preload(env)
     env["LD_LIBRARY_PATH"] = O.REF_DIR
     r0 = subprocess.run([CJPEG, "-dct", "int"] + args + ["-outfile", ref, src], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
     assert r0.returncode == 0, r0.stderr.decode()
-    env["LD_PRELOAD"] = SHIM
+    O.set_preload(env, SHIM)
     r1 = subprocess.run([CJPEG, "-dct", "int"] + args + ["-outfile", gpu, src], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
     assert r1.returncode == 0, r1.stderr.decode()
     assert open(gpu, "rb").read() == open(ref, "rb").read()
@@ -262,12 +262,12 @@ def test_libjpeg_client_scenarios(scenario, mode):
     jpeg_suppress_tables, write_all_tables FALSE over several frames of one object).  Expected output = the same binary on the
     reference's libjpeg."""
     env = dict(os.environ)
-    env.pop("LD_PRELOAD", None)
+    O.set_preload(env)
     env["LD_LIBRARY_PATH"] = O.REF_DIR
     want = subprocess.run([HARNESS, scenario], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
     assert want.returncode == 0, want.stderr.decode()
     if mode == "preload":
-        env["LD_PRELOAD"] = SHIM
+        O.set_preload(env, SHIM)
     else:
         env["LD_LIBRARY_PATH"] = STANDALONE_DIR
     got = subprocess.run([HARNESS, scenario], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
@@ -313,9 +313,9 @@ def tj_run(raw, w, h, pf, ss, q, flags, out, preload):
     libturbojpeg with its private libjpeg needs)"""
     env = dict(os.environ)
     if preload == "tj":
-        env["LD_PRELOAD"] = TJSHIM
+        O.set_preload(env, TJSHIM)
     elif preload:
-        env["LD_PRELOAD"] = SHIM
+        O.set_preload(env, SHIM)
     return subprocess.run([TJH, str(w), str(h), str(pf), str(ss), str(q), str(flags), raw, out], env=env,
                           stdout=subprocess.PIPE, stderr=subprocess.PIPE)
 

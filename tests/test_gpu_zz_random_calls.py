@@ -24,10 +24,8 @@ needs = pytest.mark.skipif(not (os.path.exists(SHIM) and os.path.exists(os.path.
 
 
 def run(cmd, preload=None, libpath=None, extra=None):
-    env = {k: v for k, v in os.environ.items() if k != "LD_PRELOAD"}
+    env = O.set_preload(dict(os.environ), preload)
     env["LD_LIBRARY_PATH"] = libpath or O.REF_DIR
-    if preload:
-        env["LD_PRELOAD"] = preload
     env.update(extra or {})
     return subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
 

@@ -19,7 +19,7 @@ have = os.path.exists(PROBE) and os.path.exists(os.path.join(STANDALONE_DIR, "li
 
 def run(libdir):
     env = dict(os.environ)
-    env.pop("LD_PRELOAD", None)
+    O.set_preload(env)
     env["LD_LIBRARY_PATH"] = libdir
     r = subprocess.run([PROBE], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
     assert r.returncode == 0, r.stderr.decode()

@@ -3,7 +3,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out/arith; mkdir -p "$O"
 [ -n "$ARITH_SKIP_TESTS" ] || timeout 900 python -m pytest tests -q -m gpu -k "arith" -n 4 -p no:cacheprovider 2>&1 | tail -3
 for c in ${ARITH_CONFIGS:-arith arith_prog}; do
-  timeout 900 python bench.py --config $c --warmup 1 --steps ${ARITH_STEPS:-2} --no-host-leg --no-inflight-leg --cpu-budget 15 > "$O/bench_$c.log" 2>&1
+  timeout 900 python bench.py --full --config $c --warmup 1 --steps ${ARITH_STEPS:-2} --no-host-leg --no-inflight-leg --cpu-budget 15 > "$O/bench_$c.log" 2>&1
   python - "$O/bench_$c.log" <<'PY'
 import json,sys
 try:

@@ -7,7 +7,7 @@ timeout 600 python -m pytest tests/test_gpu_parity.py tests/test_gpu_fuzz.py -x 
 i=0
 for envs in "$@"; do
   i=$((i+1))
-  env $envs timeout 300 python bench.py --config c3 --no-cpu-baseline --no-host-leg --no-inflight-leg > "$O/bench_$i.log" 2>&1
+  env $envs timeout 300 python bench.py --full --config c3 --no-cpu-baseline --no-host-leg --no-inflight-leg > "$O/bench_$i.log" 2>&1
   python - "$O/bench_$i.log" "$envs" <<'PY'
 import json,sys
 try:

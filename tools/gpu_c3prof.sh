@@ -3,7 +3,7 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 T=${1:-c3prof}; shift
 O=gpurun_out/$T; mkdir -p "$O"; export TMPDIR=/tmp
-env "$@" timeout 300 rocprofv3 --kernel-trace --stats -d "$O" -o c3 -f csv -- python bench.py --config c3 --steps 8 --warmup 2 --no-cpu-baseline --no-host-leg --no-inflight-leg > "$O/run.log" 2>&1
+env "$@" timeout 300 rocprofv3 --kernel-trace --stats -d "$O" -o c3 -f csv -- python bench.py --full --config c3 --steps 8 --warmup 2 --no-cpu-baseline --no-host-leg --no-inflight-leg > "$O/run.log" 2>&1
 python - "$O" <<'PY'
 import csv,sys,glob
 f=glob.glob(sys.argv[1]+'/**/c3_kernel_stats.csv', recursive=True)

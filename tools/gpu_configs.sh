@@ -2,7 +2,7 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out/${1:-configs}; mkdir -p "$O"
 for c in c3 c2 c4 c5 c5t; do
-  timeout 400 python bench.py --config $c --no-cpu-baseline --no-host-leg --no-inflight-leg > "$O/bench_$c.log" 2>&1
+  timeout 400 python bench.py --full --config $c --no-cpu-baseline --no-host-leg --no-inflight-leg > "$O/bench_$c.log" 2>&1
   python - "$O/bench_$c.log" <<'PY'
 import json,sys
 try:

@@ -20,7 +20,7 @@ for m in $MODES; do
 done
 # the BASELINE configurations at full size under the fence (bit-exact check against the reference included): GUARD_BENCH="metric c3 c5 c5t"
 for c in $GUARD_BENCH; do
-  MJH_GUARD=${GUARD_BENCH_MODE:-2} timeout 900 python bench.py --config $c --steps 3 --warmup 1 --no-cpu-baseline --no-inflight-leg --host-seconds 0.5 > "$O/bench_$c.log" 2>&1
+  MJH_GUARD=${GUARD_BENCH_MODE:-2} timeout 900 python bench.py --full --config $c --steps 3 --warmup 1 --no-cpu-baseline --no-inflight-leg --host-seconds 0.5 > "$O/bench_$c.log" 2>&1
   echo "bench $c under MJH_GUARD rc=$?"; python - "$O/bench_$c.log" <<'PY'
 import json,sys
 try:

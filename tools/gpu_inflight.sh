@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out/$TAG; mkdir -p "$O"
 Q="--no-cpu-baseline --no-host-leg --no-inflight-leg --other-configs none --verify 2"
 for v in ${VARIANTS:-"MJH_INFLIGHT=1" "MJH_INFLIGHT_MODE=0" "MJH_INFLIGHT_MODE=1" "MJH_INFLIGHT_MODE=2"}; do
-  env $v timeout 300 python bench.py --config $CFG $Q > "$O/b.log" 2>&1
+  env $v timeout 300 python bench.py --full --config $CFG $Q > "$O/b.log" 2>&1
   python - "$O/b.log" "$v" <<'PY'
 import json,sys
 try:

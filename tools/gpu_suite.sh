@@ -3,8 +3,8 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out/${1:-suite}; mkdir -p "$O"
 timeout 1500 python -m pytest tests -x -q -m gpu 2>&1 | tail -4
-timeout 300 python bench.py --no-cpu-baseline --no-host-leg --no-inflight-leg > "$O/bench_c1.log" 2>&1
-timeout 300 python bench.py --config c3 --no-cpu-baseline --no-host-leg --no-inflight-leg > "$O/bench_c3.log" 2>&1
+timeout 300 python bench.py --full --no-cpu-baseline --no-host-leg --no-inflight-leg > "$O/bench_c1.log" 2>&1
+timeout 300 python bench.py --full --config c3 --no-cpu-baseline --no-host-leg --no-inflight-leg > "$O/bench_c3.log" 2>&1
 for f in "$O/bench_c1.log" "$O/bench_c3.log"; do python - "$f" <<'PY'
 import json,sys
 try:
