@@ -72,7 +72,18 @@ typedef struct {
   float lambda_log_scale1, lambda_log_scale2;
   unsigned restart_interval;
   int restart_in_rows;
-  int num_scans;                   /* 0 = one sequential scan (baseline) */
+  /* 0 = one sequential scan (baseline).  A script whose first scan has Ss != 0 and Se == 0 is a LOSSLESS file (SOF3), as
+   * validate_script decides (jcmaster.c:300-310) and as jpeg_enable_lossless leaves the object (cinfo->Ss = PSV, Se = 0, Ah = 0,
+   * Al = Pt, jcparam.c:1016-1040): one scan of every component in order, Ss = the predictor 1..7, Ah = 0, Al = the point
+   * transform 0..precision-1 (else JERR_BAD_PROGRESSION).  The encoder applies jcmaster.c's overrides itself (1x1 sampling, no
+   * smoothing, optimal tables: jcmaster.c:1067-1094) and writes no DQT.  Input is grayscale (input_components 1) or an RGB-family
+   * layout coded as JCS_RGB (color_transform MJH_COLOR_NONE), every component with dc_tbl_no 0 (the reference's SOS names table 0
+   * for every component of a lossless scan, jcmarker.c:516), in the fastest profile (the max-compression profile writes a DQT and
+   * an empty DHT, jcmarker.c:189-254, :293-401), without trellis quantization (JERR_BAD_BUFFER_MODE) or arithmetic coding.
+   * data_precision 8, 12 or 16 (16: lossless only; 12 / 16: uint16 samples, row_pitch / image_stride in BYTES).  Restart intervals
+   * must be whole rows (JERR_BAD_RESTART, jclossls.c:289-294).  Lossless scripts of several scans are refused (one interleaved
+   * scan here).  The planes / coefficient entry points return MJH_EINVAL for a lossless encoder. */
+  int num_scans;
   mjh_scan scan_info[MJH_MAX_SCANS];
   int optimize_scans;
   int write_JFIF_header;
@@ -323,8 +334,9 @@ enum {
   MJH_TAP_COEF_Q0 = 4,   /* int16  quantized before trellis (kept only when debug taps on)  */
   MJH_TAP_HUFF_BITS = 5, /* uint8  [4 slots: DC0,AC0,DC1,AC1][17] final tables               */
   MJH_TAP_HUFF_VALS = 6, /* uint8  [4][256]                                                  */
-  MJH_TAP_PROG_SCAN_US = 7 /* uint32 [2][64] progressive: microseconds the statistics [0] / encode [1]
+  MJH_TAP_PROG_SCAN_US = 7, /* uint32 [2][64] progressive: microseconds the statistics [0] / encode [1]
                               workgroup of each scan-script entry ran (0 = not run)              */
+  MJH_TAP_LL_COUNTS = 8  /* uint32 [17] lossless: symbol histogram (difference categories 0..16) of the table */
 };
 int mjh_set_debug_taps(mjh_encoder *e, int on);
 int mjh_read_tap(mjh_encoder *e, int what, int image, int component, void *dst, size_t cap, size_t *size);

@@ -18,7 +18,7 @@ PROFILE_MAX_COMPRESSION = 0x5D083AAD
 PROFILE_FASTEST = 0x2AEA5CB4
 COLOR_YCC, COLOR_NONE, COLOR_YCC_IN = 0, 1, 2
 OK, EINVAL, EUNSUPPORTED, EHIP, ENOMEM, ETOOSMALL = 0, -1, -2, -3, -4, -5
-TAP_PLANE, TAP_COEF_UQ, TAP_COEF_Q, TAP_COEF_Q0, TAP_HUFF_BITS, TAP_HUFF_VALS, TAP_PROG_SCAN_US = 1, 2, 3, 4, 5, 6, 7
+TAP_PLANE, TAP_COEF_UQ, TAP_COEF_Q, TAP_COEF_Q0, TAP_HUFF_BITS, TAP_HUFF_VALS, TAP_PROG_SCAN_US, TAP_LL_COUNTS = 1, 2, 3, 4, 5, 6, 7, 8
 
 
 class MjhError(RuntimeError):
@@ -139,9 +139,12 @@ def make_params(width, height, *, quality=75, baseline=False, revert=False, opti
                 progressive=False, fastcrush=False, precision=8, trellis_loops=1, smooth=0, rgb=False,
                 dc_scan_opt=None, dc_ver_weight=None, use_scans_in_trellis=False, trellis_freq_split=0,
                 trellis_eob_opt=False, trellis_q_opt=False, arithmetic=False, arith_cond=None, scans=None, gray_sample=None, yccin=False, dct=None,
-                dc_tbl=None, ac_tbl=None, no_optimize=False):
+                dc_tbl=None, ac_tbl=None, no_optimize=False, lossless=None):
     """Parameters with cjpeg's switch vocabulary (cjpeg.c:371-714).  Without `baseline` or
-    `revert` this is cjpeg's default: progressive with scan search (`fastcrush`: fixed 9-scan script)."""
+    `revert` this is cjpeg's default: progressive with scan search (`fastcrush`: fixed 9-scan script).
+    lossless=(psv, pt): lossless JPEG (SOF3, cjpeg -lossless psv,Pt / jpeg_enable_lossless) with what jpeg_default_colorspace
+    makes of the input -- grayscale stays grayscale, RGB becomes a JCS_RGB file (`gray` has no effect, jcmaster.c:1067-1080);
+    precision 8, 12 or 16 (12 / 16: uint16 samples)."""
     p = Params()
     L = lib()
     per_comp = isinstance(sample[0], (tuple, list))      # ((h, v) of Y, (h, v) of Cb, (h, v) of Cr): cjpeg -sample HxV,HxV,HxV
@@ -211,6 +214,20 @@ def make_params(width, height, *, quality=75, baseline=False, revert=False, opti
             p.component_id[i] = cid
             p.h_samp_factor[i] = p.v_samp_factor[i] = 1
             p.quant_tbl_no[i] = p.dc_tbl_no[i] = p.ac_tbl_no[i] = 0
+    if lossless is not None:    # jpeg_enable_lossless: cinfo->Ss = PSV, Se = 0, Ah = 0, Al = Pt -- as a one-scan script (validate_script)
+        p.num_components = 1 if grayin else 3
+        p.num_scans, p.optimize_scans = 1, 0
+        p.scan_info[0].comps_in_scan = p.num_components
+        for j in range(p.num_components):
+            p.scan_info[0].component_index[j] = j
+        p.scan_info[0].Ss, p.scan_info[0].Se, p.scan_info[0].Ah, p.scan_info[0].Al = lossless[0], 0, 0, lossless[1]
+    if lossless is not None and not grayin:   # jpeg_default_colorspace in lossless mode: RGB input -> JCS_RGB (jcparam.c:544-546)
+        p.color_transform = COLOR_NONE
+        p.write_JFIF_header = 0
+        for i, cid in enumerate(b"RGB"):
+            p.component_id[i] = cid
+            p.h_samp_factor[i] = p.v_samp_factor[i] = 1
+            p.quant_tbl_no[i] = p.dc_tbl_no[i] = p.ac_tbl_no[i] = 0
     if restart is not None:
         if isinstance(restart, str) and restart.lower().endswith("b"):
             p.restart_interval = int(restart[:-1])
@@ -219,6 +236,8 @@ def make_params(width, height, *, quality=75, baseline=False, revert=False, opti
     if revert:
         if progressive:
             _chk(L.mjh_params_simple_progression(C.byref(p)))
+    elif lossless is not None:
+        p.optimize_scans = 0         # (cjpeg -lossless without -revert fails in the reference: the caller picks the profile)
     elif not baseline:
         # cjpeg's default in the max-compression profile: progressive, scan search unless -fastcrush
         if fastcrush or progressive:
@@ -324,7 +343,7 @@ class Encoder:
     # -- encode -------------------------------------------------------------------------------
     def encode_host(self, images):
         """images: uint8 ndarray [n, H, W, C] (or [H, W, C]); returns list of bytes."""
-        a = _as_batch(self.params, np.ascontiguousarray(images, dtype=np.uint16 if self.params.data_precision == 12 else np.uint8))
+        a = _as_batch(self.params, np.ascontiguousarray(images, dtype=np.uint16 if self.params.data_precision > 8 else np.uint8))
         n = a.shape[0]
         _chk(lib().mjh_encode_host(self._h, a.ctypes.data, a.strides[1], a.strides[0], n))
         return [self.get_jpeg(i) for i in range(n)]
@@ -355,13 +374,13 @@ class Encoder:
         _chk(lib().mjh_encode_device(self._h, ptr, row_pitch, image_stride, n, stream))
 
     def encode_tensor(self, t, stream=None):
-        """t: torch CUDA tensor [n, H, W, C] (uint8; int16/uint16 storage for 12-bit), rows contiguous.  Asynchronous.
+        """t: torch CUDA tensor [n, H, W, C] (uint8; int16/uint16 storage for 12- and 16-bit), rows contiguous.  Asynchronous.
         stream: None = the torch stream current on t's device (ordered after whatever produced t); "own" = the encoder's
         private stream (the caller guarantees t is complete, e.g. after a synchronize); or a raw hipStream_t value."""
         import torch
         p = self.params
         px = p.input_pixel_size or p.input_components
-        es = 2 if p.data_precision == 12 else 1
+        es = 2 if p.data_precision > 8 else 1
         assert t.is_cuda and t.dim() == 4 and t.element_size() == es and t.stride(3) == 1 and t.stride(2) == t.shape[3], "layout"
         assert tuple(t.shape[1:]) == (p.image_height, p.image_width, px), "tensor %s does not match the encoder (%d x %d x %d)" % (
             tuple(t.shape), p.image_height, p.image_width, px)

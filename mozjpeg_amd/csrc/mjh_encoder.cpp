@@ -24,6 +24,7 @@
 #include "../../include/mozjpeg_hip.h"
 #include "mjh_internal.h"
 #include "mjh_launch.h"
+#include "mjh_lossless.h"
 #include "mjh_guard.h"
 #include "mjh_numa.h"
 #include "mjh_arith_table.h"
@@ -56,7 +57,7 @@ extern "C" int mjh_debug_guard_check(void) { return guard_verify(); }
 extern "C" int mjh_debug_guard_mode(void) { return mjh_guard_mode(); }
 // (for mjh_pool.cpp, which is otherwise built on the public ABI: lets its argument checks leave a message too)
 int mjh_internal_fail(int code, const char *msg) { return fail(code, "%s", msg); }
-extern "C" const char *mjh_version(void) { return "mozjpeg_hip 0.3 (gfx950)"; }
+extern "C" const char *mjh_version(void) { return "mozjpeg_hip 0.4 (gfx950)"; }
 extern "C" size_t mjh_params_size(void) { return sizeof(mjh_params); }
 extern "C" int mjh_device_count(void)
 {
@@ -396,6 +397,10 @@ struct mjh_encoder {
   int arith_nscans = 0;
   void *d_arith_rates = nullptr;
   void *g_in[MJH_MAX_COMPS] = { nullptr, nullptr, nullptr, nullptr }; size_t g_in_bytes[MJH_MAX_COMPS] = { 0, 0, 0, 0 }; std::vector<void *> g_in_old;   // MJH_GUARD=2/3: fenced copies of the caller's device input
+  // lossless mode (mjh_lossless.hip): histogram, bits and final bit offset of every work unit, bits in front of every restart segment
+  bool lossless = false;
+  LlConst L{};
+  unsigned *d_ll_hist = nullptr, *d_ll_len = nullptr, *d_ll_off = nullptr, *d_ll_segE = nullptr;
 };
 
 static long div_round_up(long a, long b) { return (a + b - 1) / b; }
@@ -455,7 +460,7 @@ static int check_supported(const mjh_params *p)
 {
   if (p->image_width <= 0 || p->image_height <= 0 || p->image_width > 65500 || p->image_height > 65500)
     return fail(MJH_EINVAL, "bad image size %dx%d", p->image_width, p->image_height);
-  if (p->data_precision != 0 && p->data_precision != 8 && p->data_precision != 12) return fail(MJH_EUNSUPPORTED, "data_precision %d", p->data_precision);
+  if (p->data_precision != 0 && p->data_precision != 8 && p->data_precision != 12) return fail(MJH_EUNSUPPORTED, "data_precision %d (DCT mode: 8 or 12; 16 only in lossless mode, jcmaster.c:197-202)", p->data_precision);
   if (p->smoothing_factor < 0 || p->smoothing_factor > 100) return fail(MJH_EINVAL, "smoothing_factor %d (0..100)", p->smoothing_factor);
   if (p->trellis_num_loops < 0 || p->trellis_num_loops > 16) return fail(MJH_EINVAL, "trellis_num_loops %d (0..16)", p->trellis_num_loops);
   if (p->trellis_freq_split < 0 || p->trellis_freq_split > 63) return fail(MJH_EINVAL, "trellis_freq_split %d (0..63)", p->trellis_freq_split);
@@ -826,7 +831,7 @@ static void free_all(mjh_encoder *e)
   if (e->ev_null_in) (void)hipEventDestroy(e->ev_null_in);
   void *ptrs[] = { e->d_pixb[0], e->d_pixb[1], e->d_plin, e->d_cfin, e->d_prog_mpos, e->d_prog_ffsums, e->d_prog_chunks, e->pe.len16, e->pe.run16, e->pe.tail16, e->pe.be16, e->pe.off32, e->pe.sums, e->pe.totals, e->pe.T32, e->pe.tsums, e->pe.ttotals, e->pe.ne_bits, e->pe.ne2_bits, e->pe.e_bits, e->pe.info, e->pe.chist, e->pe.rmask, e->d_planes, e->d_uq, e->d_q, e->d_q0, e->d_quant, e->d_quant_init, e->d_tabs, e->d_tabs_init, e->d_lambda, e->d_back, e->d_eob_cost, e->d_eob_has, e->d_qsums, e->d_nzmask, e->d_nq8, e->d_dense, e->d_worklist, e->d_worklist2, e->d_prog_scans, e->d_prog_ctl, e->d_lists, e->d_pool, e->d_outpool, e->d_frame_hdr, e->d_seg_x, e->d_seg_E, e->d_seg_sums, e->d_seg_totals, e->d_mpos,
                    e->d_len16, e->d_off32, e->d_sums, e->d_totals, e->d_ffsums, e->d_fftotals, e->d_stream, e->d_out, e->d_sizes,
-                   e->d_meta, e->d_prefix, e->d_sos, e->d_arith_rates, e->d_back9, e->d_jfin, e->d_qspec, e->g_in[0], e->g_in[1], e->g_in[2], e->g_in[3] };
+                   e->d_meta, e->d_prefix, e->d_sos, e->d_ll_hist, e->d_ll_len, e->d_ll_off, e->d_ll_segE, e->d_arith_rates, e->d_back9, e->d_jfin, e->d_qspec, e->g_in[0], e->g_in[1], e->g_in[2], e->g_in[3] };
   for (void *q : ptrs) if (q) (void)mjh_guard_free(q);
   for (void *q : e->g_in_old) (void)mjh_guard_free(q);
   if (e->ev_defer) (void)hipEventDestroy(e->ev_defer);
@@ -903,10 +908,45 @@ static int mjh_streams_overlap(hipStream_t a, hipStream_t b)
 static thread_local bool g_create_twin = false;
 static thread_local hipStream_t g_twin_avoid[2] = { nullptr, nullptr };   // make_twin: the primary's main and side stream     // mjh_encoder_create is making the second buffer set of an encoder (make_twin)
 
+// The encoder's main and side stream (every encoder kind).
+static hipError_t make_streams(mjh_encoder *e)
+{
+#define STREAMCHK(x) do { const hipError_t r_ = (x); if (r_ != hipSuccess) return r_; } while (0)
+  if (e->high_priority_streams) {
+    // The twin's main and side stream must not share a hardware queue with the primary's, or the two batches take turns instead of
+    // overlapping.  Streams of the same priority (another priority level has queues of its own, but its kernels are then dispatched
+    // first and the sharing turns into alternation: measured, 4.68 against 4.43 ms) are made until two are found that overlap with
+    // both of the primary's and with each other; the others are destroyed again.
+    std::vector<hipStream_t> made;
+    for (int tries = 0; tries < 12 && !e->side_stream; tries++) {
+      hipStream_t c = nullptr;
+      STREAMCHK(hipStreamCreateWithFlags(&c, hipStreamNonBlocking));
+      made.push_back(c);
+      bool free_queue = true;
+      for (hipStream_t other : { g_twin_avoid[0], g_twin_avoid[1], e->stream })
+        if (other && mjh_streams_overlap(c, other) == 0) { free_queue = false; break; }
+      if (!free_queue) continue;
+      if (!e->stream) e->stream = c; else e->side_stream = c;
+    }
+    for (hipStream_t c : made) if (c != e->stream && c != e->side_stream) (void)hipStreamDestroy(c);
+    if (!e->stream) STREAMCHK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));           // (fewer queues than streams: share)
+    if (!e->side_stream) STREAMCHK(hipStreamCreateWithFlags(&e->side_stream, hipStreamNonBlocking));
+  } else {
+    STREAMCHK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
+    STREAMCHK(hipStreamCreateWithFlags(&e->side_stream, hipStreamNonBlocking));     // (right behind the main stream: adjacent creations never share a hardware queue)
+  }
+#undef STREAMCHK
+  return hipSuccess;
+}
+
+static int create_lossless(const mjh_params *p, int max_batch, int device, mjh_encoder **out);
+
 extern "C" int mjh_encoder_create(const mjh_params *p, int max_batch, int device, mjh_encoder **out)
 {
   if (!p || !out || max_batch < 1) return fail(MJH_EINVAL, "bad arguments");
   *out = nullptr;
+  if (p->num_scans > 0 && p->num_scans <= MJH_MAX_SCANS && p->scan_info[0].Ss != 0 && p->scan_info[0].Se == 0)   // validate_script jcmaster.c:300-310
+    return create_lossless(p, max_batch, device, out);
   // A script whose scans are all whole-block scans (Ss = 0, Se = 63) is a sequential multi-scan file, not a progressive one
   // (validate_script jcmaster.c:309-330, :386-398): every component in exactly one scan, components in ascending order.  It is
   // taken out of the parameters here -- everything in front of the entropy stage is the sequential pipeline.
@@ -973,29 +1013,7 @@ extern "C" int mjh_encoder_create(const mjh_params *p, int max_batch, int device
   e->nbands = p->trellis_quant && p->use_scans_in_trellis ? 2 : 1;          // jcmaster.c:451-460
   e->freq_split = p->trellis_freq_split > 0 ? p->trellis_freq_split : 8;   // jcparam.c:512
   HIPCHK_E(hipSetDevice(device));
-  if (e->high_priority_streams) {
-    // The twin's main and side stream must not share a hardware queue with the primary's, or the two batches take turns instead of
-    // overlapping.  Streams of the same priority (another priority level has queues of its own, but its kernels are then dispatched
-    // first and the sharing turns into alternation: measured, 4.68 against 4.43 ms) are made until two are found that overlap with
-    // both of the primary's and with each other; the others are destroyed again.
-    std::vector<hipStream_t> made;
-    for (int tries = 0; tries < 12 && !e->side_stream; tries++) {
-      hipStream_t c = nullptr;
-      HIPCHK_E(hipStreamCreateWithFlags(&c, hipStreamNonBlocking));
-      made.push_back(c);
-      bool free_queue = true;
-      for (hipStream_t other : { g_twin_avoid[0], g_twin_avoid[1], e->stream })
-        if (other && mjh_streams_overlap(c, other) == 0) { free_queue = false; break; }
-      if (!free_queue) continue;
-      if (!e->stream) e->stream = c; else e->side_stream = c;
-    }
-    for (hipStream_t c : made) if (c != e->stream && c != e->side_stream) (void)hipStreamDestroy(c);
-    if (!e->stream) HIPCHK_E(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));           // (fewer queues than streams: share)
-    if (!e->side_stream) HIPCHK_E(hipStreamCreateWithFlags(&e->side_stream, hipStreamNonBlocking));
-  } else {
-    HIPCHK_E(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-    HIPCHK_E(hipStreamCreateWithFlags(&e->side_stream, hipStreamNonBlocking));     // (right behind the main stream: adjacent creations never share a hardware queue)
-  }
+  HIPCHK_E(make_streams(e));
   HIPCHK_E(hipEventCreateWithFlags(&e->ev_done, hipEventDisableTiming));
   HIPCHK_E(hipEventCreateWithFlags(&e->ev_tier1, hipEventDisableTiming));
   if (const char *v = getenv("MJH_INFLIGHT")) { e->inflight = atoi(v); if (e->inflight < 1 || e->inflight > 2) e->inflight = 2; }
@@ -1541,10 +1559,14 @@ static MjhConst dc_chain_view(const mjh_encoder *e, const MjhConst &CV)
   return D;
 }
 
+static int run_lossless(mjh_encoder *e, const void *d_pixels, size_t row_pitch, size_t image_stride, int n, hipStream_t s,
+                        hipEvent_t input_read, hipEvent_t before_output);
+
 static int run_pipeline(mjh_encoder *e, const void *d_pixels, size_t row_pitch, size_t image_stride, int n, hipStream_t s,
                         const MjhPlaneSrc *plane_src = nullptr, const MjhCoefSrc *coef_src = nullptr,
                         hipEvent_t input_read = nullptr, hipEvent_t before_output = nullptr)
 {
+  if (e->lossless) return run_lossless(e, d_pixels, row_pitch, image_stride, n, s, input_read, before_output);
   const MjhConst &C = e->C;
   const mjh_params &p = e->p;
   const int spi = e->spi;
@@ -2088,13 +2110,13 @@ extern "C" int mjh_encode_device(mjh_encoder *e, const void *d_pixels, size_t ro
 {
   if (!e || !d_pixels || n < 1 || n > e->max_batch) return fail(MJH_EINVAL, "bad arguments (n=%d, max_batch=%d)", n, e ? e->max_batch : 0);
   {
-    const size_t row_bytes = (size_t)e->C.W * e->C.px_size * (e->C.precision == 12 ? 2 : 1);
+    const size_t row_bytes = (size_t)e->C.W * e->C.px_size * (e->C.precision > 8 ? 2 : 1);
     if (row_pitch < row_bytes || (n > 1 && image_stride < row_pitch * (size_t)(e->C.H - 1) + row_bytes))
       return fail(MJH_EINVAL, "row_pitch %zu / image_stride %zu too small for %dx%d images of %zu-byte rows", row_pitch, image_stride, e->C.W, e->C.H, row_bytes);
   }
   HIPCHK(hipSetDevice(e->device));
   {
-    const size_t row_bytes = (size_t)e->C.W * e->C.px_size * (e->C.precision == 12 ? 2 : 1);
+    const size_t row_bytes = (size_t)e->C.W * e->C.px_size * (e->C.precision > 8 ? 2 : 1);
     const int rg = guard_input(e, 0, &d_pixels, (size_t)(n - 1) * image_stride + (size_t)(e->C.H - 1) * row_pitch + row_bytes);
     if (rg) return rg;
   }
@@ -2237,7 +2259,8 @@ static int host_buffers(mjh_encoder *e)
   const size_t in_bytes = (size_t)e->max_batch * e->pix_image_bytes;
   // results: a JPEG file is normally a small fraction of its input; files that do not fit the arena are fetched from
   // the device buffer one by one (slow path, flagged in the table)
-  e->res_cap = (size_t)e->max_batch * (e->pix_image_bytes / 2 + 65536);
+  // (a lossless file is about as large as its input, and larger for noise)
+  e->res_cap = (size_t)e->max_batch * ((e->lossless ? e->pix_image_bytes * 3 / 2 : e->pix_image_bytes / 2) + 65536);
   HIPCHK(hipStreamCreateWithPriority(&e->d2h_stream, hipStreamNonBlocking, e->copy_prio));
   for (int b = 0; b < 2; b++) {
     HIPCHK(mjh_dmalloc((void **)&e->d_pixb[b], in_bytes));
@@ -2278,7 +2301,7 @@ extern "C" int mjh_encode_host(mjh_encoder *e, const void *pixels, size_t row_pi
 {
   if (!e || !pixels || n < 1 || n > e->max_batch) return fail(MJH_EINVAL, "bad arguments");
   HIPCHK(hipSetDevice(e->device));
-  const size_t row_bytes = (size_t)e->C.W * e->C.px_size * (e->C.precision == 12 ? 2 : 1);
+  const size_t row_bytes = (size_t)e->C.W * e->C.px_size * (e->C.precision > 8 ? 2 : 1);
   if (row_pitch < row_bytes) return fail(MJH_EINVAL, "row_pitch %zu is smaller than a row (%zu bytes)", row_pitch, row_bytes);
   if (n > 1 && image_stride < row_pitch * (size_t)(e->C.H - 1) + row_bytes)
     return fail(MJH_EINVAL, "image_stride %zu is smaller than one image (%zu bytes): images would overlap", image_stride, row_pitch * (size_t)(e->C.H - 1) + row_bytes);
@@ -2375,7 +2398,7 @@ extern "C" int mjh_encode_gather(mjh_encoder *e, mjh_encoder *const *members, in
   }
   HIPCHK(hipEventRecord(e->ev_h2d[b], e->copy_stream));
   HIPCHK(hipStreamWaitEvent(e->stream, e->ev_h2d[b], 0));
-  const size_t row_bytes = (size_t)e->C.W * e->C.px_size * (e->C.precision == 12 ? 2 : 1);
+  const size_t row_bytes = (size_t)e->C.W * e->C.px_size * (e->C.precision > 8 ? 2 : 1);
   rc = run_pipeline(e, e->d_pixb[b], row_bytes, e->pix_image_bytes, n, e->stream, nullptr, nullptr, e->ev_pix_free[b],
                     e->host_calls > 1 ? e->ev_packed[b ^ 1] : nullptr);
   if (rc) return rc;
@@ -2465,6 +2488,7 @@ static int check_coef_args(mjh_encoder *e, const void *const coefs[], const size
 {
   if (!e || !coefs || !blocks_per_row || n < 1 || n > e->max_batch)
     return fail(MJH_EINVAL, "bad arguments (n=%d, max_batch=%d)", n, e ? e->max_batch : 0);
+  if (e->lossless) return fail(MJH_EINVAL, "a lossless encoder has no DCT coefficients (jpeg_write_coefficients writes DCT-based files only)");
   if (e->p.trellis_quant)
     return fail(MJH_EINVAL, "trellis quantization needs the unquantized DCT output: create the encoder with trellis_quant = 0 "
                             "for coefficient input (jpeg_copy_critical_parameters does the same, jctrans.c:102)");
@@ -2531,7 +2555,8 @@ static int check_plane_args(mjh_encoder *e, const void *const planes[], const si
 {
   if (!e || !planes || !row_pitch || !plane_width || !plane_height || n < 1 || n > e->max_batch)
     return fail(MJH_EINVAL, "bad arguments (n=%d, max_batch=%d)", n, e ? e->max_batch : 0);
-  const size_t ss = e->C.precision == 12 ? 2 : 1;
+  if (e->lossless) return fail(MJH_EINVAL, "raw data input is not supported in lossless mode (jpeg_write_raw_data: JERR_NOTIMPL, jcapistd.c:154)");
+  const size_t ss = e->C.precision > 8 ? 2 : 1;
   for (int c = 0; c < e->C.ncomp; c++)
     if (!planes[c] || plane_width[c] < 1 || plane_height[c] < 1 || row_pitch[c] < (size_t)plane_width[c] * ss)
       return fail(MJH_EINVAL, "bad plane %d (pointer, size %dx%d or pitch %zu)", c, plane_width[c], plane_height[c], row_pitch[c]);
@@ -2551,7 +2576,7 @@ extern "C" int mjh_encode_planes_device(mjh_encoder *e, const void *const d_plan
   for (int c = 0; c < e->C.ncomp; c++) {
     ps.base[c] = d_planes[c]; ps.pitch[c] = (long long)row_pitch[c]; ps.stride[c] = image_stride ? (long long)image_stride[c] : 0;
     ps.w[c] = plane_width[c]; ps.h[c] = plane_height[c];
-    const int rg = guard_input(e, c, &ps.base[c], (size_t)(n - 1) * (size_t)ps.stride[c] + (size_t)(ps.h[c] - 1) * row_pitch[c] + (size_t)ps.w[c] * (e->C.precision == 12 ? 2 : 1));
+    const int rg = guard_input(e, c, &ps.base[c], (size_t)(n - 1) * (size_t)ps.stride[c] + (size_t)(ps.h[c] - 1) * row_pitch[c] + (size_t)ps.w[c] * (e->C.precision > 8 ? 2 : 1));
     if (rg) return rg;
   }
   { const int rcw = wait_pending_pack(e, stream ? (hipStream_t)stream : e->stream); if (rcw) return rcw; }
@@ -2566,7 +2591,7 @@ extern "C" int mjh_encode_planes_host(mjh_encoder *e, const void *const planes[M
   if (rc) return rc;
   if (n > 1 && !image_stride) return fail(MJH_EINVAL, "image_stride is required for n > 1");
   HIPCHK(hipSetDevice(e->device));
-  const size_t ss = e->C.precision == 12 ? 2 : 1;
+  const size_t ss = e->C.precision > 8 ? 2 : 1;
   // only the part of each plane the encoder reads (<= width_in_blocks*8 x height_in_blocks*8) is staged, tightly packed
   MjhPlaneSrc ps;
   memset(&ps, 0, sizeof(ps));
@@ -2805,6 +2830,15 @@ extern "C" int mjh_read_tap(mjh_encoder *e, int what, int image, int comp, void 
   HIPCHK(hipSetDevice(e->device));
   HIPCHK(hipDeviceSynchronize());
   const MjhConst &C = e->C;
+  if (what == MJH_TAP_LL_COUNTS) {
+    if (!e->lossless) return fail(MJH_EINVAL, "not a lossless encoder");
+    const size_t need = 17 * sizeof(uint32_t);
+    if (cap < need) return fail(MJH_ETOOSMALL, "need %zu bytes", need);
+    HIPCHK(hipMemcpy(dst, (const uint8_t *)(e->d_tabs + (size_t)image * e->spi + SLOT_FINAL) + offsetof(MjhHuffTable, counts), need, hipMemcpyDeviceToHost));
+    if (size) *size = need;
+    return MJH_OK;
+  }
+  if (e->lossless && what != MJH_TAP_HUFF_BITS && what != MJH_TAP_HUFF_VALS) return fail(MJH_EINVAL, "tap %d does not exist in lossless mode", what);
   if (what == MJH_TAP_HUFF_BITS || what == MJH_TAP_HUFF_VALS) {
     std::vector<MjhHuffTable> t(4);
     const size_t need = what == MJH_TAP_HUFF_BITS ? 4 * 17 : 4 * 256;
@@ -2860,5 +2894,198 @@ extern "C" int mjh_read_tap(mjh_encoder *e, int what, int image, int comp, void 
   HIPCHK(hipMemcpy2D(dst, (size_t)cc.nblk * 2, src + (size_t)image * C.coefs_per_image + cc.coef_off, (size_t)cc.kstride * 2,
                      (size_t)cc.nblk * 2, 64, hipMemcpyDeviceToHost));
   if (size) *size = need;
+  return MJH_OK;
+}
+
+// ---- lossless mode (SOF3: jclossls.c, jclhuff.c, jcdiffct.c; kernels in mjh_lossless.hip) -----------------------------------------
+// The encoder runs what the reference makes of the parameters in lossless mode: 1x1 sampling, no smoothing (jcmaster.c:1067-1080),
+// optimal tables (:1091), no DQT (jcmarker.c:687), SOF3 with the sample precision, a DHT of DC table 0, an SOS with Ss = PSV,
+// Se = 0, Ah = 0, Al = Pt and table selector 0 (jcmarker.c:516-525).
+static int create_lossless(const mjh_params *p, int max_batch, int device, mjh_encoder **out)
+{
+  if (p->num_components < 1 || p->num_components > 3) return fail(MJH_EUNSUPPORTED, "lossless mode with %d components", p->num_components);
+  if (p->image_width <= 0 || p->image_height <= 0 || p->image_width > 65500 || p->image_height > 65500)
+    return fail(MJH_EINVAL, "bad image size %dx%d", p->image_width, p->image_height);
+  const int P = p->data_precision == 0 ? 8 : p->data_precision;
+  if (P != 8 && P != 12 && P != 16) return fail(MJH_EINVAL, "data_precision %d (lossless: 8, 12 or 16; JERR_BAD_PRECISION)", p->data_precision);
+  const mjh_scan &sc = p->scan_info[0];
+  const int psv = sc.Ss, pt = sc.Al;
+  if (psv < 1 || psv > 7 || sc.Se != 0 || sc.Ah != 0 || pt < 0 || pt >= P)
+    return fail(MJH_EINVAL, "lossless scan: predictor %d, Se %d, Ah %d, point transform %d (1..7, 0, 0, 0..%d; JERR_BAD_PROGRESSION, jcmaster.c:390-400)", psv, sc.Se, sc.Ah, pt, P - 1);
+  if (p->trellis_quant)
+    return fail(MJH_EINVAL, "trellis quantization with lossless mode (JERR_BAD_BUFFER_MODE: \"Bogus buffer control mode\", the reference's trellis passes need a DCT coefficient buffer)");
+  if (p->arith_code) return fail(MJH_EUNSUPPORTED, "arithmetic coding with lossless mode (JERR_NOT_COMPILED: \"Sorry, arithmetic coding is not implemented\")");
+  if (p->num_scans != 1) return fail(MJH_EUNSUPPORTED, "a lossless script of %d scans: this library codes a lossless image as one interleaved scan", p->num_scans);
+  if (sc.comps_in_scan != p->num_components) return fail(MJH_EUNSUPPORTED, "a lossless scan of %d of %d components: this library codes a lossless image as one interleaved scan", sc.comps_in_scan, p->num_components);
+  for (int c = 0; c < sc.comps_in_scan; c++)
+    if (sc.component_index[c] != c) return fail(MJH_EINVAL, "lossless scan: component order (JERR_BAD_SCAN_SCRIPT)");
+  if (p->compress_profile != MJH_PROFILE_FASTEST)
+    return fail(MJH_EUNSUPPORTED, "lossless mode in the max-compression profile: the reference writes a DQT and an empty DHT marker there (emit_multi_dqt / emit_multi_dht, jcmarker.c:189-254, :293-401), a file without Huffman tables");
+  const bool gray = p->input_components == 1 && p->num_components == 1;
+  const bool rgb = p->input_components == 3 && p->num_components == 3 && p->color_transform == MJH_COLOR_NONE;
+  if (!gray && !rgb)
+    return fail(MJH_EUNSUPPORTED, "lossless mode codes grayscale input as grayscale and RGB input as RGB (color_transform MJH_COLOR_NONE): any other colour conversion is lossy (JERR_CONVERSION_NOTIMPL, jccolor.c:605-640)");
+  for (int c = 0; c < p->num_components; c++)
+    if (p->dc_tbl_no[c] != 0)
+      return fail(MJH_EUNSUPPORTED, "dc_tbl_no[%d] = %d: the reference's SOS names DC table 0 for every component of a lossless scan (jcmarker.c:516)", c, p->dc_tbl_no[c]);
+  const int W = p->image_width, H = p->image_height;
+  long ri = p->restart_interval;
+  if (p->restart_in_rows > 0) { ri = (long)p->restart_in_rows * W; if (ri > 65535L) ri = 65535L; }   // per_scan_setup jcmaster.c:595-600
+  if (ri % W != 0)
+    return fail(MJH_EINVAL, "Invalid restart interval %ld; must be an integer multiple of the number of MCUs in an MCU row (%d) (JERR_BAD_RESTART, jclossls.c:289-294)", ri, W);
+  const int px = p->input_pixel_size ? p->input_pixel_size : p->input_components;
+  int off[3] = { 0, 0, 0 };
+  if (rgb) {
+    off[0] = p->rgb_offset[0]; off[1] = p->rgb_offset[1]; off[2] = p->rgb_offset[2];
+    if (!off[0] && !off[1] && !off[2]) { off[1] = 1; off[2] = 2; }
+  }
+  for (int c = 0; c < p->num_components; c++)
+    if (off[c] < 0 || off[c] >= px) return fail(MJH_EINVAL, "sample offset %d outside a %d-sample pixel", off[c], px);
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(MJH_EHIP, "no HIP device available: libmozjpeg_hip has no CPU fallback");
+  if (device < 0 || device >= ndev) return fail(MJH_EINVAL, "device %d out of range (%d devices)", device, ndev);
+  mjh_encoder *e = new mjh_encoder();
+  e->p_created = *p;
+  e->p = *p;
+  mjh_params &q = e->p;      // jcmaster.c:1067-1094
+  for (int c = 0; c < MJH_MAX_COMPS; c++) q.h_samp_factor[c] = q.v_samp_factor[c] = 1;
+  q.smoothing_factor = 0;
+  q.optimize_coding = 1;
+  q.data_precision = P;
+  e->lossless = true;
+  e->device = device;
+  e->max_batch = max_batch;
+  e->high_priority_streams = g_create_twin;
+  MjhConst &C = e->C;
+  memset(&C, 0, sizeof(C));
+  C.W = W; C.H = H; C.in_comps = p->input_components; C.ncomp = p->num_components; C.px_size = px;
+  C.precision = P; C.restart_interval = (int)ri; C.maxh = C.maxv = 1;
+  for (int c = 0; c < C.ncomp; c++) { C.c[c].h = C.c[c].v = 1; C.c[c].pw = W; C.c[c].ph = H; }
+  LlConst &L = e->L;
+  L.W = W; L.H = H; L.ncomp = C.ncomp; L.px_size = px;
+  for (int c = 0; c < 3; c++) L.off[c] = off[c];
+  L.precision = P; L.psv = psv; L.pt = pt;
+  L.init_pred = 1 << (P - pt - 1);
+  L.rows_per_seg = (int)(ri / W);
+  L.nseg = L.rows_per_seg ? (H + L.rows_per_seg - 1) / L.rows_per_seg : 1;
+  L.units_x = (W + LL_UNIT - 1) / LL_UNIT;
+  L.units = L.units_x * H;
+  e->nseg = L.nseg;
+  HIPCHK_E(hipSetDevice(device));
+  HIPCHK_E(make_streams(e));      // (the twin's streams keep off the primary's hardware queues, as for every encoder)
+  HIPCHK_E(hipStreamCreateWithPriority(&e->copy_stream, hipStreamNonBlocking, 0));
+  for (hipEvent_t *ev : { &e->ev_done, &e->ev_tier1, &e->copy_done, &e->ev_fork, &e->ev_join })
+    HIPCHK_E(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+  if (const char *v = getenv("MJH_INFLIGHT")) { e->inflight = atoi(v); if (e->inflight < 1 || e->inflight > 2) e->inflight = 2; }
+  const size_t B = (size_t)max_batch;
+  e->pix_image_bytes = (size_t)W * H * px * (P > 8 ? 2 : 1);
+  // Budget per sample, for the scan as a whole (one sample alone can exceed it: PSV 4..7 reach category P + 1 -- 8-bit Ra = Rb = 255,
+  // Rc = 0, sample 0 gives -510 -- with a code of up to 16 bits).  A difference has at most P + 1 value bits (16-bit: at most 15, the
+  // 32768 of category 16 sends none), and the table is an optimal code for the image's own histogram over at most P + 2 categories
+  // plus the reserved symbol: its average length stays within a bit of the entropy, <= log2(P + 3) + 1 (+ the small cost of the
+  // 16-bit length limit), so the average sample costs at most P + 1 + log2(P + 3) + 2 bits: 14.5 / 18.9 / 22.2 at P = 8 / 12 / 16,
+  // under `per` = 17 / 25 / 31.  (k_ll_scan still checks the total against the buffer and reports MJH_ETOOSMALL before writing.)
+  const unsigned long long per = (unsigned long long)(P + 1 < 16 ? P + 1 : 16) + (P < 16 ? P : 15);
+  unsigned long long words = ((unsigned long long)W * H * C.ncomp * per + (unsigned long long)L.nseg * 24ull) / 32ull + 64ull;
+  if (words > (1ull << 27)) words = 1ull << 27;   // bit offsets are 32-bit (larger scans are reported by k_ll_scan)
+  e->stream_words = (size_t)((words + 63ull) & ~63ull);
+  e->ff_chunks = (int)((e->stream_words + 2047) / 2048);
+  e->spi = SLOTS_BASE;
+  HIPCHK_E(mjh_dmalloc((void **)&e->d_tabs, B * e->spi * sizeof(MjhHuffTable)));
+  HIPCHK_E(mjh_dmalloc((void **)&e->d_ll_hist, B * (size_t)L.units * 17 * 4));
+  HIPCHK_E(mjh_dmalloc((void **)&e->d_ll_len, B * (size_t)L.units * 4));
+  HIPCHK_E(mjh_dmalloc((void **)&e->d_ll_off, B * (size_t)L.units * 4));
+  HIPCHK_E(mjh_dmalloc((void **)&e->d_ll_segE, B * (size_t)L.nseg * 4));
+  HIPCHK_E(mjh_dmalloc((void **)&e->d_mpos, B * (size_t)L.nseg * 4));
+  HIPCHK_E(mjh_dmalloc((void **)&e->d_totals, B * sizeof(unsigned)));
+  HIPCHK_E(mjh_dmalloc((void **)&e->d_fftotals, B * sizeof(unsigned)));
+  HIPCHK_E(mjh_dmalloc((void **)&e->d_ffsums, B * e->ff_chunks * sizeof(unsigned)));
+  HIPCHK_E(mjh_dmalloc((void **)&e->d_stream, B * e->stream_words * 4 + 4096));
+  e->out_stride = ((size_t)2048 + e->stream_words * 8 + 255) & ~(size_t)255;   // (stuffing at most doubles the bytes)
+  HIPCHK_E(mjh_dmalloc((void **)&e->d_out, B * e->out_stride));
+  HIPCHK_E(mjh_dmalloc((void **)&e->d_sizes, B * sizeof(unsigned)));
+  HIPCHK_E(mjh_dmalloc(&e->d_meta, B * sizeof(MjhImageMeta)));
+  e->h_sizes.resize(B);
+  {
+    std::vector<uint8_t> pre, sos;
+    pre.push_back(0xFF); pre.push_back(0xD8);                  // SOI
+    if (q.write_JFIF_header) {                                  // emit_jfif_app0 jcmarker.c:534-565
+      pre.push_back(0xFF); pre.push_back(0xE0); put2(pre, 16);
+      const uint8_t jf[] = { 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0 };
+      pre.insert(pre.end(), jf, jf + sizeof(jf));
+    }
+    if (rgb) {                                                  // emit_adobe_app14: transform 0 (JCS_RGB writes the Adobe marker, jcparam.c:609)
+      const uint8_t ad[] = { 0xFF, 0xEE, 0, 14, 'A', 'd', 'o', 'b', 'e', 0, 100, 0, 0, 0, 0, 0 };
+      pre.insert(pre.end(), ad, ad + sizeof(ad));
+    }
+    e->file_hdr_len = (int)pre.size();
+    pre.push_back(0xFF); pre.push_back(0xC3);                  // SOF3, emit_sof jcmarker.c:464-490
+    put2(pre, 3 * C.ncomp + 2 + 5 + 1);
+    pre.push_back((uint8_t)P);
+    put2(pre, H); put2(pre, W);
+    pre.push_back((uint8_t)C.ncomp);
+    for (int c = 0; c < C.ncomp; c++) { pre.push_back((uint8_t)q.component_id[c]); pre.push_back(0x11); pre.push_back((uint8_t)q.quant_tbl_no[c]); }
+    if (ri) { sos.push_back(0xFF); sos.push_back(0xDD); put2(sos, 4); put2(sos, (int)ri); }   // emit_dri
+    sos.push_back(0xFF); sos.push_back(0xDA);                  // emit_sos jcmarker.c:494-526
+    put2(sos, 2 * C.ncomp + 2 + 1 + 3);
+    sos.push_back((uint8_t)C.ncomp);
+    for (int c = 0; c < C.ncomp; c++) { sos.push_back((uint8_t)q.component_id[c]); sos.push_back(0); }
+    sos.push_back((uint8_t)L.psv); sos.push_back(0); sos.push_back((uint8_t)L.pt);
+    e->prefix_len = (int)pre.size(); e->sos_len = (int)sos.size();
+    HIPCHK_E(mjh_dmalloc((void **)&e->d_prefix, pre.size()));
+    HIPCHK_E(mjh_dmalloc((void **)&e->d_sos, sos.size()));
+    HIPCHK_E(hipMemcpy(e->d_prefix, pre.data(), pre.size(), hipMemcpyHostToDevice));
+    HIPCHK_E(hipMemcpy(e->d_sos, sos.data(), sos.size(), hipMemcpyHostToDevice));
+  }
+  e->dht_slots[0] = SLOT_FINAL; e->dht_ids[0] = 0x00; e->ndht = 1;   // emit_dht jcmarker.c:257-290: DC table 0
+  HIPCHK_E(hipDeviceSynchronize());
+  *out = e;
+  return MJH_OK;
+}
+
+static int run_lossless(mjh_encoder *e, const void *d_pixels, size_t row_pitch, size_t image_stride, int n, hipStream_t s,
+                        hipEvent_t input_read, hipEvent_t before_output)
+{
+  e->sizes_valid = false;
+  e->last_n = n;
+  e->res_buf = -1;
+  e->coef_input = false;
+  e->last_stream = s;
+  if (!e->owner) e->last = nullptr;
+  Prof pr{ e, s };
+  if (e->profiling && e->prof_calls < 256) {
+    pr.enabled = true;
+    pr.first_call = e->prof_calls == 0;
+    if (pr.first_call) e->prof_names.clear();
+    pr.next = (size_t)e->prof_calls * e->prof_per_call;
+  }
+  const LlConst &L = e->L;
+  const int slot = SLOT_FINAL;
+  HIPCHK(hipMemsetAsync(e->d_tabs, 0, (size_t)n * e->spi * sizeof(MjhHuffTable), s));
+  HIPCHK(hipMemsetAsync(e->d_meta, 0, (size_t)n * sizeof(MjhImageMeta), s));
+  auto ll = [&](int phase) {
+    mjh_launch_ll(L, d_pixels, row_pitch, image_stride, e->d_tabs, e->spi, slot, e->d_ll_hist, e->d_ll_len, e->d_ll_off, e->d_ll_segE, e->d_mpos,
+                  e->d_totals, e->d_stream, e->stream_words, n, s, phase);
+  };
+  pr.mark("ll_stats");
+  ll(0);
+  pr.mark("gen_tables");
+  mjh_launch_gen_tables(e->d_tabs, e->spi, &slot, 1, n, s);
+  pr.mark("ll_len");
+  ll(1);
+  pr.mark("ll_write");
+  ll(2);
+  mjh_launch_finish_bits(e->d_totals, e->d_stream, e->stream_words, e->d_meta, n, s);   // (the last byte padded with 1-bits, flush_bits jclhuff.c)
+  if (input_read) HIPCHK(hipEventRecord(input_read, s));
+  if (before_output) HIPCHK(hipStreamWaitEvent(s, before_output, 0));
+  pr.mark("header");
+  mjh_launch_header(e->d_prefix, e->prefix_len, e->d_sos, e->sos_len, e->d_tabs, e->spi, e->dht_slots, e->dht_ids, e->ndht, 0,
+                    e->d_out, e->out_stride, e->d_meta, n, s);
+  pr.mark("byte_stuff");
+  mjh_launch_stuff(e->d_stream, e->stream_words, e->d_totals, e->d_ffsums, e->ff_chunks, e->d_fftotals, e->d_out, e->out_stride,
+                   e->d_meta, e->d_sizes, e->d_mpos, L.nseg, n, s);
+  pr.mark(nullptr);
+  pr.finish();
+  HIPCHK(hipGetLastError());
   return MJH_OK;
 }

@@ -2554,6 +2554,11 @@ void mjh_launch_header(const void *prefix, int prefix_len, const void *sos, int 
                      plan, ndht, multi_dht, (uint8_t *)out, out_stride, (MjhImageMeta *)meta, append_sizes);
 }
 
+void mjh_launch_finish_bits(unsigned *totals, unsigned *stream, size_t stream_words_per_image, void *meta, int n, hipStream_t s)
+{
+  hipLaunchKernelGGL(k_finish_bits, dim3((n + 63) / 64), dim3(64), 0, s, totals, (const unsigned *)nullptr, stream, stream_words_per_image, (MjhImageMeta *)meta, n);
+}
+
 void mjh_launch_stuff(const unsigned *stream, size_t stream_words_per_image, const unsigned *totals, unsigned *ffsums, int ff_chunks_per_image,
                       unsigned *ff_totals, void *out, size_t out_stride, void *meta, unsigned *sizes, const unsigned *mpos, int nseg, int n, hipStream_t s)
 {

@@ -39,6 +39,8 @@ void mjh_launch_encode(const MjhConst &C, const void *q, const unsigned long lon
                        int n, hipStream_t s);
 void mjh_launch_header(const void *prefix, int prefix_len, const void *sos, int sos_len, const MjhHuffTable *tabs, int spi,
                        const int dht_slots[8], const int dht_ids[8], int ndht, int multi_dht, void *out, size_t out_stride, void *meta, int n, hipStream_t s, const unsigned *append_sizes = nullptr);   // append_sizes: write over the EOI of the files so far (later scans of a sequential script)
+// the final pad of a scan whose totals[] include everything (no restart extras on top); totals 0xFFFFFFFF: the offset-range sentinel
+void mjh_launch_finish_bits(unsigned *totals, unsigned *stream, size_t stream_words_per_image, void *meta, int n, hipStream_t s);
 void mjh_launch_stuff(const unsigned *stream, size_t stream_words_per_image, const unsigned *totals, unsigned *ffsums, int ff_chunks_per_image,
                       unsigned *ff_totals, void *out, size_t out_stride, void *meta, unsigned *sizes, const unsigned *mpos, int nseg, int n, hipStream_t s);
 void mjh_launch_pack_results(const void *out, size_t out_stride, const unsigned *sizes, const void *meta, const void *prog_ctl, int n,

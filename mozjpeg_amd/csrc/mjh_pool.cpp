@@ -113,7 +113,7 @@ extern "C" int mjh_pool_encode_host(mjh_pool *pl, const void *pixels, size_t row
 {
   if (!pl || !pixels || n < 1 || !jpegs || !sizes) return mjh_internal_fail(MJH_EINVAL, "mjh_pool_encode_host: bad arguments");
   const mjh_params *p = mjh_encoder_params(pl->enc[0]);
-  const size_t row_bytes = (size_t)p->image_width * (p->input_components == 1 ? 1 : (p->input_pixel_size ? p->input_pixel_size : 3)) * (p->data_precision == 12 ? 2 : 1);
+  const size_t row_bytes = (size_t)p->image_width * (p->input_components == 1 ? 1 : (p->input_pixel_size ? p->input_pixel_size : 3)) * (p->data_precision > 8 ? 2 : 1);
   if (row_pitch < row_bytes) { pl->error = "row_pitch smaller than one row"; return mjh_internal_fail(MJH_EINVAL, pl->error.c_str()); }
   if (n > 1 && image_stride < row_pitch * (size_t)(p->image_height - 1) + row_bytes) {
     pl->error = "image_stride smaller than one image: images would overlap";

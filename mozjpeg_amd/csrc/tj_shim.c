@@ -13,7 +13,8 @@
  * density.  Exactly these are mapped onto mjh_params; the output is the byte stream the reference TurboJPEG produces.
  * The LEGACY tjCompress2 selects the fast DCT (JDCT_IFAST, jfdctfst.c) unless quality >= 96 or TJFLAG_ACCURATEDCT is given
  * (processFlags turbojpeg.c:522-527), the 3.x API through TJPARAM_FASTDCT: mjh_params.dct_method, coded bit-exactly like the
- * accurate one, 8- and 12-bit samples.  Outside the GPU path (an ERROR, never a CPU fallback): CMYK / YCCK, lossless.
+ * accurate one, 8- and 12-bit samples; lossless mode (TJPARAM_LOSSLESS*, 8 / 12 / 16 bits, tj3Compress16).  Outside the GPU path (an
+ * ERROR, never a CPU fallback): CMYK / YCCK.
  */
 #define _GNU_SOURCE
 #include <dlfcn.h>
@@ -32,7 +33,7 @@ typedef struct tjs {
   unsigned magic;
   struct tjs *self;
   /* TJPARAM_* state (tj3Set / legacy arguments) */
-  int quality, subsamp, bottom_up, no_realloc, fast_dct, optimize, progressive, arithmetic, lossless, colorspace;
+  int quality, subsamp, bottom_up, no_realloc, fast_dct, optimize, progressive, arithmetic, lossless, lossless_psv, lossless_pt, colorspace;
   int restart_blocks, restart_rows, xdensity, ydensity, density_units, stop_on_warning, precision;
   int jpeg_width, jpeg_height;
   /* one cached encoder (a handle is used by one thread at a time, like a tjinstance) */
@@ -65,6 +66,7 @@ static int fail(tjs *t, const char *fn, const char *msg)
 static void defaults(tjs *t)
 { /* tj3Init turbojpeg.c:540-600 */
   t->quality = -1; t->subsamp = TJSAMP_UNKNOWN; t->colorspace = -1; t->precision = 8;
+  t->lossless_psv = 1; t->lossless_pt = 0;   /* turbojpeg.c:560 */
   t->xdensity = 1; t->ydensity = 1; t->density_units = 0;
   t->jpeg_width = t->jpeg_height = -1;
 }
@@ -215,7 +217,8 @@ DLLEXPORT int tj3Set(tjhandle handle, int param, int value)
   case TJPARAM_SCANLIMIT: break;
   case TJPARAM_ARITHMETIC: RANGE(0, 1); t->arithmetic = value; break;
   case TJPARAM_LOSSLESS: RANGE(0, 1); t->lossless = value; break;
-  case TJPARAM_LOSSLESSPSV: case TJPARAM_LOSSLESSPT: break;
+  case TJPARAM_LOSSLESSPSV: RANGE(1, 7); t->lossless_psv = value; break;     /* turbojpeg.c:750-758 */
+  case TJPARAM_LOSSLESSPT: RANGE(0, 15); t->lossless_pt = value; break;
   case TJPARAM_RESTARTBLOCKS: RANGE(0, 65535); t->restart_blocks = value; if (value) t->restart_rows = 0; break;
   case TJPARAM_RESTARTROWS: RANGE(0, 65535); t->restart_rows = value; if (value) t->restart_blocks = 0; break;
   case TJPARAM_XDENSITY: RANGE(1, 65535); t->xdensity = value; break;
@@ -250,6 +253,8 @@ DLLEXPORT int tj3Get(tjhandle handle, int param)
   case TJPARAM_PROGRESSIVE: return t->progressive;
   case TJPARAM_ARITHMETIC: return t->arithmetic;
   case TJPARAM_LOSSLESS: return t->lossless;
+  case TJPARAM_LOSSLESSPSV: return t->lossless_psv;
+  case TJPARAM_LOSSLESSPT: return t->lossless_pt;
   case TJPARAM_RESTARTBLOCKS: return t->restart_blocks;
   case TJPARAM_RESTARTROWS: return t->restart_rows;
   case TJPARAM_XDENSITY: return t->xdensity;
@@ -263,7 +268,32 @@ DLLEXPORT int tj3Get(tjhandle handle, int param)
 static int build_params(tjs *t, const char *fn, int width, int height, int pixelFormat, int precision, mjh_params *p)
 {
   int subsamp = t->subsamp, gray_out, in_comps = 3;
-  if (t->lossless) return fail(t, fn, "lossless mode is outside the GPU path (no CPU fallback)");
+  if (t->lossless) {
+    /* setCompDefaults turbojpeg.c:346-355: jpeg_enable_lossless and nothing of quality / subsampling / colour space; at
+     * jpeg_start_compress jcmaster.c:1067-1080 re-applies jpeg_default_colorspace: gray pixels -> a gray file, RGB-family pixels
+     * -> a JCS_RGB file ('R' 'G' 'B', Adobe marker); lossless = a one-scan script with Ss = PSV, Al = Pt (mozjpeg_hip.h) */
+    int i;
+    if (pixelFormat == TJPF_CMYK) return fail(t, fn, "CMYK / YCCK are outside the GPU path (no CPU fallback)");
+    in_comps = pixelFormat == TJPF_GRAY ? 1 : 3;
+    if (mjh_params_defaults(p, width, height, in_comps, in_comps == 1, MJH_PROFILE_FASTEST, 1, 1) != MJH_OK) return fail(t, fn, mjh_last_error());
+    if (in_comps == 3) {
+      p->input_pixel_size = kPixelSize[pixelFormat];
+      p->rgb_offset[0] = kRed[pixelFormat]; p->rgb_offset[1] = kGreen[pixelFormat]; p->rgb_offset[2] = kBlue[pixelFormat];
+      p->color_transform = MJH_COLOR_NONE;
+      p->write_JFIF_header = 0;
+      for (i = 0; i < 3; i++) { p->component_id[i] = "RGB"[i]; p->quant_tbl_no[i] = p->dc_tbl_no[i] = p->ac_tbl_no[i] = 0; p->h_samp_factor[i] = p->v_samp_factor[i] = 1; }
+    }
+    p->num_scans = 1;
+    p->scan_info[0].comps_in_scan = in_comps;
+    for (i = 0; i < in_comps; i++) p->scan_info[0].component_index[i] = i;
+    p->scan_info[0].Ss = t->lossless_psv; p->scan_info[0].Se = 0; p->scan_info[0].Ah = 0; p->scan_info[0].Al = t->lossless_pt;
+    p->data_precision = precision;
+    p->restart_interval = (unsigned)t->restart_blocks;
+    p->restart_in_rows = t->restart_rows;
+    /* (TJPARAM_ARITHMETIC / _OPTIMIZE / _PROGRESSIVE are applied behind the lossless return of setCompDefaults: no effect) */
+    return 0;
+  }
+  if (precision == 16) return fail(t, fn, "16-bit data precision requires lossless JPEG");   /* (jcmaster.c:197-202) */
   if (pixelFormat == TJPF_CMYK || t->colorspace == TJCS_CMYK || t->colorspace == TJCS_YCCK) return fail(t, fn, "CMYK / YCCK are outside the GPU path (no CPU fallback)");
   if (pixelFormat == TJPF_GRAY) in_comps = 1;
   gray_out = t->colorspace == TJCS_GRAY || (t->colorspace < 0 && subsamp == TJSAMP_GRAY) || in_comps == 1;
@@ -344,19 +374,19 @@ static int compress_pixels(tjs *t, const char *fn, const void *srcBuf, int width
   int y;
   if (srcBuf == NULL || width <= 0 || pitch < 0 || height <= 0 || pixelFormat < 0 || pixelFormat >= TJ_NUMPF || jpegBuf == NULL || jpegSize == NULL)
     return fail(t, fn, "Invalid argument");
-  if (t->quality == -1) return fail(t, fn, "TJPARAM_QUALITY must be specified");
-  if (t->subsamp == TJSAMP_UNKNOWN) return fail(t, fn, "TJPARAM_SUBSAMP must be specified");
+  if (!t->lossless && t->quality == -1) return fail(t, fn, "TJPARAM_QUALITY must be specified");       /* turbojpeg-mp.c:89-92 */
+  if (!t->lossless && t->subsamp == TJSAMP_UNKNOWN) return fail(t, fn, "TJPARAM_SUBSAMP must be specified");
   if (build_params(t, fn, width, height, pixelFormat, precision, &p) || get_encoder(t, fn, &p)) return -1;
-  row_bytes = (size_t)width * kPixelSize[pixelFormat] * (precision == 12 ? 2 : 1);
+  row_bytes = (size_t)width * kPixelSize[pixelFormat] * (precision > 8 ? 2 : 1);
   if (pitch == 0) pitch = width * kPixelSize[pixelFormat];
   if (mjh_host_staging(t->enc, &stage, &cap) != MJH_OK || cap < row_bytes * (size_t)height) return fail(t, fn, mjh_last_error());
-  for (y = 0; y < height; y++) {   /* pitch counts SAMPLES (turbojpeg.h): bytes for 8-bit, 2-byte units for 12-bit */
-    const size_t src_row = (size_t)(t->bottom_up ? height - 1 - y : y) * (size_t)pitch * (precision == 12 ? 2 : 1);
+  for (y = 0; y < height; y++) {   /* pitch counts SAMPLES (turbojpeg.h): bytes for 8-bit, 2-byte units for 12- and 16-bit */
+    const size_t src_row = (size_t)(t->bottom_up ? height - 1 - y : y) * (size_t)pitch * (precision > 8 ? 2 : 1);
     memcpy((unsigned char *)stage + (size_t)y * row_bytes, (const unsigned char *)srcBuf + src_row, row_bytes);
   }
   if (mjh_encode_host(t->enc, stage, row_bytes, row_bytes * (size_t)height, 1) != MJH_OK) return fail(t, fn, mjh_last_error());
   t->jpeg_width = width; t->jpeg_height = height; t->precision = precision;
-  return deliver(t, fn, jpegBuf, jpegSize, tj3JPEGBufSize(width, height, t->subsamp));
+  return deliver(t, fn, jpegBuf, jpegSize, tj3JPEGBufSize(width, height, t->lossless ? (pixelFormat == TJPF_GRAY ? TJSAMP_GRAY : TJSAMP_444) : t->subsamp));
 }
 
 DLLEXPORT int tj3Compress8(tjhandle handle, const unsigned char *srcBuf, int width, int pitch, int height, int pixelFormat,
@@ -381,6 +411,19 @@ DLLEXPORT int tj3Compress12(tjhandle handle, const short *srcBuf, int width, int
     return f && handle ? f(handle, srcBuf, width, pitch, height, pixelFormat, jpegBuf, jpegSize) : fail(NULL, "tj3Compress12", "Invalid handle");
   }
   return compress_pixels(t, "tj3Compress12", srcBuf, width, pitch, height, pixelFormat, 12, jpegBuf, jpegSize);
+}
+
+/* 16-bit samples: lossless mode only (turbojpeg-mp.c built with BITS_IN_JSAMPLE 16) */
+DLLEXPORT int tj3Compress16(tjhandle handle, const unsigned short *srcBuf, int width, int pitch, int height, int pixelFormat,
+                            unsigned char **jpegBuf, size_t *jpegSize)
+{
+  tjs *t = ours(handle);
+  if (!t) {
+    int (*f)(tjhandle, const unsigned short *, int, int, int, int, unsigned char **, size_t *) =
+      (int (*)(tjhandle, const unsigned short *, int, int, int, int, unsigned char **, size_t *))next_sym("tj3Compress16");
+    return f && handle ? f(handle, srcBuf, width, pitch, height, pixelFormat, jpegBuf, jpegSize) : fail(NULL, "tj3Compress16", "Invalid handle");
+  }
+  return compress_pixels(t, "tj3Compress16", srcBuf, width, pitch, height, pixelFormat, 16, jpegBuf, jpegSize);
 }
 
 static void legacy_flags(tjs *t, int flags)
