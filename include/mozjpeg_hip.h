@@ -75,14 +75,18 @@ typedef struct {
   /* 0 = one sequential scan (baseline).  A script whose first scan has Ss != 0 and Se == 0 is a LOSSLESS file (SOF3), as
    * validate_script decides (jcmaster.c:300-310) and as jpeg_enable_lossless leaves the object (cinfo->Ss = PSV, Se = 0, Ah = 0,
    * Al = Pt, jcparam.c:1016-1040): one scan of every component in order, Ss = the predictor 1..7, Ah = 0, Al = the point
-   * transform 0..precision-1 (else JERR_BAD_PROGRESSION).  The encoder applies jcmaster.c's overrides itself (1x1 sampling, no
+   * transform 0..precision-1 (else JERR_BAD_PROGRESSION) -- or a lossless script of several scans, whatever validate_script
+   * accepts for 1 or 3 components (jcmaster.c:332-347, :390-416, :432-436): every component in exactly one scan, the components
+   * of a scan in frame order, and PER SCAN Ss = its predictor 1..7, Se = Ah = 0, Al = its point transform < precision; the file
+   * is SOF3, then per scan a DHT of table 0 made from that scan's statistics alone and its SOS (the DRI in front of the first
+   * SOS only).  A script the reference refuses is MJH_EINVAL with its reason in the text (JERR_BAD_SCAN_SCRIPT,
+   * JERR_BAD_PROG_SCRIPT, JERR_MISSING_DATA, with its entry number).  The encoder applies jcmaster.c's overrides itself (1x1 sampling, no
    * smoothing, optimal tables: jcmaster.c:1067-1094) and writes no DQT.  Input is grayscale (input_components 1) or an RGB-family
    * layout coded as JCS_RGB (color_transform MJH_COLOR_NONE), every component with dc_tbl_no 0 (the reference's SOS names table 0
    * for every component of a lossless scan, jcmarker.c:516), in the fastest profile (the max-compression profile writes a DQT and
    * an empty DHT, jcmarker.c:189-254, :293-401), without trellis quantization (JERR_BAD_BUFFER_MODE) or arithmetic coding.
    * data_precision 8, 12 or 16 (16: lossless only; 12 / 16: uint16 samples, row_pitch / image_stride in BYTES).  Restart intervals
-   * must be whole rows (JERR_BAD_RESTART, jclossls.c:289-294).  Lossless scripts of several scans are refused (one interleaved
-   * scan here).  The planes / coefficient entry points return MJH_EINVAL for a lossless encoder. */
+   * must be whole rows of the image in every scan (JERR_BAD_RESTART, jclossls.c:289-294).  The planes / coefficient entry points return MJH_EINVAL for a lossless encoder. */
   int num_scans;
   mjh_scan scan_info[MJH_MAX_SCANS];
   int optimize_scans;
@@ -336,7 +340,8 @@ enum {
   MJH_TAP_HUFF_VALS = 6, /* uint8  [4][256]                                                  */
   MJH_TAP_PROG_SCAN_US = 7, /* uint32 [2][64] progressive: microseconds the statistics [0] / encode [1]
                               workgroup of each scan-script entry ran (0 = not run)              */
-  MJH_TAP_LL_COUNTS = 8  /* uint32 [17] lossless: symbol histogram (difference categories 0..16) of the table */
+  MJH_TAP_LL_COUNTS = 8  /* uint32 [17] lossless: symbol histogram (difference categories 0..16) of the table (a script of several
+                            scans: of the LAST scan's table, the one the object holds as DC table 0 afterwards; so MJH_TAP_HUFF_BITS / VALS) */
 };
 int mjh_set_debug_taps(mjh_encoder *e, int on);
 int mjh_read_tap(mjh_encoder *e, int what, int image, int component, void *dst, size_t cap, size_t *size);

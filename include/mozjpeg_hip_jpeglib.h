@@ -10,6 +10,13 @@
  *                  replaces jcapistd.c:90   (declared jpeglib.h:1067)
  *   JDIMENSION jpeg12_write_scanlines(j_compress_ptr cinfo, J12SAMPARRAY scanlines, JDIMENSION num_lines);
  *                  the 12-bit twin (declared jpeglib.h:1070): rows of 16-bit samples, data_precision 12
+ *   JDIMENSION jpeg16_write_scanlines(j_compress_ptr cinfo, J16SAMPARRAY scanlines, JDIMENSION num_lines);
+ *                  the 16-bit twin (lossless mode only): data_precision 16
+ *                  Lossless mode (SOF3): an object on which jpeg_enable_lossless was called, or whose scan_info starts with
+ *                  Ss != 0, Se == 0 (validate_script jcmaster.c:302-311), is coded by the lossless encoder, scripts of several
+ *                  scans included; jpeg_start_compress leaves the object as jinit_c_master_control does (jcmaster.c:1067-1094:
+ *                  no raw data, no smoothing, jpeg_default_colorspace, 1x1 sampling, optimal tables), and what the reference
+ *                  refuses there is refused with its error code and message.
  *   void       jpeg_finish_compress(j_compress_ptr cinfo);
  *                  replaces jcapimin.c:176  (declared jpeglib.h:1076)
  *   JDIMENSION jpeg_write_raw_data(j_compress_ptr cinfo, JSAMPIMAGE data, JDIMENSION num_lines);

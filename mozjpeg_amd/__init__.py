@@ -144,7 +144,9 @@ def make_params(width, height, *, quality=75, baseline=False, revert=False, opti
     `revert` this is cjpeg's default: progressive with scan search (`fastcrush`: fixed 9-scan script).
     lossless=(psv, pt): lossless JPEG (SOF3, cjpeg -lossless psv,Pt / jpeg_enable_lossless) with what jpeg_default_colorspace
     makes of the input -- grayscale stays grayscale, RGB becomes a JCS_RGB file (`gray` has no effect, jcmaster.c:1067-1080);
-    precision 8, 12 or 16 (12 / 16: uint16 samples)."""
+    precision 8, 12 or 16 (12 / 16: uint16 samples).  With `lossless`, scans=[(components, psv, 0, 0, pt), ...] is a lossless script
+    (cjpeg -lossless 1 -scans FILE): every component in exactly one scan, each scan with its own predictor and point transform;
+    the (psv, pt) of `lossless` itself then only switches the mode on, as in the reference."""
     p = Params()
     L = lib()
     per_comp = isinstance(sample[0], (tuple, list))      # ((h, v) of Y, (h, v) of Cb, (h, v) of Cr): cjpeg -sample HxV,HxV,HxV
@@ -245,9 +247,11 @@ def make_params(width, height, *, quality=75, baseline=False, revert=False, opti
         else:
             _chk(L.mjh_params_search_progression(C.byref(p)))
     if scans is not None:      # cjpeg -scans: [(component indices, Ss, Se, Ah, Al), ...] replaces the script, no scan search
+        if len(scans) > MAX_SCANS:
+            raise ValueError("a script of %d scans (at most %d)" % (len(scans), MAX_SCANS))
         p.optimize_scans = 0
         p.num_scans = len(scans)
-        if not (scans[0][1] == 0 and scans[0][2] == 63):
+        if lossless is None and not (scans[0][1] == 0 and scans[0][2] == 63):
             p.optimize_coding = 1          # a progressive script forces optimal tables (jcmaster.c:1091-1094)
         for i, (comps, ss, se, ah, al) in enumerate(scans):
             p.scan_info[i].comps_in_scan = len(comps)

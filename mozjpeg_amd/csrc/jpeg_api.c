@@ -8,7 +8,7 @@
  * jpeg_error_mgr ... are ABI; the message texts come from that tree's jerror.h the way its own jerror.c gets them).
  * Each entry point cites the reference function whose behaviour it keeps.
  *
- * Not provided (this is the compress half): the decompressor, lossless mode, arithmetic coding, backing-store files
+ * Not provided (this is the compress half): the decompressor, backing-store files
  * of the memory manager (virtual arrays always live in memory).  The decompress symbols an unchanged cjpeg binary
  * references (it can read JPEG input files) exist as stubs that raise JERR_NOT_COMPILED.
  */
@@ -685,7 +685,7 @@ void jpeg_set_defaults(j_compress_ptr cinfo)
 }
 
 void jpeg_enable_lossless(j_compress_ptr cinfo, int predictor_selection_value, int point_transform)
-{ /* jcparam.c:1013-1040: accepted, refused at jpeg_start_compress (the GPU path has no lossless coder) */
+{ /* jcparam.c:1013-1040; jpeg_start_compress routes the object to the lossless encoder (jpeg_shim.c: capture_lossless) */
   NEED_START(cinfo);
   cinfo->master->lossless = TRUE;
   cinfo->Ss = predictor_selection_value; cinfo->Se = 0; cinfo->Ah = 0; cinfo->Al = point_transform;
@@ -1016,7 +1016,7 @@ void jpeg_copy_critical_parameters(const j_decompress_ptr srcinfo, j_compress_pt
 
 /* =====================================================================================================================
  * what this library does not do.  An unchanged cjpeg is linked with immediate binding, so every symbol it names must
- * exist; the ones of the decompressor (cjpeg can take a JPEG file as input) and of 16-bit lossless input raise
+ * exist; the ones of the decompressor (cjpeg can take a JPEG file as input) raise
  * JERR_NOT_COMPILED when they are actually called.
  * ===================================================================================================================== */
 #ifdef MJH_STANDALONE
@@ -1036,5 +1036,4 @@ void jpeg_save_markers(j_decompress_ptr cinfo, int marker_code, unsigned int len
 void jpeg_stdio_src(j_decompress_ptr cinfo, FILE *infile) { (void)infile; not_here((j_common_ptr)cinfo, "jpeg_stdio_src"); }
 void jpeg_mem_src(j_decompress_ptr cinfo, const unsigned char *inbuffer, unsigned long insize) { (void)inbuffer; (void)insize; not_here((j_common_ptr)cinfo, "jpeg_mem_src"); }
 jvirt_barray_ptr *jpeg_read_coefficients(j_decompress_ptr cinfo) { not_here((j_common_ptr)cinfo, "jpeg_read_coefficients"); return NULL; }
-JDIMENSION jpeg16_write_scanlines(j_compress_ptr cinfo, J16SAMPARRAY scanlines, JDIMENSION num_lines) { (void)scanlines; (void)num_lines; not_here((j_common_ptr)cinfo, "jpeg16_write_scanlines (lossless mode)"); return 0; }
 #endif

@@ -411,7 +411,8 @@ static void tw_htbl_body(j_compress_ptr cinfo, JHUFF_TBL *h, int id, int nvals)
 /* the tables in front of one scan's SOS: comps in scan order */
 static void tw_scan_tables(j_compress_ptr cinfo, jpeg_component_info *const *comps, int n, int Ss, int Se, int Ah)
 {
-  const int want_dc = Ss == 0 && Ah == 0, want_ac = Se != 0;
+  const int lossless = cinfo->master->lossless;     /* write_scan_header jcmarker.c:765-770: a lossless scan needs its DC table only */
+  const int want_dc = (Ss == 0 && Ah == 0) || lossless, want_ac = Se != 0 && !lossless;
   int i, j;
   if (cinfo->master->compress_profile != JCP_FASTEST) {
     /* one marker: sized in a first loop over the components, written in a second one */
@@ -503,7 +504,7 @@ static void hand_over_file(j_compress_ptr cinfo, const shim_state *s, const unsi
       }
     p = qe;
   }
-  tw_frame_tables(cinfo);
+  if (!cinfo->master->lossless) tw_frame_tables(cinfo);      /* (a lossless file has no DQT, write_frame_header jcmarker.c:687) */
   for (;;) {
     /* one scan: DHT / DAC / DRI ... SOS, entropy-coded data */
     jpeg_component_info *comps[MAX_COMPS_IN_SCAN];
@@ -593,10 +594,125 @@ typedef JDIMENSION (*raw_fn)(j_compress_ptr, JSAMPIMAGE, JDIMENSION);
 #define NEXT_SYMBOL(name) dlsym(RTLD_NEXT, name)
 #endif
 
+/* A configuration the REFERENCE refuses is refused with its error code and message (shim_begin), not as "outside the GPU path". */
+static __thread struct { int code, nparm, a, b; } g_refuse;
+static const char *refuse(int code, int nparm, int a, int b, const char *why)
+{
+  g_refuse.code = code; g_refuse.nparm = nparm; g_refuse.a = a; g_refuse.b = b;
+  return why;
+}
+
+/* rgb_red / green / blue / pixelsize of jccolor.c / jmorecfg.h; 0: not a pixel format of the RGB family, grayscale or YCbCr */
+static int input_layout(J_COLOR_SPACE cs, int *ro, int *go, int *bo)
+{
+  *ro = 0; *go = 1; *bo = 2;
+  switch (cs) {
+  case JCS_RGB: case JCS_EXT_RGB: return 3;
+  case JCS_EXT_BGR: *ro = 2; *bo = 0; return 3;
+  case JCS_EXT_RGBX: case JCS_EXT_RGBA: return 4;
+  case JCS_EXT_BGRX: case JCS_EXT_BGRA: *ro = 2; *bo = 0; return 4;
+  case JCS_EXT_XBGR: case JCS_EXT_ABGR: *ro = 3; *go = 2; *bo = 1; return 4;
+  case JCS_EXT_XRGB: case JCS_EXT_ARGB: *ro = 1; *go = 2; *bo = 3; return 4;
+  case JCS_GRAYSCALE: return 1;
+  case JCS_YCbCr: return 3;
+  default: return 0;
+  }
+}
+
+/* validate_script jcmaster.c:285-330 decides the mode from the script's first scan; jinit_c_master_control :1072-1094 then makes
+ * a lossless object what lossless mode can code: no raw data, no smoothing, the file's colour space that of the input, 1x1
+ * sampling, optimal tables.  The application reads these fields back after jpeg_start_compress. */
+static void lossless_master_setup(j_compress_ptr cinfo)
+{
+  const int search = jpeg_c_get_bool_param(cinfo, JBOOLEAN_OPTIMIZE_SCANS) && cinfo->master->num_scans_luma != 0;
+  int ci;
+  if (cinfo->scan_info != NULL && cinfo->num_scans > 0 && !search)
+    cinfo->master->lossless = cinfo->scan_info[0].Ss != 0 && cinfo->scan_info[0].Se == 0;
+  if (!cinfo->master->lossless) return;
+  cinfo->progressive_mode = FALSE;
+  cinfo->raw_data_in = FALSE;
+  cinfo->smoothing_factor = 0;
+  jpeg_default_colorspace(cinfo);
+  for (ci = 0; ci < cinfo->num_components; ci++) cinfo->comp_info[ci].h_samp_factor = cinfo->comp_info[ci].v_samp_factor = 1;
+  if (!cinfo->arith_code) cinfo->optimize_coding = TRUE;
+}
+
+/* the parameters of a lossless object (after lossless_master_setup): quality, quantization slots, DCT method, smoothing and
+ * sampling are never looked at (the reference's test suite pins a command line that sets them all "with no effect") */
+static const char *capture_lossless(j_compress_ptr cinfo, mjh_params *p)
+{
+  const int P = cinfo->data_precision, W = (int)cinfo->image_width;
+  int ci, ps, ro, go, bo;
+  long ri;
+  if (P != 8 && P != 12 && P != 16) return refuse(JERR_BAD_PRECISION, 1, P, 0, "data_precision");   /* initial_setup jcmaster.c:197-202 */
+  p->data_precision = P;
+  ps = input_layout(cinfo->in_color_space, &ro, &go, &bo);
+  if (cinfo->num_components == 4) return "lossless mode with 4 components (CMYK / YCCK)";
+  if (!ps) return "input colour space (RGB family / grayscale / YCbCr only)";
+  if (cinfo->input_components != ps) return "input_components does not match in_color_space";
+  if (!((ps == 1 && cinfo->num_components == 1) || (ps >= 3 && cinfo->num_components == 3)))
+    return refuse(JERR_CONVERSION_NOTIMPL, 0, 0, 0, "colour conversion in lossless mode");       /* jccolor.c:605-713 */
+  if (ps == 1) p->input_components = 1;
+  else { p->input_components = 3; p->input_pixel_size = ps; p->rgb_offset[0] = ro; p->rgb_offset[1] = go; p->rgb_offset[2] = bo; }
+  p->num_components = cinfo->num_components;
+  p->color_transform = MJH_COLOR_NONE;
+  p->image_width = W;
+  p->image_height = (int)cinfo->image_height;
+  for (ci = 0; ci < cinfo->num_components; ci++) {
+    const jpeg_component_info *c = &cinfo->comp_info[ci];
+    p->h_samp_factor[ci] = p->v_samp_factor[ci] = 1;
+    p->quant_tbl_no[ci] = c->quant_tbl_no; p->dc_tbl_no[ci] = 0; p->ac_tbl_no[ci] = 0;   /* (the SOS names table 0 whatever dc_tbl_no says, jcmarker.c:516) */
+    p->component_id[ci] = c->component_id;
+  }
+  p->compress_profile = jpeg_c_get_int_param(cinfo, JINT_COMPRESS_PROFILE) == JCP_FASTEST ? MJH_PROFILE_FASTEST : MJH_PROFILE_MAX_COMPRESSION;
+  if (jpeg_c_get_bool_param(cinfo, JBOOLEAN_TRELLIS_QUANT))
+    return refuse(JERR_BAD_BUFFER_MODE, 0, 0, 0, "trellis quantization in lossless mode");       /* start_pass_diff jcdiffct.c:117-135 */
+  if (cinfo->arith_code) return refuse(JERR_ARITH_NOTIMPL, 0, 0, 0, "arithmetic coding in lossless mode");   /* jcinit.c:76-77 */
+  p->optimize_coding = 1;
+  p->trellis_num_loops = 1;
+  p->restart_interval = cinfo->restart_interval;
+  p->restart_in_rows = cinfo->restart_in_rows;
+  ri = (long)cinfo->restart_interval;
+  if (cinfo->restart_in_rows > 0) { ri = (long)cinfo->restart_in_rows * W; if (ri > 65535L) ri = 65535L; }   /* per_scan_setup jcmaster.c:595-600 */
+  if (W > 0 && ri % W != 0) return refuse(JERR_BAD_RESTART, 2, (int)ri, W, "restart interval that is not whole rows");   /* jclossls.c:289-294 */
+  if (cinfo->scan_info != NULL && cinfo->num_scans > 0) {
+    int si, k;
+    if (cinfo->num_scans > MJH_MAX_SCANS) return "more than 64 scans";
+    p->num_scans = cinfo->num_scans;
+    for (si = 0; si < cinfo->num_scans; si++) {
+      const jpeg_scan_info *js = &cinfo->scan_info[si];
+      mjh_scan *ms = &p->scan_info[si];
+      ms->comps_in_scan = js->comps_in_scan;
+      for (k = 0; k < js->comps_in_scan && k < MJH_MAX_COMPS; k++) ms->component_index[k] = js->component_index[k];
+      ms->Ss = js->Ss; ms->Se = js->Se; ms->Ah = js->Ah; ms->Al = js->Al;
+    }
+  } else {      /* jpeg_enable_lossless: one scan of all components with cinfo->Ss / Al (select_scan_parameters jcmaster.c:498-512) */
+    p->num_scans = 1;
+    p->scan_info[0].comps_in_scan = cinfo->num_components;
+    for (ci = 0; ci < cinfo->num_components; ci++) p->scan_info[0].component_index[ci] = ci;
+    p->scan_info[0].Ss = cinfo->Ss; p->scan_info[0].Se = cinfo->Se; p->scan_info[0].Ah = cinfo->Ah; p->scan_info[0].Al = cinfo->Al;
+  }
+  p->write_JFIF_header = cinfo->write_JFIF_header;
+  return NULL;
+}
+
+/* mjh_encoder_create names the reference's error where it refuses a script the reference refuses (validate_script) */
+static void refuse_like_the_encoder(const char *msg)
+{
+  const char *e = strstr(msg, "entry ");
+  const int entry = e ? atoi(e + 6) : 0;
+  if (strstr(msg, "JERR_BAD_SCAN_SCRIPT")) (void)refuse(JERR_BAD_SCAN_SCRIPT, 1, entry, 0, msg);
+  else if (strstr(msg, "JERR_BAD_PROG_SCRIPT")) (void)refuse(JERR_BAD_PROG_SCRIPT, 1, entry, 0, msg);
+  else if (strstr(msg, "JERR_MISSING_DATA")) (void)refuse(JERR_MISSING_DATA, 0, 0, 0, msg);
+}
+
 static const char *capture_params(j_compress_ptr cinfo, mjh_params *p, int no_pixels)
 {
   int ci, i;
   memset(p, 0, sizeof(*p));
+  g_refuse.code = 0;
+  if (cinfo->master->lossless && no_pixels != 2) return capture_lossless(cinfo, p);   /* BEFORE the DCT method, the sampling factors and the colour space are looked at: lossless mode reads none of them */
+  if (cinfo->data_precision == 16) return refuse(JERR_BAD_PRECISION, 1, 16, 0, "16-bit samples outside lossless mode");   /* jinit_compress_master jcinit.c:100-101 */
   if (cinfo->data_precision != 8 && cinfo->data_precision != 12) return "data_precision other than 8 or 12";
   p->data_precision = cinfo->data_precision;
   if (cinfo->arith_code) {
@@ -787,7 +903,14 @@ static void shim_begin(j_compress_ptr cinfo, boolean write_all_tables, int mode,
   if (!why) {
     /* the encoder validates too (geometry limits, sampling factors ...) and is this object's until finish / abort */
     s->enc = cache_acquire(&s->p, pick_device());
-    if (!s->enc) { snprintf(whybuf, sizeof(whybuf), "%s", mjh_last_error()); why = whybuf; }
+    if (!s->enc) { snprintf(whybuf, sizeof(whybuf), "%s", mjh_last_error()); why = whybuf; refuse_like_the_encoder(whybuf); }
+  }
+  if (why && g_refuse.code) {     /* the reference refuses this too: its code, its message */
+    free_state(s);
+    cinfo->err->msg_code = g_refuse.code;
+    cinfo->err->msg_parm.i[0] = g_refuse.a; cinfo->err->msg_parm.i[1] = g_refuse.b;
+    g_refuse.code = 0;
+    (*cinfo->err->error_exit) ((j_common_ptr)cinfo);
   }
   if (why) {
     free_state(s);
@@ -841,25 +964,44 @@ static void shim_begin(j_compress_ptr cinfo, boolean write_all_tables, int mode,
      * tj3CompressFromYUVPlanes8 sizes its row buffers from width_in_blocks / max_*_samp_factor */
     int ci;
     jpeg_component_info *c;
+    const int unit = cinfo->master->lossless ? 1 : DCTSIZE;     /* data_unit of initial_setup jcmaster.c:170-178 */
     cinfo->max_h_samp_factor = cinfo->max_v_samp_factor = 1;
     for (ci = 0, c = cinfo->comp_info; ci < cinfo->num_components; ci++, c++) {
       if (c->h_samp_factor > cinfo->max_h_samp_factor) cinfo->max_h_samp_factor = c->h_samp_factor;
       if (c->v_samp_factor > cinfo->max_v_samp_factor) cinfo->max_v_samp_factor = c->v_samp_factor;
     }
     for (ci = 0, c = cinfo->comp_info; ci < cinfo->num_components; ci++, c++) {
-      const long hd = (long)cinfo->max_h_samp_factor * DCTSIZE, vd = (long)cinfo->max_v_samp_factor * DCTSIZE;
+      const long hd = (long)cinfo->max_h_samp_factor * unit, vd = (long)cinfo->max_v_samp_factor * unit;
       c->component_index = ci;
-      c->DCT_scaled_size = DCTSIZE;
+      c->DCT_scaled_size = unit;
       c->width_in_blocks = (JDIMENSION)(((long)cinfo->image_width * c->h_samp_factor + hd - 1) / hd);
       c->height_in_blocks = (JDIMENSION)(((long)cinfo->image_height * c->v_samp_factor + vd - 1) / vd);
       c->downsampled_width = (JDIMENSION)(((long)cinfo->image_width * c->h_samp_factor + cinfo->max_h_samp_factor - 1) / cinfo->max_h_samp_factor);
       c->downsampled_height = (JDIMENSION)(((long)cinfo->image_height * c->v_samp_factor + cinfo->max_v_samp_factor - 1) / cinfo->max_v_samp_factor);
       c->component_needed = TRUE;
     }
-    cinfo->total_iMCU_rows = (JDIMENSION)(((long)cinfo->image_height + cinfo->max_v_samp_factor * DCTSIZE - 1) /
-                                          ((long)cinfo->max_v_samp_factor * DCTSIZE));
+    cinfo->total_iMCU_rows = (JDIMENSION)(((long)cinfo->image_height + cinfo->max_v_samp_factor * unit - 1) /
+                                          ((long)cinfo->max_v_samp_factor * unit));
   }
-  s->row_bytes = (size_t)cinfo->image_width * cinfo->input_components * (cinfo->data_precision == 12 ? 2 : 1);
+  if (mode != 2) {
+    /* what the master leaves in the object before the first row: jinit_c_master_control jcmaster.c:1061-1064 and the first
+     * select_scan_parameters (:469-514; with the trellis on, the first pass is one of its own and is left alone here) */
+    const jpeg_scan_info *first = cinfo->scan_info;
+    if (first == NULL) { cinfo->progressive_mode = FALSE; cinfo->num_scans = 1; }
+    if (cinfo->master->lossless) {
+      if (first != NULL) { cinfo->Ss = first->Ss; cinfo->Se = first->Se; cinfo->Ah = first->Ah; cinfo->Al = first->Al; }
+      if (cinfo->restart_in_rows > 0) {      /* per_scan_setup jcmaster.c:595-600 */
+        const long nominal = (long)cinfo->restart_in_rows * (long)cinfo->image_width;
+        cinfo->restart_interval = (unsigned int)(nominal < 65535L ? nominal : 65535L);
+      }
+    } else if (first == NULL && !s->p.trellis_quant) { cinfo->Ss = 0; cinfo->Se = DCTSIZE2 - 1; cinfo->Ah = 0; cinfo->Al = 0; }
+    else if (first != NULL && !s->p.trellis_quant && !s->p.optimize_scans) {      /* validate_script :315-330, jcmaster.c:1091-1094 */
+      cinfo->progressive_mode = !(first->Ss == 0 && first->Se == DCTSIZE2 - 1);
+      if (cinfo->progressive_mode && !cinfo->arith_code) cinfo->optimize_coding = TRUE;
+      cinfo->Ss = first->Ss; cinfo->Se = first->Se; cinfo->Ah = first->Ah; cinfo->Al = first->Al;
+    }
+  }
+  s->row_bytes = (size_t)cinfo->image_width * cinfo->input_components * (cinfo->data_precision > 8 ? 2 : 1);
   /* arrays requested from this object's memory manager get realised here, as in the reference (jinit_compress_master
    * jcinit.c:143 / transencode_master_selection jctrans.c:214): an application may have asked for its own before starting --
    * cjpeg's BMP and bottom-up Targa readers keep the whole picture in one (rdbmp.c:605-609, rdtarga.c) */
@@ -893,6 +1035,8 @@ static void shim_begin(j_compress_ptr cinfo, boolean write_all_tables, int mode,
 
 void jpeg_start_compress(j_compress_ptr cinfo, boolean write_all_tables)
 {
+  if (cinfo->global_state != CSTATE_START) ERREXIT1(cinfo, JERR_BAD_STATE, cinfo->global_state);
+  lossless_master_setup(cinfo);      /* (a lossless object takes no raw data: raw_data_in is FALSE from here on) */
   shim_begin(cinfo, write_all_tables, cinfo->raw_data_in ? 1 : 0, NULL);
 }
 
@@ -900,6 +1044,7 @@ void jpeg_start_compress(j_compress_ptr cinfo, boolean write_all_tables)
  * virtual arrays may still be filled by the caller (jtransform_execute_transformation) until jpeg_finish_compress. */
 void jpeg_write_coefficients(j_compress_ptr cinfo, jvirt_barray_ptr *coef_arrays)
 {
+  if (cinfo->master->lossless) ERREXIT(cinfo, JERR_NOTIMPL);      /* jctrans.c:46-47 */
   if (cinfo->master->num_scans_luma == 0) cinfo->master->optimize_scans = FALSE;
   shim_begin(cinfo, TRUE, 2, coef_arrays);
 }
@@ -1003,6 +1148,12 @@ JDIMENSION jpeg12_write_scanlines(j_compress_ptr cinfo, J12SAMPARRAY scanlines, 
   return write_rows(cinfo, (void **)scanlines, num_lines, 12, "jpeg12_write_scanlines");
 }
 
+/* 16-bit twin (lossless mode only; J16SAMPLE = unsigned short) */
+JDIMENSION jpeg16_write_scanlines(j_compress_ptr cinfo, J16SAMPARRAY scanlines, JDIMENSION num_lines)
+{
+  return write_rows(cinfo, (void **)scanlines, num_lines, 16, "jpeg16_write_scanlines");
+}
+
 /* jpeg_write_raw_data jcapistd.c:145-199: exactly one iMCU row of caller-made component planes per call
  * (data[ci] = v_samp_factor*8 row pointers of width_in_blocks*8 samples); the rows are staged and the whole
  * image goes to the GPU at jpeg_finish_compress through mjh_encode_planes_host. */
@@ -1017,6 +1168,7 @@ static JDIMENSION write_raw(j_compress_ptr cinfo, void ***data, JDIMENSION num_l
     ERREXIT1(cinfo, JERR_BAD_STATE, cinfo->global_state);
   }
   if (cinfo->data_precision != precision) FAIL_WITH_STATE(cinfo, ERREXIT1(cinfo, JERR_BAD_PRECISION, cinfo->data_precision));
+  if (cinfo->master->lossless) FAIL_WITH_STATE(cinfo, ERREXIT(cinfo, JERR_NOTIMPL));      /* jcapistd.c:154-155 */
   if (cinfo->global_state != CSTATE_RAW_OK) FAIL_WITH_STATE(cinfo, ERREXIT1(cinfo, JERR_BAD_STATE, cinfo->global_state));
   if (cinfo->next_scanline >= cinfo->image_height) { WARNMS(cinfo, JWRN_TOO_MUCH_DATA); return 0; }
   if (cinfo->progress != NULL) {
@@ -1163,7 +1315,7 @@ void jpeg_finish_compress(j_compress_ptr cinfo)
     /* what the DEVICE wrote in front of DQT: SOI, APP0 when asked for, and always an Adobe APP14 for RGB output (build_prefix);
      * the markers the application asked for went out from the cinfo flags in jpeg_start_compress (an application may clear
      * write_Adobe_marker for JCS_RGB, which the reference honours: the device's APP14 is dropped all the same) */
-    const size_t skip = (size_t)(2 + (cinfo->write_JFIF_header ? 18 : 0) + (cinfo->jpeg_color_space == JCS_RGB ? 16 : 0));
+    const size_t skip = (size_t)(2 + (cinfo->write_JFIF_header ? 18 : 0) + (cinfo->jpeg_color_space == JCS_RGB || (cinfo->master->lossless && cinfo->num_components == 3) ? 16 : 0));   /* (a lossless file of three components carries it whatever their colour space) */
     hand_over_file(cinfo, s, file + skip, file + n);     /* (table markers under the object's sent_table flags) */
   }
   free(copy);

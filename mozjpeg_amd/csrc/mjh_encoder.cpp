@@ -401,6 +401,7 @@ struct mjh_encoder {
   bool lossless = false;
   LlConst L{};
   unsigned *d_ll_hist = nullptr, *d_ll_len = nullptr, *d_ll_off = nullptr, *d_ll_segE = nullptr;
+  int ll_sos_off[4] = { 0, 0, 0, 0 };   // scan k's SOS (the first with the DRI in front) is d_sos[ll_sos_off[k], ll_sos_off[k + 1])
 };
 
 static long div_round_up(long a, long b) { return (a + b - 1) / b; }
@@ -2908,17 +2909,32 @@ static int create_lossless(const mjh_params *p, int max_batch, int device, mjh_e
     return fail(MJH_EINVAL, "bad image size %dx%d", p->image_width, p->image_height);
   const int P = p->data_precision == 0 ? 8 : p->data_precision;
   if (P != 8 && P != 12 && P != 16) return fail(MJH_EINVAL, "data_precision %d (lossless: 8, 12 or 16; JERR_BAD_PRECISION)", p->data_precision);
-  const mjh_scan &sc = p->scan_info[0];
-  const int psv = sc.Ss, pt = sc.Al;
-  if (psv < 1 || psv > 7 || sc.Se != 0 || sc.Ah != 0 || pt < 0 || pt >= P)
-    return fail(MJH_EINVAL, "lossless scan: predictor %d, Se %d, Ah %d, point transform %d (1..7, 0, 0, 0..%d; JERR_BAD_PROGRESSION, jcmaster.c:390-400)", psv, sc.Se, sc.Ah, pt, P - 1);
+  // validate_script jcmaster.c:332-347, :390-416, :432-436, in its order: per scan the component indexes, the progression
+  // parameters, "not sent twice"; then "everything got sent"
+  const int NC = p->num_components;
+  bool sent[3] = { false, false, false };
+  for (int si = 0; si < p->num_scans; si++) {
+    const mjh_scan &sc = p->scan_info[si];
+    if (sc.comps_in_scan <= 0 || sc.comps_in_scan > 4)
+      return fail(MJH_EINVAL, "lossless scan %d: %d components (JERR_COMPONENT_COUNT, jcmaster.c:335-336)", si + 1, sc.comps_in_scan);
+    for (int c = 0; c < sc.comps_in_scan; c++) {
+      const int ci = sc.component_index[c];
+      if (ci < 0 || ci >= NC || (c > 0 && ci <= sc.component_index[c - 1]))
+        return fail(MJH_EINVAL, "Invalid scan script at entry %d: lossless scan, component order (JERR_BAD_SCAN_SCRIPT, jcmaster.c:337-344)", si + 1);
+    }
+    if (sc.Ss < 1 || sc.Ss > 7 || sc.Se != 0 || sc.Ah != 0 || sc.Al < 0 || sc.Al >= P)
+      return fail(MJH_EINVAL, "Invalid progressive/lossless parameters at scan script entry %d: lossless scan, predictor %d, Se %d, Ah %d, point transform %d (1..7, 0, 0, 0..%d; JERR_BAD_PROG_SCRIPT, jcmaster.c:390-401; jpeg_enable_lossless: JERR_BAD_PROGRESSION)", si + 1, sc.Ss, sc.Se, sc.Ah, sc.Al, P - 1);
+    for (int c = 0; c < sc.comps_in_scan; c++) {
+      if (sent[sc.component_index[c]])
+        return fail(MJH_EINVAL, "Invalid scan script at entry %d: component %d is sent twice (JERR_BAD_SCAN_SCRIPT, jcmaster.c:409-415)", si + 1, sc.component_index[c]);
+      sent[sc.component_index[c]] = true;
+    }
+  }
+  for (int c = 0; c < NC; c++)
+    if (!sent[c]) return fail(MJH_EINVAL, "Scan script does not transmit all data: component %d is in no scan (JERR_MISSING_DATA, jcmaster.c:432-436)", c);
   if (p->trellis_quant)
     return fail(MJH_EINVAL, "trellis quantization with lossless mode (JERR_BAD_BUFFER_MODE: \"Bogus buffer control mode\", the reference's trellis passes need a DCT coefficient buffer)");
   if (p->arith_code) return fail(MJH_EUNSUPPORTED, "arithmetic coding with lossless mode (JERR_NOT_COMPILED: \"Sorry, arithmetic coding is not implemented\")");
-  if (p->num_scans != 1) return fail(MJH_EUNSUPPORTED, "a lossless script of %d scans: this library codes a lossless image as one interleaved scan", p->num_scans);
-  if (sc.comps_in_scan != p->num_components) return fail(MJH_EUNSUPPORTED, "a lossless scan of %d of %d components: this library codes a lossless image as one interleaved scan", sc.comps_in_scan, p->num_components);
-  for (int c = 0; c < sc.comps_in_scan; c++)
-    if (sc.component_index[c] != c) return fail(MJH_EINVAL, "lossless scan: component order (JERR_BAD_SCAN_SCRIPT)");
   if (p->compress_profile != MJH_PROFILE_FASTEST)
     return fail(MJH_EUNSUPPORTED, "lossless mode in the max-compression profile: the reference writes a DQT and an empty DHT marker there (emit_multi_dqt / emit_multi_dht, jcmarker.c:189-254, :293-401), a file without Huffman tables");
   const bool gray = p->input_components == 1 && p->num_components == 1;
@@ -2964,8 +2980,22 @@ static int create_lossless(const mjh_params *p, int max_batch, int device, mjh_e
   LlConst &L = e->L;
   L.W = W; L.H = H; L.ncomp = C.ncomp; L.px_size = px;
   for (int c = 0; c < 3; c++) L.off[c] = off[c];
-  L.precision = P; L.psv = psv; L.pt = pt;
-  L.init_pred = 1 << (P - pt - 1);
+  L.precision = P;
+  // Scan k's table lives in slot k, the last scan's in SLOT_FINAL: what the object holds as DC table 0 after the image (and what
+  // MJH_TAP_HUFF_BITS / MJH_TAP_LL_COUNTS read) is the table the last scan defined.
+  L.nscan = p->num_scans;
+  int widest = 1;
+  for (int si = 0; si < L.nscan; si++) {
+    const mjh_scan &sc = p->scan_info[si];
+    LlScan &S = L.sc[si];
+    S.ncomp = sc.comps_in_scan;
+    for (int c = 0; c < 3; c++) S.comp[c] = c < S.ncomp ? sc.component_index[c] : 0;
+    S.psv = sc.Ss; S.pt = sc.Al;
+    S.init_pred = 1 << (P - S.pt - 1);
+    S.slot = si == L.nscan - 1 ? SLOT_FINAL : si;
+    if (S.ncomp > widest) widest = S.ncomp;
+  }
+  L.psv = L.sc[0].psv; L.pt = L.sc[0].pt; L.init_pred = L.sc[0].init_pred;
   L.rows_per_seg = (int)(ri / W);
   L.nseg = L.rows_per_seg ? (H + L.rows_per_seg - 1) / L.rows_per_seg : 1;
   L.units_x = (W + LL_UNIT - 1) / LL_UNIT;
@@ -2986,25 +3016,27 @@ static int create_lossless(const mjh_params *p, int max_batch, int device, mjh_e
   // 16-bit length limit), so the average sample costs at most P + 1 + log2(P + 3) + 2 bits: 14.5 / 18.9 / 22.2 at P = 8 / 12 / 16,
   // under `per` = 17 / 25 / 31.  (k_ll_scan still checks the total against the buffer and reports MJH_ETOOSMALL before writing.)
   const unsigned long long per = (unsigned long long)(P + 1 < 16 ? P + 1 : 16) + (P < 16 ? P : 15);
-  unsigned long long words = ((unsigned long long)W * H * C.ncomp * per + (unsigned long long)L.nseg * 24ull) / 32ull + 64ull;
-  if (words > (1ull << 27)) words = 1ull << 27;   // bit offsets are 32-bit (larger scans are reported by k_ll_scan)
+  // Every scan of every image has a stream of its own, sized for the widest scan of the script.
+  unsigned long long words = ((unsigned long long)W * H * widest * per + (unsigned long long)L.nseg * 24ull) / 32ull + 64ull;
+  if (words > (1ull << 27)) words = 1ull << 27;   // bit offsets are 32-bit (larger scans are reported by k_ll_scan, scan by scan)
   e->stream_words = (size_t)((words + 63ull) & ~63ull);
   e->ff_chunks = (int)((e->stream_words + 2047) / 2048);
   e->spi = SLOTS_BASE;
   HIPCHK_E(mjh_dmalloc((void **)&e->d_tabs, B * e->spi * sizeof(MjhHuffTable)));
-  HIPCHK_E(mjh_dmalloc((void **)&e->d_ll_hist, B * (size_t)L.units * 17 * 4));
-  HIPCHK_E(mjh_dmalloc((void **)&e->d_ll_len, B * (size_t)L.units * 4));
-  HIPCHK_E(mjh_dmalloc((void **)&e->d_ll_off, B * (size_t)L.units * 4));
-  HIPCHK_E(mjh_dmalloc((void **)&e->d_ll_segE, B * (size_t)L.nseg * 4));
-  HIPCHK_E(mjh_dmalloc((void **)&e->d_mpos, B * (size_t)L.nseg * 4));
-  HIPCHK_E(mjh_dmalloc((void **)&e->d_totals, B * sizeof(unsigned)));
+  const size_t BS = B * (size_t)L.nscan;     // "virtual images": v = scan * n + image (mjh_lossless.hip)
+  HIPCHK_E(mjh_dmalloc((void **)&e->d_ll_hist, BS * (size_t)L.units * 17 * 4));
+  HIPCHK_E(mjh_dmalloc((void **)&e->d_ll_len, BS * (size_t)L.units * 4));
+  HIPCHK_E(mjh_dmalloc((void **)&e->d_ll_off, BS * (size_t)L.units * 4));
+  HIPCHK_E(mjh_dmalloc((void **)&e->d_ll_segE, BS * (size_t)L.nseg * 4));
+  HIPCHK_E(mjh_dmalloc((void **)&e->d_mpos, BS * (size_t)L.nseg * 4));
+  HIPCHK_E(mjh_dmalloc((void **)&e->d_totals, BS * sizeof(unsigned)));
   HIPCHK_E(mjh_dmalloc((void **)&e->d_fftotals, B * sizeof(unsigned)));
   HIPCHK_E(mjh_dmalloc((void **)&e->d_ffsums, B * e->ff_chunks * sizeof(unsigned)));
-  HIPCHK_E(mjh_dmalloc((void **)&e->d_stream, B * e->stream_words * 4 + 4096));
-  e->out_stride = ((size_t)2048 + e->stream_words * 8 + 255) & ~(size_t)255;   // (stuffing at most doubles the bytes)
+  HIPCHK_E(mjh_dmalloc((void **)&e->d_stream, BS * e->stream_words * 4 + 4096));
+  e->out_stride = ((size_t)2048 + (size_t)L.nscan * e->stream_words * 8 + 255) & ~(size_t)255;   // (stuffing at most doubles the bytes; every later scan adds a DHT and an SOS, under 64 bytes, inside the 2048)
   HIPCHK_E(mjh_dmalloc((void **)&e->d_out, B * e->out_stride));
   HIPCHK_E(mjh_dmalloc((void **)&e->d_sizes, B * sizeof(unsigned)));
-  HIPCHK_E(mjh_dmalloc(&e->d_meta, B * sizeof(MjhImageMeta)));
+  HIPCHK_E(mjh_dmalloc(&e->d_meta, BS * sizeof(MjhImageMeta)));
   e->h_sizes.resize(B);
   {
     std::vector<uint8_t> pre, sos;
@@ -3025,12 +3057,18 @@ static int create_lossless(const mjh_params *p, int max_batch, int device, mjh_e
     put2(pre, H); put2(pre, W);
     pre.push_back((uint8_t)C.ncomp);
     for (int c = 0; c < C.ncomp; c++) { pre.push_back((uint8_t)q.component_id[c]); pre.push_back(0x11); pre.push_back((uint8_t)q.quant_tbl_no[c]); }
-    if (ri) { sos.push_back(0xFF); sos.push_back(0xDD); put2(sos, 4); put2(sos, (int)ri); }   // emit_dri
-    sos.push_back(0xFF); sos.push_back(0xDA);                  // emit_sos jcmarker.c:494-526
-    put2(sos, 2 * C.ncomp + 2 + 1 + 3);
-    sos.push_back((uint8_t)C.ncomp);
-    for (int c = 0; c < C.ncomp; c++) { sos.push_back((uint8_t)q.component_id[c]); sos.push_back(0); }
-    sos.push_back((uint8_t)L.psv); sos.push_back(0); sos.push_back((uint8_t)L.pt);
+    if (ri) { sos.push_back(0xFF); sos.push_back(0xDD); put2(sos, 4); put2(sos, (int)ri); }   // emit_dri: in front of the first SOS only (write_scan_header jcmarker.c:778-781, the interval is the same in every scan)
+    for (int si = 0; si < L.nscan; si++) {
+      const LlScan &S = L.sc[si];
+      e->ll_sos_off[si] = (int)sos.size();
+      sos.push_back(0xFF); sos.push_back(0xDA);                  // emit_sos jcmarker.c:494-526
+      put2(sos, 2 * S.ncomp + 2 + 1 + 3);
+      sos.push_back((uint8_t)S.ncomp);
+      for (int c = 0; c < S.ncomp; c++) { sos.push_back((uint8_t)q.component_id[S.comp[c]]); sos.push_back(0); }
+      sos.push_back((uint8_t)S.psv); sos.push_back(0); sos.push_back((uint8_t)S.pt);
+    }
+    e->ll_sos_off[0] = 0;      // (the DRI goes with the first scan's SOS)
+    e->ll_sos_off[L.nscan] = (int)sos.size();
     e->prefix_len = (int)pre.size(); e->sos_len = (int)sos.size();
     HIPCHK_E(mjh_dmalloc((void **)&e->d_prefix, pre.size()));
     HIPCHK_E(mjh_dmalloc((void **)&e->d_sos, sos.size()));
@@ -3060,30 +3098,38 @@ static int run_lossless(mjh_encoder *e, const void *d_pixels, size_t row_pitch, 
     pr.next = (size_t)e->prof_calls * e->prof_per_call;
   }
   const LlConst &L = e->L;
-  const int slot = SLOT_FINAL;
+  const int nv = n * L.nscan;      // virtual images: v = scan * n + image
   HIPCHK(hipMemsetAsync(e->d_tabs, 0, (size_t)n * e->spi * sizeof(MjhHuffTable), s));
-  HIPCHK(hipMemsetAsync(e->d_meta, 0, (size_t)n * sizeof(MjhImageMeta), s));
+  HIPCHK(hipMemsetAsync(e->d_meta, 0, (size_t)nv * sizeof(MjhImageMeta), s));
   auto ll = [&](int phase) {
-    mjh_launch_ll(L, d_pixels, row_pitch, image_stride, e->d_tabs, e->spi, slot, e->d_ll_hist, e->d_ll_len, e->d_ll_off, e->d_ll_segE, e->d_mpos,
+    mjh_launch_ll(L, d_pixels, row_pitch, image_stride, e->d_tabs, e->spi, e->d_ll_hist, e->d_ll_len, e->d_ll_off, e->d_ll_segE, e->d_mpos,
                   e->d_totals, e->d_stream, e->stream_words, n, s, phase);
   };
+  int slots[3];
+  for (int si = 0; si < L.nscan; si++) slots[si] = L.sc[si].slot;
   pr.mark("ll_stats");
   ll(0);
   pr.mark("gen_tables");
-  mjh_launch_gen_tables(e->d_tabs, e->spi, &slot, 1, n, s);
+  mjh_launch_gen_tables(e->d_tabs, e->spi, slots, L.nscan, n, s);
   pr.mark("ll_len");
   ll(1);
   pr.mark("ll_write");
   ll(2);
-  mjh_launch_finish_bits(e->d_totals, e->d_stream, e->stream_words, e->d_meta, n, s);   // (the last byte padded with 1-bits, flush_bits jclhuff.c)
+  mjh_launch_finish_bits(e->d_totals, e->d_stream, e->stream_words, e->d_meta, nv, s);   // (the last byte of every scan padded with 1-bits, flush_bits jclhuff.c)
   if (input_read) HIPCHK(hipEventRecord(input_read, s));
   if (before_output) HIPCHK(hipStreamWaitEvent(s, before_output, 0));
-  pr.mark("header");
-  mjh_launch_header(e->d_prefix, e->prefix_len, e->d_sos, e->sos_len, e->d_tabs, e->spi, e->dht_slots, e->dht_ids, e->ndht, 0,
-                    e->d_out, e->out_stride, e->d_meta, n, s);
-  pr.mark("byte_stuff");
-  mjh_launch_stuff(e->d_stream, e->stream_words, e->d_totals, e->d_ffsums, e->ff_chunks, e->d_fftotals, e->d_out, e->out_stride,
-                   e->d_meta, e->d_sizes, e->d_mpos, L.nseg, n, s);
+  // The file, scan by scan, as the sequential coder assembles a script of several scans: the scan's DHT (table 0, from its own
+  // statistics) + SOS behind the file so far, then its stuffed data.  (d_meta[image] carries hdr_len from the header to the
+  // stuffing; the out-of-range report of k_ll_scan sits in every scan's total_bits, the first scan's included.)
+  for (int si = 0; si < L.nscan; si++) {
+    const int dht_slot[8] = { L.sc[si].slot, 0, 0, 0, 0, 0, 0, 0 };
+    pr.mark("header");
+    mjh_launch_header(si == 0 ? e->d_prefix : nullptr, si == 0 ? e->prefix_len : 0, (const uint8_t *)e->d_sos + e->ll_sos_off[si], e->ll_sos_off[si + 1] - e->ll_sos_off[si],
+                      e->d_tabs, e->spi, dht_slot, e->dht_ids, 1, 0, e->d_out, e->out_stride, e->d_meta, n, s, si == 0 ? nullptr : e->d_sizes);
+    pr.mark("byte_stuff");
+    mjh_launch_stuff(e->d_stream + (size_t)si * n * e->stream_words, e->stream_words, e->d_totals + (size_t)si * n, e->d_ffsums, e->ff_chunks, e->d_fftotals,
+                     e->d_out, e->out_stride, e->d_meta, e->d_sizes, e->d_mpos + (size_t)si * n * L.nseg, L.nseg, n, s);
+  }
   pr.mark(nullptr);
   pr.finish();
   HIPCHK(hipGetLastError());

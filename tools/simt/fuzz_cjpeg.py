@@ -7,7 +7,9 @@ libraries' DT_NEEDED `libmozjpeg_hip.so` is resolved (rpath $ORIGIN) to the kern
 the host C code between the libjpeg API and the C ABI (jpeg_shim.c capture_params / markers / destination managers,
 jpeg_api.c's parameter setters and its readers of cjpeg's -qtables / -qslots / -sample / -scans / -icc state).
 Development aid, correctness only; build container only (it needs oracle/_ref).
-usage: python tools/simt/fuzz_cjpeg.py SEED COUNT [--verbose] [--from N] [--keep DIR]     one line per failure and a summary"""
+--lossless (off by default, so that replayed seeds keep their command lines): six cases in ten become lossless commands
+(-lossless psv,Pt at 8 / 12 / 16 bits, restart rows, lossless scan scripts).
+usage: python tools/simt/fuzz_cjpeg.py SEED COUNT [--verbose] [--from N] [--keep DIR] [--lossless]     one line per failure and a summary"""
 import os
 import shutil
 import subprocess
@@ -294,11 +296,34 @@ def three_ways(cmd_of, d, tmp, verbose, standalone=True):
     return bad, r0
 
 
+def draw_lossless(lr, tmp, gray_in):
+    """cjpeg in lossless mode: -lossless psv,Pt at 8 / 12 / 16 bits, restart rows, lossless scan scripts (every component in exactly
+    one scan, per-scan predictor and point transform), and switches that must have no effect"""
+    prec = int(lr.choice([8, 8, 12, 16]))
+    pts = [0, 0, 1, int(lr.integers(0, prec)), prec - 1]
+    a = ["-revert", "-lossless", "%d,%d" % (int(lr.integers(1, 8)), int(lr.choice(pts)))]
+    if prec != 8:
+        a += ["-precision", str(prec)]
+    if lr.random() < 0.4:
+        a += ["-restart", str(int(lr.integers(1, 5)))]
+    if lr.random() < 0.5:
+        groups = [[(0,)]] if gray_in else [[(0,), (1,), (2,)], [(0,), (1, 2)], [(0, 1), (2,)], [(0, 2), (1,)], [(1,), (0, 2)], [(0, 1, 2)], [(2,), (1,), (0,)]]
+        script = [(g, int(lr.integers(1, 8)), 0, 0, int(lr.choice(pts))) for g in groups[int(lr.integers(0, len(groups)))]]
+        sf = os.path.join(tmp, "lossless.scans")
+        with open(sf, "w") as f:
+            f.write(script_text(script))
+        a += ["-scans", sf]
+    if lr.random() < 0.3:
+        a += ["-quality", "1", "-smooth", "50", "-sample", "2x2", "-optimize", "-grayscale"]     # "should have no effect"
+    return a
+
+
 def main():
     seed, count = int(sys.argv[1]), int(sys.argv[2])
     verbose = "--verbose" in sys.argv
     first = int(sys.argv[sys.argv.index("--from") + 1]) if "--from" in sys.argv else 0
     keep = sys.argv[sys.argv.index("--keep") + 1] if "--keep" in sys.argv else None
+    lossless = "--lossless" in sys.argv
     d = dropin_dir()
     bad = ref_refused = 0
     t0 = time.time()
@@ -314,6 +339,12 @@ def main():
                 a = [x for x in a if x not in ("-trellis-dc",)] + ["-precision", "12", "-notrellis"]
             if i < first:
                 continue
+            if lossless and not transcode:
+                # --lossless (off by default: the seeds tests/test_simt_dropin.py replays keep their command lines): a generator of
+                # its own turns six cases in ten into a lossless command on the drawn image
+                lr = np.random.default_rng(seed * 15485863 + i)
+                if lr.random() < 0.6:
+                    a = draw_lossless(lr, tmp, gray_in)
             if not transcode:
                 # (a generator of its own for the DCT method: the cases of older seeds keep their other switches)
                 dct = "fast" if np.random.default_rng(seed * 7919 + i).random() < 0.25 else "int"
