@@ -315,6 +315,68 @@ int mjh_encode_coefficients_host(mjh_encoder *e, const void *const coefs[MJH_MAX
                                  const size_t image_stride[MJH_MAX_COMPS], int n);
 int mjh_encoder_sync(mjh_encoder *e);
 
+/* ---- re-compressing existing files ("jpegrescan": jpegtran -copy none [-optimize | -progressive | ...]) -------------------
+ * JPEG bytes in, JPEG bytes out.  The host reads marker segments only; every Huffman symbol is decoded by kernels
+ * (mjh_decode.hip), whose output feeds the entropy-coding passes of mjh_encode_coefficients_*.
+ * Accepted: Huffman-coded sequential DCT files (SOF0, SOF1), 8-bit, 1 or 3 components, one interleaved scan or several
+ * scans (every component in exactly one), any restart intervals.  MJH_EUNSUPPORTED: progressive, arithmetic, lossless,
+ * 12-bit, 2 or 4 components, DNL.  COM / APPn markers are not copied (-copy none). */
+#define MJH_MAX_FILE_SCANS 4
+#define MJH_CS_GRAYSCALE 1   /* J_COLOR_SPACE values (jpeglib.h:232-234) */
+#define MJH_CS_RGB       2
+#define MJH_CS_YCbCr     3
+typedef struct {
+  int comps_in_scan;
+  int component_index[MJH_MAX_COMPS];               /* frame index of every component of the scan */
+  int dc_tbl_no[MJH_MAX_COMPS], ac_tbl_no[MJH_MAX_COMPS];   /* per component of the scan (Td / Ta of the SOS) */
+  unsigned restart_interval;                        /* in force at this SOS (0 = none) */
+  size_t data_offset, data_size;                    /* the entropy-coded segment, RSTn markers included, up to the next other marker */
+  unsigned restart_markers;                         /* RSTn markers inside it */
+  /* the Huffman tables in force at this SOS: slot 2 t + is_ac as in mjh_params; a bit set in huff_defined = that table was defined */
+  int huff_defined;
+  uint8_t huff_bits[8][17];
+  uint8_t huff_vals[8][256];
+} mjh_jpeg_scan;
+typedef struct {
+  int sof_type;                                     /* 0 = SOF0 (baseline), 1 = SOF1 (extended sequential) */
+  int data_precision;
+  int image_width, image_height;
+  int num_components;
+  int component_id[MJH_MAX_COMPS], h_samp_factor[MJH_MAX_COMPS], v_samp_factor[MJH_MAX_COMPS], quant_tbl_no[MJH_MAX_COMPS];
+  int quant_defined;                                /* bit t: DQT table t was seen in front of the first SOS */
+  uint16_t quantval[4][64];                         /* natural order */
+  int jpeg_color_space;                             /* MJH_CS_*, as default_decompress_parms guesses it (jdapimin.c:130-205) */
+  int saw_JFIF_marker, JFIF_major_version, JFIF_minor_version, density_unit, X_density, Y_density;
+  int saw_Adobe_marker, Adobe_transform;
+  int num_scans;
+  mjh_jpeg_scan scans[MJH_MAX_FILE_SCANS];
+} mjh_jpeg_info;
+/* Walks the marker segments of one file (jdmarker.c).  Searches the entropy-coded data for 0xFF to find where a scan
+ * ends; decodes nothing.  MJH_EINVAL with the reference's reason for malformed headers, MJH_EUNSUPPORTED for file
+ * types outside the list above. */
+int mjh_jpeg_probe(const void *jpeg, size_t size, mjh_jpeg_info *info);
+/* What jpeg_copy_critical_parameters (jctrans.c:75-171) leaves in the destination object: the profile's defaults
+ * (the max-compression profile: optimal tables, progressive with scan search), trellis_quant = 0, and the source's size,
+ * colour space, precision, component ids, sampling factors, quantization-table numbers and tables -- not its Huffman tables,
+ * scan script or restart interval.  Apply jpegtran's switches to *p afterwards (optimize_coding,
+ * mjh_params_simple_progression, restart_interval, num_scans = 0 for a sequential file, ...). */
+int mjh_params_from_jpeg(const mjh_jpeg_info *info, int compress_profile, mjh_params *p);
+/* Re-codes n files with the encoder's parameters, which mjh_params_from_jpeg made (trellis_quant must be 0).  Every file has
+ * to agree with the encoder in everything mjh_params_from_jpeg copies (else MJH_EINVAL naming the file and the field) and
+ * may differ in scans, Huffman tables, restart intervals and JFIF version / density, which go into that file's own APP0
+ * (jctrans.c:162-170).  Queued like mjh_encode_host; results through mjh_collect / mjh_get_jpeg.  The bytes need not stay
+ * valid after the call returns.  Damaged entropy-coded data fails the batch with MJH_EINVAL when its results are waited
+ * for (the reference warns and writes a file); mjh_transcode_status then tells the damaged files from the good ones. */
+int mjh_transcode_host(mjh_encoder *e, const void *const jpegs[], const size_t sizes[], int n);
+/* Code (MJH_OK / MJH_EINVAL / MJH_EUNSUPPORTED) of file i of the last mjh_transcode_host batch and, in *text (may be NULL;
+ * owned by the encoder, valid until the next batch), its reason.  Synchronises with the batch. */
+int mjh_transcode_status(mjh_encoder *e, int i, const char **text);
+/* Figures of the last mjh_transcode_host call: subsequence length in bytes (0 = one lane per restart segment), the
+ * synchronisation rounds launched, host synchronisations inside the call, and -- with mjh_set_profiling(e, 1) -- the
+ * milliseconds of the decoder's phases: [0] first pass + synchronisation rounds, [1] block indices, [2] storing pass,
+ * [3] DC sums + scrub.  Any pointer may be NULL. */
+int mjh_transcode_stats(mjh_encoder *e, int *subseq, int *rounds, int *host_syncs, float ms[4]);
+
 /* Size in bytes of JPEG i of the last batch (synchronises). */
 int mjh_get_jpeg_size(mjh_encoder *e, int i, size_t *size);
 /* Copy JPEG i of the last batch to host memory (synchronises). */

@@ -17,6 +17,7 @@ MAX_COMPS, MAX_SCANS = 4, 64
 PROFILE_MAX_COMPRESSION = 0x5D083AAD
 PROFILE_FASTEST = 0x2AEA5CB4
 COLOR_YCC, COLOR_NONE, COLOR_YCC_IN = 0, 1, 2
+CS_GRAYSCALE, CS_RGB, CS_YCBCR = 1, 2, 3      # JpegInfo.jpeg_color_space
 OK, EINVAL, EUNSUPPORTED, EHIP, ENOMEM, ETOOSMALL = 0, -1, -2, -3, -4, -5
 TAP_PLANE, TAP_COEF_UQ, TAP_COEF_Q, TAP_COEF_Q0, TAP_HUFF_BITS, TAP_HUFF_VALS, TAP_PROG_SCAN_US, TAP_LL_COUNTS = 1, 2, 3, 4, 5, 6, 7, 8
 
@@ -52,6 +53,25 @@ class Params(C.Structure):
                 ("arith_dc_L", C.c_int * 2), ("arith_dc_U", C.c_int * 2), ("arith_ac_K", C.c_int * 2),
                 ("trellis_stats_Ah", C.c_int), ("trellis_stats_Al", C.c_int), ("huff_tables_given", C.c_int),
                 ("huff_bits", (C.c_uint8 * 17) * 8), ("huff_vals", (C.c_uint8 * 256) * 8), ("dct_method", C.c_int)]
+
+
+class JpegScan(C.Structure):
+    """mjh_jpeg_scan: one scan of a source file as mjh_jpeg_probe found it"""
+    _fields_ = [("comps_in_scan", C.c_int), ("component_index", C.c_int * MAX_COMPS), ("dc_tbl_no", C.c_int * MAX_COMPS),
+                ("ac_tbl_no", C.c_int * MAX_COMPS), ("restart_interval", C.c_uint), ("data_offset", C.c_size_t),
+                ("data_size", C.c_size_t), ("restart_markers", C.c_uint), ("huff_defined", C.c_int), ("huff_bits", (C.c_uint8 * 17) * 8),
+                ("huff_vals", (C.c_uint8 * 256) * 8)]
+
+
+class JpegInfo(C.Structure):
+    """mjh_jpeg_info: the marker segments of a source file (no entropy decoding)"""
+    _fields_ = [("sof_type", C.c_int), ("data_precision", C.c_int), ("image_width", C.c_int), ("image_height", C.c_int),
+                ("num_components", C.c_int), ("component_id", C.c_int * MAX_COMPS), ("h_samp_factor", C.c_int * MAX_COMPS),
+                ("v_samp_factor", C.c_int * MAX_COMPS), ("quant_tbl_no", C.c_int * MAX_COMPS), ("quant_defined", C.c_int),
+                ("quantval", (C.c_uint16 * 64) * 4), ("jpeg_color_space", C.c_int), ("saw_JFIF_marker", C.c_int),
+                ("JFIF_major_version", C.c_int), ("JFIF_minor_version", C.c_int), ("density_unit", C.c_int),
+                ("X_density", C.c_int), ("Y_density", C.c_int), ("saw_Adobe_marker", C.c_int), ("Adobe_transform", C.c_int),
+                ("num_scans", C.c_int), ("scans", JpegScan * 4)]
 
 
 class Result(C.Structure):
@@ -124,6 +144,11 @@ def lib():
         L.mjh_component_geometry.argtypes = [C.c_void_p, C.c_int] + [C.POINTER(C.c_int)] * 4
         L.mjh_get_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_char_p)),
                                            C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int)]
+        L.mjh_jpeg_probe.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(JpegInfo)]
+        L.mjh_params_from_jpeg.argtypes = [C.POINTER(JpegInfo), C.c_int, C.POINTER(Params)]
+        L.mjh_transcode_host.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int]
+        L.mjh_transcode_status.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p)]
+        L.mjh_transcode_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float)]
         _lib = L
     return _lib
 
@@ -259,6 +284,92 @@ def make_params(width, height, *, quality=75, baseline=False, revert=False, opti
                 p.scan_info[i].component_index[j] = c
             p.scan_info[i].Ss, p.scan_info[i].Se, p.scan_info[i].Ah, p.scan_info[i].Al = ss, se, ah, al
     return p
+
+
+def jpeg_info(data):
+    """The marker segments of a JPEG file (mjh_jpeg_probe): frame, tables, colour space, JFIF / Adobe fields, and per scan its
+    components, Huffman tables, restart interval and the byte range of its entropy-coded data.  Raises MjhError (EUNSUPPORTED:
+    progressive, arithmetic, lossless, 12-bit, 4 components; EINVAL: malformed)."""
+    info = JpegInfo()
+    data = bytes(data)
+    _chk(lib().mjh_jpeg_probe(data, len(data), C.byref(info)))
+    return info
+
+
+def params_from_jpeg(data, *, revert=False, optimize=False, progressive=None, fastcrush=False, restart=0):
+    """Parameters of a `jpegtran -copy none` run on this file (mjh_params_from_jpeg = jpeg_copy_critical_parameters) plus
+    jpegtran's switches in make_params' vocabulary.  `data`: the file's bytes or a JpegInfo."""
+    info = data if isinstance(data, JpegInfo) else jpeg_info(data)
+    p = Params()
+    L = lib()
+    _chk(L.mjh_params_from_jpeg(C.byref(info), PROFILE_FASTEST if revert else PROFILE_MAX_COMPRESSION, C.byref(p)))
+    if optimize:
+        p.optimize_coding = 1
+    if restart:
+        if isinstance(restart, str) and restart.lower().endswith("b"):
+            p.restart_interval = int(restart[:-1])
+        else:
+            p.restart_in_rows = int(restart)
+    if revert:
+        if progressive:
+            _chk(L.mjh_params_simple_progression(C.byref(p)))
+    elif fastcrush:     # (-progressive alone keeps the profile's scan search: jpeg_simple_progression defers to it while optimize_scans is set, jcparam.c:867-870)
+        _chk(L.mjh_params_simple_progression(C.byref(p)))
+    return p
+
+
+def _signature(info):
+    """what the files of one mjh_transcode_host batch have in common (everything mjh_params_from_jpeg copies)"""
+    nc = info.num_components
+    used = sorted(set(info.quant_tbl_no[c] for c in range(nc)))
+    return (info.image_width, info.image_height, nc, info.jpeg_color_space,
+            tuple((info.component_id[c], info.h_samp_factor[c], info.v_samp_factor[c], info.quant_tbl_no[c]) for c in range(nc)),
+            tuple(bytes(info.quantval[t]) for t in used))
+
+
+_recompress_encoders = {}
+
+
+def recompress(files, *, max_batch=64, device=0, **switches):
+    """Re-compress JPEG files on the GPU: what `jpegtran -copy none` + the switches (revert, optimize, progressive, fastcrush,
+    restart) writes for each of them, in input order.  The files are grouped by what a batch must have in common; one encoder
+    per group is kept for later calls.  In the max-compression profile without `revert` / `progressive` a source that is
+    smaller than its re-coded file is returned as it came (jpegtran.c:171, :774-777).  A file that cannot be re-coded
+    (unsupported type, malformed headers, damaged entropy-coded data) gets the MjhError in its slot; the others are unaffected."""
+    files = [bytes(f) for f in files]
+    out = [None] * len(files)
+    groups = {}
+    for i, f in enumerate(files):
+        try:
+            info = jpeg_info(f)
+        except MjhError as exc:
+            out[i] = exc
+            continue
+        groups.setdefault(_signature(info), (info, []))[1].append(i)
+    prefer_smallest = not (switches.get("revert") or switches.get("progressive"))
+    key_sw = tuple(sorted(switches.items()))
+    for sig, (info, idx) in groups.items():
+        key = (sig, key_sw, device, LIB_PATH)
+        enc = _recompress_encoders.get(key)
+        if enc is None or enc.max_batch < min(max_batch, len(idx)):
+            if enc is not None:
+                enc.close()
+            enc = _recompress_encoders[key] = Encoder(params_from_jpeg(info, **switches), max_batch=min(max_batch, len(idx)), device=device)
+        for o in range(0, len(idx), enc.max_batch):
+            part = idx[o:o + enc.max_batch]
+            res = enc.transcode_host([files[i] for i in part], errors="return")
+            bad = [k for k, r in enumerate(res) if isinstance(r, MjhError)]
+            if bad and len(bad) < len(part):           # the good files of the batch once more, without the damaged ones
+                good = [k for k in range(len(part)) if k not in bad]
+                again = enc.transcode_host([files[part[k]] for k in good], errors="return")
+                for k, r in zip(good, again):
+                    res[k] = r
+            for k, i in enumerate(part):
+                r = res[k]
+                if prefer_smallest and not isinstance(r, MjhError) and len(files[i]) < len(r):
+                    r = files[i]
+                out[i] = r
+    return out
 
 
 def pinned_empty(shape, dtype=np.uint8):
@@ -446,6 +557,45 @@ class Encoder:
         _chk(lib().mjh_encode_coefficients_device(self._h, (C.c_void_p * 4)(*pad([t.data_ptr() for t in coefs], None)),
                                                   (C.c_size_t * 4)(*pad([t.shape[2] for t in coefs], 0)),
                                                   (C.c_size_t * 4)(*pad([t.stride(0) * 2 for t in coefs], 0)), n, stream))
+
+    # existing files in (jpegtran -copy none): Huffman decoding on the device, then the entropy-coding passes
+    def submit_transcode(self, files):
+        """Asynchronous mjh_transcode_host; results through collect() / get_jpeg()."""
+        files = [bytes(f) for f in files]
+        n = len(files)
+        _chk(lib().mjh_transcode_host(self._h, (C.c_char_p * n)(*files), (C.c_size_t * n)(*[len(f) for f in files]), n))
+        return n
+
+    def transcode_status(self, i):
+        """(code, text) of file i of the last transcode batch (mjh_transcode_status)"""
+        t = C.c_char_p()
+        rc = lib().mjh_transcode_status(self._h, i, C.byref(t))
+        return rc, (t.value or b"").decode()
+
+    def transcode_stats(self):
+        """subsequence bytes, synchronisation rounds, host synchronisations and decoder phase times (ms, with profiling) of the last transcode call"""
+        a, b, c, ms = C.c_int(), C.c_int(), C.c_int(), (C.c_float * 4)()
+        _chk(lib().mjh_transcode_stats(self._h, C.byref(a), C.byref(b), C.byref(c), ms))
+        return dict(subseq=a.value, rounds=b.value, host_syncs=c.value, ms=dict(zip(("sync", "prefix", "store", "dc"), [float(x) for x in ms])))
+
+    def transcode_host(self, files, errors="raise"):
+        """files: JPEG byte strings that agree with the encoder's parameters (params_from_jpeg).  Returns the re-coded files.
+        errors="return": no exception for a batch with damaged files -- their slots hold the MjhError, the slots of the good
+        files None (nothing of such a batch is handed out: submit the good ones again)."""
+        n = len(files)
+        try:
+            self.submit_transcode(files)
+            return [self.get_jpeg(i) for i in range(n)]
+        except MjhError:
+            if errors != "return":
+                raise
+            res = []
+            for i in range(n):
+                rc, text = self.transcode_status(i)
+                res.append(MjhError(rc, text) if rc != OK else None)
+            if all(r is None for r in res):
+                raise
+            return res
 
     def set_inflight(self, batches):
         """device-resident batches in flight inside the encoder: 2 (default) or 1 (mjh_set_inflight)"""

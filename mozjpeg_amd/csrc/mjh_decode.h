@@ -1,0 +1,78 @@
+// mjh_decode.h -- descriptors shared by the host side of mjh_transcode_host (mjh_encoder.cpp) and the Huffman decoder kernels
+// (mjh_decode.hip).  The host reads marker segments only (mjh_jpeg_probe); every Huffman symbol is decoded on the device.
+#ifndef MJH_DECODE_H
+#define MJH_DECODE_H
+#include <hip/hip_runtime.h>
+#include "mjh_internal.h"
+
+#define MJH_DEC_WG 256           // lanes (= subsequences) per workgroup; a workgroup serves ONE (image, scan)
+
+// jpeg_make_d_derived_tbl (jdhuff.c:169-308) of one table: 8-bit look-ahead (nbits << 8 | symbol, 0 = longer code),
+// maxcode[1..16] (-1: no code of that length; [17] ends the search), valoff[l] = index of the first symbol of length l - its code
+struct MjhDecTable {
+  uint16_t look[256];
+  int maxcode[18];
+  int valoff[18];
+  uint8_t huffval[256];
+};
+
+// one (image, scan) pair
+struct MjhDecScan {
+  int image;
+  int ncomp;                 // components of the scan
+  int comp[MJH_MAXC];        // their frame indices
+  int dctab[MJH_MAXC], actab[MJH_MAXC];   // indices into the batch's MjhDecTable array
+  int nb[MJH_MAXC];          // blocks of each component per MCU (h * v; 1 in a single-component scan)
+  int bpm;                   // blocks per MCU
+  int canon[10];             // block-in-MCU index b -> the smallest b' from which the same sequence of tables follows: states that differ only in
+                             // such b decode alike for ever (three components on one table pair never tell b), so they count as one state
+  int ri;                    // restart interval in MCUs (no interval: the scan's MCU count)
+  int mcus, mcus_per_row;    // single-component scan: the component's real blocks, raster order (per_scan_setup jdinput.c:116-140)
+  long long diff_off;        // element offset of the scan's first component inside one image's DC-difference array
+};
+
+// one restart segment: bytes [off, off + len) of the batch buffer (no marker inside), MCUs [mcu0, mcu0 + nmcu) of its scan
+struct MjhDecSeg {
+  unsigned long long off;
+  unsigned len;
+  int scan;
+  int mcu0, nmcu;
+  int sub0, nsub;            // its subsequences: entries [sub0, sub0 + nsub) of the batch's subsequence arrays
+};
+
+// decoder state between two code words: p = bit position inside the segment (never inside a stuffed zero byte), k = next
+// coefficient position of the block in progress (0: its DC symbol comes next), b = block inside the MCU; n = blocks
+// completed inside the subsequence the record belongs to (not part of the comparison)
+struct MjhDecState { unsigned p, kb, n, pad; };
+struct MjhDecCarry { unsigned p, kb; int next, active; };
+
+// per-image status bits of a transcode batch
+#define MJH_DEC_CORRUPT 1u     // the entropy-coded data does not decode to exactly the scan's blocks
+#define MJH_DEC_BADCOEF 2u     // an AC value beyond what jchuff.c:596,624 can code
+
+struct MjhDecBatch {
+  const uint8_t *bytes;            // the files, back to back
+  const MjhDecScan *scans;
+  const MjhDecSeg *segs;
+  const unsigned *sub_seg;         // subsequence -> segment (0xFFFFFFFF: padding up to the workgroup size)
+  const MjhDecTable *tables;
+  MjhDecState *state;              // [subsequence] state at its END
+  MjhDecCarry *carry;              // [subsequence] the lane that started there
+  unsigned *ord;                   // [subsequence] blocks of the segment completed in front of it
+  unsigned *changed;               // [round of the group]
+  unsigned *status;                // [image]
+  int16_t *diff;                   // [image][C.total_mcu_blocks] DC differences in scan order, dummy blocks included
+  int nsub_padded, nseg, nscan, n;
+  int S;                           // subsequence length in bytes
+};
+
+// phase 0: every lane decodes its own subsequence from the guessed state; q >= 1: one synchronisation round (exits at once when
+// round q - 1 of the group changed nothing); then block indices, the storing pass, the DC prefix sums and the scrub of damaged images
+void mjh_launch_dec_sync(const MjhConst &C, const MjhDecBatch &B, int q, int first, hipStream_t s);
+void mjh_launch_dec_prefix(const MjhDecBatch &B, hipStream_t s);
+void mjh_launch_dec_store(const MjhConst &C, const MjhDecBatch &B, int16_t *coef_q, hipStream_t s);
+void mjh_launch_dec_dc(const MjhConst &C, const MjhDecBatch &B, int16_t *coef_q, hipStream_t s);
+void mjh_launch_dec_scrub(const MjhConst &C, const MjhDecBatch &B, int16_t *coef_q, void *meta, hipStream_t s);
+// after the encode: image i's JFIF version / density bytes (7 bytes at file offset 11) and its status from the encoder's own checks
+void mjh_launch_dec_finish(const uint8_t *jfif7, int patch, uint8_t *out, size_t out_stride, const void *meta, unsigned *status, int n, hipStream_t s);
+#endif

@@ -25,6 +25,7 @@
 #include "mjh_internal.h"
 #include "mjh_launch.h"
 #include "mjh_lossless.h"
+#include "mjh_decode.h"
 #include "mjh_guard.h"
 #include "mjh_numa.h"
 #include "mjh_arith_table.h"
@@ -402,6 +403,20 @@ struct mjh_encoder {
   LlConst L{};
   unsigned *d_ll_hist = nullptr, *d_ll_len = nullptr, *d_ll_off = nullptr, *d_ll_segE = nullptr;
   int ll_sos_off[4] = { 0, 0, 0, 0 };   // scan k's SOS (the first with the DRI in front) is d_sos[ll_sos_off[k], ll_sos_off[k + 1])
+  // mjh_transcode_host (mjh_decode.hip): the batch's files and descriptor tables (pinned staging + device copy, grown on demand),
+  // the decoder's per-subsequence arrays, per-image status
+  int dec_subseq = 512;                 // MJH_DECODE_SUBSEQ: bytes per subsequence, 0 = one lane per restart segment (the default: profiles/transcode_bench.md)
+  bool tc_preloaded = false;            // run_pipeline: the coefficient planes are in d_q already (no k_import_coefs)
+  bool tc_batch[2] = { false, false };  // the results in arena b come from mjh_transcode_host: h_tstat[b] holds their status
+  uint8_t *h_tc = nullptr, *d_tc = nullptr; size_t tc_cap = 0;
+  uint8_t *h_tdesc = nullptr, *d_tdesc = nullptr; size_t tdesc_cap = 0;
+  void *d_tsub = nullptr; size_t tsub_cap = 0;      // MjhDecState + MjhDecCarry + ord per subsequence
+  int16_t *d_tdiff = nullptr;
+  unsigned *d_tstat = nullptr, *d_tchanged = nullptr, *h_tstat[2] = { nullptr, nullptr }, *h_tflag = nullptr;
+  std::vector<int> tc_code; std::vector<std::string> tc_text;   // per file of the last transcode batch: what the host found
+  int tc_n = 0, tc_rounds = 0, tc_syncs = 0, tc_S = 0;
+  bool tc_queued = false;               // the last mjh_transcode_host call got as far as queueing its batch (else only the host's findings exist)
+  hipEvent_t tc_ev[5] = { nullptr, nullptr, nullptr, nullptr, nullptr }; bool tc_timed = false;
 };
 
 static long div_round_up(long a, long b) { return (a + b - 1) / b; }
@@ -846,6 +861,9 @@ static void free_all(mjh_encoder *e)
   if (e->d2h_stream) (void)hipStreamDestroy(e->d2h_stream);
   if (e->h_plin) (void)hipHostFree(e->h_plin);
   if (e->h_cfin) (void)hipHostFree(e->h_cfin);
+  for (void *q : { (void *)e->d_tc, (void *)e->d_tdesc, e->d_tsub, (void *)e->d_tdiff, (void *)e->d_tstat, (void *)e->d_tchanged }) if (q) (void)mjh_guard_free(q);
+  for (void *q : { (void *)e->h_tc, (void *)e->h_tdesc, (void *)e->h_tstat[0], (void *)e->h_tstat[1], (void *)e->h_tflag }) if (q) (void)hipHostFree(q);
+  for (hipEvent_t ev : e->tc_ev) if (ev) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : e->prof_events) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : e->side_events) (void)hipEventDestroy(ev);
   if (e->copy_done) (void)hipEventDestroy(e->copy_done);
@@ -1084,6 +1102,7 @@ extern "C" int mjh_encoder_create(const mjh_params *p, int max_batch, int device
   e->dc_window_ok = 1;
   for (int i = 0; i < C.ncomp; i++) if (p->quantval[p->quant_tbl_no[i]][0] < 5) e->dc_window_ok = 0;
   if (const char *v = getenv("MJH_DC_SPEC")) e->dc_spec = atoi(v);
+  if (const char *v = getenv("MJH_DECODE_SUBSEQ")) { e->dec_subseq = atoi(v); if (e->dec_subseq < 0 || (e->dec_subseq > 0 && e->dec_subseq < 16)) e->dec_subseq = 16; }   // (a code word + its value bits + stuffing stay inside two subsequences)
   HIPCHK_E(mjh_dmalloc((void **)&e->d_len16, B * (size_t)C.total_mcu_blocks * 2));
   HIPCHK_E(mjh_dmalloc((void **)&e->d_off32, B * (size_t)C.total_mcu_blocks * 4));
   e->chunks = (C.total_mcu_blocks + 2047) / 2048;
@@ -1595,7 +1614,9 @@ static int run_pipeline(mjh_encoder *e, const void *d_pixels, size_t row_pitch, 
   HIPCHK(hipMemcpyAsync(e->d_tabs, e->d_tabs_init, (size_t)n * spi * sizeof(MjhHuffTable), hipMemcpyDeviceToDevice, s));
   if (!coef_src && e->fdct_div_zero)
     return fail(MJH_EINVAL, "a quantization step of 8192, 16384 or 24576 with 8-bit samples: the reference's FDCT manager divides by zero there (compute_reciprocal, jcdctmgr.c:182-203 with `quantval << 3` as its UINT16 argument)");
-  if (coef_src) {    // jpeg_write_coefficients: the caller's quantized blocks go straight to the entropy-coding passes
+  if (coef_src && e->tc_preloaded) {
+    // mjh_transcode_host: the decoder kernels have left the planes in d_q (and the status in d_meta)
+  } else if (coef_src) {    // jpeg_write_coefficients: the caller's quantized blocks go straight to the entropy-coding passes
     pr.mark("import_coefs");
     mjh_launch_import_coefs(C, *coef_src, e->d_q, e->d_meta, n, s);
   } else {
@@ -2295,6 +2316,7 @@ static int queue_pack(mjh_encoder *e, int b, int n)
   e->res_buf = b;
   e->res_n[b] = n;
   e->res_waited[b] = false;
+  e->tc_batch[b] = false;
   return MJH_OK;
 }
 
@@ -2465,6 +2487,12 @@ static int wait_results(mjh_encoder *e, int b)
   const unsigned long long err = e->h_tab[b][1];
   if (err & 1) return fail(MJH_ETOOSMALL, "entropy-coded data of an image exceeds the 32-bit bit-offset range of one scan / the bit-stream pool");
   if (err & 2) return fail(MJH_EHIP, "internal: scan size prediction mismatch");
+  if (e->tc_batch[b])     // mjh_transcode_host: what the decoder (and the coefficient checks behind it) found in every file
+    for (int i = 0; i < e->res_n[b]; i++)
+      if (e->h_tstat[b][i]) {
+        if (e->h_tstat[b][i] & MJH_DEC_CORRUPT) return fail(MJH_EINVAL, "file %d: corrupt or truncated entropy-coded data (mjh_transcode_status tells which files of the batch are good)", i);
+        return fail(MJH_EINVAL, "image %d holds a DCT coefficient out of range (JERR_BAD_DCT_COEF, jchuff.c:489,596,624)", i);
+      }
   return MJH_OK;
 }
 
@@ -2623,6 +2651,344 @@ extern "C" int mjh_encode_planes_host(mjh_encoder *e, const void *const planes[M
   for (int c = 0; c < e->C.ncomp; c++) { ps.base[c] = e->d_plin + off[c]; ps.stride[c] = (long long)per_image; }
   { const int rcw = wait_pending_pack(e, e->stream); if (rcw) return rcw; }
   return run_pipeline(e, nullptr, 0, 0, n, e->stream, &ps);
+}
+
+
+// ---- re-compressing files: JPEG bytes -> device Huffman decoder (mjh_decode.hip) -> the entropy-coding passes ----------------------
+// The decoder's view of one Huffman table (ITU-T T.81 C.2 code assignment, F.2.2.3 decoding tables; what jpeg_make_d_derived_tbl
+// jdhuff.c:143-261 derives, with its checks): canonical codes length by length, the first 8 bits of every short code as a direct look-up
+static bool make_dec_table(const uint8_t bits[17], const uint8_t vals[256], bool is_dc, MjhDecTable *T)
+{
+  memset(T, 0, sizeof(*T));
+  unsigned code = 0;
+  int idx = 0;
+  for (int len = 1; len <= 16; len++, code <<= 1) {
+    const int cnt = bits[len];
+    T->maxcode[len] = -1;
+    if (!cnt) continue;
+    if (idx + cnt > 256 || code + (unsigned)cnt >= (1u << len)) return false;      // too many symbols / an all-ones code
+    T->valoff[len] = idx - (int)code;
+    if (len <= 8)
+      for (int c = 0; c < cnt; c++) {
+        const unsigned first = (code + (unsigned)c) << (8 - len);
+        for (unsigned f = 0; f < (1u << (8 - len)); f++) T->look[first + f] = (uint16_t)((len << 8) | vals[idx + c]);
+      }
+    if (is_dc) for (int c = 0; c < cnt; c++) if (vals[idx + c] > 15) return false;   // a DC symbol is a bit count 0..15
+    code += (unsigned)cnt;
+    idx += cnt;
+    T->maxcode[len] = (int)code - 1;
+  }
+  T->maxcode[17] = 0xFFFFF;
+  memcpy(T->huffval, vals, 256);
+  return true;
+}
+
+static size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+extern "C" int mjh_transcode_host(mjh_encoder *e, const void *const jpegs[], const size_t sizes[], int n)
+{
+  if (!e || !jpegs || !sizes || n < 1 || n > e->max_batch) return fail(MJH_EINVAL, "bad arguments (n=%d, max_batch=%d)", n, e ? e->max_batch : 0);
+  if (e->lossless) return fail(MJH_EINVAL, "a lossless encoder has no DCT coefficients (jpeg_copy_critical_parameters: JERR_NOTIMPL, jctrans.c:83)");
+  if (e->p.trellis_quant)
+    return fail(MJH_EINVAL, "trellis quantization needs the unquantized DCT output: create the encoder with trellis_quant = 0 "
+                            "for re-compression (mjh_params_from_jpeg does, as jpeg_copy_critical_parameters jctrans.c:102)");
+  HIPCHK(hipSetDevice(e->device));
+  const MjhConst &C = e->C;
+  e->tc_code.assign((size_t)n, MJH_OK);
+  e->tc_text.assign((size_t)n, std::string());
+  e->tc_n = n; e->tc_rounds = 0; e->tc_syncs = 0; e->tc_timed = false; e->tc_queued = false;
+  e->tc_S = e->dec_subseq;
+  // ---- 1. marker segments of every file (a few worker threads; nothing is decoded) and the comparison with the encoder
+  std::vector<mjh_jpeg_info> infos((size_t)n);
+  CopyPool::get().run(n, [&](int i) {
+    int rc = (!jpegs[i] || !sizes[i]) ? fail(MJH_EINVAL, "empty file") : mjh_jpeg_probe(jpegs[i], sizes[i], &infos[i]);
+    if (rc == MJH_OK) {
+      const mjh_jpeg_info &f = infos[i];
+      const mjh_params &p = e->p_created;
+      static thread_local mjh_params q;
+      rc = mjh_params_from_jpeg(&f, p.compress_profile, &q);
+      const char *field = nullptr;
+      if (rc == MJH_OK) {
+        if (q.image_width != p.image_width || q.image_height != p.image_height) field = "image size";
+        else if (q.num_components != p.num_components) field = "number of components";
+        else if (q.color_transform != p.color_transform || q.write_JFIF_header != p.write_JFIF_header) field = "colour space";
+        else if ((p.data_precision ? p.data_precision : 8) != 8) field = "data precision";
+        for (int c = 0; c < q.num_components && !field; c++) {
+          if (q.component_id[c] != p.component_id[c]) field = "component ids";
+          else if (q.h_samp_factor[c] != p.h_samp_factor[c] || q.v_samp_factor[c] != p.v_samp_factor[c]) field = "sampling factors";
+          else if (q.quant_tbl_no[c] != p.quant_tbl_no[c]) field = "quantization table numbers";
+          else if (memcmp(q.quantval[q.quant_tbl_no[c]], p.quantval[p.quant_tbl_no[c]], sizeof(q.quantval[0])) != 0) field = "quantization tables";
+        }
+        if (field) rc = fail(MJH_EINVAL, "does not match the encoder's parameters: %s", field);
+      }
+    }
+    if (rc != MJH_OK) { e->tc_code[(size_t)i] = rc; e->tc_text[(size_t)i] = g_err; }
+  });
+  // ---- 2. descriptors: scans, restart segments (RSTn positions: a byte search), subsequences, derived Huffman tables
+  const int S = e->dec_subseq;
+  const int frame_mcus = C.mcus_per_row * C.mcu_rows;
+  std::vector<MjhDecScan> scans;
+  std::vector<MjhDecSeg> segs;
+  std::vector<unsigned> sub_seg;
+  std::vector<MjhDecTable> tables;
+  std::vector<size_t> file_off((size_t)n);
+  size_t total_bytes = 0;
+  int max_nsub = 1;
+  for (int i = 0; i < n; i++) { file_off[(size_t)i] = total_bytes; total_bytes += up16(sizes[i]); }
+  for (int i = 0; i < n; i++) {
+    if (e->tc_code[(size_t)i] != MJH_OK) continue;
+    const mjh_jpeg_info &f = infos[(size_t)i];
+    const uint8_t *d = (const uint8_t *)jpegs[i];
+    const size_t scans0 = scans.size(), segs0 = segs.size(), subs0 = sub_seg.size(), tabs0 = tables.size();
+    const char *why = nullptr;
+    long long diff_off = 0;
+    for (int k = 0; k < f.num_scans && !why; k++) {
+      const mjh_jpeg_scan &fs = f.scans[k];
+      MjhDecScan sc;
+      memset(&sc, 0, sizeof(sc));
+      sc.image = i;
+      sc.ncomp = fs.comps_in_scan;
+      sc.bpm = 0;
+      for (int j = 0; j < sc.ncomp; j++) {
+        const int ci = fs.component_index[j];
+        sc.comp[j] = ci;
+        sc.nb[j] = sc.ncomp == 1 ? 1 : C.c[ci].h * C.c[ci].v;
+        sc.bpm += sc.nb[j];
+        MjhDecTable T;
+        if (!make_dec_table(fs.huff_bits[2 * fs.dc_tbl_no[j]], fs.huff_vals[2 * fs.dc_tbl_no[j]], true, &T)) { why = "Bogus Huffman table definition (JERR_BAD_HUFF_TABLE)"; break; }
+        sc.dctab[j] = (int)tables.size(); tables.push_back(T);
+        if (!make_dec_table(fs.huff_bits[2 * fs.ac_tbl_no[j] + 1], fs.huff_vals[2 * fs.ac_tbl_no[j] + 1], false, &T)) { why = "Bogus Huffman table definition (JERR_BAD_HUFF_TABLE)"; break; }
+        sc.actab[j] = (int)tables.size(); tables.push_back(T);
+      }
+      if (why) break;
+      if (sc.bpm > 10) { why = "Sampling factors too large for interleaved scan (JERR_BAD_MCU_SIZE)"; break; }
+      {
+        int pair[10], nbk = 0;
+        for (int j = 0; j < sc.ncomp; j++) for (int t = 0; t < sc.nb[j]; t++) pair[nbk++] = fs.dc_tbl_no[j] * 4 + fs.ac_tbl_no[j];
+        for (int b = 0; b < sc.bpm; b++) {
+          sc.canon[b] = b;
+          for (int c = 0; c < b; c++) {
+            bool same = true;
+            for (int t = 0; t < sc.bpm && same; t++) same = pair[(c + t) % sc.bpm] == pair[(b + t) % sc.bpm];
+            if (same) { sc.canon[b] = c; break; }
+          }
+        }
+      }
+      sc.mcus = sc.ncomp == 1 ? C.c[sc.comp[0]].nblk : frame_mcus;
+      sc.mcus_per_row = sc.ncomp == 1 ? C.c[sc.comp[0]].wib : C.mcus_per_row;
+      sc.ri = (fs.restart_interval && (long long)fs.restart_interval < sc.mcus) ? (int)fs.restart_interval : sc.mcus;
+      sc.diff_off = diff_off;
+      diff_off += (long long)sc.mcus * sc.bpm;
+      if (diff_off > C.total_mcu_blocks) { why = "internal: DC difference array too small"; break; }
+      if (fs.data_size >= ((size_t)1 << 28)) { why = "a scan of 256 MB or more (bit positions inside a restart segment are 32-bit)"; break; }
+      // restart segments: RSTn markers are the only 0xFF not followed by 0x00 inside the range (mjh_jpeg_probe)
+      const int nseg_expected = (sc.mcus + sc.ri - 1) / sc.ri;
+      const size_t a = fs.data_offset, b = a + fs.data_size;
+      size_t seg_start = a, q = a;
+      int k_seg = 0;
+      const size_t sub_first = sub_seg.size();
+      auto close_seg = [&](size_t end) {
+        MjhDecSeg sg;
+        memset(&sg, 0, sizeof(sg));
+        sg.off = file_off[(size_t)i] + seg_start;
+        sg.len = (unsigned)(end - seg_start);
+        sg.scan = (int)scans.size();
+        sg.mcu0 = k_seg * sc.ri;
+        sg.nmcu = sc.mcus - sg.mcu0 < sc.ri ? sc.mcus - sg.mcu0 : sc.ri;
+        sg.sub0 = (int)sub_seg.size();
+        sg.nsub = S > 0 ? (int)((sg.len + (unsigned)S - 1) / (unsigned)S) : 1;
+        if (sg.nsub < 1) sg.nsub = 1;
+        if (sg.nsub > max_nsub) max_nsub = sg.nsub;
+        for (int t = 0; t < sg.nsub; t++) sub_seg.push_back((unsigned)segs.size());
+        segs.push_back(sg);
+        k_seg++;
+      };
+      while (fs.restart_markers && q < b && !why) {      // (a scan without RSTn markers -- the probe counted them -- is one segment: no second search)
+        const uint8_t *ff = (const uint8_t *)memchr(d + q, 0xFF, b - q);
+        if (!ff) break;
+        q = (size_t)(ff - d);
+        if (q + 1 >= b) break;
+        if (d[q + 1] == 0) { q += 2; continue; }
+        size_t r = q + 1;
+        while (r < b && d[r] == 0xFF) r++;
+        if (r >= b) break;
+        // RSTn: its number is checked modulo 8 (read_restart_marker jdmarker.c:1010-1035), one marker per interval
+        if (k_seg + 1 >= nseg_expected || d[r] != 0xD0 + (k_seg & 7)) { why = "Corrupt JPEG data: unexpected restart marker in the entropy-coded data (JWRN_MUST_RESYNC)"; break; }
+        close_seg(q);
+        seg_start = q = r + 1;
+      }
+      if (why) break;
+      close_seg(b);
+      if (k_seg != nseg_expected) { why = "Corrupt JPEG data: restart markers missing in the entropy-coded data (JWRN_HIT_MARKER)"; break; }
+      while ((sub_seg.size() - sub_first) % MJH_DEC_WG) sub_seg.push_back(0xFFFFFFFFu);   // a workgroup serves one (image, scan)
+      scans.push_back(sc);
+    }
+    if (why) {
+      scans.resize(scans0); segs.resize(segs0); sub_seg.resize(subs0); tables.resize(tabs0);
+      e->tc_code[(size_t)i] = MJH_EINVAL; e->tc_text[(size_t)i] = why;
+    }
+  }
+  for (int i = 0; i < n; i++)
+    if (e->tc_code[(size_t)i] != MJH_OK) return fail(e->tc_code[(size_t)i], "file %d: %s", i, e->tc_text[(size_t)i].c_str());
+  // ---- 3. staging: the files as they are + one descriptor block, two host->device copies
+  int rc = host_buffers(e);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(e->stream));   // the staging buffers may still feed the previous batch
+  e->tc_syncs++;
+  const size_t nsubp = sub_seg.size();
+  const size_t o_scans = 0, o_segs = up16(o_scans + scans.size() * sizeof(MjhDecScan)), o_subs = up16(o_segs + segs.size() * sizeof(MjhDecSeg)),
+               o_tabs = up16(o_subs + nsubp * 4), o_jfif = up16(o_tabs + tables.size() * sizeof(MjhDecTable)), desc_bytes = up16(o_jfif + (size_t)n * 8);
+  if (total_bytes > e->tc_cap) {
+    if (e->d_tc) { (void)mjh_guard_free(e->d_tc); e->d_tc = nullptr; }
+    if (e->h_tc) { (void)hipHostFree(e->h_tc); e->h_tc = nullptr; }
+    e->tc_cap = 0;
+    const size_t cap = total_bytes + total_bytes / 4;
+    HIPCHK(mjh_dmalloc((void **)&e->d_tc, cap));
+    HIPCHK(mjh_numa_host_alloc((void **)&e->h_tc, cap, hipHostMallocDefault, e->device));
+    e->tc_cap = cap;
+  }
+  if (desc_bytes > e->tdesc_cap) {
+    if (e->d_tdesc) { (void)mjh_guard_free(e->d_tdesc); e->d_tdesc = nullptr; }
+    if (e->h_tdesc) { (void)hipHostFree(e->h_tdesc); e->h_tdesc = nullptr; }
+    e->tdesc_cap = 0;
+    const size_t cap = desc_bytes + desc_bytes / 4;
+    HIPCHK(mjh_dmalloc((void **)&e->d_tdesc, cap));
+    HIPCHK(mjh_numa_host_alloc((void **)&e->h_tdesc, cap, hipHostMallocDefault, e->device));
+    e->tdesc_cap = cap;
+  }
+  const size_t per_sub = sizeof(MjhDecState) + sizeof(MjhDecCarry) + sizeof(unsigned);
+  if (nsubp * per_sub > e->tsub_cap) {
+    if (e->d_tsub) { (void)mjh_guard_free(e->d_tsub); e->d_tsub = nullptr; }
+    e->tsub_cap = 0;
+    const size_t cap = nsubp * per_sub + nsubp * per_sub / 4;
+    HIPCHK(mjh_dmalloc(&e->d_tsub, cap));
+    e->tsub_cap = cap;
+  }
+  if (!e->d_tdiff) {
+    HIPCHK(mjh_dmalloc((void **)&e->d_tdiff, (size_t)e->max_batch * (size_t)C.total_mcu_blocks * 2));
+    HIPCHK(mjh_dmalloc((void **)&e->d_tstat, (size_t)e->max_batch * 4));
+    HIPCHK(mjh_dmalloc((void **)&e->d_tchanged, 64 * 4));
+    for (int b = 0; b < 2; b++) HIPCHK(mjh_numa_host_alloc((void **)&e->h_tstat[b], (size_t)e->max_batch * 4, hipHostMallocDefault, e->device));
+    HIPCHK(mjh_numa_host_alloc((void **)&e->h_tflag, 64, hipHostMallocDefault, e->device));
+    for (hipEvent_t &ev : e->tc_ev) HIPCHK(hipEventCreate(&ev));
+  }
+  CopyPool::get().run(n, [&](int i) { memcpy(e->h_tc + file_off[(size_t)i], jpegs[i], sizes[i]); });
+  memcpy(e->h_tdesc + o_scans, scans.data(), scans.size() * sizeof(MjhDecScan));
+  memcpy(e->h_tdesc + o_segs, segs.data(), segs.size() * sizeof(MjhDecSeg));
+  memcpy(e->h_tdesc + o_subs, sub_seg.data(), nsubp * 4);
+  memcpy(e->h_tdesc + o_tabs, tables.data(), tables.size() * sizeof(MjhDecTable));
+  for (int i = 0; i < n; i++) {       // this file's APP0 fields (jctrans.c:162-170): version only from a 1.x file, density whenever JFIF was seen
+    const mjh_jpeg_info &f = infos[(size_t)i];
+    uint8_t *j = e->h_tdesc + o_jfif + (size_t)i * 8;
+    j[0] = 1; j[1] = 1; j[2] = 0; j[3] = 0; j[4] = 1; j[5] = 0; j[6] = 1; j[7] = 0;      // jpeg_set_defaults: 1.01, no unit, 1:1
+    if (f.saw_JFIF_marker) {
+      if (f.JFIF_major_version == 1) { j[0] = (uint8_t)f.JFIF_major_version; j[1] = (uint8_t)f.JFIF_minor_version; }
+      j[2] = (uint8_t)f.density_unit; j[3] = (uint8_t)(f.X_density >> 8); j[4] = (uint8_t)f.X_density; j[5] = (uint8_t)(f.Y_density >> 8); j[6] = (uint8_t)f.Y_density;
+    }
+  }
+  hipStream_t s = e->stream;
+  HIPCHK(hipMemcpyAsync(e->d_tc, e->h_tc, total_bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(e->d_tdesc, e->h_tdesc, desc_bytes, hipMemcpyHostToDevice, s));
+  // ---- 4. the decoder
+  MjhDecBatch B;
+  memset(&B, 0, sizeof(B));
+  B.bytes = e->d_tc;
+  B.scans = (const MjhDecScan *)(e->d_tdesc + o_scans);
+  B.segs = (const MjhDecSeg *)(e->d_tdesc + o_segs);
+  B.sub_seg = (const unsigned *)(e->d_tdesc + o_subs);
+  B.tables = (const MjhDecTable *)(e->d_tdesc + o_tabs);
+  B.state = (MjhDecState *)e->d_tsub;
+  B.carry = (MjhDecCarry *)((uint8_t *)e->d_tsub + nsubp * sizeof(MjhDecState));
+  B.ord = (unsigned *)((uint8_t *)e->d_tsub + nsubp * (sizeof(MjhDecState) + sizeof(MjhDecCarry)));
+  B.changed = e->d_tchanged;
+  B.status = e->d_tstat;
+  B.diff = e->d_tdiff;
+  B.nsub_padded = (int)nsubp; B.nseg = (int)segs.size(); B.nscan = (int)scans.size(); B.n = n;
+  B.S = S > 0 ? S : 1;
+  const bool timed = e->profiling != 0;
+  HIPCHK(hipMemsetAsync(e->d_q, 0, (size_t)n * C.coefs_per_image * 2, s));
+  HIPCHK(hipMemsetAsync(e->d_tdiff, 0, (size_t)n * (size_t)C.total_mcu_blocks * 2, s));
+  HIPCHK(hipMemsetAsync(e->d_tstat, 0, (size_t)n * 4, s));
+  HIPCHK(hipMemsetAsync(e->d_meta, 0, (size_t)n * sizeof(MjhImageMeta), s));
+  if (timed) HIPCHK(hipEventRecord(e->tc_ev[0], s));
+  mjh_launch_dec_sync(C, B, 0, 1, s);
+  // Synchronisation rounds in groups of launches: the rounds of a group run back to back (a round that finds the one before it
+  // unchanged returns at once), the host reads the group's last flag and launches the next group only when it was set.  A round
+  // extends the true prefix of every segment by one subsequence at least: max_nsub - 1 rounds always suffice.
+  for (int done = 0, group = 3; done < max_nsub - 1;) {
+    const int g = group < max_nsub - 1 - done ? group : max_nsub - 1 - done;
+    HIPCHK(hipMemsetAsync(e->d_tchanged, 0, 64 * 4, s));
+    for (int q = 0; q < g; q++) mjh_launch_dec_sync(C, B, q, 0, s);
+    done += g;
+    e->tc_rounds += g;
+    if (done >= max_nsub - 1) break;
+    HIPCHK(hipMemcpyAsync(e->h_tflag, e->d_tchanged + (g - 1), 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    e->tc_syncs++;
+    if (!*(volatile unsigned *)e->h_tflag) break;
+    group = group * 2 < 64 ? group * 2 : 64;
+  }
+  if (timed) HIPCHK(hipEventRecord(e->tc_ev[1], s));
+  mjh_launch_dec_prefix(B, s);
+  if (timed) HIPCHK(hipEventRecord(e->tc_ev[2], s));
+  mjh_launch_dec_store(C, B, e->d_q, s);
+  if (timed) HIPCHK(hipEventRecord(e->tc_ev[3], s));
+  mjh_launch_dec_dc(C, B, e->d_q, s);
+  mjh_launch_dec_scrub(C, B, e->d_q, e->d_meta, s);
+  if (timed) { HIPCHK(hipEventRecord(e->tc_ev[4], s)); e->tc_timed = true; }
+  HIPCHK(hipGetLastError());
+  // ---- 5. the entropy-coding passes, as for coefficient input; then this file's APP0 fields and the hand-over
+  const int b = (int)(e->host_calls & 1u);
+  e->host_calls++;
+  MjhCoefSrc cs;
+  memset(&cs, 0, sizeof(cs));
+  e->tc_preloaded = true;
+  rc = run_pipeline(e, nullptr, 0, 0, n, s, nullptr, &cs, nullptr, e->host_calls > 1 ? e->ev_packed[b ^ 1] : nullptr);
+  e->tc_preloaded = false;
+  if (rc) return rc;
+  mjh_launch_dec_finish(e->d_tdesc + o_jfif, e->p.write_JFIF_header ? 1 : 0, e->d_out, e->out_stride, e->d_meta, e->d_tstat, n, s);
+  HIPCHK(hipMemcpyAsync(e->h_tstat[b], e->d_tstat, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  rc = queue_pack(e, b, n);
+  if (rc) return rc;
+  e->tc_batch[b] = true;
+  e->tc_queued = true;
+  return MJH_OK;
+}
+
+extern "C" int mjh_transcode_status(mjh_encoder *e, int i, const char **text)
+{
+  if (!e || i < 0 || i >= e->tc_n) return fail(MJH_EINVAL, "bad file index");
+  if (text) *text = "";
+  if (e->tc_code[(size_t)i] == MJH_OK && e->tc_queued && e->res_buf >= 0 && e->tc_batch[e->res_buf] && i < e->res_n[e->res_buf]) {
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipEventSynchronize(e->ev_packed[e->res_buf]));
+    const unsigned st = e->h_tstat[e->res_buf][i];
+    if (st) {
+      e->tc_code[(size_t)i] = MJH_EINVAL;
+      e->tc_text[(size_t)i] = (st & MJH_DEC_CORRUPT) ? "Corrupt JPEG data: the entropy-coded data does not decode to the scan's blocks (premature end, extraneous bytes or a bad Huffman code; the reference warns: JWRN_HIT_MARKER / JWRN_EXTRANEOUS_DATA / JWRN_HUFF_BAD_CODE)"
+                                                         : "a DCT coefficient out of range (JERR_BAD_DCT_COEF, jchuff.c:489,596,624)";
+    }
+  }
+  if (text) *text = e->tc_text[(size_t)i].c_str();
+  if (e->tc_code[(size_t)i] != MJH_OK) return fail(e->tc_code[(size_t)i], "file %d: %s", i, e->tc_text[(size_t)i].c_str());
+  return MJH_OK;
+}
+
+extern "C" int mjh_transcode_stats(mjh_encoder *e, int *subseq, int *rounds, int *host_syncs, float ms[4])
+{
+  if (!e) return fail(MJH_EINVAL, "null encoder");
+  if (subseq) *subseq = e->tc_S;
+  if (rounds) *rounds = e->tc_rounds;
+  if (host_syncs) *host_syncs = e->tc_syncs;
+  if (ms) {
+    for (int k = 0; k < 4; k++) ms[k] = 0.f;
+    if (e->tc_timed) {
+      HIPCHK(hipSetDevice(e->device));
+      HIPCHK(hipEventSynchronize(e->tc_ev[4]));
+      for (int k = 0; k < 4; k++) HIPCHK(hipEventElapsedTime(&ms[k], e->tc_ev[k], e->tc_ev[k + 1]));
+    }
+  }
+  return MJH_OK;
 }
 
 extern "C" int mjh_encoder_sync(mjh_encoder *e)

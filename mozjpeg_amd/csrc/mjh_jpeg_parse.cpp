@@ -1,0 +1,246 @@
+// mjh_jpeg_parse.cpp -- host side of the re-compression path that needs no device: the marker segments of a JPEG file
+// (jdmarker.c) and the parameters jpeg_copy_critical_parameters derives from them (jctrans.c:75-171).  Nothing here decodes
+// a Huffman symbol: the entropy-coded data is only searched for 0xFF to find where a scan ends.
+#include <stdarg.h>
+#include <stdio.h>
+#include <string.h>
+
+#include "../../include/mozjpeg_hip.h"
+
+int mjh_internal_fail(int code, const char *msg);
+
+static int pfail(int code, const char *fmt, ...)
+{
+  char buf[400];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  return mjh_internal_fail(code, buf);
+}
+
+static const int kNatural[64] = {
+  0,  1,  8, 16,  9,  2,  3, 10, 17, 24, 32, 25, 18, 11,  4,  5,
+  12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13,  6,  7, 14, 21, 28,
+  35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
+  58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63 };
+
+extern "C" int mjh_jpeg_probe(const void *jpeg, size_t size, mjh_jpeg_info *info)
+{
+  if (!jpeg || !info) return pfail(MJH_EINVAL, "bad arguments");
+  const uint8_t *d = (const uint8_t *)jpeg;
+  memset(info, 0, sizeof(*info));
+  if (size < 4 || d[0] != 0xFF || d[1] != 0xD8) return pfail(MJH_EINVAL, "Not a JPEG file: no SOI marker (JERR_NO_SOI)");
+  // the tables in force (DHT segments redefine them between scans)
+  static thread_local uint8_t hbits[8][17], hvals[8][256];
+  int hdef = 0;
+  unsigned ri = 0;
+  bool saw_sof = false, saw_eoi = false;
+  int comp_scans[MJH_MAX_COMPS] = { 0, 0, 0, 0 };
+  size_t pos = 2;
+  while (!saw_eoi) {
+    // next_marker (jdmarker.c:910-955): any number of 0xFF fill bytes, then the code
+    if (pos >= size) return pfail(MJH_EINVAL, "Premature end of JPEG file (JWRN_JPEG_EOF)");
+    if (d[pos] != 0xFF) return pfail(MJH_EINVAL, "Corrupt JPEG data: extraneous bytes before marker at offset %zu (JWRN_EXTRANEOUS_DATA)", pos);
+    while (pos < size && d[pos] == 0xFF) pos++;
+    if (pos >= size) return pfail(MJH_EINVAL, "Premature end of JPEG file (JWRN_JPEG_EOF)");
+    const int m = d[pos++];
+    if (m == 0) return pfail(MJH_EINVAL, "Corrupt JPEG data: extraneous bytes before marker at offset %zu (JWRN_EXTRANEOUS_DATA)", pos);
+    if (m == 0xD9) { saw_eoi = true; break; }
+    if (m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;              // TEM, a stray RSTn: no parameters
+    if (m == 0xD8) return pfail(MJH_EINVAL, "Invalid JPEG file structure: two SOI markers (JERR_SOI_DUPLICATE)");
+    if (pos + 2 > size) return pfail(MJH_EINVAL, "Premature end of JPEG file (JWRN_JPEG_EOF)");
+    const size_t len = ((size_t)d[pos] << 8) | d[pos + 1];
+    if (len < 2) return pfail(MJH_EINVAL, "Bogus marker length (JERR_BAD_LENGTH)");
+    if (pos + len > size) return pfail(MJH_EINVAL, "Premature end of JPEG file (JWRN_JPEG_EOF)");
+    const uint8_t *s = d + pos + 2;
+    const size_t n = len - 2;
+    pos += len;
+    switch (m) {
+    case 0xC0: case 0xC1: case 0xC2: case 0xC3: case 0xC9: case 0xCA: case 0xCB:
+    case 0xC5: case 0xC6: case 0xC7: case 0xCD: case 0xCE: case 0xCF: {
+      if (m == 0xC2) return pfail(MJH_EUNSUPPORTED, "progressive source file (SOF2): only sequential Huffman-coded files are decoded on the device");
+      if (m == 0xC3) return pfail(MJH_EUNSUPPORTED, "lossless source file (SOF3): jpeg_copy_critical_parameters refuses it as well (JERR_NOTIMPL, jctrans.c:83)");
+      if (m == 0xC9 || m == 0xCA || m == 0xCB) return pfail(MJH_EUNSUPPORTED, "arithmetic-coded source file (SOF%d)", m - 0xC0);
+      if (m != 0xC0 && m != 0xC1) return pfail(MJH_EUNSUPPORTED, "Unsupported JPEG process: SOF type 0x%02x (JERR_SOF_UNSUPPORTED)", m);
+      if (saw_sof) return pfail(MJH_EINVAL, "Invalid JPEG file structure: two SOF markers (JERR_SOF_DUPLICATE)");
+      if (n < 6) return pfail(MJH_EINVAL, "Bogus marker length (JERR_BAD_LENGTH)");
+      info->sof_type = m - 0xC0;
+      info->data_precision = s[0];
+      info->image_height = (s[1] << 8) | s[2];
+      info->image_width = (s[3] << 8) | s[4];
+      info->num_components = s[5];
+      if (info->image_height == 0) return pfail(MJH_EUNSUPPORTED, "image height 0 in the frame header: a DNL marker would define it, which is not supported");
+      if (info->image_width <= 0 || info->num_components <= 0) return pfail(MJH_EINVAL, "Empty JPEG image (JERR_EMPTY_IMAGE)");
+      if (n != 6 + 3 * (size_t)info->num_components) return pfail(MJH_EINVAL, "Bogus marker length (JERR_BAD_LENGTH)");
+      if (info->data_precision != 8) return pfail(MJH_EUNSUPPORTED, "%d-bit source file: only 8-bit samples", info->data_precision);
+      if (info->num_components != 1 && info->num_components != 3)
+        return pfail(MJH_EUNSUPPORTED, "%d components in the source file: 1 or 3 are supported", info->num_components);
+      for (int c = 0; c < info->num_components; c++) {
+        info->component_id[c] = s[6 + 3 * c];
+        info->h_samp_factor[c] = s[7 + 3 * c] >> 4;
+        info->v_samp_factor[c] = s[7 + 3 * c] & 15;
+        info->quant_tbl_no[c] = s[8 + 3 * c];
+        if (info->h_samp_factor[c] < 1 || info->h_samp_factor[c] > 4 || info->v_samp_factor[c] < 1 || info->v_samp_factor[c] > 4)
+          return pfail(MJH_EINVAL, "Bogus sampling factors (JERR_BAD_SAMPLING)");
+        if (info->quant_tbl_no[c] > 3) return pfail(MJH_EINVAL, "Quantization table 0x%02x was not defined (JERR_NO_QUANT_TABLE)", info->quant_tbl_no[c]);
+      }
+      saw_sof = true;
+      break;
+    }
+    case 0xC4: {          // DHT (get_dht jdmarker.c:455-533): any number of tables
+      size_t o = 0;
+      while (o < n) {
+        if (n - o < 17) return pfail(MJH_EINVAL, "Bogus marker length (JERR_BAD_LENGTH)");
+        const int idx = s[o];
+        int count = 0;
+        for (int i = 1; i <= 16; i++) count += s[o + i];
+        if (count > 256 || (size_t)count > n - o - 17) return pfail(MJH_EINVAL, "Bogus Huffman table definition (JERR_BAD_HUFF_TABLE)");
+        if ((idx & 0xEF) > 3) return pfail(MJH_EINVAL, "Bogus DHT index %d (JERR_DHT_INDEX)", idx);
+        const int slot = 2 * (idx & 3) + ((idx & 0x10) ? 1 : 0);
+        hbits[slot][0] = 0;
+        memcpy(&hbits[slot][1], s + o + 1, 16);
+        memset(hvals[slot], 0, 256);
+        memcpy(hvals[slot], s + o + 17, (size_t)count);
+        hdef |= 1 << slot;
+        o += 17 + (size_t)count;
+      }
+      break;
+    }
+    case 0xCC: return pfail(MJH_EUNSUPPORTED, "arithmetic-coding conditioning (DAC) in the source file");
+    case 0xDB: {          // DQT (get_dqt jdmarker.c:536-620)
+      size_t o = 0;
+      while (o < n) {
+        const int pq = s[o] >> 4, t = s[o] & 15;
+        if (t > 3) return pfail(MJH_EINVAL, "Bogus DQT index %d (JERR_DQT_INDEX)", t);
+        const size_t need = pq ? 128 : 64;
+        if (n - o - 1 < need) return pfail(MJH_EINVAL, "Bogus marker length (JERR_BAD_LENGTH)");
+        uint16_t q[64];
+        for (int i = 0; i < 64; i++) q[kNatural[i]] = pq ? (uint16_t)((s[o + 1 + 2 * i] << 8) | s[o + 2 + 2 * i]) : s[o + 1 + i];
+        if (info->num_scans > 0 && ((info->quant_defined >> t) & 1) && memcmp(q, info->quantval[t], sizeof(q)) != 0)
+          return pfail(MJH_EINVAL, "Cannot transcode due to multiple use of quantization table %d (JERR_MISMATCHED_QUANT_TABLE)", t);
+        memcpy(info->quantval[t], q, sizeof(q));
+        info->quant_defined |= 1 << t;
+        o += 1 + need;
+      }
+      break;
+    }
+    case 0xDC: return pfail(MJH_EUNSUPPORTED, "DNL marker in the source file");
+    case 0xDD:
+      if (n != 2) return pfail(MJH_EINVAL, "Bogus marker length (JERR_BAD_LENGTH)");
+      ri = ((unsigned)s[0] << 8) | s[1];
+      break;
+    case 0xE0:            // get_interesting_appn / examine_app0 (jdmarker.c:623-690)
+      if (n >= 14 && s[0] == 0x4A && s[1] == 0x46 && s[2] == 0x49 && s[3] == 0x46 && s[4] == 0) {
+        info->saw_JFIF_marker = 1;
+        info->JFIF_major_version = s[5];
+        info->JFIF_minor_version = s[6];
+        info->density_unit = s[7];
+        info->X_density = (s[8] << 8) | s[9];
+        info->Y_density = (s[10] << 8) | s[11];
+      }
+      break;
+    case 0xEE:            // examine_app14 (jdmarker.c:693-718)
+      if (n >= 12 && s[0] == 0x41 && s[1] == 0x64 && s[2] == 0x6F && s[3] == 0x62 && s[4] == 0x65) {
+        info->saw_Adobe_marker = 1;
+        info->Adobe_transform = s[11];
+      }
+      break;
+    case 0xDA: {          // SOS (get_sos jdmarker.c:312-393) + the entropy-coded segment behind it
+      if (!saw_sof) return pfail(MJH_EINVAL, "Invalid JPEG file structure: SOS before SOF (JERR_SOS_NO_SOF)");
+      if (n < 1) return pfail(MJH_EINVAL, "Bogus marker length (JERR_BAD_LENGTH)");
+      const int nc = s[0];
+      if (n != (size_t)(2 * nc + 4) || nc < 1 || nc > MJH_MAX_COMPS) return pfail(MJH_EINVAL, "Bogus marker length (JERR_BAD_LENGTH)");
+      if (info->num_scans >= MJH_MAX_FILE_SCANS) return pfail(MJH_EINVAL, "more than %d scans in a sequential file", MJH_MAX_FILE_SCANS);
+      mjh_jpeg_scan *sc = &info->scans[info->num_scans];
+      sc->comps_in_scan = nc;
+      for (int i = 0; i < nc; i++) {
+        const int id = s[1 + 2 * i];
+        int ci = -1;
+        for (int c = 0; c < info->num_components; c++) if (info->component_id[c] == id) { ci = c; break; }
+        if (ci < 0) return pfail(MJH_EINVAL, "Invalid component ID %d in SOS (JERR_BAD_COMPONENT_ID)", id);
+        if (i > 0 && ci <= sc->component_index[i - 1]) return pfail(MJH_EINVAL, "Invalid component ID %d in SOS (JERR_BAD_COMPONENT_ID)", id);
+        if (comp_scans[ci]++) return pfail(MJH_EINVAL, "component %d is coded by two scans of a sequential file (JERR_BAD_SCAN_SCRIPT)", ci);
+        sc->component_index[i] = ci;
+        sc->dc_tbl_no[i] = s[2 + 2 * i] >> 4;
+        sc->ac_tbl_no[i] = s[2 + 2 * i] & 15;
+        if (sc->dc_tbl_no[i] > 3 || sc->ac_tbl_no[i] > 3 || !((hdef >> (2 * sc->dc_tbl_no[i])) & 1) || !((hdef >> (2 * sc->ac_tbl_no[i] + 1)) & 1))
+          return pfail(MJH_EINVAL, "Huffman table 0x%02x was not defined (JERR_NO_HUFF_TABLE)", s[2 + 2 * i]);
+        if (!((info->quant_defined >> info->quant_tbl_no[ci]) & 1))
+          return pfail(MJH_EINVAL, "Quantization table 0x%02x was not defined (JERR_NO_QUANT_TABLE)", info->quant_tbl_no[ci]);
+      }
+      const uint8_t *t = s + 1 + 2 * nc;
+      if (t[0] != 0 || t[1] != 63 || t[2] != 0)
+        return pfail(MJH_EINVAL, "Invalid progressive parameters Ss=%d Se=%d Ah=%d Al=%d in a sequential file (JERR_BAD_PROGRESSION)", t[0], t[1], t[2] >> 4, t[2] & 15);
+      sc->restart_interval = ri;
+      sc->huff_defined = hdef;
+      memcpy(sc->huff_bits, hbits, sizeof(hbits));
+      memcpy(sc->huff_vals, hvals, sizeof(hvals));
+      sc->data_offset = pos;
+      // the segment ends at the first 0xFF that is followed by neither 0x00 nor RSTn (fill bytes 0xFF 0xFF belong to that marker)
+      size_t q = pos;
+      unsigned nrst = 0;
+      for (;;) {
+        const uint8_t *f = q < size ? (const uint8_t *)memchr(d + q, 0xFF, size - q) : nullptr;
+        if (!f || (size_t)(f - d) + 1 >= size) return pfail(MJH_EINVAL, "Premature end of JPEG file (JWRN_JPEG_EOF)");
+        q = (size_t)(f - d);
+        const int c = d[q + 1];
+        if (c == 0) { q += 2; continue; }
+        if (c >= 0xD0 && c <= 0xD7) { nrst++; q += 2; continue; }
+        if (c == 0xFF) {                                   // fill bytes: they belong to the marker behind them
+          size_t r = q + 1;
+          while (r < size && d[r] == 0xFF) r++;
+          if (r < size && d[r] >= 0xD0 && d[r] <= 0xD7) { nrst++; q = r + 1; continue; }
+        }
+        break;
+      }
+      sc->data_size = q - pos;
+      sc->restart_markers = nrst;
+      pos = q;
+      info->num_scans++;
+      break;
+    }
+    default:              // APPn, COM and the rest: skipped (-copy none)
+      break;
+    }
+  }
+  if (!saw_sof) return pfail(MJH_EINVAL, "Invalid JPEG file structure: missing SOF marker (JERR_NO_IMAGE)");
+  if (info->num_scans == 0) return pfail(MJH_EINVAL, "JPEG datastream contains no image (JERR_NO_IMAGE)");
+  for (int c = 0; c < info->num_components; c++)
+    if (!comp_scans[c]) return pfail(MJH_EINVAL, "component %d of the source file is in no scan (JERR_MISSING_DATA)", c);
+  // default_decompress_parms (jdapimin.c:130-205)
+  if (info->num_components == 1) info->jpeg_color_space = MJH_CS_GRAYSCALE;
+  else if (info->saw_JFIF_marker) info->jpeg_color_space = MJH_CS_YCbCr;
+  else if (info->saw_Adobe_marker) info->jpeg_color_space = info->Adobe_transform == 0 ? MJH_CS_RGB : MJH_CS_YCbCr;
+  else info->jpeg_color_space = (info->component_id[0] == 82 && info->component_id[1] == 71 && info->component_id[2] == 66) ? MJH_CS_RGB : MJH_CS_YCbCr;
+  return MJH_OK;
+}
+
+extern "C" int mjh_params_from_jpeg(const mjh_jpeg_info *info, int compress_profile, mjh_params *p)
+{
+  if (!info || !p) return pfail(MJH_EINVAL, "bad arguments");
+  const int nc = info->num_components;
+  if (nc != 1 && nc != 3) return pfail(MJH_EUNSUPPORTED, "%d components", nc);
+  // jpeg_set_defaults + jpeg_set_colorspace(srcinfo->jpeg_color_space)
+  int rc = mjh_params_defaults(p, info->image_width, info->image_height, nc == 1 ? 1 : 3, nc == 1, compress_profile, 2, 2);
+  if (rc) return rc;
+  p->trellis_quant = 0;                                   // jctrans.c:102
+  p->data_precision = info->data_precision;
+  if (info->jpeg_color_space == MJH_CS_RGB) {             // jcparam.c:604-619: no JFIF, Adobe marker, every component on tables 0
+    p->color_transform = MJH_COLOR_NONE;
+    p->write_JFIF_header = 0;
+    for (int c = 0; c < 3; c++) p->dc_tbl_no[c] = p->ac_tbl_no[c] = 0;
+  }
+  for (int t = 0; t < 4; t++)
+    if ((info->quant_defined >> t) & 1) memcpy(p->quantval[t], info->quantval[t], sizeof(p->quantval[t]));
+  for (int c = 0; c < nc; c++) {
+    p->component_id[c] = info->component_id[c];
+    p->h_samp_factor[c] = info->h_samp_factor[c];
+    p->v_samp_factor[c] = info->v_samp_factor[c];
+    p->quant_tbl_no[c] = info->quant_tbl_no[c];
+    if (p->quant_tbl_no[c] < 0 || p->quant_tbl_no[c] > 3 || !((info->quant_defined >> p->quant_tbl_no[c]) & 1))
+      return pfail(MJH_EINVAL, "Quantization table 0x%02x was not defined (JERR_NO_QUANT_TABLE)", p->quant_tbl_no[c]);
+  }
+  if (p->compress_profile == MJH_PROFILE_MAX_COMPRESSION) return mjh_params_search_progression(p);   // what jpeg_set_defaults selects there (jcparam.c:497-503)
+  return MJH_OK;
+}

@@ -1,0 +1,122 @@
+#!/usr/bin/env python3
+"""Re-compression throughput on one GPU: JPEG bytes in host memory -> re-coded JPEG bytes in host memory (mjh_transcode_host +
+mjh_collect), `-revert -optimize`, against the reference's jpegtran on the same files.
+
+Workload A: 64 distinct seeded 4K 4:2:0 q75 sequential files without restart markers per call.  Workload B: 1024 files of 320x240.
+Per workload: files/s with the default subsequence length and with MJH_DECODE_SUBSEQ=0 (one lane per restart segment), alternating
+in the same run (--repeats rounds, >= --seconds timed per round after a warm-up), the run-to-run spread, the synchronisation rounds
+and host synchronisations per call, the decoder's phase times and the per-kernel times of the schedule behind it
+(mjh_set_profiling(1), a separate pass), and the yardstick: oracle/_ref/jpegtran -copy none -revert -optimize over the same files,
+16 processes at a time, files on a RAM disk.  The first call's files are compared with the reference's.
+usage: python tools/bench_transcode.py [--workloads A,B] [--seconds 2] [--repeats 3] [--subseq 512,0] [--out profiles/transcode_bench]"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import tempfile
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import torch  # noqa: E402,F401  (torch's runtime first: tests/conftest.py)
+import numpy as np  # noqa: E402,F401
+import mozjpeg_amd as M  # noqa: E402
+import oracle_lib as O  # noqa: E402
+import transcode_cases as TC  # noqa: E402
+
+SWITCHES = ["-copy", "none", "-revert", "-optimize"]
+
+
+def sources(workload):
+    if workload == "A":
+        imgs = [O.synthetic_frame(3840, 2160, seed=1234 + i) for i in range(64)]
+    else:
+        big = [O.synthetic_frame(3840, 2160, seed=77 + i) for i in range(4)]
+        imgs = [big[i % 4][y:y + 240, x:x + 320] for i, (y, x) in enumerate((y, x) for y in range(0, 1920, 120) for x in range(0, 3520, 55))][:1024]
+        assert len(imgs) == 1024
+    with ThreadPoolExecutor(16) as ex:
+        return list(ex.map(lambda a: TC.cjpeg(a, ["-revert", "-quality", "75", "-sample", "2x2"]), imgs))
+
+
+def reference_rate(files, procs=16):
+    """files/s of the reference's jpegtran, `procs` processes at a time, input and output on a RAM disk; also its output files"""
+    base = "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) else None
+    with tempfile.TemporaryDirectory(dir=base) as td:
+        for i, f in enumerate(files):
+            with open(os.path.join(td, "%d.jpg" % i), "wb") as fh:
+                fh.write(f)
+
+        def one(i):
+            subprocess.check_call([TC.JPEGTRAN] + SWITCHES + ["-outfile", os.path.join(td, "o%d.jpg" % i), os.path.join(td, "%d.jpg" % i)])
+        with ThreadPoolExecutor(procs) as ex:
+            list(ex.map(one, range(min(len(files), 2 * procs))))          # warm-up
+            t0 = time.perf_counter()
+            list(ex.map(one, range(len(files))))
+            dt = time.perf_counter() - t0
+        outs = [open(os.path.join(td, "o%d.jpg" % i), "rb").read() for i in range(len(files))]
+    return len(files) / dt, outs, base is not None
+
+
+def timed(enc, files, seconds):
+    calls, t0 = 0, time.perf_counter()
+    while True:
+        enc.submit_transcode(files)
+        enc.collect(0, copy=True)
+        calls += 1
+        dt = time.perf_counter() - t0
+        if dt >= seconds:
+            return calls * len(files) / dt
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workloads", default="A,B")
+    ap.add_argument("--seconds", type=float, default=2.0)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--subseq", default="512,0")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    result = {"switches": SWITCHES, "workloads": {}}
+    for wl in a.workloads.split(","):
+        files = sources(wl)
+        ref_rate, ref_outs, ramdisk = reference_rate(files)
+        r = {"files": len(files), "source_bytes": sum(len(f) for f in files), "reference_files_per_s": ref_rate, "reference_on_ramdisk": ramdisk, "configs": {}}
+        encs = {}
+        for s in a.subseq.split(","):
+            os.environ["MJH_DECODE_SUBSEQ"] = s
+            encs[s] = M.Encoder(M.params_from_jpeg(files[0], revert=True, optimize=True), max_batch=len(files))
+        os.environ.pop("MJH_DECODE_SUBSEQ", None)
+        for s, enc in encs.items():
+            outs = enc.transcode_host(files)
+            r["configs"][s] = {"identical_to_reference": outs == ref_outs, "stats": enc.transcode_stats(), "files_per_s": []}
+            enc.submit_transcode(files)
+            enc.collect(0)                      # warm-up
+        for _ in range(a.repeats):             # alternating
+            for s, enc in encs.items():
+                r["configs"][s]["files_per_s"].append(timed(enc, files, a.seconds))
+        for s, enc in encs.items():
+            c = r["configs"][s]
+            v = c["files_per_s"]
+            c["median_files_per_s"] = sorted(v)[len(v) // 2]
+            c["spread"] = (max(v) - min(v)) / c["median_files_per_s"]
+            c["ratio_to_reference"] = c["median_files_per_s"] / ref_rate
+            enc.set_profiling(1)
+            for _ in range(3):
+                enc.submit_transcode(files)
+                enc.collect(0)
+            c["decoder_ms"] = enc.transcode_stats()["ms"]
+            c["kernel_ms"] = enc.kernel_times()
+            enc.set_profiling(0)
+            enc.close()
+        result["workloads"][wl] = r
+        print(json.dumps({wl: r}), flush=True)
+    if a.out:
+        with open(a.out + ".json", "w") as f:
+            json.dump(result, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
