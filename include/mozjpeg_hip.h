@@ -377,6 +377,13 @@ int mjh_transcode_status(mjh_encoder *e, int i, const char **text);
  * [3] DC sums + scrub.  Any pointer may be NULL. */
 int mjh_transcode_stats(mjh_encoder *e, int *subseq, int *rounds, int *host_syncs, float ms[4]);
 
+/* The sequential Huffman coder writes a scan without restart intervals in one walk over its blocks (MJH_ENC_ONEPASS=0 in
+ * the environment of mjh_encoder_create: the length pass and the second walk of the restart path for every scan).  enabled:
+ * that setting.  long_blocks: blocks whose bits outgrew their staging column (256 bits) and were walked twice; big_groups:
+ * groups of 256 blocks whose bits outgrew their window (64 Kbit) and were coded by the direct path -- both counted since
+ * the encoder was made.  Any pointer may be NULL.  Synchronises with the device. */
+int mjh_enc_onepass_stats(mjh_encoder *e, int *enabled, unsigned long long *long_blocks, unsigned long long *big_groups);
+
 /* Size in bytes of JPEG i of the last batch (synchronises). */
 int mjh_get_jpeg_size(mjh_encoder *e, int i, size_t *size);
 /* Copy JPEG i of the last batch to host memory (synchronises). */

@@ -149,6 +149,8 @@ def lib():
         L.mjh_transcode_host.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int]
         L.mjh_transcode_status.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p)]
         L.mjh_transcode_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float)]
+        if hasattr(L, "mjh_enc_onepass_stats"):       # (absent from a MOZJPEG_AMD_LIB variant built from an older tree: A/B runs against it)
+            L.mjh_enc_onepass_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
         _lib = L
     return _lib
 
@@ -577,6 +579,12 @@ class Encoder:
         a, b, c, ms = C.c_int(), C.c_int(), C.c_int(), (C.c_float * 4)()
         _chk(lib().mjh_transcode_stats(self._h, C.byref(a), C.byref(b), C.byref(c), ms))
         return dict(subseq=a.value, rounds=b.value, host_syncs=c.value, ms=dict(zip(("sync", "prefix", "store", "dc"), [float(x) for x in ms])))
+
+    def enc_onepass_stats(self):
+        """the one-walk Huffman coder (MJH_ENC_ONEPASS): whether it is on, and how often its two slower paths ran since the encoder was made"""
+        on, a, b = C.c_int(), C.c_ulonglong(), C.c_ulonglong()
+        _chk(lib().mjh_enc_onepass_stats(self._h, C.byref(on), C.byref(a), C.byref(b)))
+        return dict(enabled=bool(on.value), long_blocks=a.value, big_groups=b.value)
 
     def transcode_host(self, files, errors="raise"):
         """files: JPEG byte strings that agree with the encoder's parameters (params_from_jpeg).  Returns the re-coded files.

@@ -211,7 +211,9 @@ __device__ __forceinline__ void stuff_store_round(uint8_t *__restrict__ o, unsig
 }
 
 // the same writer for a window of the stream kept in LDS (the words become ds_or) or, LDSW = false, for the stream itself
-template <bool LDSW>   // (two instantiations so that the window's words become ds_or and the direct path's global atomics)
+// SWAP = false: the words stay in bit order (most significant bit first in the VALUE, not in memory) -- the window of the one-walk
+// schedule, whose words are shifted once more before they are byte-swapped into the stream
+template <bool LDSW, bool SWAP = true>   // (two instantiations so that the window's words become ds_or and the direct path's global atomics)
 struct BitSink {
   unsigned *words;
   unsigned long long acc;
@@ -224,7 +226,7 @@ struct BitSink {
     nacc += n;
     if (nacc >= 32) {
       const unsigned w = (unsigned)(acc >> (nacc - 32));
-      atomicOr(&words[widx], __builtin_bswap32(w));
+      atomicOr(&words[widx], SWAP ? __builtin_bswap32(w) : w);
       widx++;
       nacc -= 32;
     }
@@ -238,16 +240,70 @@ struct BitSink {
     nacc += n;
     if (nacc >= 32) {
       const unsigned w = (unsigned)(acc >> (nacc - 32));
-      atomicOr(&words[widx], __builtin_bswap32(w));
+      atomicOr(&words[widx], SWAP ? __builtin_bswap32(w) : w);
       widx++;
       nacc -= 32;
     }
   }
   __device__ __forceinline__ void flush()
   {
-    if (nacc > 0) atomicOr(&words[widx], __builtin_bswap32((unsigned)(acc << (32 - nacc))));
+    if (nacc > 0) { const unsigned w = (unsigned)(acc << (32 - nacc)); atomicOr(&words[widx], SWAP ? __builtin_bswap32(w) : w); }
   }
   __device__ __forceinline__ unsigned bitpos() const { return widx * 32u + (unsigned)nacc; }
 };
+
+// the same writer for a lane-private column of DEPTH words (word k at col[k * STRIDE], bit order, starting at bit 0): plain stores, no
+// atomics.  A bit string longer than the column is counted to its end but stored only as far as the column reaches (bitpos() tells).
+template <int DEPTH, int STRIDE>
+struct StageSink {
+  unsigned *col;
+  unsigned long long acc;
+  int nacc;
+  unsigned widx;
+  __device__ __forceinline__ void init(unsigned *c) { col = c; widx = 0; nacc = 0; acc = 0; }
+  __device__ __forceinline__ void put(unsigned code, int n)
+  {
+    acc = (acc << n) | (unsigned long long)(code & ((1u << n) - 1u));
+    nacc += n;
+    if (nacc >= 32) {
+      if (widx < (unsigned)DEPTH) col[widx * STRIDE] = (unsigned)(acc >> (nacc - 32));
+      widx++;
+      nacc -= 32;
+    }
+  }
+  __device__ __forceinline__ void put_sym(unsigned e, unsigned val, int nbits)
+  {
+    const int n = (int)(e >> 16) + nbits;
+    acc = (acc << n) | (unsigned long long)(((e & 0xFFFFu) << nbits) | (val & ((1u << nbits) - 1u)));
+    nacc += n;
+    if (nacc >= 32) {
+      if (widx < (unsigned)DEPTH) col[widx * STRIDE] = (unsigned)(acc >> (nacc - 32));
+      widx++;
+      nacc -= 32;
+    }
+  }
+  __device__ __forceinline__ void flush()
+  {
+    if (nacc > 0 && widx < (unsigned)DEPTH) col[widx * STRIDE] = (unsigned)(acc << (32 - nacc));
+  }
+  __device__ __forceinline__ unsigned bitpos() const { return widx * 32u + (unsigned)nacc; }
+};
+
+// counts the bits only (the walk of a workgroup whose bits fit no window)
+struct CountSink {
+  unsigned n;
+  __device__ __forceinline__ void init() { n = 0; }
+  __device__ __forceinline__ void put(unsigned, int k) { n += (unsigned)k; }
+  __device__ __forceinline__ void put_sym(unsigned e, unsigned, int nbits) { n += (e >> 16) + (unsigned)nbits; }
+  __device__ __forceinline__ void flush() {}
+  __device__ __forceinline__ unsigned bitpos() const { return n; }
+};
+
+// the low word of hi:lo >> s, 0 <= s < 32: word j of a bit string moved s bits towards its end is funnel_shift(w[j - 1], w[j], s)
+// (one v_alignbit_b32)
+__device__ __forceinline__ unsigned funnel_shift(unsigned hi, unsigned lo, unsigned s)
+{
+  return (unsigned)(((((unsigned long long)hi) << 32) | (unsigned long long)lo) >> s);
+}
 
 #endif

@@ -343,6 +343,10 @@ struct mjh_encoder {
   unsigned *d_off32 = nullptr, *d_sums = nullptr, *d_totals = nullptr, *d_ffsums = nullptr, *d_fftotals = nullptr;
   unsigned *d_stream = nullptr;
   size_t stream_words = 0;         // per image
+  int enc_onepass = 1;             // MJH_ENC_ONEPASS: scans without restart intervals are coded in one walk (k_enc_write_pack / _place)
+  unsigned *d_pack = nullptr;      // the one-walk coder's workgroup slots (pack_words per image)
+  size_t pack_words = 0;
+  unsigned *d_enc_slow = nullptr;  // its two slow-path counters (mjh_enc_onepass_stats)
   int chunks = 0, ff_chunks = 0;
   uint8_t *d_out = nullptr;
   size_t out_stride = 0;
@@ -846,7 +850,7 @@ static void free_all(mjh_encoder *e)
   for (hipEvent_t ev : { e->ev_done, e->ev_tier1 }) if (ev) (void)hipEventDestroy(ev);
   if (e->ev_null_in) (void)hipEventDestroy(e->ev_null_in);
   void *ptrs[] = { e->d_pixb[0], e->d_pixb[1], e->d_plin, e->d_cfin, e->d_prog_mpos, e->d_prog_ffsums, e->d_prog_chunks, e->pe.len16, e->pe.run16, e->pe.tail16, e->pe.be16, e->pe.off32, e->pe.sums, e->pe.totals, e->pe.T32, e->pe.tsums, e->pe.ttotals, e->pe.ne_bits, e->pe.ne2_bits, e->pe.e_bits, e->pe.info, e->pe.chist, e->pe.rmask, e->d_planes, e->d_uq, e->d_q, e->d_q0, e->d_quant, e->d_quant_init, e->d_tabs, e->d_tabs_init, e->d_lambda, e->d_back, e->d_eob_cost, e->d_eob_has, e->d_qsums, e->d_nzmask, e->d_nq8, e->d_dense, e->d_worklist, e->d_worklist2, e->d_prog_scans, e->d_prog_ctl, e->d_lists, e->d_pool, e->d_outpool, e->d_frame_hdr, e->d_seg_x, e->d_seg_E, e->d_seg_sums, e->d_seg_totals, e->d_mpos,
-                   e->d_len16, e->d_off32, e->d_sums, e->d_totals, e->d_ffsums, e->d_fftotals, e->d_stream, e->d_out, e->d_sizes,
+                   e->d_len16, e->d_off32, e->d_pack, e->d_enc_slow, e->d_sums, e->d_totals, e->d_ffsums, e->d_fftotals, e->d_stream, e->d_out, e->d_sizes,
                    e->d_meta, e->d_prefix, e->d_sos, e->d_ll_hist, e->d_ll_len, e->d_ll_off, e->d_ll_segE, e->d_arith_rates, e->d_back9, e->d_jfin, e->d_qspec, e->g_in[0], e->g_in[1], e->g_in[2], e->g_in[3] };
   for (void *q : ptrs) if (q) (void)mjh_guard_free(q);
   for (void *q : e->g_in_old) (void)mjh_guard_free(q);
@@ -925,6 +929,7 @@ static int mjh_streams_overlap(hipStream_t a, hipStream_t b)
 }
 
 static thread_local bool g_create_twin = false;
+static thread_local int g_twin_onepass = 1;     // the twin takes the primary's setting (the environment is read once, for the primary)
 static thread_local hipStream_t g_twin_avoid[2] = { nullptr, nullptr };   // make_twin: the primary's main and side stream     // mjh_encoder_create is making the second buffer set of an encoder (make_twin)
 
 // The encoder's main and side stream (every encoder kind).
@@ -1106,13 +1111,21 @@ extern "C" int mjh_encoder_create(const mjh_params *p, int max_batch, int device
   HIPCHK_E(mjh_dmalloc((void **)&e->d_len16, B * (size_t)C.total_mcu_blocks * 2));
   HIPCHK_E(mjh_dmalloc((void **)&e->d_off32, B * (size_t)C.total_mcu_blocks * 4));
   e->chunks = (C.total_mcu_blocks + 2047) / 2048;
+  if (g_create_twin) e->enc_onepass = g_twin_onepass;
+  else if (const char *v = getenv("MJH_ENC_ONEPASS")) e->enc_onepass = atoi(v) != 0;   // A/B knob: 0 = length pass + offsets + k_enc_write_mcu for every scan
+  if (e->enc_onepass) {
+    e->pack_words = mjh_encode_pack_words(C);
+    HIPCHK_E(mjh_dmalloc((void **)&e->d_pack, B * e->pack_words * 4));
+    HIPCHK_E(mjh_dmalloc((void **)&e->d_enc_slow, 2 * sizeof(unsigned)));
+    HIPCHK_E(hipMemset(e->d_enc_slow, 0, 2 * sizeof(unsigned)));
+  }
   // worst case per block: DC 16+11, 63 x (16+10) = 1665 bits -> 53 words (12-bit: 16+15, 63 x (16+14) -> 61 words)
   size_t words = (size_t)C.total_mcu_blocks * (C.precision == 12 ? 61 : 53) + 64;
   if (C.restart_interval) words += (size_t)(C.mcus_per_row * C.mcu_rows) / C.restart_interval + 1;   // pad + RSTn per interval
   if (words > (size_t)1 << 27) words = (size_t)1 << 27;   // bit offsets are 32-bit
   e->stream_words = (words + 63) & ~(size_t)63;
   e->ff_chunks = (int)((e->stream_words + 2047) / 2048);
-  HIPCHK_E(mjh_dmalloc((void **)&e->d_sums, B * e->chunks * sizeof(unsigned)));
+  HIPCHK_E(mjh_dmalloc((void **)&e->d_sums, B * (size_t)std::max(e->chunks, mjh_encode_segments(C)) * sizeof(unsigned)));   // (one-walk coder: one sum per 256 blocks)
   HIPCHK_E(mjh_dmalloc((void **)&e->d_ffsums, B * e->ff_chunks * sizeof(unsigned)));
   HIPCHK_E(mjh_dmalloc((void **)&e->d_totals, B * sizeof(unsigned)));
   HIPCHK_E(mjh_dmalloc((void **)&e->d_fftotals, B * sizeof(unsigned)));
@@ -2017,7 +2030,8 @@ static int run_pipeline(mjh_encoder *e, const void *d_pixels, size_t row_pitch, 
                         p.compress_profile != MJH_PROFILE_FASTEST, e->d_out, e->out_stride, e->d_meta, n, s, si == 0 ? nullptr : e->d_sizes);
       pr.mark("huff_encode");
       mjh_launch_encode(V, e->d_q, nzm, e->d_tabs, spi, v_dc, v_ac, e->d_len16, e->d_off32, e->d_sums, e->chunks, e->d_totals,
-                        e->d_stream, e->stream_words, e->d_meta, e->d_seg_x, e->d_seg_E, e->d_seg_sums, e->d_seg_totals, e->d_mpos, q.nseg, n, s);
+                        e->d_stream, e->stream_words, e->d_meta, e->d_seg_x, e->d_seg_E, e->d_seg_sums, e->d_seg_totals, e->d_mpos, q.nseg, n, s,
+                        e->d_pack, e->pack_words, e->d_enc_slow);
       pr.mark("byte_stuff");
       mjh_launch_stuff(e->d_stream, e->stream_words, e->d_totals, e->d_ffsums, e->ff_chunks, e->d_fftotals, e->d_out, e->out_stride,
                        e->d_meta, e->d_sizes, e->d_mpos, q.nseg, n, s);
@@ -2045,7 +2059,8 @@ static int run_pipeline(mjh_encoder *e, const void *d_pixels, size_t row_pitch, 
                       p.compress_profile != MJH_PROFILE_FASTEST, e->d_out, e->out_stride, e->d_meta, n, s);
     pr.mark("huff_encode");
     mjh_launch_encode(C, e->d_q, nzm, e->d_tabs, spi, fin_dc, fin_ac, e->d_len16, e->d_off32, e->d_sums, e->chunks, e->d_totals,
-                      e->d_stream, e->stream_words, e->d_meta, e->d_seg_x, e->d_seg_E, e->d_seg_sums, e->d_seg_totals, e->d_mpos, e->nseg, n, s);
+                      e->d_stream, e->stream_words, e->d_meta, e->d_seg_x, e->d_seg_E, e->d_seg_sums, e->d_seg_totals, e->d_mpos, e->nseg, n, s,
+                      e->d_pack, e->pack_words, e->d_enc_slow);
     if (if_mode == 2) { HIPCHK(hipEventRecord(e->ev_done, s)); e->ev_done_set = true; }      // (the bit writer is the tail's last VALU-bound kernel)
     pr.mark("byte_stuff");
     mjh_launch_stuff(e->d_stream, e->stream_words, e->d_totals, e->d_ffsums, e->ff_chunks, e->d_fftotals, e->d_out, e->out_stride,
@@ -2081,6 +2096,7 @@ static int make_twin(mjh_encoder *e)
 {
   mjh_encoder *t = nullptr;
   g_create_twin = true;
+  g_twin_onepass = e->enc_onepass;
   g_twin_avoid[0] = e->stream; g_twin_avoid[1] = e->side_stream;
   const int rc = mjh_encoder_create(&e->p_created, e->max_batch, e->device, &t);
   g_create_twin = false;
@@ -2988,6 +3004,26 @@ extern "C" int mjh_transcode_stats(mjh_encoder *e, int *subseq, int *rounds, int
       for (int k = 0; k < 4; k++) HIPCHK(hipEventElapsedTime(&ms[k], e->tc_ev[k], e->tc_ev[k + 1]));
     }
   }
+  return MJH_OK;
+}
+
+// The one-walk entropy coder's slow paths since the encoder was made (both buffer sets): blocks longer than their staging column
+// (walked twice), workgroups larger than their window (left to k_enc_write_big).  enabled: MJH_ENC_ONEPASS.  Waits for the device.
+extern "C" int mjh_enc_onepass_stats(mjh_encoder *e, int *enabled, unsigned long long *long_blocks, unsigned long long *big_groups)
+{
+  if (!e) return fail(MJH_EINVAL, "null encoder");
+  if (enabled) *enabled = e->enc_onepass;
+  unsigned long long a = 0, b = 0;
+  for (mjh_encoder *x : { e, e->twin }) {
+    if (!x || !x->d_enc_slow) continue;
+    unsigned h[2] = { 0, 0 };
+    HIPCHK(hipSetDevice(x->device));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(h, x->d_enc_slow, sizeof(h), hipMemcpyDeviceToHost));
+    a += h[0]; b += h[1];
+  }
+  if (long_blocks) *long_blocks = a;
+  if (big_groups) *big_groups = b;
   return MJH_OK;
 }
 

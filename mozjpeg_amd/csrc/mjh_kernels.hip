@@ -2001,7 +2001,8 @@ struct MarkerCursor {
 
 template <bool COMPACT, class W>
 __device__ __forceinline__ void enc_write_block(const MjhConst &C, const MjhComp &cc, W &bw, const unsigned *s_ac, const unsigned *s_dc,
-                                                const int16_t *__restrict__ q, const unsigned long long *__restrict__ nzmask_img, int r, int c)
+                                                const int16_t *__restrict__ q, const unsigned long long *__restrict__ nzmask_img, int r, int c,
+                                                int *dc_nbits = nullptr)   // dc_nbits: the size category of the DC difference (the caller's range check)
 {
   const int dc = q[dc_source_block(cc, r, c)];
   int pr, pc, pred = 0;
@@ -2010,6 +2011,7 @@ __device__ __forceinline__ void enc_write_block(const MjhConst &C, const MjhComp
     const int df = dc - pred;
     const int a = df < 0 ? -df : df;
     const int nb = bitlen((unsigned)a);
+    if (dc_nbits) *dc_nbits = nb;
     const unsigned e = s_dc[nb];
     bw.put(e & 0xFFFF, (int)(e >> 16));
     if (nb) bw.put((unsigned)(df < 0 ? df - 1 : df), nb);
@@ -2126,6 +2128,198 @@ k_enc_write_mcu(MjhConst C, const int16_t *__restrict__ coef_q, const unsigned l
       if (i == 0u || i == nw - 1u) atomicOr(&g[w0 + i], v);   // shared with the neighbouring workgroup
       else g[w0 + i] = v;
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The one-walk schedule (scans without restart intervals): no length pass.  k_enc_write_pack walks every block ONCE; a lane's bits
+// go into a column of its own in LDS (StageSink, layout [word][lane]: no bank conflicts, no atomics) starting at bit 0, and the
+// lane's bit count falls out of the sink.  A workgroup-wide scan gives the lane its offset inside the workgroup; the lane shifts
+// its staged words into the workgroup's window (one funnel shift and one ds_or per word: 34 bits per block on the metric frames,
+// one or two words), and the window leaves as coalesced stores into the workgroup's slot of `pack`, at workgroup-local bit 0,
+// in bit order (not yet byte-swapped).  k_scan_sums over the workgroup totals gives every slot its place in the stream, and
+// k_enc_write_place (a wave per slot) funnel-shifts the slot's words to that place.  Ordering comes from the kernel boundaries.
+// Two slower paths, both counted (slow[0], slow[1]; mjh_enc_onepass_stats):
+//   * a block longer than its column (ENCP_DEPTH words): the lane has counted all of its bits; it walks the block again with the
+//     window as its sink, as k_enc_write_mcu does
+//   * a workgroup whose bits do not fit the window (ENCP_WIN words): it stores its total only, and k_enc_write_big walks its blocks
+//     again (count, scan, then straight into the zeroed stream)
+// ---------------------------------------------------------------------------------------------
+#define ENCP_DEPTH 8      // 256 bits per block
+#define ENCP_WIN 2048     // 256 bits per block on average
+
+__device__ __forceinline__ void enc_load_tables(unsigned (*s_ac)[256], unsigned (*s_dc)[32], const MjhConst &C, const MjhHuffTable *__restrict__ tabs_img,
+                                                const int4 &dc_slot_of_comp, const int4 &ac_slot_of_comp)
+{
+  const int tid = threadIdx.x;
+  for (int ci = 0; ci < C.ncomp; ci++) {
+    const int dslot = ci == 0 ? dc_slot_of_comp.x : ci == 1 ? dc_slot_of_comp.y : ci == 2 ? dc_slot_of_comp.z : dc_slot_of_comp.w;
+    const int aslot = ci == 0 ? ac_slot_of_comp.x : ci == 1 ? ac_slot_of_comp.y : ci == 2 ? ac_slot_of_comp.z : ac_slot_of_comp.w;
+    const MjhHuffTable *TD = tabs_img + dslot;
+    const MjhHuffTable *TA = tabs_img + aslot;
+    s_ac[ci][tid] = ((unsigned)TA->ehufsi[tid] << 16) | TA->ehufco[tid];
+    if (tid < 32) s_dc[ci][tid] = tid < 16 ? ((unsigned)TD->ehufsi[tid] << 16) | TD->ehufco[tid] : 0u;
+  }
+}
+
+// scan position p (MCU order) -> component, block row and column (dummy blocks included)
+__device__ __forceinline__ int enc_scan_position(const MjhConst &C, int p, int &r, int &c)
+{
+  const int mcu = p / C.blocks_per_mcu, bi = p - mcu * C.blocks_per_mcu;
+  int comp = 0;
+  for (int ci = 1; ci < C.ncomp; ci++) if (bi >= C.c[ci].mcu_blk0) comp = ci;
+  const int h = C.c[comp].h, v = C.c[comp].v;
+  const int local = bi - C.c[comp].mcu_blk0, yi = local / h, xi = local - yi * h;
+  const int mrow = mcu / C.mcus_per_row, mcol = mcu - mrow * C.mcus_per_row;
+  r = mrow * v + yi;
+  c = mcol * h + xi;
+  return comp;
+}
+
+template <bool COMPACT>
+__global__ void __launch_bounds__(256)
+k_enc_write_pack(MjhConst C, const int16_t *__restrict__ coef_q, const unsigned long long *__restrict__ nzmask, const MjhHuffTable *__restrict__ tabs,
+                 int slots_per_image, int4 dc_slot_of_comp, int4 ac_slot_of_comp,
+                 unsigned *__restrict__ pack, size_t pack_words_per_image, unsigned *__restrict__ sums, int segs_per_image,
+                 MjhImageMeta *__restrict__ meta, unsigned *__restrict__ slow)
+{
+  __shared__ unsigned s_ac[MJH_MAXC][256];   // size << 16 | code, per component
+  __shared__ unsigned s_dc[MJH_MAXC][32];
+  __shared__ unsigned s_stage[ENCP_DEPTH * 256];
+  __shared__ uint4 s_win4[ENCP_WIN / 4];
+  __shared__ unsigned sh[8];
+  unsigned *s_win = reinterpret_cast<unsigned *>(s_win4);
+  const int img = blockIdx.y, tid = threadIdx.x;
+  const int N = C.total_mcu_blocks, p = blockIdx.x * 256 + tid;
+  enc_load_tables(s_ac, s_dc, C, tabs + (size_t)img * slots_per_image, dc_slot_of_comp, ac_slot_of_comp);
+  for (int i = tid; i < ENCP_WIN / 4; i += 256) s_win4[i] = make_uint4(0u, 0u, 0u, 0u);   // (the whole window, two stores per lane: no barrier of its own behind the scan)
+  __syncthreads();
+  int r = 0, c = 0;
+  const int comp = enc_scan_position(C, p < N ? p : 0, r, c);
+  const MjhComp cc = C.c[comp];
+  const int16_t *q = coef_q + (size_t)img * C.coefs_per_image + cc.coef_off;
+  const unsigned long long *nzi = COMPACT ? nzmask + (size_t)img * C.total_real_blocks : nullptr;
+  unsigned bits = 0;
+  if (p < N) {
+    MJH_DIVERGENT_SCOPE;      // (the ballot of for_each_nonzero)
+    StageSink<ENCP_DEPTH, 256> bw;
+    bw.init(s_stage + tid);
+    int nb = 0;
+    enc_write_block<COMPACT>(C, cc, bw, s_ac[comp], s_dc[comp], q, nzi, r, c, &nb);
+    bw.flush();
+    bits = bw.bitpos();
+    if (nb > (C.precision == 12 ? 15 : 11)) meta[img].bad_coef = 1u;   // MAX_COEF_BITS + 1 (jchuff.c:489)
+  }
+  unsigned tot;
+  const unsigned ex = block_excl_scan_256_1b(bits, sh, 0, &tot);
+  if (tid == 0) sums[(size_t)img * segs_per_image + blockIdx.x] = tot;
+  const unsigned nw = (tot + 31u) >> 5;
+  if (nw > (unsigned)ENCP_WIN) {          // left to k_enc_write_big
+    if (tid == 0) atomicAdd(&slow[1], 1u);
+    return;
+  }
+  if (bits > ENCP_DEPTH * 32u) {
+    MJH_DIVERGENT_SCOPE;
+    atomicAdd(&slow[0], 1u);
+    BitSink<true, false> bw;
+    bw.init(s_win, ex);
+    enc_write_block<COMPACT>(C, cc, bw, s_ac[comp], s_dc[comp], q, nzi, r, c);
+    bw.flush();
+  } else {
+    const unsigned s = ex & 31u, w0 = ex >> 5, nsw = (bits + 31u) >> 5, ndw = (s + bits + 31u) >> 5;
+    unsigned prev = 0u;
+    for (unsigned k = 0; k < ndw; k++) {
+      const unsigned cur = k < nsw ? s_stage[k * 256 + tid] : 0u;
+      const unsigned v = funnel_shift(prev, cur, s);
+      if (v) atomicOr(&s_win[w0 + k], v);
+      prev = cur;
+    }
+  }
+  __syncthreads();
+  unsigned *g = pack + (size_t)img * pack_words_per_image + (size_t)blockIdx.x * ENCP_WIN;
+  for (unsigned i = tid; i < nw; i += 256) g[i] = s_win[i];
+}
+
+// sums: the exclusive prefix of the workgroup totals (k_scan_sums).  One wave per slot; the first and the last word of a slot's
+// place are shared with the neighbours (atomicOr on words k_zero_stream has cleared), the words between are plain stores.
+__global__ void __launch_bounds__(256)
+k_enc_write_place(const unsigned *__restrict__ pack, size_t pack_words_per_image, const unsigned *__restrict__ sums, int segs_per_image,
+                  const unsigned *__restrict__ totals, unsigned *__restrict__ stream, size_t stream_words_per_image)
+{
+  const int img = blockIdx.y, lane = threadIdx.x & 63;
+  const int seg = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (seg >= segs_per_image) return;
+  const unsigned total = totals[img];
+  if (total == 0xFFFFFFFFu) return;     // scan beyond the 32-bit offset range: reported by k_finish_bits
+  const unsigned *sm = sums + (size_t)img * segs_per_image;
+  const unsigned base = sm[seg], len = (seg + 1 < segs_per_image ? sm[seg + 1] : total) - base;
+  const unsigned nsw = (len + 31u) >> 5;
+  if (nsw > (unsigned)ENCP_WIN) return;   // k_enc_write_big
+  const unsigned s = base & 31u, ndw = (s + len + 31u) >> 5;
+  const unsigned *src = pack + (size_t)img * pack_words_per_image + (size_t)seg * ENCP_WIN;
+  unsigned *g = stream + (size_t)img * stream_words_per_image + (base >> 5);
+  for (unsigned k = lane; k < ndw; k += 64) {
+    const unsigned hi = k > 0u ? src[k - 1] : 0u, lo = k < nsw ? src[k] : 0u;
+    const unsigned v = __builtin_bswap32(funnel_shift(hi, lo, s));
+    if (k == 0u || k == ndw - 1u) { if (v) atomicOr(&g[k], v); }
+    else g[k] = v;
+  }
+}
+
+// the groups whose bits did not fit the window (a lane per group looks for them; a workgroup that finds none among its 256
+// leaves at once): lengths, scan, then the blocks' bits straight into the zeroed stream
+template <bool COMPACT>
+__global__ void __launch_bounds__(256)
+k_enc_write_big(MjhConst C, const int16_t *__restrict__ coef_q, const unsigned long long *__restrict__ nzmask, const MjhHuffTable *__restrict__ tabs,
+                int slots_per_image, int4 dc_slot_of_comp, int4 ac_slot_of_comp, const unsigned *__restrict__ sums, int segs_per_image,
+                const unsigned *__restrict__ totals, unsigned *__restrict__ stream, size_t stream_words_per_image)
+{
+  __shared__ unsigned s_ac[MJH_MAXC][256];
+  __shared__ unsigned s_dc[MJH_MAXC][32];
+  __shared__ unsigned sh[4];
+  __shared__ unsigned s_base[256];      // bit offset of a group that is this kernel's to code, else ~0
+  const int img = blockIdx.y, tid = threadIdx.x, N = C.total_mcu_blocks;
+  const unsigned total = totals[img];
+  if (total == 0xFFFFFFFFu) return;
+  const unsigned *sm = sums + (size_t)img * segs_per_image;
+  unsigned *g = stream + (size_t)img * stream_words_per_image;
+  const int seg0 = blockIdx.x * 256;
+  unsigned mine = 0xFFFFFFFFu;
+  if (seg0 + tid < segs_per_image) {
+    const int sg = seg0 + tid;
+    const unsigned base = sm[sg], len = (sg + 1 < segs_per_image ? sm[sg + 1] : total) - base;
+    if (((len + 31u) >> 5) > (unsigned)ENCP_WIN) mine = base;
+  }
+  s_base[tid] = mine;
+  if (!__syncthreads_or(mine != 0xFFFFFFFFu)) return;      // (nearly always)
+  enc_load_tables(s_ac, s_dc, C, tabs + (size_t)img * slots_per_image, dc_slot_of_comp, ac_slot_of_comp);
+  __syncthreads();
+  for (int i = 0; i < 256 && seg0 + i < segs_per_image; i++) {
+    const unsigned base = s_base[i];
+    if (base == 0xFFFFFFFFu) continue;      // (uniform)
+    const int seg = seg0 + i;
+    const int p = seg * 256 + tid;
+    int r = 0, c = 0;
+    const int comp = enc_scan_position(C, p < N ? p : 0, r, c);
+    const MjhComp cc = C.c[comp];
+    const int16_t *q = coef_q + (size_t)img * C.coefs_per_image + cc.coef_off;
+    const unsigned long long *nzi = COMPACT ? nzmask + (size_t)img * C.total_real_blocks : nullptr;
+    unsigned bits = 0;
+    if (p < N) {
+      MJH_DIVERGENT_SCOPE;
+      CountSink cs;
+      cs.init();
+      enc_write_block<COMPACT>(C, cc, cs, s_ac[comp], s_dc[comp], q, nzi, r, c);
+      bits = cs.bitpos();
+    }
+    const unsigned ex = block_excl_scan_256(bits, sh, nullptr);
+    if (p < N) {
+      MJH_DIVERGENT_SCOPE;
+      BitSink<false> bw;
+      bw.init(g, base + ex);
+      enc_write_block<COMPACT>(C, cc, bw, s_ac[comp], s_dc[comp], q, nzi, r, c);
+      bw.flush();
+    }
+  }
 }
 
 // zero exactly the words the entropy coder is going to OR its bits into (the buffer itself is sized for the
@@ -2411,6 +2605,9 @@ void mjh_launch_color(const MjhConst &C, const void *pix, size_t row_pitch, size
 #undef LC
 }
 
+int mjh_encode_segments(const MjhConst &C) { return (C.total_mcu_blocks + 255) / 256; }
+size_t mjh_encode_pack_words(const MjhConst &C) { return (size_t)mjh_encode_segments(C) * ENCP_WIN; }
+
 static int max_nblk(const MjhConst &C) { int m = 0; for (int i = 0; i < C.ncomp; i++) m = C.c[i].nblk > m ? C.c[i].nblk : m; return m; }
 static int max_padblk(const MjhConst &C) { int m = 0; for (int i = 0; i < C.ncomp; i++) { int v = C.c[i].wpad * C.c[i].hpad; m = v > m ? v : m; } return m; }
 
@@ -2504,10 +2701,30 @@ void mjh_launch_encode(const MjhConst &C, const void *q, const unsigned long lon
                        void *len16, void *off32, unsigned *sums, int chunks_per_image, unsigned *totals,
                        unsigned *stream, size_t stream_words_per_image, void *meta,
                        unsigned *seg_x, unsigned *seg_E, unsigned *seg_sums, unsigned *seg_totals, unsigned *mpos, int nseg,
-                       int n, hipStream_t s)
+                       int n, hipStream_t s, unsigned *pack, size_t pack_words_per_image, unsigned *slow)
 {
   const int4 ds = make_int4(dc_slot[0], dc_slot[1], dc_slot[2], dc_slot[3]);
   const int4 as = make_int4(ac_slot[0], ac_slot[1], ac_slot[2], ac_slot[3]);
+  if (pack && C.restart_interval == 0) {
+    // the one-walk schedule: every block is walked once (k_enc_write_pack), the workgroups' slots are placed by their totals' scan
+    const int segs = mjh_encode_segments(C);
+    dim3 gridp(segs, n);
+    if (nzmask) hipLaunchKernelGGL((k_enc_write_pack<true>), gridp, dim3(256), 0, s, C, (const int16_t *)q, nzmask, tabs, spi, ds, as, pack, pack_words_per_image, sums, segs,
+                                   (MjhImageMeta *)meta, slow);
+    else hipLaunchKernelGGL((k_enc_write_pack<false>), gridp, dim3(256), 0, s, C, (const int16_t *)q, nzmask, tabs, spi, ds, as, pack, pack_words_per_image, sums, segs,
+                            (MjhImageMeta *)meta, slow);
+    hipLaunchKernelGGL(k_scan_sums, dim3(n), dim3(256), 0, s, sums, segs, totals, (const unsigned *)nullptr);
+    hipLaunchKernelGGL(k_zero_stream, dim3(64, n), dim3(256), 0, s, stream, stream_words_per_image, (const unsigned *)totals, (const unsigned *)nullptr);
+    hipLaunchKernelGGL(k_enc_write_place, dim3((segs + 3) / 4, n), dim3(256), 0, s, (const unsigned *)pack, pack_words_per_image, (const unsigned *)sums, segs,
+                       (const unsigned *)totals, stream, stream_words_per_image);
+    dim3 gridb((segs + 255) / 256, n);
+    if (nzmask) hipLaunchKernelGGL((k_enc_write_big<true>), gridb, dim3(256), 0, s, C, (const int16_t *)q, nzmask, tabs, spi, ds, as, (const unsigned *)sums, segs,
+                                   (const unsigned *)totals, stream, stream_words_per_image);
+    else hipLaunchKernelGGL((k_enc_write_big<false>), gridb, dim3(256), 0, s, C, (const int16_t *)q, nzmask, tabs, spi, ds, as, (const unsigned *)sums, segs,
+                            (const unsigned *)totals, stream, stream_words_per_image);
+    hipLaunchKernelGGL(k_finish_bits, dim3((n + 63) / 64), dim3(64), 0, s, totals, (const unsigned *)nullptr, stream, stream_words_per_image, (MjhImageMeta *)meta, n);
+    return;
+  }
   dim3 grid((max_padblk(C) + 255) / 256, C.ncomp, n);
   if (nzmask) hipLaunchKernelGGL((k_enc_len<true>), grid, dim3(256), 0, s, C, (const int16_t *)q, nzmask, tabs, spi, ds, as, (uint16_t *)len16, (MjhImageMeta *)meta);
   else hipLaunchKernelGGL((k_enc_len<false>), grid, dim3(256), 0, s, C, (const int16_t *)q, nzmask, tabs, spi, ds, as, (uint16_t *)len16, (MjhImageMeta *)meta);

@@ -36,7 +36,12 @@ void mjh_launch_encode(const MjhConst &C, const void *q, const unsigned long lon
                        void *len16, void *off32, unsigned *sums, int chunks_per_image, unsigned *totals,
                        unsigned *stream, size_t stream_words_per_image, void *meta,
                        unsigned *seg_x, unsigned *seg_E, unsigned *seg_sums, unsigned *seg_totals, unsigned *mpos, int nseg,
-                       int n, hipStream_t s);
+                       int n, hipStream_t s, unsigned *pack = nullptr, size_t pack_words_per_image = 0, unsigned *slow = nullptr);
+// pack != nullptr and a scan without restart intervals: the one-walk schedule (k_enc_write_pack / _place / _big).  pack: mjh_encode_pack_words(C)
+// words per image; sums: at least mjh_encode_segments(C) words per image; slow: two counters (blocks longer than their staging column,
+// workgroups larger than their window), only ever added to.  len16 / off32 are not touched then.
+int mjh_encode_segments(const MjhConst &C);
+size_t mjh_encode_pack_words(const MjhConst &C);
 void mjh_launch_header(const void *prefix, int prefix_len, const void *sos, int sos_len, const MjhHuffTable *tabs, int spi,
                        const int dht_slots[8], const int dht_ids[8], int ndht, int multi_dht, void *out, size_t out_stride, void *meta, int n, hipStream_t s, const unsigned *append_sizes = nullptr);   // append_sizes: write over the EOI of the files so far (later scans of a sequential script)
 // the final pad of a scan whose totals[] include everything (no restart extras on top); totals 0xFFFFFFFF: the offset-range sentinel
