@@ -377,6 +377,51 @@ int mjh_transcode_status(mjh_encoder *e, int i, const char **text);
  * [3] DC sums + scrub.  Any pointer may be NULL. */
 int mjh_transcode_stats(mjh_encoder *e, int *subseq, int *rounds, int *host_syncs, float ms[4]);
 
+/* ---- lossless transforms while re-compressing (jpegtran -rotate / -flip / -transpose / -transverse / -crop / -grayscale) ----
+ * The semantics are transupp.c's as jpegtran.c drives them: the bytes of `jpegtran -copy none <transform> <coding switches>`.
+ * The decoder kernels store every coefficient straight into its place in the DESTINATION frame (block moved, position inside
+ * the block transposed, sign of odd columns / rows changed): no second set of coefficient planes and no extra pass.
+ * Edges as the reference: without trim the partial iMCU column / row at a mirrored edge stays where it is (copied or only
+ * transposed), with trim it is cut off, perfect refuses such a size.  crop applies in output coordinates; its offset moves
+ * down to an iMCU boundary and the size grows by the remainder.  grayscale keeps component 0 of a YCbCr file (1x1 factors,
+ * its quantization table number); a one-component file gets 1x1 factors as well.
+ * MJH_EUNSUPPORTED: crop extension (a crop larger than the image), the f / r suffixes of a crop specification, grayscale on
+ * a file that is neither YCbCr nor gray or whose component 0 is not sampled at the maximum (JERR_CONVERSION_NOTIMPL);
+ * -drop and -wipe have no operation number here.  MJH_EINVAL: a crop outside the image (JERR_BAD_CROP_SPEC), perfect on a
+ * size that is not ("transformation is not perfect").  Markers are not copied (-copy none), so no Exif size is adjusted. */
+#define MJH_XFORM_NONE       0   /* JXFORM_CODE (transupp.h) */
+#define MJH_XFORM_FLIP_H     1
+#define MJH_XFORM_FLIP_V     2
+#define MJH_XFORM_TRANSPOSE  3
+#define MJH_XFORM_TRANSVERSE 4
+#define MJH_XFORM_ROT_90     5
+#define MJH_XFORM_ROT_180    6
+#define MJH_XFORM_ROT_270    7
+#define MJH_CROP_UNSET   0       /* JCROP_CODE */
+#define MJH_CROP_POS     1
+#define MJH_CROP_NEG     2
+#define MJH_CROP_FORCE   3       /* parsed, refused */
+#define MJH_CROP_REFLECT 4       /* parsed, refused */
+typedef struct {
+  int transform;                 /* MJH_XFORM_* */
+  int trim, perfect, grayscale;  /* -trim, -perfect, -grayscale */
+  int crop;                      /* the crop fields below are in force (mjh_transform_parse_crop sets it) */
+  unsigned crop_width, crop_height, crop_xoffset, crop_yoffset;
+  int crop_width_set, crop_height_set, crop_xoffset_set, crop_yoffset_set;   /* MJH_CROP_*; NEG: the offset counts from the right / bottom edge */
+} mjh_transform;
+/* jtransform_parse_crop_spec: WxH+X+Y with any subset of the four numbers and `-` offsets into the crop fields of *t (the other
+ * fields stay).  MJH_EINVAL "bogus -crop argument" for anything else. */
+int mjh_transform_parse_crop(mjh_transform *t, const char *spec);
+/* mjh_params_from_jpeg + jtransform_request_workspace + jtransform_adjust_parameters: the destination's size, sampling factors
+ * (swapped by the four transposing operations), quantization tables (transposed by them) and components.  t == NULL or a
+ * transform that asks for nothing: exactly mjh_params_from_jpeg. */
+int mjh_params_from_jpeg_transform(const mjh_jpeg_info *info, const mjh_transform *t, int compress_profile, mjh_params *p);
+/* The transform of the following mjh_transcode_host calls on e (NULL: none, today's path).  The encoder's parameters are the
+ * DESTINATION's (mjh_params_from_jpeg_transform).  The source geometry cannot be derived from them (225 and 227 both trim
+ * to 224): the first good file of a call defines it, every other file of the call must have the same size and sampling
+ * factors, and every file's own destination parameters must equal the encoder's, else MJH_EINVAL naming file and field. */
+int mjh_encoder_set_transform(mjh_encoder *e, const mjh_transform *t);
+
 /* The sequential Huffman coder writes a scan without restart intervals in one walk over its blocks (MJH_ENC_ONEPASS=0 in
  * the environment of mjh_encoder_create: the length pass and the second walk of the restart path for every scan).  enabled:
  * that setting.  long_blocks: blocks whose bits outgrew their staging column (256 bits) and were walked twice; big_groups:

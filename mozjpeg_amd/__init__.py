@@ -63,6 +63,14 @@ class JpegScan(C.Structure):
                 ("huff_vals", (C.c_uint8 * 256) * 8)]
 
 
+class Transform(C.Structure):
+    """mjh_transform: a lossless transform of the re-compression path (jpegtran -rotate / -flip / -transpose / -transverse,
+    -trim, -perfect, -crop, -grayscale); make one with transform_spec()"""
+    _fields_ = [("transform", C.c_int), ("trim", C.c_int), ("perfect", C.c_int), ("grayscale", C.c_int), ("crop", C.c_int),
+                ("crop_width", C.c_uint), ("crop_height", C.c_uint), ("crop_xoffset", C.c_uint), ("crop_yoffset", C.c_uint),
+                ("crop_width_set", C.c_int), ("crop_height_set", C.c_int), ("crop_xoffset_set", C.c_int), ("crop_yoffset_set", C.c_int)]
+
+
 class JpegInfo(C.Structure):
     """mjh_jpeg_info: the marker segments of a source file (no entropy decoding)"""
     _fields_ = [("sof_type", C.c_int), ("data_precision", C.c_int), ("image_width", C.c_int), ("image_height", C.c_int),
@@ -146,6 +154,9 @@ def lib():
                                            C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int)]
         L.mjh_jpeg_probe.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(JpegInfo)]
         L.mjh_params_from_jpeg.argtypes = [C.POINTER(JpegInfo), C.c_int, C.POINTER(Params)]
+        L.mjh_transform_parse_crop.argtypes = [C.POINTER(Transform), C.c_char_p]
+        L.mjh_params_from_jpeg_transform.argtypes = [C.POINTER(JpegInfo), C.POINTER(Transform), C.c_int, C.POINTER(Params)]
+        L.mjh_encoder_set_transform.argtypes = [C.c_void_p, C.POINTER(Transform)]
         L.mjh_transcode_host.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int]
         L.mjh_transcode_status.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p)]
         L.mjh_transcode_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float)]
@@ -298,13 +309,44 @@ def jpeg_info(data):
     return info
 
 
-def params_from_jpeg(data, *, revert=False, optimize=False, progressive=None, fastcrush=False, restart=0):
+TRANSFORMS = {"flip_h": 1, "flip_v": 2, "transpose": 3, "transverse": 4, "rot90": 5, "rot180": 6, "rot270": 7}   # JXFORM_CODE
+
+
+def transform_spec(transform=None, trim=False, perfect=False, crop=None, grayscale=False):
+    """The Transform of jpegtran's transform switches, or None when they ask for nothing.  transform: one of TRANSFORMS
+    ("rot90" = -rotate 90, "flip_h" = -flip horizontal, ...); crop: the -crop string, "WxH+X+Y" with any subset of the numbers."""
+    if isinstance(transform, Transform):
+        return transform
+    if transform is None and crop is None and not (trim or perfect or grayscale):
+        return None
+    t = Transform()
+    if transform is not None:
+        if transform not in TRANSFORMS:
+            raise MjhError(EINVAL, "transform %r (one of %s)" % (transform, ", ".join(TRANSFORMS)))
+        t.transform = TRANSFORMS[transform]
+    if crop is not None:
+        _chk(lib().mjh_transform_parse_crop(C.byref(t), str(crop).encode()))
+    t.trim, t.perfect, t.grayscale = int(bool(trim)), int(bool(perfect)), int(bool(grayscale))
+    return t
+
+
+def params_from_jpeg(data, *, revert=False, optimize=False, progressive=None, fastcrush=False, restart=0,
+                     transform=None, trim=False, perfect=False, crop=None, grayscale=False):
     """Parameters of a `jpegtran -copy none` run on this file (mjh_params_from_jpeg = jpeg_copy_critical_parameters) plus
-    jpegtran's switches in make_params' vocabulary.  `data`: the file's bytes or a JpegInfo."""
+    jpegtran's switches in make_params' vocabulary.  `data`: the file's bytes or a JpegInfo.
+    transform / trim / perfect / crop / grayscale (transform_spec): the parameters of the DESTINATION of that lossless transform
+    (mjh_params_from_jpeg_transform); the Transform rides along as `.transform`, and an Encoder made from these parameters
+    applies it in transcode_host."""
     info = data if isinstance(data, JpegInfo) else jpeg_info(data)
     p = Params()
     L = lib()
-    _chk(L.mjh_params_from_jpeg(C.byref(info), PROFILE_FASTEST if revert else PROFILE_MAX_COMPRESSION, C.byref(p)))
+    t = transform_spec(transform, trim, perfect, crop, grayscale)
+    profile = PROFILE_FASTEST if revert else PROFILE_MAX_COMPRESSION
+    if t is None:
+        _chk(L.mjh_params_from_jpeg(C.byref(info), profile, C.byref(p)))
+    else:
+        _chk(L.mjh_params_from_jpeg_transform(C.byref(info), C.byref(t), profile, C.byref(p)))
+        p.transform = t
     if optimize:
         p.optimize_coding = 1
     if restart:
@@ -337,7 +379,10 @@ def recompress(files, *, max_batch=64, device=0, **switches):
     restart) writes for each of them, in input order.  The files are grouped by what a batch must have in common; one encoder
     per group is kept for later calls.  In the max-compression profile without `revert` / `progressive` a source that is
     smaller than its re-coded file is returned as it came (jpegtran.c:171, :774-777).  A file that cannot be re-coded
-    (unsupported type, malformed headers, damaged entropy-coded data) gets the MjhError in its slot; the others are unaffected."""
+    (unsupported type, malformed headers, damaged entropy-coded data) gets the MjhError in its slot; the others are unaffected.
+    transform / trim / perfect / crop / grayscale (transform_spec): jpegtran's lossless transforms in the same pass; with any of
+    them but `perfect` a source is never returned in place of its result (jpegtran clears prefer_smallest), and a file whose
+    geometry refuses the request (not perfect, a crop outside the image) gets that MjhError in its slot."""
     files = [bytes(f) for f in files]
     out = [None] * len(files)
     groups = {}
@@ -349,14 +394,26 @@ def recompress(files, *, max_batch=64, device=0, **switches):
             continue
         groups.setdefault(_signature(info), (info, []))[1].append(i)
     prefer_smallest = not (switches.get("revert") or switches.get("progressive"))
-    key_sw = tuple(sorted(switches.items()))
+    # every transform switch clears it as well (jpegtran.c:227, :293, :396-428), -perfect alone does not
+    transforming = switches.get("transform") is not None or switches.get("crop") is not None or bool(switches.get("grayscale") or switches.get("trim"))
+    if transforming:
+        prefer_smallest = False
+    key_sw = tuple(sorted((k, bytes(v) if isinstance(v, Transform) else v) for k, v in switches.items()))
     for sig, (info, idx) in groups.items():
         key = (sig, key_sw, device, LIB_PATH)
         enc = _recompress_encoders.get(key)
         if enc is None or enc.max_batch < min(max_batch, len(idx)):
             if enc is not None:
                 enc.close()
-            enc = _recompress_encoders[key] = Encoder(params_from_jpeg(info, **switches), max_batch=min(max_batch, len(idx)), device=device)
+            try:
+                enc = _recompress_encoders[key] = Encoder(params_from_jpeg(info, **switches), max_batch=min(max_batch, len(idx)), device=device)
+            except MjhError as exc:         # a transform this group's geometry refuses (perfect, a crop outside the image, ...)
+                _recompress_encoders.pop(key, None)
+                if not (transforming or switches.get("perfect")):
+                    raise
+                for i in idx:
+                    out[i] = exc
+                continue
         for o in range(0, len(idx), enc.max_batch):
             part = idx[o:o + enc.max_batch]
             res = enc.transcode_host([files[i] for i in part], errors="return")
@@ -445,6 +502,14 @@ class Encoder:
         self.params = params
         self.max_batch = max_batch
         _chk(lib().mjh_encoder_create(C.byref(params), max_batch, device, C.byref(self._h)))
+        if getattr(params, "transform", None) is not None:      # params_from_jpeg(..., transform=...)
+            self.set_transform(params.transform)
+
+    def set_transform(self, transform=None, **spec):
+        """The lossless transform of the following transcode calls (mjh_encoder_set_transform): a Transform, transform_spec()'s
+        keywords, or None for none.  The encoder's parameters must be the transform's destination (params_from_jpeg)."""
+        t = transform_spec(transform, **spec)
+        _chk(lib().mjh_encoder_set_transform(self._h, C.byref(t) if t is not None else None))
 
     def close(self):
         if self._h:
@@ -586,11 +651,14 @@ class Encoder:
         _chk(lib().mjh_enc_onepass_stats(self._h, C.byref(on), C.byref(a), C.byref(b)))
         return dict(enabled=bool(on.value), long_blocks=a.value, big_groups=b.value)
 
-    def transcode_host(self, files, errors="raise"):
+    def transcode_host(self, files, errors="raise", **transform):
         """files: JPEG byte strings that agree with the encoder's parameters (params_from_jpeg).  Returns the re-coded files.
+        transform=..., trim=..., crop=... (transform_spec): set_transform() first; it stays in force for later calls.
         errors="return": no exception for a batch with damaged files -- their slots hold the MjhError, the slots of the good
         files None (nothing of such a batch is handed out: submit the good ones again)."""
         n = len(files)
+        if transform:
+            self.set_transform(transform_spec(**transform))
         try:
             self.submit_transcode(files)
             return [self.get_jpeg(i) for i in range(n)]

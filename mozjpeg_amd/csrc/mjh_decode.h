@@ -66,12 +66,35 @@ struct MjhDecBatch {
   int S;                           // subsequence length in bytes
 };
 
+// A lossless transform fused into the two places that store coefficients (mjh_encoder_set_transform): the kernels decode in the
+// SOURCE frame's geometry (the MjhConst they get is the source's) and store into the DESTINATION frame's planes.  Every operation
+// of transupp.c is: transpose or not; mirror the whole iMCUs in x and / or y (a partial iMCU at that edge stays in place); cut.
+// Inside a block the same: zig-zag position k goes to zz_t[k] under a transposition, and a block that was mirrored in x / y has
+// the coefficients of its odd columns / rows negated (bit k of odd_col / odd_row: destination position k lies in one).
+struct MjhXformComp {        // indexed by SOURCE component
+  int nblk;                  // blocks of the destination component (0: the component is dropped)
+  int wib, hib, kstride;     // of the destination component
+  int cw, ch;                // blocks across / down that mirror (whole iMCUs of the uncropped image)
+  int xcb, ycb;              // crop offset in blocks
+  long long coef_off;        // of the destination component inside one image's plane set
+};
+struct MjhXform {
+  int transpose, mirror_x, mirror_y, pad;
+  long long coefs_per_image; // of the destination
+  unsigned long long odd_col, odd_row;
+  MjhXformComp c[MJH_MAXC];
+  uint8_t zz_t[64];
+};
+
 // phase 0: every lane decodes its own subsequence from the guessed state; q >= 1: one synchronisation round (exits at once when
 // round q - 1 of the group changed nothing); then block indices, the storing pass, the DC prefix sums and the scrub of damaged images
 void mjh_launch_dec_sync(const MjhConst &C, const MjhDecBatch &B, int q, int first, hipStream_t s);
 void mjh_launch_dec_prefix(const MjhDecBatch &B, hipStream_t s);
 void mjh_launch_dec_store(const MjhConst &C, const MjhDecBatch &B, int16_t *coef_q, hipStream_t s);
 void mjh_launch_dec_dc(const MjhConst &C, const MjhDecBatch &B, int16_t *coef_q, hipStream_t s);
+// the storing pass and the DC sums with a transform: Cs = the SOURCE frame's geometry, X (device memory) = where things go
+void mjh_launch_dec_store_x(const MjhConst &Cs, const MjhDecBatch &B, int16_t *coef_q, const MjhXform *X, hipStream_t s);
+void mjh_launch_dec_dc_x(const MjhConst &Cs, const MjhDecBatch &B, int16_t *coef_q, const MjhXform *X, hipStream_t s);
 void mjh_launch_dec_scrub(const MjhConst &C, const MjhDecBatch &B, int16_t *coef_q, void *meta, hipStream_t s);
 // after the encode: image i's JFIF version / density bytes (7 bytes at file offset 11) and its status from the encoder's own checks
 void mjh_launch_dec_finish(const uint8_t *jfif7, int patch, uint8_t *out, size_t out_stride, const void *meta, unsigned *status, int n, hipStream_t s);

@@ -8,6 +8,9 @@
 // subsequences -- one subsequence per launch -- until the state they arrive with is the one recorded there.  No launch waits
 // for another workgroup; a round extends the correctly decoded prefix of every segment by at least one subsequence.
 // Every read is bounded by the segment's length and every store by the component's block count, whatever the bytes say.
+//
+// Lossless transforms (transupp.c's flips, rotations, transpositions, trim, crop, grayscale) are fused into the stores: k_dec_store_x
+// and k_dec_dc_x decode in the source frame's geometry and write every coefficient to its place in the destination frame (MjhXform).
 #include <hip/hip_runtime.h>
 #include "mjh_device.h"
 #include "mjh_decode.h"
@@ -77,20 +80,41 @@ __device__ __forceinline__ DecWhere dec_locate(const MjhComp *lc, const MjhDecSc
   return w;
 }
 
+// Where block (row, col) of a source component goes in the destination frame (-1: trimmed or cropped away, or the component is
+// dropped) and, in cls, whether it was mirrored in x (1) / y (2).  The inverse of the do_* routines of transupp.c, which exists
+// because each of them permutes the blocks it keeps.  The result is checked against the destination's block grid whatever
+// the descriptors say.
+__device__ __forceinline__ int dec_xf_block(const MjhXform &X, const MjhXformComp &xc, int row, int col, unsigned &cls)
+{
+  int x = X.transpose ? row : col, y = X.transpose ? col : row;
+  cls = 0;
+  if (X.mirror_x && x < xc.cw) { x = xc.cw - 1 - x; cls |= 1u; }
+  if (X.mirror_y && y < xc.ch) { y = xc.ch - 1 - y; cls |= 2u; }
+  x -= xc.xcb; y -= xc.ycb;
+  if (x < 0 || y < 0 || x >= xc.wib || y >= xc.hib) return -1;
+  const int blk = y * xc.wib + x;
+  return blk < xc.nblk ? blk : -1;
+}
+
 // Decodes from (p, k, b) while the next code word starts in front of end_bits.  STORE: also while ord < total (the segment's
 // blocks), coefficients and DC differences written; returns true when the segment's last block was completed here.
-template <bool STORE>
+template <bool STORE, bool XF = false>
 __device__ __forceinline__ bool dec_run(const MjhComp *lc, const MjhDecScan &sc, const MjhDecTable *T, DecReader &R, unsigned end_bits,
                                         unsigned &p, int &k, int &b, unsigned &n, unsigned ord, unsigned total, int mcu,
-                                        int16_t *coef_img, int16_t *diff_img, unsigned &flags)
+                                        int16_t *coef_img, int16_t *diff_img, unsigned &flags, const MjhXform *X = nullptr)
 {
   DecWhere wh{ 0, -1, 0 };
+  unsigned cls = 0;
+  // XF: wh.blk becomes the block's index in the DESTINATION component
+  auto remap = [&]() {
+    if (XF && wh.blk >= 0) { const int wib = lc[wh.j].wib, row = wh.blk / wib; wh.blk = dec_xf_block(*X, X->c[sc.comp[wh.j]], row, wh.blk - row * wib, cls); }
+  };
   int j = 0;
   {
     int t = b;
     while (j < sc.ncomp - 1 && t >= sc.nb[j]) { t -= sc.nb[j]; j++; }
   }
-  if (STORE) wh = dec_locate(lc, sc, mcu, b);
+  if (STORE) { wh = dec_locate(lc, sc, mcu, b); remap(); }
   bool bad = false;
   while (p < end_bits) {
     if (STORE && ord >= total) break;
@@ -119,6 +143,14 @@ __device__ __forceinline__ bool dec_run(const MjhComp *lc, const MjhDecScan &sc,
           const int val = v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
           if (val > 1023 || val < -1023) flags |= MJH_DEC_BADCOEF;
           // a run that passes position 63 lands in the spare entries of jpeg_natural_order, all 63 (jdhuff.c:619-628)
+          if (XF) {
+            if (wh.blk >= 0) {
+              const MjhXformComp &xc = X->c[sc.comp[j]];
+              const int kk = k > 63 ? 63 : k, kd = X->transpose ? (int)X->zz_t[kk] : kk;
+              const bool neg = (((cls & 1u) && ((X->odd_col >> kd) & 1ull)) != ((cls & 2u) && ((X->odd_row >> kd) & 1ull)));
+              coef_img[xc.coef_off + (long long)kd * xc.kstride + wh.blk] = (int16_t)(neg ? -val : val);
+            }
+          } else
           if (wh.blk >= 0) coef_img[lc[j].coef_off + (long long)(k > 63 ? 63 : k) * lc[j].kstride + wh.blk] = (int16_t)val;
         }
         p = R.advance(p, nb + s);
@@ -140,6 +172,7 @@ __device__ __forceinline__ bool dec_run(const MjhComp *lc, const MjhDecScan &sc,
         ord++;
         if (ord >= total) { if (bad) flags |= MJH_DEC_CORRUPT; return true; }
         wh = dec_locate(lc, sc, mcu, b);
+        remap();
       }
     }
   }
@@ -290,6 +323,57 @@ k_dec_store(MjhConst C, MjhDecBatch B, int16_t *__restrict__ coef_q)
   if (flags) atomicOr(&B.status[sc.image], flags);
 }
 
+// the descriptor of the transform into LDS: lanes index its tables by their own k
+__device__ __forceinline__ void dec_load_xform(const MjhXform *Xg, MjhXform *X)
+{
+  const unsigned *src = reinterpret_cast<const unsigned *>(Xg);
+  unsigned *dst = reinterpret_cast<unsigned *>(X);
+  for (unsigned i = threadIdx.x; i < sizeof(MjhXform) / 4; i += MJH_DEC_WG) dst[i] = src[i];
+  __syncthreads();
+}
+
+// k_dec_store with a transform: C = the SOURCE frame's geometry, the stores go where *Xg says (the destination's planes)
+__global__ void __launch_bounds__(MJH_DEC_WG)
+k_dec_store_x(MjhConst C, MjhDecBatch B, int16_t *__restrict__ coef_q, const MjhXform *__restrict__ Xg)
+{
+  __shared__ MjhDecScan sc;
+  __shared__ MjhDecTable T[2 * MJH_MAXC];
+  __shared__ MjhComp lc[MJH_MAXC];
+  __shared__ MjhXform X;
+  dec_load_xform(Xg, &X);
+  const unsigned g = blockIdx.x * MJH_DEC_WG + threadIdx.x;
+  const unsigned sg0 = B.sub_seg[blockIdx.x * MJH_DEC_WG];
+  dec_load_scan(C, B, B.segs[sg0].scan, &sc, T, lc);
+  const unsigned sg = B.sub_seg[g];
+  if (sg == 0xFFFFFFFFu) return;
+  const MjhDecSeg seg = B.segs[sg];
+  const unsigned i = g - (unsigned)seg.sub0, S = (unsigned)B.S;
+  DecReader R;
+  R.d = B.bytes + seg.off;
+  R.len = seg.len;
+  unsigned p = 0, n = 0, flags = 0;
+  int k = 0, b = 0;
+  if (i > 0) { const MjhDecState e = B.state[g - 1]; p = e.p; k = (int)(e.kb & 0xFFu); b = (int)(e.kb >> 8); }
+  const unsigned ord = B.ord[g], total = (unsigned)seg.nmcu * (unsigned)sc.bpm;
+  const bool last = i + 1 == (unsigned)seg.nsub;
+  if (ord < total) {
+    // (the entry state's b is ord mod bpm whenever the chain of states is the true one; a damaged stream may leave anything: the
+    //  block index decides where stores go, the state only how the bits are read)
+    b = (int)(ord % (unsigned)sc.bpm);
+    const int mcu = seg.mcu0 + (int)(ord / (unsigned)sc.bpm);
+    const bool fin = dec_run<true, true>(lc, sc, T, R, dec_sub_end_bits(R.len, i, (unsigned)seg.nsub, S), p, k, b, n, ord, total, mcu,
+                                   coef_q + (size_t)sc.image * X.coefs_per_image, B.diff + (size_t)sc.image * C.total_mcu_blocks, flags, &X);
+    if (fin) {
+      // the last block ends here: nothing but the padding of its last byte may follow (jdmarker.c next_marker: "extraneous bytes"),
+      // and it must not have read past the end ("Premature end of JPEG file" / JWRN_HIT_MARKER)
+      unsigned nbp = p >> 3;
+      if (p & 7u) { const unsigned byte = nbp < R.len ? (unsigned)R.d[nbp] : 0u; nbp += 1u + (byte == 0xFFu ? 1u : 0u); }
+      if (p > R.len * 8u || nbp < R.len) flags |= MJH_DEC_CORRUPT;
+    } else if (last) flags |= MJH_DEC_CORRUPT;               // the data ends in front of the segment's last block
+  } else if (i == 0) flags |= MJH_DEC_CORRUPT;
+  if (flags) atomicOr(&B.status[sc.image], flags);
+}
+
 // DC values = per component and restart segment the running sum of the stored differences (dummy blocks take part, jdhuff.c:588-592)
 __global__ void __launch_bounds__(MJH_DEC_WG)
 k_dec_dc(MjhConst C, MjhDecBatch B, int16_t *__restrict__ coef_q)
@@ -341,6 +425,65 @@ k_dec_dc(MjhConst C, MjhDecBatch B, int16_t *__restrict__ coef_q)
   }
 }
 
+// k_dec_dc with a transform: C = the SOURCE frame's geometry (the prediction chain is the source's, dummy blocks included); only the
+// final store is mapped
+__global__ void __launch_bounds__(MJH_DEC_WG)
+k_dec_dc_x(MjhConst C, MjhDecBatch B, int16_t *__restrict__ coef_q, const MjhXform *__restrict__ X)
+{
+  __shared__ int s_sum[MJH_DEC_WG];
+  __shared__ int s_rst[MJH_DEC_WG];
+  const MjhDecScan *scp = B.scans + blockIdx.y;        // (uniform: read through scalar loads, no private copy)
+  const int j = blockIdx.x, ncomp = scp->ncomp;
+  if (j >= ncomp) return;
+  const MjhXformComp xc = X->c[scp->comp[j]];
+  if (xc.nblk == 0) return;      // (uniform: a dropped component)
+  const int mcus = scp->mcus, mpr = scp->mcus_per_row, image = scp->image;
+  long long doff = scp->diff_off;
+  for (int t = 0; t < j; t++) doff += (long long)scp->nb[t] * mcus;
+  const MjhComp cc = C.c[scp->comp[j]];
+  const int nbj = scp->nb[j];
+  const int N = mcus * nbj, L = scp->ri * nbj;     // blocks of the component in the scan / per restart segment
+  const int per = (N + MJH_DEC_WG - 1) / MJH_DEC_WG;
+  const int m0 = per * (int)threadIdx.x < N ? per * (int)threadIdx.x : N, m1 = m0 + per < N ? m0 + per : N;
+  const int16_t *diff = B.diff + (size_t)image * C.total_mcu_blocks + doff;
+  int sum = 0, rst = 0;
+  {
+    int ph = m0 % L;
+    for (int m = m0; m < m1; m++) {
+      if (ph == 0) { sum = 0; rst = 1; }
+      sum += diff[m];
+      if (++ph == L) ph = 0;
+    }
+  }
+  s_sum[threadIdx.x] = sum; s_rst[threadIdx.x] = rst;
+  __syncthreads();
+  int pred = 0;
+  for (int t = 0; t < (int)threadIdx.x; t++) pred = s_rst[t] ? s_sum[t] : pred + s_sum[t];
+  int16_t *dc = coef_q + (size_t)image * X->coefs_per_image + xc.coef_off;
+  int ph = m0 % L;
+  int mcu = m0 / nbj, t = m0 - mcu * nbj;
+  int my = mcu / mpr, mx = mcu - my * mpr;
+  for (int m = m0; m < m1; m++) {
+    if (ph == 0) pred = 0;
+    pred += diff[m];
+    int blk;
+    if (ncomp == 1) blk = m;
+    else {
+      const int by = t / cc.h, bx = t - by * cc.h;
+      const int row = my * cc.v + by, col = mx * cc.h + bx;
+      blk = (row < cc.hib && col < cc.wib) ? row * cc.wib + col : -1;
+    }
+    if (blk >= 0 && blk < cc.nblk) {
+      unsigned cls;
+      const int row = blk / cc.wib;
+      blk = dec_xf_block(*X, xc, row, blk - row * cc.wib, cls);
+      if (blk >= 0) dc[blk] = (int16_t)pred;
+    }
+    if (++ph == L) ph = 0;
+    if (++t == nbj) { t = 0; if (++mx == mpr) { mx = 0; my++; } }
+  }
+}
+
 // a damaged image continues through the schedule as zeroed blocks; its status goes where the coefficient checks report
 __global__ void __launch_bounds__(256)
 k_dec_scrub(MjhConst C, MjhDecBatch B, int16_t *__restrict__ coef_q, MjhImageMeta *__restrict__ meta)
@@ -378,6 +521,14 @@ void mjh_launch_dec_store(const MjhConst &C, const MjhDecBatch &B, int16_t *coef
 void mjh_launch_dec_dc(const MjhConst &C, const MjhDecBatch &B, int16_t *coef_q, hipStream_t s)
 {
   hipLaunchKernelGGL(k_dec_dc, dim3(C.ncomp, B.nscan), dim3(MJH_DEC_WG), 0, s, C, B, coef_q);
+}
+void mjh_launch_dec_store_x(const MjhConst &Cs, const MjhDecBatch &B, int16_t *coef_q, const MjhXform *X, hipStream_t s)
+{
+  hipLaunchKernelGGL(k_dec_store_x, dim3(B.nsub_padded / MJH_DEC_WG), dim3(MJH_DEC_WG), 0, s, Cs, B, coef_q, X);
+}
+void mjh_launch_dec_dc_x(const MjhConst &Cs, const MjhDecBatch &B, int16_t *coef_q, const MjhXform *X, hipStream_t s)
+{
+  hipLaunchKernelGGL(k_dec_dc_x, dim3(Cs.ncomp, B.nscan), dim3(MJH_DEC_WG), 0, s, Cs, B, coef_q, X);
 }
 void mjh_launch_dec_scrub(const MjhConst &C, const MjhDecBatch &B, int16_t *coef_q, void *meta, hipStream_t s)
 {

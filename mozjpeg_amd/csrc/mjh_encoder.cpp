@@ -416,6 +416,11 @@ struct mjh_encoder {
   uint8_t *h_tdesc = nullptr, *d_tdesc = nullptr; size_t tdesc_cap = 0;
   void *d_tsub = nullptr; size_t tsub_cap = 0;      // MjhDecState + MjhDecCarry + ord per subsequence
   int16_t *d_tdiff = nullptr;
+  // mjh_encoder_set_transform: the DC differences are the SOURCE frame's (larger than the encoder's own under trim, crop and
+  // grayscale): a buffer of their own, made when a transform is first used and grown when a call's source needs more
+  bool xf_on = false;
+  mjh_transform xf_t{};
+  int16_t *d_tdiff_x = nullptr; size_t tdiff_x_cap = 0;
   unsigned *d_tstat = nullptr, *d_tchanged = nullptr, *h_tstat[2] = { nullptr, nullptr }, *h_tflag = nullptr;
   std::vector<int> tc_code; std::vector<std::string> tc_text;   // per file of the last transcode batch: what the host found
   int tc_n = 0, tc_rounds = 0, tc_syncs = 0, tc_S = 0;
@@ -865,7 +870,7 @@ static void free_all(mjh_encoder *e)
   if (e->d2h_stream) (void)hipStreamDestroy(e->d2h_stream);
   if (e->h_plin) (void)hipHostFree(e->h_plin);
   if (e->h_cfin) (void)hipHostFree(e->h_cfin);
-  for (void *q : { (void *)e->d_tc, (void *)e->d_tdesc, e->d_tsub, (void *)e->d_tdiff, (void *)e->d_tstat, (void *)e->d_tchanged }) if (q) (void)mjh_guard_free(q);
+  for (void *q : { (void *)e->d_tc, (void *)e->d_tdesc, e->d_tsub, (void *)e->d_tdiff, (void *)e->d_tdiff_x, (void *)e->d_tstat, (void *)e->d_tchanged }) if (q) (void)mjh_guard_free(q);
   for (void *q : { (void *)e->h_tc, (void *)e->h_tdesc, (void *)e->h_tstat[0], (void *)e->h_tstat[1], (void *)e->h_tflag }) if (q) (void)hipHostFree(q);
   for (hipEvent_t ev : e->tc_ev) if (ev) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : e->prof_events) (void)hipEventDestroy(ev);
@@ -2701,6 +2706,44 @@ static bool make_dec_table(const uint8_t bits[17], const uint8_t vals[256], bool
 
 static size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
+int mjh_transform_plan(const mjh_jpeg_info *f, const mjh_transform *t, MjhXformPlan *g);   // mjh_jpeg_parse.cpp
+
+extern "C" int mjh_encoder_set_transform(mjh_encoder *e, const mjh_transform *t)
+{
+  if (!e) return fail(MJH_EINVAL, "null encoder");
+  e->xf_on = false;
+  if (!t) return MJH_OK;
+  if (t->transform < MJH_XFORM_NONE || t->transform > MJH_XFORM_ROT_270) return fail(MJH_EINVAL, "transform %d (MJH_XFORM_NONE .. MJH_XFORM_ROT_270)", t->transform);
+  e->xf_t = *t;
+  e->xf_on = t->transform != MJH_XFORM_NONE || t->crop || t->grayscale;     // (anything else asks for nothing: today's path)
+  return MJH_OK;
+}
+
+// The device's view of a plan: per SOURCE component where its blocks go in the encoder's (= the destination's) planes, and the
+// position / sign tables from their definition -- a horizontal mirror negates the odd columns of a block, a vertical one its odd
+// rows, a transposition swaps row and column (k, zz_t[k] and the masks count in zig-zag order)
+static void build_xform(const MjhXformPlan &g, const MjhConst &Cd, MjhXform *X)
+{
+  memset(X, 0, sizeof(*X));
+  X->transpose = g.transpose; X->mirror_x = g.mirror_x; X->mirror_y = g.mirror_y;
+  X->coefs_per_image = Cd.coefs_per_image;
+  int zz_of[64];
+  for (int k = 0; k < 64; k++) zz_of[kZZ[k]] = k;
+  for (int k = 0; k < 64; k++) {
+    const int r = kZZ[k] >> 3, c = kZZ[k] & 7;
+    X->zz_t[k] = (uint8_t)zz_of[c * 8 + r];
+    if (c & 1) X->odd_col |= 1ull << k;
+    if (r & 1) X->odd_row |= 1ull << k;
+  }
+  for (int c = 0; c < Cd.ncomp && c < MJH_MAXC; c++) {        // (component c of the source is component c of the destination, or dropped)
+    const MjhComp &d = Cd.c[c];
+    MjhXformComp &x = X->c[c];
+    x.nblk = d.nblk; x.wib = d.wib; x.hib = d.hib; x.kstride = d.kstride; x.coef_off = d.coef_off;
+    x.cw = g.mir_cols * d.h; x.ch = g.mir_rows * d.v;
+    x.xcb = g.x_crop * d.h; x.ycb = g.y_crop * d.v;
+  }
+}
+
 extern "C" int mjh_transcode_host(mjh_encoder *e, const void *const jpegs[], const size_t sizes[], int n)
 {
   if (!e || !jpegs || !sizes || n < 1 || n > e->max_batch) return fail(MJH_EINVAL, "bad arguments (n=%d, max_batch=%d)", n, e ? e->max_batch : 0);
@@ -2722,7 +2765,7 @@ extern "C" int mjh_transcode_host(mjh_encoder *e, const void *const jpegs[], con
       const mjh_jpeg_info &f = infos[i];
       const mjh_params &p = e->p_created;
       static thread_local mjh_params q;
-      rc = mjh_params_from_jpeg(&f, p.compress_profile, &q);
+      rc = e->xf_on ? mjh_params_from_jpeg_transform(&f, &e->xf_t, p.compress_profile, &q) : mjh_params_from_jpeg(&f, p.compress_profile, &q);
       const char *field = nullptr;
       if (rc == MJH_OK) {
         if (q.image_width != p.image_width || q.image_height != p.image_height) field = "image size";
@@ -2740,9 +2783,42 @@ extern "C" int mjh_transcode_host(mjh_encoder *e, const void *const jpegs[], con
     }
     if (rc != MJH_OK) { e->tc_code[(size_t)i] = rc; e->tc_text[(size_t)i] = g_err; }
   });
+  // ---- 1b. with a transform the kernels decode in the SOURCE frame's geometry: the first good file of the call defines it
+  const bool xf = e->xf_on;
+  MjhConst Cs;
+  MjhXform X;
+  MjhXformPlan plan;
+  memset(&plan, 0, sizeof(plan));
+  if (xf) {
+    int first = -1;
+    for (int i = 0; i < n; i++) {
+      if (e->tc_code[(size_t)i] != MJH_OK) continue;
+      const mjh_jpeg_info &f = infos[(size_t)i];
+      if (first < 0) { first = i; continue; }
+      const mjh_jpeg_info &f0 = infos[(size_t)first];
+      const char *field = nullptr;
+      if (f.image_width != f0.image_width || f.image_height != f0.image_height) field = "image size";
+      else if (f.num_components != f0.num_components) field = "number of components";
+      for (int c = 0; c < f.num_components && !field; c++)
+        if (f.h_samp_factor[c] != f0.h_samp_factor[c] || f.v_samp_factor[c] != f0.v_samp_factor[c]) field = "sampling factors";
+      if (field) {
+        e->tc_code[(size_t)i] = fail(MJH_EINVAL, "does not match the source geometry of file %d, which a transform needs the whole call to share: %s", first, field);
+        e->tc_text[(size_t)i] = g_err;
+      }
+    }
+    if (first >= 0) {
+      static thread_local mjh_params qs;
+      int rc = mjh_transform_plan(&infos[(size_t)first], &e->xf_t, &plan);
+      if (rc == MJH_OK) rc = mjh_params_from_jpeg(&infos[(size_t)first], e->p_created.compress_profile, &qs);
+      if (rc != MJH_OK) return rc;
+      build_const(&qs, &Cs);
+      build_xform(plan, C, &X);
+    }
+  }
+  const MjhConst &G = xf ? Cs : C;          // the geometry the entropy-coded data is laid out in
   // ---- 2. descriptors: scans, restart segments (RSTn positions: a byte search), subsequences, derived Huffman tables
   const int S = e->dec_subseq;
-  const int frame_mcus = C.mcus_per_row * C.mcu_rows;
+  const int frame_mcus = G.mcus_per_row * G.mcu_rows;
   std::vector<MjhDecScan> scans;
   std::vector<MjhDecSeg> segs;
   std::vector<unsigned> sub_seg;
@@ -2760,6 +2836,11 @@ extern "C" int mjh_transcode_host(mjh_encoder *e, const void *const jpegs[], con
     long long diff_off = 0;
     for (int k = 0; k < f.num_scans && !why; k++) {
       const mjh_jpeg_scan &fs = f.scans[k];
+      if (xf) {      // a scan that holds only dropped components (grayscale on a non-interleaved file) is not decoded
+        bool kept = false;
+        for (int j = 0; j < fs.comps_in_scan; j++) kept = kept || fs.component_index[j] < plan.num_components;
+        if (!kept) continue;
+      }
       MjhDecScan sc;
       memset(&sc, 0, sizeof(sc));
       sc.image = i;
@@ -2768,7 +2849,7 @@ extern "C" int mjh_transcode_host(mjh_encoder *e, const void *const jpegs[], con
       for (int j = 0; j < sc.ncomp; j++) {
         const int ci = fs.component_index[j];
         sc.comp[j] = ci;
-        sc.nb[j] = sc.ncomp == 1 ? 1 : C.c[ci].h * C.c[ci].v;
+        sc.nb[j] = sc.ncomp == 1 ? 1 : G.c[ci].h * G.c[ci].v;
         sc.bpm += sc.nb[j];
         MjhDecTable T;
         if (!make_dec_table(fs.huff_bits[2 * fs.dc_tbl_no[j]], fs.huff_vals[2 * fs.dc_tbl_no[j]], true, &T)) { why = "Bogus Huffman table definition (JERR_BAD_HUFF_TABLE)"; break; }
@@ -2790,12 +2871,12 @@ extern "C" int mjh_transcode_host(mjh_encoder *e, const void *const jpegs[], con
           }
         }
       }
-      sc.mcus = sc.ncomp == 1 ? C.c[sc.comp[0]].nblk : frame_mcus;
-      sc.mcus_per_row = sc.ncomp == 1 ? C.c[sc.comp[0]].wib : C.mcus_per_row;
+      sc.mcus = sc.ncomp == 1 ? G.c[sc.comp[0]].nblk : frame_mcus;
+      sc.mcus_per_row = sc.ncomp == 1 ? G.c[sc.comp[0]].wib : G.mcus_per_row;
       sc.ri = (fs.restart_interval && (long long)fs.restart_interval < sc.mcus) ? (int)fs.restart_interval : sc.mcus;
       sc.diff_off = diff_off;
       diff_off += (long long)sc.mcus * sc.bpm;
-      if (diff_off > C.total_mcu_blocks) { why = "internal: DC difference array too small"; break; }
+      if (diff_off > G.total_mcu_blocks) { why = "internal: DC difference array too small"; break; }
       if (fs.data_size >= ((size_t)1 << 28)) { why = "a scan of 256 MB or more (bit positions inside a restart segment are 32-bit)"; break; }
       // restart segments: RSTn markers are the only 0xFF not followed by 0x00 inside the range (mjh_jpeg_probe)
       const int nseg_expected = (sc.mcus + sc.ri - 1) / sc.ri;
@@ -2853,7 +2934,8 @@ extern "C" int mjh_transcode_host(mjh_encoder *e, const void *const jpegs[], con
   e->tc_syncs++;
   const size_t nsubp = sub_seg.size();
   const size_t o_scans = 0, o_segs = up16(o_scans + scans.size() * sizeof(MjhDecScan)), o_subs = up16(o_segs + segs.size() * sizeof(MjhDecSeg)),
-               o_tabs = up16(o_subs + nsubp * 4), o_jfif = up16(o_tabs + tables.size() * sizeof(MjhDecTable)), desc_bytes = up16(o_jfif + (size_t)n * 8);
+               o_tabs = up16(o_subs + nsubp * 4), o_jfif = up16(o_tabs + tables.size() * sizeof(MjhDecTable)), o_xf = up16(o_jfif + (size_t)n * 8),
+               desc_bytes = xf ? up16(o_xf + sizeof(MjhXform)) : o_xf;
   if (total_bytes > e->tc_cap) {
     if (e->d_tc) { (void)mjh_guard_free(e->d_tc); e->d_tc = nullptr; }
     if (e->h_tc) { (void)hipHostFree(e->h_tc); e->h_tc = nullptr; }
@@ -2888,6 +2970,16 @@ extern "C" int mjh_transcode_host(mjh_encoder *e, const void *const jpegs[], con
     HIPCHK(mjh_numa_host_alloc((void **)&e->h_tflag, 64, hipHostMallocDefault, e->device));
     for (hipEvent_t &ev : e->tc_ev) HIPCHK(hipEventCreate(&ev));
   }
+  if (xf) {
+    const size_t need = (size_t)e->max_batch * (size_t)G.total_mcu_blocks * 2;
+    if (need > e->tdiff_x_cap) {
+      if (e->d_tdiff_x) { (void)mjh_guard_free(e->d_tdiff_x); e->d_tdiff_x = nullptr; }
+      e->tdiff_x_cap = 0;
+      HIPCHK(mjh_dmalloc((void **)&e->d_tdiff_x, need));
+      e->tdiff_x_cap = need;
+    }
+    memcpy(e->h_tdesc + o_xf, &X, sizeof(X));
+  }
   CopyPool::get().run(n, [&](int i) { memcpy(e->h_tc + file_off[(size_t)i], jpegs[i], sizes[i]); });
   memcpy(e->h_tdesc + o_scans, scans.data(), scans.size() * sizeof(MjhDecScan));
   memcpy(e->h_tdesc + o_segs, segs.data(), segs.size() * sizeof(MjhDecSeg));
@@ -2918,23 +3010,23 @@ extern "C" int mjh_transcode_host(mjh_encoder *e, const void *const jpegs[], con
   B.ord = (unsigned *)((uint8_t *)e->d_tsub + nsubp * (sizeof(MjhDecState) + sizeof(MjhDecCarry)));
   B.changed = e->d_tchanged;
   B.status = e->d_tstat;
-  B.diff = e->d_tdiff;
+  B.diff = xf ? e->d_tdiff_x : e->d_tdiff;
   B.nsub_padded = (int)nsubp; B.nseg = (int)segs.size(); B.nscan = (int)scans.size(); B.n = n;
   B.S = S > 0 ? S : 1;
   const bool timed = e->profiling != 0;
   HIPCHK(hipMemsetAsync(e->d_q, 0, (size_t)n * C.coefs_per_image * 2, s));
-  HIPCHK(hipMemsetAsync(e->d_tdiff, 0, (size_t)n * (size_t)C.total_mcu_blocks * 2, s));
+  HIPCHK(hipMemsetAsync(B.diff, 0, (size_t)n * (size_t)G.total_mcu_blocks * 2, s));
   HIPCHK(hipMemsetAsync(e->d_tstat, 0, (size_t)n * 4, s));
   HIPCHK(hipMemsetAsync(e->d_meta, 0, (size_t)n * sizeof(MjhImageMeta), s));
   if (timed) HIPCHK(hipEventRecord(e->tc_ev[0], s));
-  mjh_launch_dec_sync(C, B, 0, 1, s);
+  mjh_launch_dec_sync(G, B, 0, 1, s);
   // Synchronisation rounds in groups of launches: the rounds of a group run back to back (a round that finds the one before it
   // unchanged returns at once), the host reads the group's last flag and launches the next group only when it was set.  A round
   // extends the true prefix of every segment by one subsequence at least: max_nsub - 1 rounds always suffice.
   for (int done = 0, group = 3; done < max_nsub - 1;) {
     const int g = group < max_nsub - 1 - done ? group : max_nsub - 1 - done;
     HIPCHK(hipMemsetAsync(e->d_tchanged, 0, 64 * 4, s));
-    for (int q = 0; q < g; q++) mjh_launch_dec_sync(C, B, q, 0, s);
+    for (int q = 0; q < g; q++) mjh_launch_dec_sync(G, B, q, 0, s);
     done += g;
     e->tc_rounds += g;
     if (done >= max_nsub - 1) break;
@@ -2947,9 +3039,12 @@ extern "C" int mjh_transcode_host(mjh_encoder *e, const void *const jpegs[], con
   if (timed) HIPCHK(hipEventRecord(e->tc_ev[1], s));
   mjh_launch_dec_prefix(B, s);
   if (timed) HIPCHK(hipEventRecord(e->tc_ev[2], s));
-  mjh_launch_dec_store(C, B, e->d_q, s);
+  const MjhXform *d_X = (const MjhXform *)(e->d_tdesc + o_xf);
+  if (xf) mjh_launch_dec_store_x(G, B, e->d_q, d_X, s);
+  else mjh_launch_dec_store(C, B, e->d_q, s);
   if (timed) HIPCHK(hipEventRecord(e->tc_ev[3], s));
-  mjh_launch_dec_dc(C, B, e->d_q, s);
+  if (xf) mjh_launch_dec_dc_x(G, B, e->d_q, d_X, s);
+  else mjh_launch_dec_dc(C, B, e->d_q, s);
   mjh_launch_dec_scrub(C, B, e->d_q, e->d_meta, s);
   if (timed) { HIPCHK(hipEventRecord(e->tc_ev[4], s)); e->tc_timed = true; }
   HIPCHK(hipGetLastError());

@@ -83,6 +83,18 @@ struct MjhCoefSrc {
   long long stride[MJH_MAXC];        // bytes between images
 };
 
+// What jtransform_request_workspace decides for one source file and one mjh_transform (mjh_transform_plan, mjh_jpeg_parse.cpp):
+// every operation is "transpose or not, then mirror the whole iMCUs in x and / or y, then cut".  Coordinates are the
+// DESTINATION's (after the transposition).
+struct MjhXformPlan {
+  int active;                // 0: the transform asks for nothing, today's path
+  int transpose, mirror_x, mirror_y;
+  int num_components;        // of the destination (1 under grayscale)
+  int out_w, out_h;          // destination size in pixels
+  int x_crop, y_crop;        // crop offset in iMCUs (transupp.c:1715-1716)
+  int mir_cols, mir_rows;    // whole iMCUs of the uncropped image across / down: what mirrors (MCU_cols / MCU_rows of the do_* routines)
+};
+
 // per-table-slot constant data uploaded once per encoder
 struct MjhQuant {
   uint16_t q[4][64];        // zig-zag order quantizer step

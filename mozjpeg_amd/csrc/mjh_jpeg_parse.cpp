@@ -1,12 +1,15 @@
 // mjh_jpeg_parse.cpp -- host side of the re-compression path that needs no device: the marker segments of a JPEG file
 // (jdmarker.c) and the parameters jpeg_copy_critical_parameters derives from them (jctrans.c:75-171).  Nothing here decodes
 // a Huffman symbol: the entropy-coded data is only searched for 0xFF to find where a scan ends.
+#include <initializer_list>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
 
 #include "../../include/mozjpeg_hip.h"
+#include "mjh_internal.h"
 
+int mjh_transform_plan(const mjh_jpeg_info *f, const mjh_transform *t, MjhXformPlan *g);   // (also used by mjh_encoder.cpp)
 int mjh_internal_fail(int code, const char *msg);
 
 static int pfail(int code, const char *fmt, ...)
@@ -242,5 +245,136 @@ extern "C" int mjh_params_from_jpeg(const mjh_jpeg_info *info, int compress_prof
       return pfail(MJH_EINVAL, "Quantization table 0x%02x was not defined (JERR_NO_QUANT_TABLE)", p->quant_tbl_no[c]);
   }
   if (p->compress_profile == MJH_PROFILE_MAX_COMPRESSION) return mjh_params_search_progression(p);   // what jpeg_set_defaults selects there (jcparam.c:497-503)
+  return MJH_OK;
+}
+
+// ---- lossless transforms (transupp.c as jpegtran.c drives it) ---------------------------------------------------------------------
+// jtransform_parse_crop_spec (transupp.c:1395-1450): [W[f|r]][xH[f|r]][{+-}X[{+-}Y]], every part optional, nothing behind it
+static bool crop_number(const char *&s, unsigned *v)
+{
+  const char *b = s;
+  unsigned x = 0;
+  while (*s >= '0' && *s <= '9') x = x * 10u + (unsigned)(*s++ - '0');
+  *v = x;
+  return s != b;
+}
+static int crop_suffix(const char *&s)
+{
+  if (*s == 'f' || *s == 'F') { s++; return MJH_CROP_FORCE; }
+  if (*s == 'r' || *s == 'R') { s++; return MJH_CROP_REFLECT; }
+  return MJH_CROP_POS;
+}
+
+extern "C" int mjh_transform_parse_crop(mjh_transform *t, const char *spec)
+{
+  if (!t || !spec) return pfail(MJH_EINVAL, "bad arguments");
+  const char *s = spec;
+  t->crop = 0;
+  t->crop_width_set = t->crop_height_set = t->crop_xoffset_set = t->crop_yoffset_set = MJH_CROP_UNSET;
+  t->crop_width = t->crop_height = t->crop_xoffset = t->crop_yoffset = 0;
+  bool ok = true;
+  if (*s >= '0' && *s <= '9') { ok = crop_number(s, &t->crop_width); t->crop_width_set = crop_suffix(s); }
+  if (ok && (*s == 'x' || *s == 'X')) { s++; ok = crop_number(s, &t->crop_height); if (ok) t->crop_height_set = crop_suffix(s); }
+  if (ok && (*s == '+' || *s == '-')) { t->crop_xoffset_set = *s++ == '-' ? MJH_CROP_NEG : MJH_CROP_POS; ok = crop_number(s, &t->crop_xoffset); }
+  if (ok && (*s == '+' || *s == '-')) { t->crop_yoffset_set = *s++ == '-' ? MJH_CROP_NEG : MJH_CROP_POS; ok = crop_number(s, &t->crop_yoffset); }
+  if (!ok || *s) return pfail(MJH_EINVAL, "bogus -crop argument '%s'", spec);
+  t->crop = 1;
+  return MJH_OK;
+}
+
+// one axis of the crop request (transupp.c:1585-1716): the size after cropping and the offset in iMCUs
+static int crop_axis(int transform, unsigned full, unsigned imcu, unsigned size, int size_set, unsigned off, int off_set, unsigned *out, unsigned *off_imcu)
+{
+  if (off_set == MJH_CROP_UNSET) off = 0;
+  if (size_set == MJH_CROP_UNSET) {
+    if (off >= full) return pfail(MJH_EINVAL, "Invalid crop request (JERR_BAD_CROP_SPEC)");
+    size = full - off;
+  } else if (size > full) {
+    if (transform != MJH_XFORM_NONE || off >= size || off > size - full) return pfail(MJH_EINVAL, "Invalid crop request (JERR_BAD_CROP_SPEC)");
+    return pfail(MJH_EUNSUPPORTED, "crop extension: a crop of %u on an image of %u (do_crop_ext_* of transupp.c is not built)", size, full);
+  } else if (off >= full || size == 0 || off > full - size) return pfail(MJH_EINVAL, "Invalid crop request (JERR_BAD_CROP_SPEC)");
+  const unsigned o = off_set == MJH_CROP_NEG ? full - size - off : off;
+  *out = size + o % imcu;
+  *off_imcu = o / imcu;
+  return MJH_OK;
+}
+
+int mjh_transform_plan(const mjh_jpeg_info *f, const mjh_transform *t, MjhXformPlan *g)
+{
+  memset(g, 0, sizeof(*g));
+  g->num_components = f->num_components;
+  g->out_w = f->image_width; g->out_h = f->image_height;
+  if (!t) return MJH_OK;
+  if (t->transform < MJH_XFORM_NONE || t->transform > MJH_XFORM_ROT_270)
+    return pfail(t->transform == 8 || t->transform == 9 ? MJH_EUNSUPPORTED : MJH_EINVAL, "transform %d (MJH_XFORM_NONE .. MJH_XFORM_ROT_270; -wipe and -drop are not built)", t->transform);
+  if (t->transform == MJH_XFORM_NONE && !t->crop && !t->grayscale) return MJH_OK;      // (-trim / -perfect alone change nothing)
+  const int nc = f->num_components;
+  if (nc != 1 && nc != 3) return pfail(MJH_EUNSUPPORTED, "%d components", nc);
+  if (t->crop)
+    for (int s : { t->crop_width_set, t->crop_height_set })
+      if (s == MJH_CROP_FORCE || s == MJH_CROP_REFLECT)
+        return pfail(MJH_EUNSUPPORTED, "the f / r suffixes of a crop specification (crop extension, do_crop_ext_* of transupp.c is not built)");
+  g->active = 1;
+  int maxh = 1, maxv = 1;
+  for (int c = 0; c < nc; c++) { if (f->h_samp_factor[c] > maxh) maxh = f->h_samp_factor[c]; if (f->v_samp_factor[c] > maxv) maxv = f->v_samp_factor[c]; }
+  g->num_components = (t->grayscale && f->jpeg_color_space == MJH_CS_YCbCr && nc == 3) ? 1 : nc;
+  unsigned imw = g->num_components == 1 ? 8u : (unsigned)maxh * 8u, imh = g->num_components == 1 ? 8u : (unsigned)maxv * 8u;
+  unsigned W = (unsigned)f->image_width, H = (unsigned)f->image_height;
+  const int x = t->transform;
+  if (t->perfect) {
+    const bool need_w = x == MJH_XFORM_FLIP_H || x == MJH_XFORM_ROT_270 || x == MJH_XFORM_TRANSVERSE || x == MJH_XFORM_ROT_180;
+    const bool need_h = x == MJH_XFORM_FLIP_V || x == MJH_XFORM_ROT_90 || x == MJH_XFORM_TRANSVERSE || x == MJH_XFORM_ROT_180;
+    if ((need_w && W % imw) || (need_h && H % imh)) return pfail(MJH_EINVAL, "transformation is not perfect (%ux%u, iMCU %ux%u)", W, H, imw, imh);
+  }
+  g->transpose = x == MJH_XFORM_TRANSPOSE || x == MJH_XFORM_TRANSVERSE || x == MJH_XFORM_ROT_90 || x == MJH_XFORM_ROT_270;
+  g->mirror_x = x == MJH_XFORM_FLIP_H || x == MJH_XFORM_ROT_90 || x == MJH_XFORM_ROT_180 || x == MJH_XFORM_TRANSVERSE;
+  g->mirror_y = x == MJH_XFORM_FLIP_V || x == MJH_XFORM_ROT_270 || x == MJH_XFORM_ROT_180 || x == MJH_XFORM_TRANSVERSE;
+  if (g->transpose) { unsigned s = W; W = H; H = s; s = imw; imw = imh; imh = s; }
+  // W x H, imw x imh: the uncropped destination and its iMCU from here on
+  unsigned ow = W, oh = H, xc = 0, yc = 0;
+  if (t->crop) {
+    int rc = crop_axis(x, W, imw, t->crop_width, t->crop_width_set, t->crop_xoffset, t->crop_xoffset_set, &ow, &xc);
+    if (rc == MJH_OK) rc = crop_axis(x, H, imh, t->crop_height, t->crop_height_set, t->crop_yoffset, t->crop_yoffset_set, &oh, &yc);
+    if (rc) return rc;
+  }
+  // trim_right_edge / trim_bottom_edge (transupp.c:1455-1475): only a destination that reaches the partial iMCU loses it
+  if (t->trim && g->mirror_x) { const unsigned m = ow / imw; if (m > 0 && xc + m == W / imw) ow = m * imw; }
+  if (t->trim && g->mirror_y) { const unsigned m = oh / imh; if (m > 0 && yc + m == H / imh) oh = m * imh; }
+  g->out_w = (int)ow; g->out_h = (int)oh;
+  g->x_crop = (int)xc; g->y_crop = (int)yc;
+  g->mir_cols = (int)(W / imw); g->mir_rows = (int)(H / imh);
+  return MJH_OK;
+}
+
+extern "C" int mjh_params_from_jpeg_transform(const mjh_jpeg_info *info, const mjh_transform *t, int compress_profile, mjh_params *p)
+{
+  if (!info || !p) return pfail(MJH_EINVAL, "bad arguments");
+  MjhXformPlan g;
+  int rc = mjh_transform_plan(info, t, &g);
+  if (rc) return rc;
+  if (!g.active) return mjh_params_from_jpeg(info, compress_profile, p);
+  static thread_local mjh_jpeg_info d;       // the frame jtransform_adjust_parameters leaves (transupp.c:2048-2079)
+  d = *info;
+  if (t->grayscale) {
+    int maxh = 1, maxv = 1;
+    for (int c = 0; c < info->num_components; c++) { if (info->h_samp_factor[c] > maxh) maxh = info->h_samp_factor[c]; if (info->v_samp_factor[c] > maxv) maxv = info->v_samp_factor[c]; }
+    const bool known = (info->jpeg_color_space == MJH_CS_YCbCr && info->num_components == 3) || (info->jpeg_color_space == MJH_CS_GRAYSCALE && info->num_components == 1);
+    if (!known || info->h_samp_factor[0] != maxh || info->v_samp_factor[0] != maxv)
+      return pfail(MJH_EUNSUPPORTED, "Unsupported color conversion request (JERR_CONVERSION_NOTIMPL): grayscale needs a YCbCr or gray file whose first component is sampled at the maximum");
+    d.num_components = 1;                    // jpeg_set_colorspace(JCS_GRAYSCALE): id 1, its quantization table number kept
+    d.jpeg_color_space = MJH_CS_GRAYSCALE;
+    d.component_id[0] = 1;
+  }
+  if (g.num_components == 1) d.h_samp_factor[0] = d.v_samp_factor[0] = 1;
+  d.image_width = g.out_w; d.image_height = g.out_h;
+  if (g.transpose) {                          // transpose_critical_parameters (transupp.c:1831-1872)
+    for (int c = 0; c < d.num_components; c++) { const int s = d.h_samp_factor[c]; d.h_samp_factor[c] = d.v_samp_factor[c]; d.v_samp_factor[c] = s; }
+  }
+  rc = mjh_params_from_jpeg(&d, compress_profile, p);
+  if (rc) return rc;
+  if (g.transpose)                            // every table of the destination object, the profile's defaults included
+    for (int tb = 0; tb < 4; tb++)
+      for (int i = 0; i < 8; i++)
+        for (int j = 0; j < i; j++) { const uint16_t s = p->quantval[tb][i * 8 + j]; p->quantval[tb][i * 8 + j] = p->quantval[tb][j * 8 + i]; p->quantval[tb][j * 8 + i] = s; }
   return MJH_OK;
 }

@@ -8,7 +8,11 @@ in the same run (--repeats rounds, >= --seconds timed per round after a warm-up)
 and host synchronisations per call, the decoder's phase times and the per-kernel times of the schedule behind it
 (mjh_set_profiling(1), a separate pass), and the yardstick: oracle/_ref/jpegtran -copy none -revert -optimize over the same files,
 16 processes at a time, files on a RAM disk.  The first call's files are compared with the reference's.
-usage: python tools/bench_transcode.py [--workloads A,B] [--seconds 2] [--repeats 3] [--subseq 512,0] [--out profiles/transcode_bench]"""
+--transform NAME [--trim]: the same under a lossless transform (mozjpeg_amd.TRANSFORMS; the reference side runs jpegtran with the same
+switch), and next to the decoder's phase times what a plain device-to-device copy and a zeroing of the batch's coefficient planes take
+(the yardstick a separate permutation pass would have to be measured against).
+usage: python tools/bench_transcode.py [--workloads A,B] [--seconds 2] [--repeats 3] [--subseq 512,0] [--transform rot90 [--trim]]
+                                       [--out profiles/transcode_bench]"""
 import argparse
 import json
 import os
@@ -26,8 +30,34 @@ import numpy as np  # noqa: E402,F401
 import mozjpeg_amd as M  # noqa: E402
 import oracle_lib as O  # noqa: E402
 import transcode_cases as TC  # noqa: E402
+import transform_cases as XC  # noqa: E402
 
 SWITCHES = ["-copy", "none", "-revert", "-optimize"]
+
+
+def plane_probe(p, n, rounds=5):
+    """(bytes, copy ms, zeroing ms) of the coefficient planes of n images with parameters p: int16, per component 64 zig-zag planes of
+    the block count rounded up to 64; a plain device-to-device copy and a memset of that size, the best of `rounds`"""
+    per_image = 0
+    maxh = max(p.h_samp_factor[c] for c in range(p.num_components))
+    maxv = max(p.v_samp_factor[c] for c in range(p.num_components))
+    for c in range(p.num_components):
+        wib = -(-p.image_width * p.h_samp_factor[c] // (maxh * 8))
+        hib = -(-p.image_height * p.v_samp_factor[c] // (maxv * 8))
+        per_image += ((wib * hib + 63) & ~63) * 64
+    a = torch.empty(n * per_image, dtype=torch.int16, device="cuda")
+    b = torch.empty_like(a)
+    best = [1e9, 1e9]
+    for _ in range(rounds + 1):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        ev[0].record()
+        b.copy_(a)
+        ev[1].record()
+        a.zero_()
+        ev[2].record()
+        torch.cuda.synchronize()
+        best = [min(best[0], ev[0].elapsed_time(ev[1])), min(best[1], ev[1].elapsed_time(ev[2]))]
+    return a.numel() * 2, best[0], best[1]
 
 
 def sources(workload):
@@ -41,7 +71,7 @@ def sources(workload):
         return list(ex.map(lambda a: TC.cjpeg(a, ["-revert", "-quality", "75", "-sample", "2x2"]), imgs))
 
 
-def reference_rate(files, procs=16):
+def reference_rate(files, procs=16, switches=None):
     """files/s of the reference's jpegtran, `procs` processes at a time, input and output on a RAM disk; also its output files"""
     base = "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) else None
     with tempfile.TemporaryDirectory(dir=base) as td:
@@ -50,7 +80,7 @@ def reference_rate(files, procs=16):
                 fh.write(f)
 
         def one(i):
-            subprocess.check_call([TC.JPEGTRAN] + SWITCHES + ["-outfile", os.path.join(td, "o%d.jpg" % i), os.path.join(td, "%d.jpg" % i)])
+            subprocess.check_call([TC.JPEGTRAN] + (switches or SWITCHES) + ["-outfile", os.path.join(td, "o%d.jpg" % i), os.path.join(td, "%d.jpg" % i)])
         with ThreadPoolExecutor(procs) as ex:
             list(ex.map(one, range(min(len(files), 2 * procs))))          # warm-up
             t0 = time.perf_counter()
@@ -77,17 +107,21 @@ def main():
     ap.add_argument("--seconds", type=float, default=2.0)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--subseq", default="512,0")
+    ap.add_argument("--transform", default=None, choices=sorted(M.TRANSFORMS))
+    ap.add_argument("--trim", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    result = {"switches": SWITCHES, "workloads": {}}
+    xf = dict(transform=a.transform, trim=a.trim) if a.transform else {}
+    switches = SWITCHES[:2] + XC.jpegtran_args(**xf) + SWITCHES[2:]
+    result = {"switches": switches, "workloads": {}}
     for wl in a.workloads.split(","):
         files = sources(wl)
-        ref_rate, ref_outs, ramdisk = reference_rate(files)
+        ref_rate, ref_outs, ramdisk = reference_rate(files, switches=switches)
         r = {"files": len(files), "source_bytes": sum(len(f) for f in files), "reference_files_per_s": ref_rate, "reference_on_ramdisk": ramdisk, "configs": {}}
         encs = {}
         for s in a.subseq.split(","):
             os.environ["MJH_DECODE_SUBSEQ"] = s
-            encs[s] = M.Encoder(M.params_from_jpeg(files[0], revert=True, optimize=True), max_batch=len(files))
+            encs[s] = M.Encoder(M.params_from_jpeg(files[0], revert=True, optimize=True, **xf), max_batch=len(files))
         os.environ.pop("MJH_DECODE_SUBSEQ", None)
         for s, enc in encs.items():
             outs = enc.transcode_host(files)
@@ -111,6 +145,8 @@ def main():
             c["kernel_ms"] = enc.kernel_times()
             enc.set_profiling(0)
             enc.close()
+        if xf:
+            r["plane_bytes"], r["plane_copy_ms"], r["plane_zero_ms"] = plane_probe(M.params_from_jpeg(files[0], revert=True, optimize=True, **xf), len(files))
         result["workloads"][wl] = r
         print(json.dumps({wl: r}), flush=True)
     if a.out:
