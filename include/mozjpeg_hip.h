@@ -371,6 +371,10 @@ int mjh_transcode_host(mjh_encoder *e, const void *const jpegs[], const size_t s
 /* Code (MJH_OK / MJH_EINVAL / MJH_EUNSUPPORTED) of file i of the last mjh_transcode_host batch and, in *text (may be NULL;
  * owned by the encoder, valid until the next batch), its reason.  Synchronises with the batch. */
 int mjh_transcode_status(mjh_encoder *e, int i, const char **text);
+/* Files of the last mjh_transcode_host / mjh_decode_host call that mjh_transcode_status knows about: n once the call has looked at
+ * its files, 0 when it was refused as a whole (bad arguments or options, an encoder that cannot take it) -- such a call leaves
+ * no per-file status, and none of an earlier batch. */
+int mjh_transcode_batch_size(mjh_encoder *e);
 /* Figures of the last mjh_transcode_host call: subsequence length in bytes (0 = one lane per restart segment), the
  * synchronisation rounds launched, host synchronisations inside the call, and -- with mjh_set_profiling(e, 1) -- the
  * milliseconds of the decoder's phases: [0] first pass + synchronisation rounds, [1] block indices, [2] storing pass,
@@ -421,6 +425,48 @@ int mjh_params_from_jpeg_transform(const mjh_jpeg_info *info, const mjh_transfor
  * to 224): the first good file of a call defines it, every other file of the call must have the same size and sampling
  * factors, and every file's own destination parameters must equal the encoder's, else MJH_EINVAL naming file and field. */
 int mjh_encoder_set_transform(mjh_encoder *e, const mjh_transform *t);
+
+/* ---- decoding existing files to pixels (djpeg [-nosmooth] [-grayscale | -rgb]) -----------------------------------------------
+ * JPEG bytes in host memory in, interleaved 8-bit pixels in device memory out (and in host memory on request): the marker walk
+ * and the Huffman decoder kernels of mjh_transcode_host, then dequantization + inverse DCT and upsampling + colour conversion
+ * (mjh_idct.hip).  The pixels are the bytes the reference's djpeg writes with the slow integer IDCT (-dct int, its default):
+ * every sample, every edge, and the wrap of its range-limit table on files with absurd coefficients.
+ * The encoder is one made from mjh_params_from_jpeg: it owns the geometry, the quantization tables and the coefficient planes;
+ * the files accepted and the agreement every file of a batch must show are those of mjh_transcode_host.
+ * out_color_space: 0 = djpeg's default for the file (gray for a one-component file, RGB otherwise), MJH_CS_GRAYSCALE
+ * (a YCbCr file: its Y alone, no chroma is transformed; an RGB file: rgb_gray_convert) or MJH_CS_RGB (a gray file: replicated).
+ * pixel_size / rgb_offset: the layouts mjh_params.input_pixel_size / rgb_offset name for input -- 3 or 4 bytes per RGB pixel
+ * (0 = 3), the byte of R, G and B inside it (all 0 = 0, 1, 2); the fourth byte of a 4-byte pixel is 0xFF.  Gray pixels are
+ * one byte.  fancy_upsampling: 1 = djpeg's default, 0 = -nosmooth.  MJH_EINVAL: an unknown colour space, pixel size or offsets.
+ * MJH_EUNSUPPORTED: a lossless transform set on the encoder; other IDCT methods, scaling, cropping and colour quantization
+ * have no option here. */
+typedef struct {
+  int out_color_space;
+  int pixel_size;
+  int rgb_offset[3];
+  int fancy_upsampling;
+} mjh_decode_opts;
+void mjh_decode_opts_defaults(mjh_decode_opts *o);
+/* Decodes n files (opts == NULL: the defaults).  Queued on the encoder's stream; the bytes need not stay valid after the call.
+ * Damaged entropy-coded data fails the batch with MJH_EINVAL when its pixels are waited for (mjh_get_pixels);
+ * mjh_transcode_status then tells the damaged files from the good ones, and a damaged file has no pixels.  Decoding does not
+ * apply the entropy coder's coefficient-range check: a value no Huffman code could carry again is still a sample to djpeg. */
+int mjh_decode_host(mjh_encoder *e, const void *const jpegs[], const size_t sizes[], int n, const mjh_decode_opts *opts);
+/* Waits for the last mjh_decode_host batch and tells whether it is clean: MJH_OK, or MJH_EINVAL naming the first damaged file
+ * (whose slot of the device buffer then holds no pixels of this batch).  For callers who stay on the device: the one call
+ * between mjh_decode_host and reading mjh_get_pixels_device's buffer. */
+int mjh_decode_wait(mjh_encoder *e);
+/* Copies image i of the last mjh_decode_host batch to host memory, row_pitch bytes between rows (synchronises). */
+int mjh_get_pixels(mjh_encoder *e, int i, void *dst, size_t row_pitch);
+/* The device buffer of the last mjh_decode_host batch: pixel (x, y) of image i starts at base + i * image_stride + y * row_pitch
+ * + x * pixel_size.  Rows are padded (whole groups of four pixels, 16-byte aligned).  Does not wait: the work is queued on the
+ * encoder's stream; mjh_decode_wait waits for it AND reports damaged files, mjh_encoder_sync only waits.  The buffer is reused
+ * by the next decode call. */
+int mjh_get_pixels_device(mjh_encoder *e, void **d_base, size_t *row_pitch, size_t *image_stride);
+/* Size and pixel size of the last decoded batch and, with mjh_set_profiling(e, 1), the milliseconds of its two pixel kernels:
+ * [0] dequantization + inverse DCT, [1] upsampling + colour conversion (the Huffman decoder's phases: mjh_transcode_stats).
+ * Any pointer may be NULL. */
+int mjh_decode_stats(mjh_encoder *e, int *width, int *height, int *pixel_size, float ms[2]);
 
 /* The sequential Huffman coder writes a scan without restart intervals in one walk over its blocks (MJH_ENC_ONEPASS=0 in
  * the environment of mjh_encoder_create: the length pass and the second walk of the restart path for every scan).  enabled:

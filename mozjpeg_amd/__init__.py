@@ -82,6 +82,11 @@ class JpegInfo(C.Structure):
                 ("num_scans", C.c_int), ("scans", JpegScan * 4)]
 
 
+class DecodeOpts(C.Structure):
+    """mjh_decode_opts: what djpeg's -grayscale / -rgb / -nosmooth and the extended pixel layouts choose"""
+    _fields_ = [("out_color_space", C.c_int), ("pixel_size", C.c_int), ("rgb_offset", C.c_int * 3), ("fancy_upsampling", C.c_int)]
+
+
 class Result(C.Structure):
     """mjh_result: one finished file inside the pinned result arena"""
     _fields_ = [("offset", C.c_uint64), ("size", C.c_uint64)]
@@ -160,6 +165,15 @@ def lib():
         L.mjh_transcode_host.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int]
         L.mjh_transcode_status.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p)]
         L.mjh_transcode_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float)]
+        if hasattr(L, "mjh_decode_host"):             # (absent from an older MOZJPEG_AMD_LIB variant, as below)
+            L.mjh_decode_opts_defaults.argtypes = [C.POINTER(DecodeOpts)]
+            L.mjh_decode_opts_defaults.restype = None
+            L.mjh_decode_host.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(DecodeOpts)]
+            L.mjh_get_pixels.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+            L.mjh_get_pixels_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+            L.mjh_decode_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float)]
+            L.mjh_decode_wait.argtypes = [C.c_void_p]
+            L.mjh_transcode_batch_size.argtypes = [C.c_void_p]
         if hasattr(L, "mjh_enc_onepass_stats"):       # (absent from a MOZJPEG_AMD_LIB variant built from an older tree: A/B runs against it)
             L.mjh_enc_onepass_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
         _lib = L
@@ -431,6 +445,87 @@ def recompress(files, *, max_batch=64, device=0, **switches):
     return out
 
 
+PIXEL_LAYOUTS = {"rgb": (3, (0, 1, 2)), "bgr": (3, (2, 1, 0)), "rgbx": (4, (0, 1, 2)), "bgrx": (4, (2, 1, 0)),
+                 "xbgr": (4, (3, 2, 1)), "xrgb": (4, (1, 2, 3))}      # name -> pixel_size, rgb_offset (the extended colour spaces)
+
+
+def decode_opts(color=None, layout=None, pixel_size=0, rgb_offset=None, fancy_upsampling=True):
+    """DecodeOpts from djpeg's vocabulary.  color: None (the file's default: gray stays gray, everything else RGB), "gray" /
+    "grayscale" (-grayscale), "rgb" (-rgb) or a CS_* number; layout: a name out of PIXEL_LAYOUTS, or pixel_size and rgb_offset;
+    fancy_upsampling=False: -nosmooth."""
+    o = DecodeOpts()
+    lib().mjh_decode_opts_defaults(C.byref(o))
+    if isinstance(color, str):
+        names = {"gray": CS_GRAYSCALE, "grayscale": CS_GRAYSCALE, "rgb": CS_RGB}
+        if color not in names:
+            raise MjhError(EINVAL, "color %r (None, 'gray' or 'rgb')" % (color,))
+        o.out_color_space = names[color]
+    elif color is not None:
+        o.out_color_space = int(color)
+    if layout is not None:
+        if layout not in PIXEL_LAYOUTS:
+            raise MjhError(EINVAL, "layout %r (one of %s)" % (layout, ", ".join(PIXEL_LAYOUTS)))
+        pixel_size, rgb_offset = PIXEL_LAYOUTS[layout]
+    o.pixel_size = int(pixel_size)
+    if rgb_offset is not None:
+        o.rgb_offset[:] = [int(v) for v in rgb_offset]
+    o.fancy_upsampling = int(bool(fancy_upsampling))
+    # the library's own checks (plan_pixels), made here as well so that decode() can refuse its options before it groups files
+    if o.out_color_space not in (0, CS_GRAYSCALE, CS_RGB):
+        raise MjhError(EINVAL, "out_color_space %d (0, CS_GRAYSCALE or CS_RGB)" % o.out_color_space)
+    if o.out_color_space == CS_GRAYSCALE:
+        if o.pixel_size not in (0, 1):
+            raise MjhError(EINVAL, "pixel_size %d of grayscale output (0 or 1)" % o.pixel_size)
+    elif o.pixel_size not in ((0, 3, 4) if o.out_color_space == CS_RGB else (0, 1, 3, 4)):     # (the file's default: 1 is a gray file's)
+        raise MjhError(EINVAL, "pixel_size %d of RGB output (0, 3 or 4)" % o.pixel_size)
+    off = list(o.rgb_offset)
+    if off != [0, 0, 0] and o.pixel_size in (0, 3, 4):
+        px = o.pixel_size or 3
+        if any(v < 0 or v >= px for v in off) or len(set(off)) != 3:
+            raise MjhError(EINVAL, "rgb_offset %d,%d,%d of %d-byte pixels" % (off[0], off[1], off[2], px))
+    return o
+
+
+_decode_encoders = {}
+
+
+def decode(files, *, max_batch=64, device=0, **opts):
+    """Decode JPEG files to pixels on the GPU: the bytes `djpeg` (+ -grayscale / -rgb / -nosmooth, see decode_opts) writes for
+    each of them, as numpy arrays [H, W, C] ([H, W] for gray) in input order.  The files are grouped by what a batch must have in
+    common; one encoder per group is kept for later calls.  A file that cannot be decoded (unsupported type, malformed headers,
+    damaged entropy-coded data) gets the MjhError in its slot; the others are unaffected."""
+    files = [bytes(f) for f in files]
+    out = [None] * len(files)
+    groups = {}
+    o = decode_opts(**opts)
+    for i, f in enumerate(files):
+        try:
+            info = jpeg_info(f)
+        except MjhError as exc:
+            out[i] = exc
+            continue
+        groups.setdefault(_signature(info), (info, []))[1].append(i)
+    for sig, (info, idx) in groups.items():
+        key = (sig, device, LIB_PATH)
+        enc = _decode_encoders.get(key)
+        if enc is None or enc.max_batch < min(max_batch, len(idx)):
+            if enc is not None:
+                enc.close()
+            enc = _decode_encoders[key] = Encoder(params_from_jpeg(info, revert=True), max_batch=min(max_batch, len(idx)), device=device)
+        for a in range(0, len(idx), enc.max_batch):
+            part = idx[a:a + enc.max_batch]
+            res = enc.decode_host([files[i] for i in part], errors="return", opts=o)
+            bad = [k for k, r in enumerate(res) if isinstance(r, MjhError)]
+            if bad and len(bad) < len(part):           # the good files of the batch once more, without the damaged ones
+                good = [k for k in range(len(part)) if k not in bad]
+                again = enc.decode_host([files[part[k]] for k in good], errors="return", opts=o)
+                for k, r in zip(good, again):
+                    res[k] = r
+            for k, i in enumerate(part):
+                out[i] = res[k]
+    return out
+
+
 def pinned_empty(shape, dtype=np.uint8):
     """numpy array in pinned host memory (mjh_host_alloc): mjh_encode_host reads it by DMA, without a staging copy.
     The memory is released when the array (and every view of it) is gone."""
@@ -665,11 +760,72 @@ class Encoder:
         except MjhError:
             if errors != "return":
                 raise
-            res = []
-            for i in range(n):
-                rc, text = self.transcode_status(i)
-                res.append(MjhError(rc, text) if rc != OK else None)
-            if all(r is None for r in res):
+            res = self._file_errors(n)
+            if res is None:
+                raise
+            return res
+
+    # existing files in, pixels out (djpeg): Huffman decoding, inverse DCT, upsampling and colour conversion on the device
+    def submit_decode(self, files, opts=None, **kw):
+        """Asynchronous mjh_decode_host (opts: a DecodeOpts, or decode_opts()' keywords); results through get_pixels() /
+        pixels_device()."""
+        files = [bytes(f) for f in files]
+        n = len(files)
+        o = opts if opts is not None else decode_opts(**kw)
+        _chk(lib().mjh_decode_host(self._h, (C.c_char_p * n)(*files), (C.c_size_t * n)(*[len(f) for f in files]), n, C.byref(o)))
+        return n
+
+    def wait_decode(self):
+        """Waits for the last decoded batch and raises the MjhError of its first damaged file (mjh_decode_wait): the call between
+        submit_decode() and reading the buffer pixels_device() names."""
+        _chk(lib().mjh_decode_wait(self._h))
+
+    def _file_errors(self, n):
+        """after a failed transcode / decode call of n files: the per-file MjhError / None list, or None when the call was refused as
+        a whole (bad options, an encoder that cannot take it) or every file is fine -- then the call's own error is the answer"""
+        if lib().mjh_transcode_batch_size(self._h) != n:
+            return None
+        res = []
+        for i in range(n):
+            rc, text = self.transcode_status(i)
+            res.append(MjhError(rc, text) if rc != OK else None)
+        return None if all(r is None for r in res) else res
+
+    def decode_stats(self):
+        """width, height and pixel size of the last decoded batch, and the times of its two pixel kernels (ms, with profiling)"""
+        w, h, px, ms = C.c_int(), C.c_int(), C.c_int(), (C.c_float * 2)()
+        _chk(lib().mjh_decode_stats(self._h, C.byref(w), C.byref(h), C.byref(px), ms))
+        return dict(width=w.value, height=h.value, pixel_size=px.value, ms=dict(idct=float(ms[0]), upcolor=float(ms[1])))
+
+    def get_pixels(self, i, out=None):
+        """image i of the last decoded batch: uint8 [H, W, C], [H, W] for gray (mjh_get_pixels); out: an array of that shape with
+        contiguous rows to fill instead of a new one"""
+        st = self.decode_stats()
+        shape = (st["height"], st["width"]) + ((st["pixel_size"],) if st["pixel_size"] > 1 else ())
+        a = np.empty(shape, np.uint8) if out is None else out
+        assert a.shape == shape and a.dtype == np.uint8 and a.strides[1:] == np.empty(shape[1:], np.uint8).strides, "expected uint8 %s" % (shape,)
+        _chk(lib().mjh_get_pixels(self._h, i, a.ctypes.data, a.strides[0]))
+        return a
+
+    def pixels_device(self):
+        """(device pointer, row pitch, image stride, decode_stats()) of the last decoded batch (mjh_get_pixels_device); wait_decode() first"""
+        base, pitch, stride = C.c_void_p(), C.c_size_t(), C.c_size_t()
+        _chk(lib().mjh_get_pixels_device(self._h, C.byref(base), C.byref(pitch), C.byref(stride)))
+        return base.value, pitch.value, stride.value, self.decode_stats()
+
+    def decode_host(self, files, errors="raise", opts=None, **kw):
+        """files: JPEG byte strings that agree with the encoder's parameters (params_from_jpeg).  Returns their pixels, a list of
+        numpy arrays.  errors="return": no exception for a batch with damaged files -- their slots hold the MjhError, the slots
+        of the good files None (nothing of such a batch is handed out: submit the good ones again)."""
+        n = len(files)
+        try:
+            self.submit_decode(files, opts=opts, **kw)
+            return [self.get_pixels(i) for i in range(n)]
+        except MjhError:
+            if errors != "return":
+                raise
+            res = self._file_errors(n)
+            if res is None:
                 raise
             return res
 

@@ -26,6 +26,7 @@
 #include "mjh_launch.h"
 #include "mjh_lossless.h"
 #include "mjh_decode.h"
+#include "mjh_idct.h"
 #include "mjh_guard.h"
 #include "mjh_numa.h"
 #include "mjh_arith_table.h"
@@ -426,6 +427,15 @@ struct mjh_encoder {
   int tc_n = 0, tc_rounds = 0, tc_syncs = 0, tc_S = 0;
   bool tc_queued = false;               // the last mjh_transcode_host call got as far as queueing its batch (else only the host's findings exist)
   hipEvent_t tc_ev[5] = { nullptr, nullptr, nullptr, nullptr, nullptr }; bool tc_timed = false;
+  // mjh_decode_host (mjh_idct.hip): the interleaved pixels of the last decoded batch (made at the first call, grown when a later
+  // call asks for larger pixels), its layout, its status words on the host and the event behind everything it queued
+  uint8_t *d_pixout = nullptr; size_t pixout_cap = 0;
+  MjhPixOut dp{};
+  unsigned *h_dstat = nullptr;
+  hipEvent_t dp_ev[3] = { nullptr, nullptr, nullptr }, dp_done = nullptr; bool dp_timed = false;
+  bool dp_waited = false;               // ... and has been waited for (the guard check runs once per batch)
+  bool dp_queued = false;               // the last batch of files went through mjh_decode_host and got as far as its kernels
+  int dp_n = 0;
 };
 
 static long div_round_up(long a, long b) { return (a + b - 1) / b; }
@@ -873,6 +883,9 @@ static void free_all(mjh_encoder *e)
   for (void *q : { (void *)e->d_tc, (void *)e->d_tdesc, e->d_tsub, (void *)e->d_tdiff, (void *)e->d_tdiff_x, (void *)e->d_tstat, (void *)e->d_tchanged }) if (q) (void)mjh_guard_free(q);
   for (void *q : { (void *)e->h_tc, (void *)e->h_tdesc, (void *)e->h_tstat[0], (void *)e->h_tstat[1], (void *)e->h_tflag }) if (q) (void)hipHostFree(q);
   for (hipEvent_t ev : e->tc_ev) if (ev) (void)hipEventDestroy(ev);
+  if (e->d_pixout) (void)mjh_guard_free(e->d_pixout);
+  if (e->h_dstat) (void)hipHostFree(e->h_dstat);
+  for (hipEvent_t ev : { e->dp_ev[0], e->dp_ev[1], e->dp_ev[2], e->dp_done }) if (ev) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : e->prof_events) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : e->side_events) (void)hipEventDestroy(ev);
   if (e->copy_done) (void)hipEventDestroy(e->copy_done);
@@ -2744,8 +2757,12 @@ static void build_xform(const MjhXformPlan &g, const MjhConst &Cd, MjhXform *X)
   }
 }
 
-extern "C" int mjh_transcode_host(mjh_encoder *e, const void *const jpegs[], const size_t sizes[], int n)
+// The front half both mjh_transcode_host and mjh_decode_host run: marker walk, agreement with the encoder, descriptors, staging and
+// the K-D kernels.  It leaves the batch's coefficient planes in d_q and its per-image status in d_tstat, both queued on e->stream.
+// pixels: the caller is mjh_decode_host (no result arenas are made); *o_jfif_out: where the files' APP0 fields lie in d_tdesc
+static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t sizes[], int n, bool pixels, size_t *o_jfif_out)
 {
+  if (e) { e->tc_n = 0; e->tc_code.clear(); e->tc_text.clear(); e->tc_queued = false; e->dp_queued = false; }   // a call refused as a whole leaves no per-file status, and none of an earlier batch
   if (!e || !jpegs || !sizes || n < 1 || n > e->max_batch) return fail(MJH_EINVAL, "bad arguments (n=%d, max_batch=%d)", n, e ? e->max_batch : 0);
   if (e->lossless) return fail(MJH_EINVAL, "a lossless encoder has no DCT coefficients (jpeg_copy_critical_parameters: JERR_NOTIMPL, jctrans.c:83)");
   if (e->p.trellis_quant)
@@ -2928,7 +2945,7 @@ extern "C" int mjh_transcode_host(mjh_encoder *e, const void *const jpegs[], con
   for (int i = 0; i < n; i++)
     if (e->tc_code[(size_t)i] != MJH_OK) return fail(e->tc_code[(size_t)i], "file %d: %s", i, e->tc_text[(size_t)i].c_str());
   // ---- 3. staging: the files as they are + one descriptor block, two host->device copies
-  int rc = host_buffers(e);
+  int rc = pixels ? MJH_OK : host_buffers(e);
   if (rc) return rc;
   HIPCHK(hipStreamSynchronize(e->stream));   // the staging buffers may still feed the previous batch
   e->tc_syncs++;
@@ -3048,6 +3065,16 @@ extern "C" int mjh_transcode_host(mjh_encoder *e, const void *const jpegs[], con
   mjh_launch_dec_scrub(C, B, e->d_q, e->d_meta, s);
   if (timed) { HIPCHK(hipEventRecord(e->tc_ev[4], s)); e->tc_timed = true; }
   HIPCHK(hipGetLastError());
+  *o_jfif_out = o_jfif;
+  return MJH_OK;
+}
+
+extern "C" int mjh_transcode_host(mjh_encoder *e, const void *const jpegs[], const size_t sizes[], int n)
+{
+  size_t o_jfif = 0;
+  int rc = decode_front(e, jpegs, sizes, n, false, &o_jfif);
+  if (rc) return rc;
+  hipStream_t s = e->stream;
   // ---- 5. the entropy-coding passes, as for coefficient input; then this file's APP0 fields and the hand-over
   const int b = (int)(e->host_calls & 1u);
   e->host_calls++;
@@ -3070,6 +3097,14 @@ extern "C" int mjh_transcode_status(mjh_encoder *e, int i, const char **text)
 {
   if (!e || i < 0 || i >= e->tc_n) return fail(MJH_EINVAL, "bad file index");
   if (text) *text = "";
+  if (e->tc_code[(size_t)i] == MJH_OK && e->dp_queued && i < e->dp_n) {      // mjh_decode_host: the decoder's status alone
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipEventSynchronize(e->dp_done));
+    if (e->h_dstat[i]) {
+      e->tc_code[(size_t)i] = MJH_EINVAL;
+      e->tc_text[(size_t)i] = "Corrupt JPEG data: the entropy-coded data does not decode to the scan's blocks (premature end, extraneous bytes or a bad Huffman code; the reference warns: JWRN_HIT_MARKER / JWRN_EXTRANEOUS_DATA / JWRN_HUFF_BAD_CODE)";
+    }
+  }
   if (e->tc_code[(size_t)i] == MJH_OK && e->tc_queued && e->res_buf >= 0 && e->tc_batch[e->res_buf] && i < e->res_n[e->res_buf]) {
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipEventSynchronize(e->ev_packed[e->res_buf]));
@@ -3097,6 +3132,178 @@ extern "C" int mjh_transcode_stats(mjh_encoder *e, int *subseq, int *rounds, int
       HIPCHK(hipSetDevice(e->device));
       HIPCHK(hipEventSynchronize(e->tc_ev[4]));
       for (int k = 0; k < 4; k++) HIPCHK(hipEventElapsedTime(&ms[k], e->tc_ev[k], e->tc_ev[k + 1]));
+    }
+  }
+  return MJH_OK;
+}
+
+// ---- decoding files to pixels: the front half above, then K-I1 / K-I2 (mjh_idct.hip) instead of the entropy-coding passes ---------
+extern "C" void mjh_decode_opts_defaults(mjh_decode_opts *o)
+{
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  o->rgb_offset[1] = 1; o->rgb_offset[2] = 2;
+  o->fancy_upsampling = 1;
+}
+
+// the layout of the output and the road to it: djpeg's choices for this frame (jdmaster.c, jinit_upsampler jdsample.c:444-525,
+// jinit_color_deconverter jdcolor.c)
+static int plan_pixels(const mjh_encoder *e, const mjh_decode_opts *o, MjhPixOut *P)
+{
+  const MjhConst &C = e->C;
+  memset(P, 0, sizeof(*P));
+  if (C.ncomp != 1 && C.ncomp != 3) return fail(MJH_EUNSUPPORTED, "decoding files of %d components", C.ncomp);
+  if (C.precision != 8) return fail(MJH_EUNSUPPORTED, "decoding %d-bit files", C.precision);
+  const bool src_gray = C.ncomp == 1, src_rgb = C.ncomp == 3 && e->p_created.color_transform == MJH_COLOR_NONE;
+  int cs = o->out_color_space;
+  if (cs == 0) cs = src_gray ? MJH_CS_GRAYSCALE : MJH_CS_RGB;
+  if (cs != MJH_CS_GRAYSCALE && cs != MJH_CS_RGB) return fail(MJH_EINVAL, "out_color_space %d (0, MJH_CS_GRAYSCALE or MJH_CS_RGB)", o->out_color_space);
+  int px = o->pixel_size;
+  if (cs == MJH_CS_GRAYSCALE) {
+    if (px != 0 && px != 1) return fail(MJH_EINVAL, "pixel_size %d of grayscale output (0 or 1)", px);
+    px = 1;
+    P->conv = src_rgb ? MJH_CC_RGB_GRAY : MJH_CC_GRAY;
+  } else {
+    if (px != 0 && px != 3 && px != 4) return fail(MJH_EINVAL, "pixel_size %d of RGB output (0, 3 or 4)", px);
+    if (px == 0) px = 3;
+    P->conv = src_gray ? MJH_CC_GRAY_RGB : (src_rgb ? MJH_CC_RGB_RGB : MJH_CC_YCC_RGB);
+    P->off_r = o->rgb_offset[0]; P->off_g = o->rgb_offset[1]; P->off_b = o->rgb_offset[2];
+    if (P->off_r == 0 && P->off_g == 0 && P->off_b == 0) { P->off_g = 1; P->off_b = 2; }
+    const int off[3] = { P->off_r, P->off_g, P->off_b };
+    for (int k = 0; k < 3; k++)
+      if (off[k] < 0 || off[k] >= px || off[k] == off[(k + 1) % 3]) return fail(MJH_EINVAL, "rgb_offset %d,%d,%d of %d-byte pixels", off[0], off[1], off[2], px);
+  }
+  P->W = C.W; P->H = C.H;
+  P->px_size = px;
+  P->ncomp = (P->conv == MJH_CC_GRAY || P->conv == MJH_CC_GRAY_RGB) ? 1 : 3;     // component_needed: a YCbCr file's gray output reads Y alone
+  P->row_pitch = (long long)up16((size_t)px * (((size_t)C.W + 3) & ~(size_t)3));
+  P->image_stride = P->row_pitch * C.H;
+  P->planes_per_image = C.planes_per_image;
+  const bool fancy = o->fancy_upsampling != 0;
+  for (int c = 0; c < P->ncomp; c++) {
+    const MjhComp &cc = C.c[c];
+    MjhUpComp &u = P->c[c];
+    u.dw = (int)div_round_up((long)C.W * cc.h, C.maxh);
+    u.dh = (int)div_round_up((long)C.H * cc.v, C.maxv);
+    u.pw = cc.pw; u.plane_off = cc.plane_off;
+    u.mode = MJH_UP_REPLICATE;
+    if (C.maxh % cc.h || C.maxv % cc.v) return fail(MJH_EUNSUPPORTED, "fractional sampling ratios (JERR_FRACT_SAMPLE_NOTIMPL, jdsample.c:529)");
+    u.hexp = C.maxh / cc.h; u.vexp = C.maxv / cc.v;
+    if (u.hexp == 2 && u.vexp == 1) { if (fancy && u.dw > 2) u.mode = MJH_UP_H2V1_FANCY; }
+    else if (u.hexp == 1 && u.vexp == 2) { if (fancy) u.mode = MJH_UP_H1V2_FANCY; }
+    else if (u.hexp == 2 && u.vexp == 2) { if (fancy && u.dw > 2) u.mode = MJH_UP_H2V2_FANCY; }
+  }
+  return MJH_OK;
+}
+
+extern "C" int mjh_decode_host(mjh_encoder *e, const void *const jpegs[], const size_t sizes[], int n, const mjh_decode_opts *opts)
+{
+  if (!e) return fail(MJH_EINVAL, "null encoder");
+  e->tc_n = 0; e->tc_code.clear(); e->tc_text.clear(); e->tc_queued = false; e->dp_queued = false;     // (as decode_front: the refusals below are the call's, not a file's)
+  if (e->xf_on) return fail(MJH_EUNSUPPORTED, "a lossless transform (mjh_encoder_set_transform) together with decoding to pixels");
+  mjh_decode_opts o;
+  if (opts) o = *opts; else mjh_decode_opts_defaults(&o);
+  MjhPixOut P;
+  int rc = plan_pixels(e, &o, &P);
+  if (rc) return rc;
+  size_t o_jfif = 0;
+  rc = decode_front(e, jpegs, sizes, n, true, &o_jfif);
+  if (rc) return rc;
+  const MjhConst &C = e->C;
+  const size_t need = (size_t)e->max_batch * (size_t)P.image_stride;
+  if (need > e->pixout_cap) {
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (e->d_pixout) { (void)mjh_guard_free(e->d_pixout); e->d_pixout = nullptr; }
+    e->pixout_cap = 0;
+    HIPCHK(mjh_dmalloc((void **)&e->d_pixout, need));
+    e->pixout_cap = need;
+  }
+  if (!e->h_dstat) {
+    HIPCHK(mjh_numa_host_alloc((void **)&e->h_dstat, (size_t)e->max_batch * 4, hipHostMallocDefault, e->device));
+    for (hipEvent_t &ev : e->dp_ev) HIPCHK(hipEventCreate(&ev));
+    HIPCHK(hipEventCreateWithFlags(&e->dp_done, hipEventDisableTiming));
+  }
+  MjhIdctQ Q;
+  memset(&Q, 0, sizeof(Q));
+  for (int c = 0; c < C.ncomp; c++)
+    for (int k = 0; k < 64; k++) Q.q[c][k] = (int)e->p_created.quantval[e->p_created.quant_tbl_no[c]][k];
+  hipStream_t s = e->stream;
+  const bool timed = e->profiling != 0;
+  e->dp = P; e->dp_n = n;
+  e->last_n = n; e->compact_last = false; e->last = nullptr;      // (mjh_read_tap: d_q holds this batch's plain planes, d_planes its samples)
+  if (timed) HIPCHK(hipEventRecord(e->dp_ev[0], s));
+  mjh_launch_idct(C, Q, P.ncomp, e->d_q, e->d_planes, e->d_tstat, n, s);
+  if (timed) HIPCHK(hipEventRecord(e->dp_ev[1], s));
+  mjh_launch_upcolor(P, e->d_planes, e->d_pixout, e->d_tstat, n, s);
+  if (timed) HIPCHK(hipEventRecord(e->dp_ev[2], s));
+  e->dp_timed = timed;
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(e->h_dstat, e->d_tstat, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipEventRecord(e->dp_done, s));
+  e->last_stream = s;
+  e->dp_queued = true;
+  e->dp_waited = false;
+  return MJH_OK;
+}
+
+// waits for the last mjh_decode_host batch; a damaged file fails the whole batch, as in wait_results
+static int wait_pixels(mjh_encoder *e)
+{
+  if (!e->dp_queued) return fail(MJH_EINVAL, "the last batch was not decoded through mjh_decode_host");
+  if (!e->dp_waited) {
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipEventSynchronize(e->dp_done));
+    e->dp_waited = true;
+    { const int rg = guard_verify(); if (rg) return rg; }
+  }
+  for (int i = 0; i < e->dp_n; i++)
+    if (e->h_dstat[i]) return fail(MJH_EINVAL, "file %d: corrupt or truncated entropy-coded data (mjh_transcode_status tells which files of the batch are good)", i);
+  return MJH_OK;
+}
+
+extern "C" int mjh_decode_wait(mjh_encoder *e)
+{
+  if (!e) return fail(MJH_EINVAL, "null encoder");
+  return wait_pixels(e);
+}
+
+extern "C" int mjh_transcode_batch_size(mjh_encoder *e) { return e ? e->tc_n : 0; }
+
+extern "C" int mjh_get_pixels(mjh_encoder *e, int i, void *dst, size_t row_pitch)
+{
+  if (!e || !dst) return fail(MJH_EINVAL, "bad arguments");
+  int rc = wait_pixels(e);
+  if (rc) return rc;
+  if (i < 0 || i >= e->dp_n) return fail(MJH_EINVAL, "image %d of a batch of %d", i, e->dp_n);
+  const size_t row_bytes = (size_t)e->dp.W * (size_t)e->dp.px_size;
+  if (row_pitch < row_bytes) return fail(MJH_EINVAL, "row_pitch %zu is smaller than a row (%zu bytes)", row_pitch, row_bytes);
+  HIPCHK(hipMemcpy2D(dst, row_pitch, e->d_pixout + (size_t)i * (size_t)e->dp.image_stride, (size_t)e->dp.row_pitch, row_bytes, (size_t)e->dp.H, hipMemcpyDeviceToHost));
+  return MJH_OK;
+}
+
+extern "C" int mjh_get_pixels_device(mjh_encoder *e, void **d_base, size_t *row_pitch, size_t *image_stride)
+{
+  if (!e) return fail(MJH_EINVAL, "null encoder");
+  if (!e->dp_queued) return fail(MJH_EINVAL, "the last batch was not decoded through mjh_decode_host");
+  if (d_base) *d_base = e->d_pixout;
+  if (row_pitch) *row_pitch = (size_t)e->dp.row_pitch;
+  if (image_stride) *image_stride = (size_t)e->dp.image_stride;
+  return MJH_OK;
+}
+
+extern "C" int mjh_decode_stats(mjh_encoder *e, int *width, int *height, int *pixel_size, float ms[2])
+{
+  if (!e) return fail(MJH_EINVAL, "null encoder");
+  if (!e->dp_queued) return fail(MJH_EINVAL, "the last batch was not decoded through mjh_decode_host");
+  if (width) *width = e->dp.W;
+  if (height) *height = e->dp.H;
+  if (pixel_size) *pixel_size = e->dp.px_size;
+  if (ms) {
+    ms[0] = ms[1] = 0.f;
+    if (e->dp_timed) {
+      HIPCHK(hipSetDevice(e->device));
+      HIPCHK(hipEventSynchronize(e->dp_ev[2]));
+      for (int k = 0; k < 2; k++) HIPCHK(hipEventElapsedTime(&ms[k], e->dp_ev[k], e->dp_ev[k + 1]));
     }
   }
   return MJH_OK;

@@ -1,0 +1,46 @@
+// mjh_idct.h -- descriptors shared by the host side of mjh_decode_host (mjh_encoder.cpp) and the pixel kernels (mjh_idct.hip)
+#ifndef MJH_IDCT_H
+#define MJH_IDCT_H
+#include <hip/hip_runtime.h>
+#include "mjh_internal.h"
+
+// the multipliers of the inverse transform: quantval of every component's table, natural order, as 32-bit words (the reference
+// built without SIMD keeps them as int: MULTIPLIER, jmorecfg.h:367-372; wave-uniform reads become scalar loads)
+struct MjhIdctQ { int q[MJH_MAXC][64]; };
+
+// how one component reaches full size (jinit_upsampler jdsample.c:444-525)
+#define MJH_UP_REPLICATE 0       // fullsize_upsample, h2v1_upsample, h2v2_upsample, int_upsample: sample (x / hexp, y / vexp)
+#define MJH_UP_H2V1_FANCY 1
+#define MJH_UP_H1V2_FANCY 2
+#define MJH_UP_H2V2_FANCY 3
+struct MjhUpComp {
+  int mode;
+  int hexp, vexp;
+  int dw, dh;                // downsampled_width / downsampled_height: the samples the reference ever reads
+  int pw;                    // samples per row of the plane
+  long long plane_off;
+};
+
+// the colour conversion behind it (jdcolor.c)
+#define MJH_CC_GRAY 0            // component 0 alone: grayscale_convert (a YCbCr file's Y as well)
+#define MJH_CC_GRAY_RGB 1        // gray_rgb_convert
+#define MJH_CC_YCC_RGB 2         // ycc_rgb_convert
+#define MJH_CC_RGB_RGB 3         // a JCS_RGB file: the components as they are
+#define MJH_CC_RGB_GRAY 4        // rgb_gray_convert
+struct MjhPixOut {
+  int W, H;
+  int conv;                  // MJH_CC_*
+  int ncomp;                 // components the conversion reads (1 or 3)
+  int px_size;               // bytes per output pixel: 1, 3 or 4
+  int off_r, off_g, off_b;   // byte of every colour inside a pixel; the fourth byte of a 4-byte pixel is 0xFF
+  long long row_pitch, image_stride;      // of the output, bytes; rows hold whole groups of 4 pixels
+  long long planes_per_image;
+  MjhUpComp c[3];
+};
+
+// K-I1: coefficient planes (what k_dec_store / k_dec_dc leave) -> 8-bit sample planes, real blocks only; comps: the first
+// `comps` components.  status != 0: that image is skipped.
+void mjh_launch_idct(const MjhConst &C, const MjhIdctQ &Q, int comps, const int16_t *coef_q, uint8_t *planes, const unsigned *status, int n, hipStream_t s);
+// K-I2: sample planes -> interleaved pixels
+void mjh_launch_upcolor(const MjhPixOut &P, const uint8_t *planes, uint8_t *pixels, const unsigned *status, int n, hipStream_t s);
+#endif

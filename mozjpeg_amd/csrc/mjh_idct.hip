@@ -1,0 +1,207 @@
+// mjh_idct.hip -- K-I: from the quantized coefficient planes the Huffman decoder leaves (mjh_decode.hip) to interleaved 8-bit
+// pixels (mjh_decode_host).  Integer-only, bit-exact with the reference's decompressor as djpeg drives it: JDCT_ISLOW, the C
+// upsamplers (no SIMD), fancy upsampling on or off.
+//
+// K-I1 k_idct: one lane per real block.  Dequantization inside the transform (DEQUANTIZE jdct.h, multiplier = quantval
+//   jddctmgr.c), the two passes of jpeg_idct_islow (jidctint.c:173-413) in 64-bit arithmetic as the reference's JLONG (a
+//   damaged or hostile file reaches products beyond 32 bits, and the descaling shifts do not commute with a wrap), the
+//   workspace truncated to int between the passes as there, and the post-IDCT range-limit table reproduced WITH its wrap
+//   (prepare_range_limit_table jdmaster.c:415ff: index & 1023).  The zero-AC shortcuts of the reference give the numbers of the
+//   general path and are not branches here.
+//   Memory: plane k of coef_q is read by 64 consecutive blocks per wave (coalesced 128-byte rows); the 8 x 8 samples of a block
+//   leave as eight 8-byte vector stores, one per sample row: the lanes of a wave hold horizontally adjacent blocks, so every
+//   store instruction writes one contiguous 512-byte run of a sample row.  The rows wait in registers; a pass through LDS would
+//   add a write and a read per sample and change nothing about the shape of the stores.
+// K-I2 k_upcolor: one lane per 4 output pixels of a row.  Per component the upsampler jinit_upsampler picks (jdsample.c:444-525),
+//   evaluated per output sample from the samples it reads, then the colour conversion of jdcolor.c / jdcolext.c, then one 4-byte,
+//   three 4-byte (12 contiguous bytes) or one 16-byte store (rows of the output hold whole groups of 4 pixels).
+//   Edges: neighbours are clamped to [0, downsampled_width) x [0, downsampled_height), which is what the special
+//   first / last column cases of the fancy upsamplers (jdsample.c:289-303, :386-404) and the duplicated context rows of the main
+//   controller (jdmainct.c make_funny_pointers / set_bottom_pointers) amount to; samples beyond are never read.
+#include <hip/hip_runtime.h>
+#include "mjh_device.h"
+#include "mjh_idct.h"
+
+// zig-zag position of every natural-order position (the inverse of jpeg_natural_order)
+__constant__ int kZigOfNat[64] = {
+   0,  1,  5,  6, 14, 15, 27, 28,
+   2,  4,  7, 13, 16, 26, 29, 42,
+   3,  8, 12, 17, 25, 30, 41, 43,
+   9, 11, 18, 24, 31, 40, 44, 53,
+  10, 19, 23, 32, 39, 45, 52, 54,
+  20, 22, 33, 38, 46, 51, 55, 60,
+  21, 34, 37, 47, 50, 56, 59, 61,
+  35, 36, 48, 49, 57, 58, 62, 63 };
+
+// the 1-D inverse transform of jidctint.c (CONST_BITS 13): eight inputs -> the eight sums in front of the descaling shift
+__device__ __forceinline__ void idct8(const int (&x)[8], long long (&o)[8])
+{
+  long long z2 = x[2], z3 = x[6];
+  long long z1 = (z2 + z3) * 4433;                     // FIX_0_541196100
+  long long tmp2 = z1 - z3 * 15137;                    // FIX_1_847759065
+  long long tmp3 = z1 + z2 * 6270;                     // FIX_0_765366865
+  long long tmp0 = ((long long)x[0] + x[4]) * 8192;
+  long long tmp1 = ((long long)x[0] - x[4]) * 8192;
+  const long long tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+  tmp0 = x[7]; tmp1 = x[5]; tmp2 = x[3]; tmp3 = x[1];
+  z1 = tmp0 + tmp3; z2 = tmp1 + tmp2; z3 = tmp0 + tmp2;
+  long long z4 = tmp1 + tmp3;
+  const long long z5 = (z3 + z4) * 9633;               // FIX_1_175875602
+  tmp0 *= 2446;                                        // FIX_0_298631336
+  tmp1 *= 16819;                                       // FIX_2_053119869
+  tmp2 *= 25172;                                       // FIX_3_072711026
+  tmp3 *= 12299;                                       // FIX_1_501321110
+  z1 *= -7373;                                         // FIX_0_899976223
+  z2 *= -20995;                                        // FIX_2_562915447
+  z3 = z3 * -16069 + z5;                               // FIX_1_961570560
+  z4 = z4 * -3196 + z5;                                // FIX_0_390180644
+  tmp0 += z1 + z3; tmp1 += z2 + z4; tmp2 += z2 + z3; tmp3 += z1 + z4;
+  o[0] = tmp10 + tmp3; o[7] = tmp10 - tmp3;
+  o[1] = tmp11 + tmp2; o[6] = tmp11 - tmp2;
+  o[2] = tmp12 + tmp1; o[5] = tmp12 - tmp1;
+  o[3] = tmp13 + tmp0; o[4] = tmp13 - tmp0;
+}
+
+// the post-IDCT table of prepare_range_limit_table at index v & 1023: 128..255, 255 x 384, 0 x 384, 0..127
+__device__ __forceinline__ unsigned idct_range_limit(int v)
+{
+  v &= 1023;
+  return (unsigned)(v < 128 ? v + 128 : (v < 512 ? 255 : (v < 896 ? 0 : v - 896)));
+}
+
+__global__ void __launch_bounds__(256)
+k_idct(MjhConst C, MjhIdctQ Q, const int16_t *__restrict__ coef_q, uint8_t *__restrict__ planes, const unsigned *__restrict__ status)
+{
+  const int img = blockIdx.z, ci = blockIdx.y;
+  const MjhComp &cc = C.c[ci];
+  const int b = (int)(blockIdx.x * 256u + threadIdx.x);
+  if (b >= cc.nblk) return;
+  if (status[img] != 0u) return;
+  const int16_t *in = coef_q + (size_t)img * C.coefs_per_image + cc.coef_off + b;
+  const int *q = Q.q[ci];
+  int ws[64];
+  // pass 1: columns, results scaled up by 2^PASS1_BITS (2)
+#pragma unroll
+  for (int c = 0; c < 8; c++) {
+    int x[8];
+#pragma unroll
+    for (int r = 0; r < 8; r++) x[r] = (int)in[(size_t)kZigOfNat[r * 8 + c] * cc.kstride] * q[r * 8 + c];
+    long long o[8];
+    idct8(x, o);
+#pragma unroll
+    for (int r = 0; r < 8; r++) ws[r * 8 + c] = (int)((o[r] + 1024) >> 11);
+  }
+  // pass 2: rows; descale by 2^(CONST_BITS + PASS1_BITS + 3), then the range limit with the sample's centre added
+  const int by = b / cc.wib, bx = b - by * cc.wib;
+  uint8_t *out = planes + (size_t)img * C.planes_per_image + cc.plane_off + (size_t)(by * 8) * cc.pw + (size_t)bx * 8;
+#pragma unroll
+  for (int r = 0; r < 8; r++) {
+    int x[8];
+#pragma unroll
+    for (int c = 0; c < 8; c++) x[c] = ws[r * 8 + c];
+    long long o[8];
+    idct8(x, o);
+    unsigned s[8];
+#pragma unroll
+    for (int c = 0; c < 8; c++) s[c] = idct_range_limit((int)((o[c] + (1 << 17)) >> 18));
+    uint2 v;
+    v.x = s[0] | (s[1] << 8) | (s[2] << 16) | (s[3] << 24);
+    v.y = s[4] | (s[5] << 8) | (s[6] << 16) | (s[7] << 24);
+    *reinterpret_cast<uint2 *>(out + (size_t)r * cc.pw) = v;
+  }
+}
+
+// one sample of component uc at output position (x, y), 0 <= x < W, 0 <= y < H
+__device__ __forceinline__ int up_sample(const MjhUpComp &uc, const uint8_t *__restrict__ pl, int x, int y)
+{
+  if (uc.mode == MJH_UP_REPLICATE) {
+    int c = x / uc.hexp, r = y / uc.vexp;
+    c = c < uc.dw ? c : uc.dw - 1; r = r < uc.dh ? r : uc.dh - 1;
+    return pl[(size_t)r * uc.pw + c];
+  }
+  if (uc.mode == MJH_UP_H2V1_FANCY) {                  // jdsample.c:276-305
+    const int c = x >> 1, odd = x & 1;
+    int n = odd ? c + 1 : c - 1;
+    n = n < 0 ? 0 : (n < uc.dw ? n : uc.dw - 1);
+    const uint8_t *row = pl + (size_t)y * uc.pw;
+    return (3 * (int)row[c] + (int)row[n] + 1 + odd) >> 2;
+  }
+  const int r = y >> 1, below = y & 1;
+  int rn = below ? r + 1 : r - 1;
+  rn = rn < 0 ? 0 : (rn < uc.dh ? rn : uc.dh - 1);
+  const uint8_t *row0 = pl + (size_t)r * uc.pw, *row1 = pl + (size_t)rn * uc.pw;
+  if (uc.mode == MJH_UP_H1V2_FANCY)                    // jdsample.c:316-350
+    return (3 * (int)row0[x] + (int)row1[x] + 1 + below) >> 2;
+  const int c = x >> 1, odd = x & 1;                   // h2v2_fancy_upsample jdsample.c:362-408
+  int n = odd ? c + 1 : c - 1;
+  n = n < 0 ? 0 : (n < uc.dw ? n : uc.dw - 1);
+  const int here = 3 * (int)row0[c] + (int)row1[c], there = 3 * (int)row0[n] + (int)row1[n];
+  return (3 * here + there + 8 - odd) >> 4;
+}
+
+__device__ __forceinline__ int clamp255(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+
+__global__ void __launch_bounds__(256)
+k_upcolor(MjhPixOut P, const uint8_t *__restrict__ planes, uint8_t *__restrict__ pixels, const unsigned *__restrict__ status)
+{
+  const int img = blockIdx.z, y = blockIdx.y;
+  const int x0 = (int)(blockIdx.x * 256u + threadIdx.x) * 4;
+  if (x0 >= P.W) return;
+  if (status[img] != 0u) return;
+  const uint8_t *pl = planes + (size_t)img * P.planes_per_image;
+  unsigned px[4][3];
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const int x = x0 + i < P.W ? x0 + i : P.W - 1;      // (the pad of the last group: an in-range position, its bytes mean nothing)
+    const int a = up_sample(P.c[0], pl + P.c[0].plane_off, x, y);
+    int r = a, g = a, b = a;
+    if (P.ncomp == 3) {
+      const int c1 = up_sample(P.c[1], pl + P.c[1].plane_off, x, y), c2 = up_sample(P.c[2], pl + P.c[2].plane_off, x, y);
+      if (P.conv == MJH_CC_YCC_RGB) {                  // ycc_rgb_convert with the tables of build_ycc_rgb_table (jdcolor.c:215-251), SCALEBITS 16
+        const int cb = c1 - 128, cr = c2 - 128;
+        r = clamp255(a + ((91881 * cr + 32768) >> 16));
+        g = clamp255(a + ((-22554 * cb + 32768 - 46802 * cr) >> 16));
+        b = clamp255(a + ((116130 * cb + 32768) >> 16));
+      } else if (P.conv == MJH_CC_RGB_GRAY) {           // rgb_gray_convert (build_rgb_y_table jdcolor.c:306-327)
+        r = g = b = (19595 * a + 38470 * c1 + 7471 * c2 + 32768) >> 16;
+      } else { g = c1; b = c2; }
+    }
+    px[i][0] = (unsigned)r; px[i][1] = (unsigned)g; px[i][2] = (unsigned)b;
+  }
+  uint8_t *out = pixels + (size_t)img * P.image_stride + (size_t)y * P.row_pitch + (size_t)x0 * P.px_size;
+  if (P.px_size == 1) {
+    *reinterpret_cast<unsigned *>(out) = px[0][0] | (px[1][0] << 8) | (px[2][0] << 16) | (px[3][0] << 24);
+  } else if (P.px_size == 4) {
+    uint4 v;
+    unsigned w[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) w[i] = 0xFFFFFFFFu ^ ((0xFFu ^ px[i][0]) << (8 * P.off_r)) ^ ((0xFFu ^ px[i][1]) << (8 * P.off_g)) ^ ((0xFFu ^ px[i][2]) << (8 * P.off_b));
+    v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
+    *reinterpret_cast<uint4 *>(out) = v;
+  } else {
+    // twelve bytes: byte j of pixel i is the colour whose offset is j
+    unsigned w[3] = { 0u, 0u, 0u };
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const unsigned p24 = (px[i][0] << (8 * P.off_r)) | (px[i][1] << (8 * P.off_g)) | (px[i][2] << (8 * P.off_b));
+      const unsigned long long sh = (unsigned long long)p24 << (8 * (3 * i & 3));     // pixel i starts at byte 3 i: word 3 i / 4, byte 3 i % 4
+      w[(3 * i) >> 2] |= (unsigned)sh;
+      if (((3 * i) >> 2) + 1 < 3) w[((3 * i) >> 2) + 1] |= (unsigned)(sh >> 32);
+    }
+    unsigned *o32 = reinterpret_cast<unsigned *>(out);
+    o32[0] = w[0]; o32[1] = w[1]; o32[2] = w[2];
+  }
+}
+
+void mjh_launch_idct(const MjhConst &C, const MjhIdctQ &Q, int comps, const int16_t *coef_q, uint8_t *planes, const unsigned *status, int n, hipStream_t s)
+{
+  int nblk = 1;
+  for (int c = 0; c < comps; c++) if (C.c[c].nblk > nblk) nblk = C.c[c].nblk;
+  hipLaunchKernelGGL(k_idct, dim3((nblk + 255) / 256, comps, n), dim3(256), 0, s, C, Q, coef_q, planes, status);
+}
+
+void mjh_launch_upcolor(const MjhPixOut &P, const uint8_t *planes, uint8_t *pixels, const unsigned *status, int n, hipStream_t s)
+{
+  const int groups = (P.W + 3) / 4;
+  hipLaunchKernelGGL(k_upcolor, dim3((groups + 255) / 256, P.H, n), dim3(256), 0, s, P, planes, pixels, status);
+}
