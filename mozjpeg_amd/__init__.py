@@ -423,7 +423,7 @@ def recompress(files, *, max_batch=64, device=0, **switches):
                 enc = _recompress_encoders[key] = Encoder(params_from_jpeg(info, **switches), max_batch=min(max_batch, len(idx)), device=device)
             except MjhError as exc:         # a transform this group's geometry refuses (perfect, a crop outside the image, ...)
                 _recompress_encoders.pop(key, None)
-                if not (transforming or switches.get("perfect")):
+                if not (transforming or switches.get("perfect") or exc.code == EUNSUPPORTED):      # (a frame no encoder exists for)
                     raise
                 for i in idx:
                     out[i] = exc
@@ -511,7 +511,15 @@ def decode(files, *, max_batch=64, device=0, **opts):
         if enc is None or enc.max_batch < min(max_batch, len(idx)):
             if enc is not None:
                 enc.close()
-            enc = _decode_encoders[key] = Encoder(params_from_jpeg(info, revert=True), max_batch=min(max_batch, len(idx)), device=device)
+            try:
+                enc = _decode_encoders[key] = Encoder(params_from_jpeg(info, revert=True), max_batch=min(max_batch, len(idx)), device=device)
+            except MjhError as exc:         # a frame no encoder exists for (fractional sampling ratios): this group's files alone
+                _decode_encoders.pop(key, None)
+                if exc.code != EUNSUPPORTED:
+                    raise
+                for i in idx:
+                    out[i] = exc
+                continue
         for a in range(0, len(idx), enc.max_batch):
             part = idx[a:a + enc.max_batch]
             res = enc.decode_host([files[i] for i in part], errors="return", opts=o)

@@ -48,7 +48,7 @@ struct MjhDecCarry { unsigned p, kb; int next, active; };
 
 // per-image status bits of a transcode batch
 #define MJH_DEC_CORRUPT 1u     // the entropy-coded data does not decode to exactly the scan's blocks
-#define MJH_DEC_BADCOEF 2u     // an AC value beyond what jchuff.c:596,624 can code
+#define MJH_DEC_BADCOEF 2u     // an AC value beyond MjhDecBatch::coef_limit (re-compression: what jchuff.c:596,624 can code)
 
 struct MjhDecBatch {
   const uint8_t *bytes;            // the files, back to back
@@ -64,6 +64,8 @@ struct MjhDecBatch {
   int16_t *diff;                   // [image][C.total_mcu_blocks] DC differences in scan order, dummy blocks included
   int nsub_padded, nseg, nscan, n;
   int S;                           // subsequence length in bytes
+  int coef_limit;                  // an AC value beyond +-coef_limit sets MJH_DEC_BADCOEF: 1023 where the file is coded again (the encoder has no
+                                   // symbol for more), 32767 = never on the way to pixels (the decompressor takes any amplitude a symbol exists for)
 };
 
 // A lossless transform fused into the two places that store coefficients (mjh_encoder_set_transform): the kernels decode in the

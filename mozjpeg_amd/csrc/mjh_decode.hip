@@ -101,7 +101,7 @@ __device__ __forceinline__ int dec_xf_block(const MjhXform &X, const MjhXformCom
 template <bool STORE, bool XF = false>
 __device__ __forceinline__ bool dec_run(const MjhComp *lc, const MjhDecScan &sc, const MjhDecTable *T, DecReader &R, unsigned end_bits,
                                         unsigned &p, int &k, int &b, unsigned &n, unsigned ord, unsigned total, int mcu,
-                                        int16_t *coef_img, int16_t *diff_img, unsigned &flags, const MjhXform *X = nullptr)
+                                        int16_t *coef_img, int16_t *diff_img, unsigned &flags, int lim, const MjhXform *X = nullptr)
 {
   DecWhere wh{ 0, -1, 0 };
   unsigned cls = 0;
@@ -141,7 +141,7 @@ __device__ __forceinline__ bool dec_run(const MjhComp *lc, const MjhDecScan &sc,
         if (STORE) {
           const int v = (int)((w << nb) >> (64 - s));
           const int val = v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
-          if (val > 1023 || val < -1023) flags |= MJH_DEC_BADCOEF;
+          if (val > lim || val < -lim) flags |= MJH_DEC_BADCOEF;
           // a run that passes position 63 lands in the spare entries of jpeg_natural_order, all 63 (jdhuff.c:619-628)
           if (XF) {
             if (wh.blk >= 0) {
@@ -243,7 +243,7 @@ k_dec_sync(MjhConst C, MjhDecBatch B, int q, int first)
     p = c.p; k = (int)(c.kb & 0xFFu); b = (int)(c.kb >> 8);
     j = (unsigned)c.next;
   }
-  (void)dec_run<false>(lc, sc, T, R, dec_sub_end_bits(R.len, j, (unsigned)seg.nsub, S), p, k, b, n, 0u, 0u, 0, nullptr, nullptr, flags);
+  (void)dec_run<false>(lc, sc, T, R, dec_sub_end_bits(R.len, j, (unsigned)seg.nsub, S), p, k, b, n, 0u, 0u, 0, nullptr, nullptr, flags, 0);
   b = sc.canon[b];
   const unsigned kb = (unsigned)k | ((unsigned)b << 8);
   MjhDecState *st = B.state + seg.sub0 + j;
@@ -311,7 +311,7 @@ k_dec_store(MjhConst C, MjhDecBatch B, int16_t *__restrict__ coef_q)
     b = (int)(ord % (unsigned)sc.bpm);
     const int mcu = seg.mcu0 + (int)(ord / (unsigned)sc.bpm);
     const bool fin = dec_run<true>(lc, sc, T, R, dec_sub_end_bits(R.len, i, (unsigned)seg.nsub, S), p, k, b, n, ord, total, mcu,
-                                   coef_q + (size_t)sc.image * C.coefs_per_image, B.diff + (size_t)sc.image * C.total_mcu_blocks, flags);
+                                   coef_q + (size_t)sc.image * C.coefs_per_image, B.diff + (size_t)sc.image * C.total_mcu_blocks, flags, B.coef_limit);
     if (fin) {
       // the last block ends here: nothing but the padding of its last byte may follow (jdmarker.c next_marker: "extraneous bytes"),
       // and it must not have read past the end ("Premature end of JPEG file" / JWRN_HIT_MARKER)
@@ -362,7 +362,7 @@ k_dec_store_x(MjhConst C, MjhDecBatch B, int16_t *__restrict__ coef_q, const Mjh
     b = (int)(ord % (unsigned)sc.bpm);
     const int mcu = seg.mcu0 + (int)(ord / (unsigned)sc.bpm);
     const bool fin = dec_run<true, true>(lc, sc, T, R, dec_sub_end_bits(R.len, i, (unsigned)seg.nsub, S), p, k, b, n, ord, total, mcu,
-                                   coef_q + (size_t)sc.image * X.coefs_per_image, B.diff + (size_t)sc.image * C.total_mcu_blocks, flags, &X);
+                                   coef_q + (size_t)sc.image * X.coefs_per_image, B.diff + (size_t)sc.image * C.total_mcu_blocks, flags, B.coef_limit, &X);
     if (fin) {
       // the last block ends here: nothing but the padding of its last byte may follow (jdmarker.c next_marker: "extraneous bytes"),
       // and it must not have read past the end ("Premature end of JPEG file" / JWRN_HIT_MARKER)

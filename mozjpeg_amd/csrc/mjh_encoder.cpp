@@ -3030,6 +3030,7 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
   B.diff = xf ? e->d_tdiff_x : e->d_tdiff;
   B.nsub_padded = (int)nsubp; B.nseg = (int)segs.size(); B.nscan = (int)scans.size(); B.n = n;
   B.S = S > 0 ? S : 1;
+  B.coef_limit = pixels ? 32767 : 1023;     // jchuff.c:596,624 refuses what it cannot code (JERR_BAD_DCT_COEF); jdhuff.c / jidctint.c take every amplitude
   const bool timed = e->profiling != 0;
   HIPCHK(hipMemsetAsync(e->d_q, 0, (size_t)n * C.coefs_per_image * 2, s));
   HIPCHK(hipMemsetAsync(B.diff, 0, (size_t)n * (size_t)G.total_mcu_blocks * 2, s));
@@ -3093,6 +3094,13 @@ extern "C" int mjh_transcode_host(mjh_encoder *e, const void *const jpegs[], con
   return MJH_OK;
 }
 
+// the text of a per-image decoder status: a refusal of an amplitude is never reported as damage
+static const char *status_text(unsigned st)
+{
+  return (st & MJH_DEC_CORRUPT) ? "Corrupt JPEG data: the entropy-coded data does not decode to the scan's blocks (premature end, extraneous bytes or a bad Huffman code; the reference warns: JWRN_HIT_MARKER / JWRN_EXTRANEOUS_DATA / JWRN_HUFF_BAD_CODE)"
+                                : "a DCT coefficient out of range (JERR_BAD_DCT_COEF, jchuff.c:489,596,624)";
+}
+
 extern "C" int mjh_transcode_status(mjh_encoder *e, int i, const char **text)
 {
   if (!e || i < 0 || i >= e->tc_n) return fail(MJH_EINVAL, "bad file index");
@@ -3102,7 +3110,7 @@ extern "C" int mjh_transcode_status(mjh_encoder *e, int i, const char **text)
     HIPCHK(hipEventSynchronize(e->dp_done));
     if (e->h_dstat[i]) {
       e->tc_code[(size_t)i] = MJH_EINVAL;
-      e->tc_text[(size_t)i] = "Corrupt JPEG data: the entropy-coded data does not decode to the scan's blocks (premature end, extraneous bytes or a bad Huffman code; the reference warns: JWRN_HIT_MARKER / JWRN_EXTRANEOUS_DATA / JWRN_HUFF_BAD_CODE)";
+      e->tc_text[(size_t)i] = status_text(e->h_dstat[i]);
     }
   }
   if (e->tc_code[(size_t)i] == MJH_OK && e->tc_queued && e->res_buf >= 0 && e->tc_batch[e->res_buf] && i < e->res_n[e->res_buf]) {
@@ -3111,8 +3119,7 @@ extern "C" int mjh_transcode_status(mjh_encoder *e, int i, const char **text)
     const unsigned st = e->h_tstat[e->res_buf][i];
     if (st) {
       e->tc_code[(size_t)i] = MJH_EINVAL;
-      e->tc_text[(size_t)i] = (st & MJH_DEC_CORRUPT) ? "Corrupt JPEG data: the entropy-coded data does not decode to the scan's blocks (premature end, extraneous bytes or a bad Huffman code; the reference warns: JWRN_HIT_MARKER / JWRN_EXTRANEOUS_DATA / JWRN_HUFF_BAD_CODE)"
-                                                         : "a DCT coefficient out of range (JERR_BAD_DCT_COEF, jchuff.c:489,596,624)";
+      e->tc_text[(size_t)i] = status_text(st);
     }
   }
   if (text) *text = e->tc_text[(size_t)i].c_str();
@@ -3257,7 +3264,7 @@ static int wait_pixels(mjh_encoder *e)
     { const int rg = guard_verify(); if (rg) return rg; }
   }
   for (int i = 0; i < e->dp_n; i++)
-    if (e->h_dstat[i]) return fail(MJH_EINVAL, "file %d: corrupt or truncated entropy-coded data (mjh_transcode_status tells which files of the batch are good)", i);
+    if (e->h_dstat[i]) return fail(MJH_EINVAL, "file %d: %s (mjh_transcode_status tells which files of the batch are good)", i, status_text(e->h_dstat[i]));
   return MJH_OK;
 }
 

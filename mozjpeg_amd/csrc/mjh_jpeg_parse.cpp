@@ -241,6 +241,9 @@ extern "C" int mjh_params_from_jpeg(const mjh_jpeg_info *info, int compress_prof
     p->h_samp_factor[c] = info->h_samp_factor[c];
     p->v_samp_factor[c] = info->v_samp_factor[c];
     p->quant_tbl_no[c] = info->quant_tbl_no[c];
+    // a single component is always written 1x1, whatever the source's frame header says ("some decoders choke on grayscale images
+    // with other sampling factors", jtransform_adjust_parameters transupp.c:2072-2079); its non-interleaved scan is laid out alike
+    if (nc == 1) p->h_samp_factor[c] = p->v_samp_factor[c] = 1;
     if (p->quant_tbl_no[c] < 0 || p->quant_tbl_no[c] > 3 || !((info->quant_defined >> p->quant_tbl_no[c]) & 1))
       return pfail(MJH_EINVAL, "Quantization table 0x%02x was not defined (JERR_NO_QUANT_TABLE)", p->quant_tbl_no[c]);
   }
