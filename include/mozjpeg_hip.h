@@ -426,7 +426,7 @@ int mjh_params_from_jpeg_transform(const mjh_jpeg_info *info, const mjh_transfor
  * factors, and every file's own destination parameters must equal the encoder's, else MJH_EINVAL naming file and field. */
 int mjh_encoder_set_transform(mjh_encoder *e, const mjh_transform *t);
 
-/* ---- decoding existing files to pixels (djpeg [-nosmooth] [-grayscale | -rgb]) -----------------------------------------------
+/* ---- decoding existing files to pixels (djpeg [-scale M/N] [-nosmooth] [-grayscale | -rgb]) -------------------------------------
  * JPEG bytes in host memory in, interleaved 8-bit pixels in device memory out (and in host memory on request): the marker walk
  * and the Huffman decoder kernels of mjh_transcode_host, then dequantization + inverse DCT and upsampling + colour conversion
  * (mjh_idct.hip).  The pixels are the bytes the reference's djpeg writes with the slow integer IDCT (-dct int, its default):
@@ -437,14 +437,22 @@ int mjh_encoder_set_transform(mjh_encoder *e, const mjh_transform *t);
  * (a YCbCr file: its Y alone, no chroma is transformed; an RGB file: rgb_gray_convert) or MJH_CS_RGB (a gray file: replicated).
  * pixel_size / rgb_offset: the layouts mjh_params.input_pixel_size / rgb_offset name for input -- 3 or 4 bytes per RGB pixel
  * (0 = 3), the byte of R, G and B inside it (all 0 = 0, 1, 2); the fourth byte of a 4-byte pixel is 0xFF.  Gray pixels are
- * one byte.  fancy_upsampling: 1 = djpeg's default, 0 = -nosmooth.  MJH_EINVAL: an unknown colour space, pixel size or offsets.
- * MJH_EUNSUPPORTED: a lossless transform set on the encoder; other IDCT methods, scaling, cropping and colour quantization
- * have no option here. */
+ * one byte.  fancy_upsampling: 1 = djpeg's default, 0 = -nosmooth.
+ * scale_num / scale_denom: djpeg -scale M/N, decoding at a reduced size inside the inverse DCT (jidctred.c).  The fraction is
+ * resolved as jpeg_core_output_dimensions does (jdmaster.c:105ff): to k / 8 with the smallest k in 1..16 for which
+ * scale_num * 8 <= scale_denom * k, 16 if there is none -- 1/5 decodes at 2/8.  k = 1, 2, 4 and 8 are built; 8 is the
+ * full-size path, which 1/1 and 0/0 (a zeroed struct) name.  The output is ceil(W k / 8) x ceil(H k / 8): mjh_decode_stats
+ * reports that size, mjh_get_pixels and mjh_get_pixels_device address that image.  The encoder is still the one made from
+ * mjh_params_from_jpeg at the file's own size, and serves calls at different scales one after the other.
+ * MJH_EINVAL: an unknown colour space, pixel size or offsets; a scale_num or scale_denom below 1 (other than 0/0).
+ * MJH_EUNSUPPORTED: a lossless transform set on the encoder; a scale that resolves to an IDCT size of 3, 5, 6, 7 or 9 to 16;
+ * other IDCT methods, cropping and colour quantization have no option here. */
 typedef struct {
   int out_color_space;
   int pixel_size;
   int rgb_offset[3];
   int fancy_upsampling;
+  int scale_num, scale_denom;
 } mjh_decode_opts;
 void mjh_decode_opts_defaults(mjh_decode_opts *o);
 /* Decodes n files (opts == NULL: the defaults).  Queued on the encoder's stream; the bytes need not stay valid after the call.
@@ -463,7 +471,7 @@ int mjh_get_pixels(mjh_encoder *e, int i, void *dst, size_t row_pitch);
  * encoder's stream; mjh_decode_wait waits for it AND reports damaged files, mjh_encoder_sync only waits.  The buffer is reused
  * by the next decode call. */
 int mjh_get_pixels_device(mjh_encoder *e, void **d_base, size_t *row_pitch, size_t *image_stride);
-/* Size and pixel size of the last decoded batch and, with mjh_set_profiling(e, 1), the milliseconds of its two pixel kernels:
+/* Size (the scaled one) and pixel size of the last decoded batch and, with mjh_set_profiling(e, 1), the milliseconds of its two pixel kernels:
  * [0] dequantization + inverse DCT, [1] upsampling + colour conversion (the Huffman decoder's phases: mjh_transcode_stats).
  * Any pointer may be NULL. */
 int mjh_decode_stats(mjh_encoder *e, int *width, int *height, int *pixel_size, float ms[2]);

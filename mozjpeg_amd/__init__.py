@@ -83,8 +83,9 @@ class JpegInfo(C.Structure):
 
 
 class DecodeOpts(C.Structure):
-    """mjh_decode_opts: what djpeg's -grayscale / -rgb / -nosmooth and the extended pixel layouts choose"""
-    _fields_ = [("out_color_space", C.c_int), ("pixel_size", C.c_int), ("rgb_offset", C.c_int * 3), ("fancy_upsampling", C.c_int)]
+    """mjh_decode_opts: what djpeg's -grayscale / -rgb / -nosmooth / -scale and the extended pixel layouts choose"""
+    _fields_ = [("out_color_space", C.c_int), ("pixel_size", C.c_int), ("rgb_offset", C.c_int * 3), ("fancy_upsampling", C.c_int),
+                ("scale_num", C.c_int), ("scale_denom", C.c_int)]
 
 
 class Result(C.Structure):
@@ -449,10 +450,45 @@ PIXEL_LAYOUTS = {"rgb": (3, (0, 1, 2)), "bgr": (3, (2, 1, 0)), "rgbx": (4, (0, 1
                  "xbgr": (4, (3, 2, 1)), "xrgb": (4, (1, 2, 3))}      # name -> pixel_size, rgb_offset (the extended colour spaces)
 
 
-def decode_opts(color=None, layout=None, pixel_size=0, rgb_offset=None, fancy_upsampling=True):
+SCALED_IDCT_SIZES = (1, 2, 4, 8)      # the k of output = input * k / 8 that the pixel kernels are built for
+
+
+def scale_idct_size(num, denom):
+    """the IDCT size k that djpeg -scale num/denom decodes with (jpeg_core_output_dimensions, jdmaster.c:105ff): the smallest k in
+    1..16 with num * 8 <= denom * k, else 16.  The output is ceil(W k / 8) x ceil(H k / 8)."""
+    k = 1
+    while k < 16 and num * 8 > denom * k:
+        k += 1
+    return k
+
+
+def _parse_scale(scale):
+    """(num, denom) of a pair or a string "M/N"; None is 1/1"""
+    if scale is None:
+        return 1, 1
+    try:
+        if isinstance(scale, str):
+            num, denom = scale.split("/")
+        else:
+            num, denom = scale
+        num, denom = int(num), int(denom)
+    except (TypeError, ValueError):
+        raise MjhError(EINVAL, "scale %r (a pair (num, denom) or a string 'M/N')" % (scale,))
+    if num < 1 or denom < 1:
+        raise MjhError(EINVAL, "scale %d/%d (both at least 1)" % (num, denom))
+    if not (-2 ** 31 <= num < 2 ** 31 and -2 ** 31 <= denom < 2 ** 31):
+        raise MjhError(EINVAL, "scale %d/%d (beyond an int)" % (num, denom))
+    k = scale_idct_size(num, denom)
+    if k not in SCALED_IDCT_SIZES:
+        raise MjhError(EUNSUPPORTED, "scale %d/%d decodes with the %dx%d inverse DCT; the sizes built are 1x1, 2x2, 4x4 and 8x8" % (num, denom, k, k))
+    return num, denom
+
+
+def decode_opts(color=None, layout=None, pixel_size=0, rgb_offset=None, fancy_upsampling=True, scale=None):
     """DecodeOpts from djpeg's vocabulary.  color: None (the file's default: gray stays gray, everything else RGB), "gray" /
     "grayscale" (-grayscale), "rgb" (-rgb) or a CS_* number; layout: a name out of PIXEL_LAYOUTS, or pixel_size and rgb_offset;
-    fancy_upsampling=False: -nosmooth."""
+    fancy_upsampling=False: -nosmooth; scale: -scale, a pair (num, denom) or a string "M/N" that resolves to 1/8, 2/8, 4/8 or
+    8/8 as djpeg resolves it (scale_idct_size)."""
     o = DecodeOpts()
     lib().mjh_decode_opts_defaults(C.byref(o))
     if isinstance(color, str):
@@ -470,6 +506,7 @@ def decode_opts(color=None, layout=None, pixel_size=0, rgb_offset=None, fancy_up
     if rgb_offset is not None:
         o.rgb_offset[:] = [int(v) for v in rgb_offset]
     o.fancy_upsampling = int(bool(fancy_upsampling))
+    o.scale_num, o.scale_denom = _parse_scale(scale)
     # the library's own checks (plan_pixels), made here as well so that decode() can refuse its options before it groups files
     if o.out_color_space not in (0, CS_GRAYSCALE, CS_RGB):
         raise MjhError(EINVAL, "out_color_space %d (0, CS_GRAYSCALE or CS_RGB)" % o.out_color_space)
@@ -490,9 +527,10 @@ _decode_encoders = {}
 
 
 def decode(files, *, max_batch=64, device=0, **opts):
-    """Decode JPEG files to pixels on the GPU: the bytes `djpeg` (+ -grayscale / -rgb / -nosmooth, see decode_opts) writes for
-    each of them, as numpy arrays [H, W, C] ([H, W] for gray) in input order.  The files are grouped by what a batch must have in
-    common; one encoder per group is kept for later calls.  A file that cannot be decoded (unsupported type, malformed headers,
+    """Decode JPEG files to pixels on the GPU: the bytes `djpeg` (+ -grayscale / -rgb / -nosmooth / -scale, see decode_opts) writes
+    for each of them, as numpy arrays [H, W, C] ([H, W] for gray) in input order; with scale=, [ceil(H k / 8), ceil(W k / 8), C].
+    The files are grouped by what a batch must have in common, which the scale is not part of; one encoder per group is kept for
+    later calls.  A file that cannot be decoded (unsupported type, malformed headers,
     damaged entropy-coded data) gets the MjhError in its slot; the others are unaffected."""
     files = [bytes(f) for f in files]
     out = [None] * len(files)
@@ -800,7 +838,7 @@ class Encoder:
         return None if all(r is None for r in res) else res
 
     def decode_stats(self):
-        """width, height and pixel size of the last decoded batch, and the times of its two pixel kernels (ms, with profiling)"""
+        """width, height (the scaled ones) and pixel size of the last decoded batch, and the times of its two pixel kernels (ms, with profiling)"""
         w, h, px, ms = C.c_int(), C.c_int(), C.c_int(), (C.c_float * 2)()
         _chk(lib().mjh_decode_stats(self._h, C.byref(w), C.byref(h), C.byref(px), ms))
         return dict(width=w.value, height=h.value, pixel_size=px.value, ms=dict(idct=float(ms[0]), upcolor=float(ms[1])))

@@ -3151,11 +3151,30 @@ extern "C" void mjh_decode_opts_defaults(mjh_decode_opts *o)
   memset(o, 0, sizeof(*o));
   o->rgb_offset[1] = 1; o->rgb_offset[2] = 2;
   o->fancy_upsampling = 1;
+  o->scale_num = o->scale_denom = 1;
+}
+
+// the IDCT size k of djpeg -scale num/denom (output = input * k / 8), as jpeg_core_output_dimensions resolves the fraction
+// (jdmaster.c:105-235): the smallest k in 1..16 with num * 8 <= denom * k, else 16.  0/0 is 1/1.
+static int resolve_scale(const mjh_decode_opts *o, int *k)
+{
+  *k = 8;
+  if (o->scale_num == 0 && o->scale_denom == 0) return MJH_OK;
+  if (o->scale_num < 1 || o->scale_denom < 1) return fail(MJH_EINVAL, "scale %d/%d (both at least 1, or 0/0 for 1/1)", o->scale_num, o->scale_denom);
+  int s = 1;
+  while (s < 16 && (long long)o->scale_num * 8 > (long long)o->scale_denom * s) s++;
+  if (s != 1 && s != 2 && s != 4 && s != 8)
+    return fail(MJH_EUNSUPPORTED, "scale %d/%d decodes with the %dx%d inverse DCT (jidctint.c); the sizes built are 1x1, 2x2, 4x4 (jidctred.c) and 8x8", o->scale_num, o->scale_denom, s, s);
+  *k = s;
+  return MJH_OK;
 }
 
 // the layout of the output and the road to it: djpeg's choices for this frame (jdmaster.c, jinit_upsampler jdsample.c:444-525,
 // jinit_color_deconverter jdcolor.c)
-static int plan_pixels(const mjh_encoder *e, const mjh_decode_opts *o, MjhPixOut *P)
+// k: the IDCT size of the call (resolve_scale).  ssize[c]: DCT_scaled_size of component c -- k, doubled while the sampling
+// ratios allow it (jpeg_calc_output_dimensions jdmaster.c:287-320), so that the transform does the upsampling where it can.
+// At k = 8 every component is at size 8 and this is the full-size plan.
+static int plan_pixels(const mjh_encoder *e, const mjh_decode_opts *o, int k, MjhPixOut *P, int ssize[3])
 {
   const MjhConst &C = e->C;
   memset(P, 0, sizeof(*P));
@@ -3180,22 +3199,27 @@ static int plan_pixels(const mjh_encoder *e, const mjh_decode_opts *o, MjhPixOut
     for (int k = 0; k < 3; k++)
       if (off[k] < 0 || off[k] >= px || off[k] == off[(k + 1) % 3]) return fail(MJH_EINVAL, "rgb_offset %d,%d,%d of %d-byte pixels", off[0], off[1], off[2], px);
   }
-  P->W = C.W; P->H = C.H;
+  P->W = (int)div_round_up((long)C.W * k, 8); P->H = (int)div_round_up((long)C.H * k, 8);
   P->px_size = px;
   P->ncomp = (P->conv == MJH_CC_GRAY || P->conv == MJH_CC_GRAY_RGB) ? 1 : 3;     // component_needed: a YCbCr file's gray output reads Y alone
-  P->row_pitch = (long long)up16((size_t)px * (((size_t)C.W + 3) & ~(size_t)3));
-  P->image_stride = P->row_pitch * C.H;
+  P->row_pitch = (long long)up16((size_t)px * (((size_t)P->W + 3) & ~(size_t)3));
+  P->image_stride = P->row_pitch * P->H;
   P->planes_per_image = C.planes_per_image;
-  const bool fancy = o->fancy_upsampling != 0;
+  const bool fancy = o->fancy_upsampling != 0 && k > 1;       // do_fancy: && min_DCT_scaled_size > 1 (jdsample.c:444)
   for (int c = 0; c < P->ncomp; c++) {
     const MjhComp &cc = C.c[c];
     MjhUpComp &u = P->c[c];
-    u.dw = (int)div_round_up((long)C.W * cc.h, C.maxh);
-    u.dh = (int)div_round_up((long)C.H * cc.v, C.maxv);
-    u.pw = cc.pw; u.plane_off = cc.plane_off;
-    u.mode = MJH_UP_REPLICATE;
     if (C.maxh % cc.h || C.maxv % cc.v) return fail(MJH_EUNSUPPORTED, "fractional sampling ratios (JERR_FRACT_SAMPLE_NOTIMPL, jdsample.c:529)");
-    u.hexp = C.maxh / cc.h; u.vexp = C.maxv / cc.v;
+    int ss = k;
+    while (ss < 8 && (C.maxh * k) % (cc.h * ss * 2) == 0 && (C.maxv * k) % (cc.v * ss * 2) == 0) ss *= 2;
+    ssize[c] = ss;
+    u.dw = (int)div_round_up((long)C.W * cc.h * ss, (long)C.maxh * 8);
+    u.dh = (int)div_round_up((long)C.H * cc.v * ss, (long)C.maxv * 8);
+    // the reduced plane sits where the full-size one does; its rows hold whole words of k_idct_scaled's lanes (ss = 8: pw itself)
+    u.pw = (cc.wib * ss + 3) & ~3; u.plane_off = cc.plane_off;
+    u.mode = MJH_UP_REPLICATE;
+    // the upsampler's groups: h_in_group = h * ssize / k samples become h_out_group = max_h (jdsample.c:454-459)
+    u.hexp = C.maxh * k / (cc.h * ss); u.vexp = C.maxv * k / (cc.v * ss);
     if (u.hexp == 2 && u.vexp == 1) { if (fancy && u.dw > 2) u.mode = MJH_UP_H2V1_FANCY; }
     else if (u.hexp == 1 && u.vexp == 2) { if (fancy) u.mode = MJH_UP_H1V2_FANCY; }
     else if (u.hexp == 2 && u.vexp == 2) { if (fancy && u.dw > 2) u.mode = MJH_UP_H2V2_FANCY; }
@@ -3210,8 +3234,11 @@ extern "C" int mjh_decode_host(mjh_encoder *e, const void *const jpegs[], const 
   if (e->xf_on) return fail(MJH_EUNSUPPORTED, "a lossless transform (mjh_encoder_set_transform) together with decoding to pixels");
   mjh_decode_opts o;
   if (opts) o = *opts; else mjh_decode_opts_defaults(&o);
+  int k = 8, ssize[3] = { 8, 8, 8 };
+  int rc = resolve_scale(&o, &k);
+  if (rc) return rc;
   MjhPixOut P;
-  int rc = plan_pixels(e, &o, &P);
+  rc = plan_pixels(e, &o, k, &P, ssize);
   if (rc) return rc;
   size_t o_jfif = 0;
   rc = decode_front(e, jpegs, sizes, n, true, &o_jfif);
@@ -3239,7 +3266,22 @@ extern "C" int mjh_decode_host(mjh_encoder *e, const void *const jpegs[], const 
   e->dp = P; e->dp_n = n;
   e->last_n = n; e->compact_last = false; e->last = nullptr;      // (mjh_read_tap: d_q holds this batch's plain planes, d_planes its samples)
   if (timed) HIPCHK(hipEventRecord(e->dp_ev[0], s));
-  mjh_launch_idct(C, Q, P.ncomp, e->d_q, e->d_planes, e->d_tstat, n, s);
+  if (k == 8) mjh_launch_idct(C, Q, P.ncomp, e->d_q, e->d_planes, e->d_tstat, n, s);
+  else {
+    // a scaled call: the reduced transforms component by component; the components the ratios leave at size 8 (chroma of a
+    // 4:2:0 file at 1/2) go through k_idct, handed a descriptor that lists them alone
+    MjhConst C8 = C;
+    MjhIdctQ Q8;
+    memset(&Q8, 0, sizeof(Q8));
+    int n8 = 0;
+    for (int c = 0; c < P.ncomp; c++) {
+      if (ssize[c] != 8) { mjh_launch_idct_scaled(C, Q, c, ssize[c], P.c[c].pw, e->d_q, e->d_planes, e->d_tstat, n, s); continue; }
+      C8.c[n8] = C.c[c];
+      memcpy(Q8.q[n8], Q.q[c], sizeof(Q8.q[n8]));
+      n8++;
+    }
+    if (n8) mjh_launch_idct(C8, Q8, n8, e->d_q, e->d_planes, e->d_tstat, n, s);
+  }
   if (timed) HIPCHK(hipEventRecord(e->dp_ev[1], s));
   mjh_launch_upcolor(P, e->d_planes, e->d_pixout, e->d_tstat, n, s);
   if (timed) HIPCHK(hipEventRecord(e->dp_ev[2], s));

@@ -41,6 +41,11 @@ struct MjhPixOut {
 // K-I1: coefficient planes (what k_dec_store / k_dec_dc leave) -> 8-bit sample planes, real blocks only; comps: the first
 // `comps` components.  status != 0: that image is skipped.
 void mjh_launch_idct(const MjhConst &C, const MjhIdctQ &Q, int comps, const int16_t *coef_q, uint8_t *planes, const unsigned *status, int n, hipStream_t s);
-// K-I2: sample planes -> interleaved pixels
+// K-I1 at a reduced size (djpeg -scale): component ci alone at DCT_scaled_size N of 1, 2 or 4 (jpeg_idct_1x1 / 2x2 / 4x4 of
+// jidctred.c), its N x N samples per block into a plane at the component's plane_off whose rows are `pitch` samples apart (a
+// multiple of 4, at least wib * N; never more than the full-size plane holds).  Components left at size 8: mjh_launch_idct.
+void mjh_launch_idct_scaled(const MjhConst &C, const MjhIdctQ &Q, int ci, int N, int pitch, const int16_t *coef_q, uint8_t *planes, const unsigned *status, int n, hipStream_t s);
+// K-I2: sample planes -> interleaved pixels.  Everything it knows of the planes and the image comes from P, so a scaled decode
+// is the same kernel given the reduced planes (dw, dh, pw), the group ratios of jdsample.c:454-459 and the scaled W x H.
 void mjh_launch_upcolor(const MjhPixOut &P, const uint8_t *planes, uint8_t *pixels, const unsigned *status, int n, hipStream_t s);
 #endif

@@ -12,6 +12,9 @@
 //   leave as eight 8-byte vector stores, one per sample row: the lanes of a wave hold horizontally adjacent blocks, so every
 //   store instruction writes one contiguous 512-byte run of a sample row.  The rows wait in registers; a pass through LDS would
 //   add a write and a read per sample and change nothing about the shape of the stores.
+// K-I1s k_idct_scaled<N>: the same at DCT_scaled_size N = 1, 2, 4 (jidctred.c), one component per launch, for djpeg -scale.
+//   Fewer coefficient planes read, N x N samples per block written; see the kernel.  Components a scaled decode leaves at
+//   size 8 (and every component of an unscaled call) go through k_idct.
 // K-I2 k_upcolor: one lane per 4 output pixels of a row.  Per component the upsampler jinit_upsampler picks (jdsample.c:444-525),
 //   evaluated per output sample from the samples it reads, then the colour conversion of jdcolor.c / jdcolext.c, then one 4-byte,
 //   three 4-byte (12 contiguous bytes) or one 16-byte store (rows of the output hold whole groups of 4 pixels).
@@ -111,6 +114,101 @@ k_idct(MjhConst C, MjhIdctQ Q, const int16_t *__restrict__ coef_q, uint8_t *__re
   }
 }
 
+// ---- K-I1 at a reduced size (djpeg -scale): the transforms of jidctred.c ------------------------------------------------------
+// which of the eight coefficients of a column or row the transform to N samples reads: all but 4 (4), 0 and the odd ones (2),
+// the DC alone (1); a further size of jidctint.c is one more line here and one more idct_1d
+__host__ __device__ constexpr bool idct_reads(int N, int i) { return N == 4 ? i != 4 : (N == 2 ? (i == 0 || (i & 1)) : i == 0); }
+
+// the 1-D transforms, chosen by the number of outputs: the sums in front of the descaling shift.  Those of jidctred.c carry
+// one (4 outputs) or two (2 outputs) more fraction bits than jidctint.c's (its LEFT_SHIFT of the DC by CONST_BITS + 1 / + 2).
+__device__ __forceinline__ void idct_1d(const int (&x)[8], long long (&o)[4])     // jpeg_idct_4x4 jidctred.c:160-199
+{
+  const long long tmp0 = (long long)x[0] * 16384;
+  const long long tmp2 = (long long)x[2] * 15137 + (long long)x[6] * -6270;      // FIX_1_847759065, -FIX_0_765366865
+  const long long tmp10 = tmp0 + tmp2, tmp12 = tmp0 - tmp2;
+  const long long z1 = x[7], z2 = x[5], z3 = x[3], z4 = x[1];
+  const long long odd0 = z1 * -1730 + z2 * 11893 + z3 * -17799 + z4 * 8697;      // -FIX_0_211164243 FIX_1_451774981 -FIX_2_172734803 FIX_1_061594337
+  const long long odd2 = z1 * -4176 + z2 * -4926 + z3 * 7373 + z4 * 20995;       // -FIX_0_509795579 -FIX_0_601344887 FIX_0_899976223 FIX_2_562915447
+  o[0] = tmp10 + odd2; o[3] = tmp10 - odd2;
+  o[1] = tmp12 + odd0; o[2] = tmp12 - odd0;
+}
+__device__ __forceinline__ void idct_1d(const int (&x)[8], long long (&o)[2])     // jpeg_idct_2x2 jidctred.c:316-335
+{
+  const long long tmp10 = (long long)x[0] * 32768;
+  // -FIX_0_720959822 FIX_0_850430095 -FIX_1_272758580 FIX_3_624509785
+  const long long tmp0 = (long long)x[7] * -5906 + (long long)x[5] * 6967 + (long long)x[3] * -10426 + (long long)x[1] * 29692;
+  o[0] = tmp10 + tmp0; o[1] = tmp10 - tmp0;
+}
+
+// one block to its N x N samples, OR-ed into the row words w at byte j * N of every row (j: the block's place in its lane's
+// group).  `in`: the block's entry of zig-zag plane 0.  Only the planes idct_reads names are loaded.
+// The zero-AC shortcuts of both passes of jidctred.c are the general formulas with zeros put in and are no
+// branches here.
+template <int N>
+__device__ __forceinline__ void idct_block(const int16_t *__restrict__ in, int kstride, const int *__restrict__ q, unsigned (&w)[N], int j)
+{
+  constexpr int X = N == 4 ? 1 : 2;                    // the fraction bits the 1-D sums carry beyond jidctint.c's
+  int ws[N][8];
+#pragma unroll
+  for (int c = 0; c < 8; c++) {
+    if (!idct_reads(N, c)) {
+#pragma unroll
+      for (int r = 0; r < N; r++) ws[r][c] = 0;
+      continue;
+    }
+    int x[8];
+#pragma unroll
+    for (int r = 0; r < 8; r++) x[r] = idct_reads(N, r) ? (int)in[(size_t)kZigOfNat[r * 8 + c] * kstride] * q[r * 8 + c] : 0;
+    long long o[N];
+    idct_1d(x, o);
+#pragma unroll
+    for (int r = 0; r < N; r++) ws[r][c] = (int)((o[r] + (1LL << (10 + X))) >> (11 + X));
+  }
+#pragma unroll
+  for (int r = 0; r < N; r++) {
+    long long o[N];
+    idct_1d(ws[r], o);
+#pragma unroll
+    for (int c = 0; c < N; c++) w[r] |= idct_range_limit((int)((o[c] + (1LL << (17 + X))) >> (18 + X))) << (8 * (j * N + c));
+  }
+}
+template <>
+__device__ __forceinline__ void idct_block<1>(const int16_t *__restrict__ in, int, const int *__restrict__ q, unsigned (&w)[1], int j)
+{
+  w[0] |= idct_range_limit((int)(((long long)((int)in[0] * q[0]) + 4) >> 3)) << (8 * j);       // jpeg_idct_1x1: one eighth of the DC
+}
+
+// One lane per G = 4 / N horizontally adjacent blocks of component ci: a lane holds N rows of four samples and stores each as
+// one word, and the lanes of a wave write one contiguous run per sample row.  pitch: samples between rows of the reduced
+// plane, a multiple of 4 that holds ceil(wib / G) such words; the blocks a last group has beyond wib are not read and leave
+// zeros in that pad.
+template <int N>
+__global__ void __launch_bounds__(256)
+k_idct_scaled(MjhConst C, MjhIdctQ Q, int ci, int pitch, const int16_t *__restrict__ coef_q, uint8_t *__restrict__ planes, const unsigned *__restrict__ status)
+{
+  constexpr int G = 4 / N;
+  const int img = blockIdx.z;
+  const MjhComp &cc = C.c[ci];
+  const int gpr = (cc.wib + G - 1) / G;
+  const int t = (int)(blockIdx.x * 256u + threadIdx.x);
+  if (t >= gpr * cc.hib) return;
+  if (status[img] != 0u) return;
+  const int by = t / gpr, gx = t - by * gpr;
+  const int16_t *in = coef_q + (size_t)img * C.coefs_per_image + cc.coef_off + (size_t)by * cc.wib;
+  unsigned w[N];
+#pragma unroll
+  for (int r = 0; r < N; r++) w[r] = 0u;
+#pragma unroll
+  for (int j = 0; j < G; j++) {
+    const int bx = gx * G + j;
+    if (bx >= cc.wib) continue;
+    idct_block<N>(in + bx, cc.kstride, Q.q[ci], w, j);
+  }
+  uint8_t *out = planes + (size_t)img * C.planes_per_image + cc.plane_off + (size_t)(by * N) * pitch + (size_t)gx * 4;
+#pragma unroll
+  for (int r = 0; r < N; r++) *reinterpret_cast<unsigned *>(out + (size_t)r * pitch) = w[r];
+}
+
 // one sample of component uc at output position (x, y), 0 <= x < W, 0 <= y < H
 __device__ __forceinline__ int up_sample(const MjhUpComp &uc, const uint8_t *__restrict__ pl, int x, int y)
 {
@@ -204,4 +302,15 @@ void mjh_launch_upcolor(const MjhPixOut &P, const uint8_t *planes, uint8_t *pixe
 {
   const int groups = (P.W + 3) / 4;
   hipLaunchKernelGGL(k_upcolor, dim3((groups + 255) / 256, P.H, n), dim3(256), 0, s, P, planes, pixels, status);
+}
+
+void mjh_launch_idct_scaled(const MjhConst &C, const MjhIdctQ &Q, int ci, int N, int pitch, const int16_t *coef_q, uint8_t *planes, const unsigned *status, int n, hipStream_t s)
+{
+  const MjhComp &cc = C.c[ci];
+  const int G = 4 / N;
+  const int lanes = (cc.wib + G - 1) / G * cc.hib;
+  const dim3 grid((lanes + 255) / 256, 1, n);
+  if (N == 4) hipLaunchKernelGGL((k_idct_scaled<4>), grid, dim3(256), 0, s, C, Q, ci, pitch, coef_q, planes, status);
+  else if (N == 2) hipLaunchKernelGGL((k_idct_scaled<2>), grid, dim3(256), 0, s, C, Q, ci, pitch, coef_q, planes, status);
+  else hipLaunchKernelGGL((k_idct_scaled<1>), grid, dim3(256), 0, s, C, Q, ci, pitch, coef_q, planes, status);
 }

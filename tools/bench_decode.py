@@ -9,7 +9,8 @@ after a warm-up) with the run-to-run spread; the phase times of the Huffman deco
 (mjh_set_profiling(1), a separate pass) with the bytes per second the pixel kernels reach against their byte counts; and the
 yardstick: oracle/_ref/djpeg -pnm over the same files, 16 processes at a time, input on a RAM disk and output discarded (that
 figure includes process start and PPM formatting).  The first call's pixels are compared with djpeg's before anything is timed.
-usage: python tools/bench_decode.py [--workloads A,B] [--seconds 2] [--repeats 3] [--out profiles/decode_bench]"""
+--scale M/N: both workloads decoded at that scale (1/2, 1/4, 1/8: the reduced inverse DCTs), the reference being djpeg -scale M/N.
+usage: python tools/bench_decode.py [--workloads A,B] [--scale 1/1] [--seconds 2] [--repeats 3] [--out profiles/decode_bench]"""
 import argparse
 import json
 import os
@@ -30,7 +31,7 @@ import decode_cases as DC  # noqa: E402
 from bench_transcode import sources  # noqa: E402
 
 
-def reference_rate(files, procs=16):
+def reference_rate(files, args=(), procs=16):
     """files/s of the reference's djpeg, `procs` processes at a time, input on a RAM disk, output discarded"""
     base = "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) else None
     with tempfile.TemporaryDirectory(dir=base) as td:
@@ -39,7 +40,7 @@ def reference_rate(files, procs=16):
                 fh.write(f)
 
         def one(i):
-            subprocess.check_call([DC.DJPEG, "-pnm", "-outfile", os.devnull, os.path.join(td, "%d.jpg" % i)])
+            subprocess.check_call([DC.DJPEG, "-pnm"] + list(args) + ["-outfile", os.devnull, os.path.join(td, "%d.jpg" % i)])
         with ThreadPoolExecutor(procs) as ex:
             list(ex.map(one, range(min(len(files), 2 * procs))))          # warm-up
             t0 = time.perf_counter()
@@ -48,10 +49,10 @@ def reference_rate(files, procs=16):
     return len(files) / dt, base is not None
 
 
-def timed(enc, files, seconds, host):
+def timed(enc, files, seconds, host, opts):
     calls, t0 = 0, time.perf_counter()
     while True:
-        enc.submit_decode(files)
+        enc.submit_decode(files, opts=opts)
         if host is None:
             enc.sync()
         else:
@@ -66,34 +67,40 @@ def timed(enc, files, seconds, host):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", default="A,B")
+    ap.add_argument("--scale", default="1/1")
     ap.add_argument("--seconds", type=float, default=2.0)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    opts = M.decode_opts(scale=a.scale)
+    k = M.scale_idct_size(opts.scale_num, opts.scale_denom)
+    dj_args = ["-scale", a.scale] if k != 8 else []
     isa = json.load(open(os.path.join(ROOT, "mozjpeg_amd", "kernel_isa.json")))["kernels"]
-    result = {"kernel_sha": {k: isa[k]["sha"] for k in ("k_dec_sync", "k_dec_prefix", "k_dec_store", "k_dec_dc", "k_idct", "k_upcolor") if k in isa},
-              "workloads": {}}
+    result = {"kernel_sha": {k: isa[k]["sha"] for k in isa if k in ("k_dec_sync", "k_dec_prefix", "k_dec_store", "k_dec_dc", "k_idct", "k_upcolor") or k.startswith("k_idct_scaled")},
+              "scale": a.scale, "idct_size": k, "workloads": {}}
     for wl in a.workloads.split(","):
         files = sources(wl)
         n = len(files)
         info = M.jpeg_info(files[0])
         w, h = info.image_width, info.image_height
         enc = M.Encoder(M.params_from_jpeg(files[0], revert=True), max_batch=n)
-        outs = enc.decode_host(files)
+        outs = enc.decode_host(files, opts=opts)
+        ow, oh = -(-w * k // 8), -(-h * k // 8)
+        assert outs[0].shape == (oh, ow, 3)
         with ThreadPoolExecutor(16) as ex:
-            same = list(ex.map(lambda i: bool(np.array_equal(outs[i], DC.djpeg(files[i]))), range(n)))
+            same = list(ex.map(lambda i: bool(np.array_equal(outs[i], DC.djpeg(files[i], dj_args))), range(n)))
         del outs
-        ref_rate, ramdisk = reference_rate(files)
-        r = {"files": n, "width": w, "height": h, "source_bytes": sum(len(f) for f in files), "identical_to_reference": all(same),
+        ref_rate, ramdisk = reference_rate(files, dj_args)
+        r = {"files": n, "width": w, "height": h, "out_width": ow, "out_height": oh, "source_bytes": sum(len(f) for f in files), "identical_to_reference": all(same),
              "reference_files_per_s": ref_rate, "reference_on_ramdisk": ramdisk, "stats": {k: v for k, v in enc.transcode_stats().items() if k != "ms"}, "paths": {}}
-        host = M.pinned_empty((n, h, w, 3))
+        host = M.pinned_empty((n, oh, ow, 3))
         paths = {"device": None, "host": host}
         for name, dst in paths.items():
-            timed(enc, files, 0.0, dst)                # warm-up
+            timed(enc, files, 0.0, dst, opts)          # warm-up
             r["paths"][name] = {"files_per_s": []}
         for _ in range(a.repeats):                     # alternating
             for name, dst in paths.items():
-                r["paths"][name]["files_per_s"].append(timed(enc, files, a.seconds, dst))
+                r["paths"][name]["files_per_s"].append(timed(enc, files, a.seconds, dst, opts))
         for name in paths:
             c = r["paths"][name]
             v = c["files_per_s"]
@@ -104,15 +111,17 @@ def main():
         enc.set_profiling(1)
         ms = []
         for _ in range(5):
-            enc.submit_decode(files)
+            enc.submit_decode(files, opts=opts)
             enc.sync()
             ms.append(dict(enc.transcode_stats()["ms"], **enc.decode_stats()["ms"]))
         enc.set_profiling(0)
         r["phase_ms"] = {k: sorted(m[k] for m in ms)[len(ms) // 2] for k in ms[0]}
         # byte counts of the pixel kernels: coefficients read + planes written; planes read + pixels written (4:2:0: 1.5 samples a pixel)
-        coef_bytes, plane_bytes, pix_bytes = n * w * h * 1.5 * 2, n * w * h * 1.5, n * w * h * 3
-        r["idct_gbytes_per_s"] = (coef_bytes + plane_bytes) / r["phase_ms"]["idct"] / 1e6
-        r["upcolor_gbytes_per_s"] = (plane_bytes + pix_bytes) / r["phase_ms"]["upcolor"] / 1e6
+        # (full size only: a reduced transform reads a subset of the coefficient planes that depends on every component's size)
+        if k == 8:
+            coef_bytes, plane_bytes, pix_bytes = n * w * h * 1.5 * 2, n * w * h * 1.5, n * w * h * 3
+            r["idct_gbytes_per_s"] = (coef_bytes + plane_bytes) / r["phase_ms"]["idct"] / 1e6
+            r["upcolor_gbytes_per_s"] = (plane_bytes + pix_bytes) / r["phase_ms"]["upcolor"] / 1e6
         kd = sum(r["phase_ms"][k] for k in ("sync", "prefix", "store", "dc"))
         r["pixel_kernels_to_huffman_decoder"] = (r["phase_ms"]["idct"] + r["phase_ms"]["upcolor"]) / kd
         enc.close()
