@@ -429,8 +429,9 @@ int mjh_encoder_set_transform(mjh_encoder *e, const mjh_transform *t);
 /* ---- decoding existing files to pixels (djpeg [-scale M/N] [-nosmooth] [-grayscale | -rgb]) -------------------------------------
  * JPEG bytes in host memory in, interleaved 8-bit pixels in device memory out (and in host memory on request): the marker walk
  * and the Huffman decoder kernels of mjh_transcode_host, then dequantization + inverse DCT and upsampling + colour conversion
- * (mjh_idct.hip).  The pixels are the bytes the reference's djpeg writes with the slow integer IDCT (-dct int, its default):
- * every sample, every edge, and the wrap of its range-limit table on files with absurd coefficients.
+ * (mjh_idct.hip).  The pixels are the bytes the reference's djpeg writes with the slow integer IDCT (-dct int, its default) or,
+ * with dct_method 1, the fast one (-dct fast): every sample, every edge, and the wrap of its range-limit table on files with
+ * absurd coefficients.
  * The encoder is one made from mjh_params_from_jpeg: it owns the geometry, the quantization tables and the coefficient planes;
  * the files accepted and the agreement every file of a batch must show are those of mjh_transcode_host.
  * out_color_space: 0 = djpeg's default for the file (gray for a one-component file, RGB otherwise), MJH_CS_GRAYSCALE
@@ -444,15 +445,31 @@ int mjh_encoder_set_transform(mjh_encoder *e, const mjh_transform *t);
  * full-size path, which 1/1 and 0/0 (a zeroed struct) name.  The output is ceil(W k / 8) x ceil(H k / 8): mjh_decode_stats
  * reports that size, mjh_get_pixels and mjh_get_pixels_device address that image.  The encoder is still the one made from
  * mjh_params_from_jpeg at the file's own size, and serves calls at different scales one after the other.
- * MJH_EINVAL: an unknown colour space, pixel size or offsets; a scale_num or scale_denom below 1 (other than 0/0).
+ * dct_method: the numbers of mjh_params.dct_method -- 0 = JDCT_ISLOW (jidctint.c), 1 = JDCT_IFAST (jidctfst.c: djpeg -dct fast,
+ * TurboJPEG's FASTDCT).  As in the reference (jddctmgr.c start_pass) the method holds for components transformed at size 8;
+ * the reduced sizes of a scaled call have one transform each.  The fast method's sums are 32-bit as the reference's; on a file
+ * whose quantization tables make them overflow (undefined behaviour there) they wrap here.
+ * bottom_up: row y of the image is stored at row H - 1 - y of the output, H the scaled height (TurboJPEG's BOTTOMUP).
+ * raw_planes: the call stops after the inverse DCT and produces no pixels: the components' sample planes at the call's scale
+ * (jpeg_read_raw_data, TurboJPEG's planar YUV output), through mjh_get_plane / mjh_get_planes_device.  EVERY component is then
+ * transformed at the scale's own size k (the pixel path may leave subsampled chroma at a larger one, jdmaster.c:287-320), as
+ * TurboJPEG forces it (turbojpeg.c:2151-2167): the planes keep the file's subsampling at every scale.  (With dct_method 1
+ * the reference then runs the reduced transform of a component the pixel path would have left at size 8 -- chroma of a 4:2:0
+ * file at 1/2 -- on the fast method's multiplier table; so does this call, for the reference's bytes.)  out_color_space,
+ * pixel_size, rgb_offset, fancy_upsampling and bottom_up are ignored.
+ * The three fields were appended; 0 in all of them is the behaviour of the struct without them.
+ * MJH_EINVAL: an unknown colour space, pixel size, offsets or dct_method; a scale_num or scale_denom below 1 (other than 0/0).
  * MJH_EUNSUPPORTED: a lossless transform set on the encoder; a scale that resolves to an IDCT size of 3, 5, 6, 7 or 9 to 16;
- * other IDCT methods, cropping and colour quantization have no option here. */
+ * the float IDCT, cropping and colour quantization have no option here. */
 typedef struct {
   int out_color_space;
   int pixel_size;
   int rgb_offset[3];
   int fancy_upsampling;
   int scale_num, scale_denom;
+  int dct_method;
+  int bottom_up;
+  int raw_planes;
 } mjh_decode_opts;
 void mjh_decode_opts_defaults(mjh_decode_opts *o);
 /* Decodes n files (opts == NULL: the defaults).  Queued on the encoder's stream; the bytes need not stay valid after the call.
@@ -471,7 +488,15 @@ int mjh_get_pixels(mjh_encoder *e, int i, void *dst, size_t row_pitch);
  * encoder's stream; mjh_decode_wait waits for it AND reports damaged files, mjh_encoder_sync only waits.  The buffer is reused
  * by the next decode call. */
 int mjh_get_pixels_device(mjh_encoder *e, void **d_base, size_t *row_pitch, size_t *image_stride);
-/* Size (the scaled one) and pixel size of the last decoded batch and, with mjh_set_profiling(e, 1), the milliseconds of its two pixel kernels:
+/* After a raw_planes call: copies the top-left width x height samples of component comp of image i to host memory, row_pitch
+ * bytes between rows (synchronises).  The plane holds the component's real blocks at the call's IDCT size k: (blocks across * k)
+ * x (blocks down * k) samples, never fewer than ceil(W h k / (8 hmax)) x ceil(H v k / (8 vmax)); more than that is MJH_EINVAL.
+ * After a call that made pixels: MJH_EINVAL (and mjh_get_pixels after a raw_planes call likewise). */
+int mjh_get_plane(mjh_encoder *e, int i, int comp, void *dst, size_t row_pitch, int width, int height);
+/* The device view of the same planes: sample (x, y) of component comp of image i is at base + i * image_stride + y * row_pitch
+ * + x, for x < width and y < height.  Does not wait (see mjh_get_pixels_device).  Any pointer may be NULL. */
+int mjh_get_planes_device(mjh_encoder *e, int comp, void **d_base, size_t *row_pitch, size_t *image_stride, int *width, int *height);
+/* Size (the scaled one) and pixel size of the last decoded batch (0 after a raw_planes call) and, with mjh_set_profiling(e, 1), the milliseconds of its two pixel kernels:
  * [0] dequantization + inverse DCT, [1] upsampling + colour conversion (the Huffman decoder's phases: mjh_transcode_stats).
  * Any pointer may be NULL. */
 int mjh_decode_stats(mjh_encoder *e, int *width, int *height, int *pixel_size, float ms[2]);

@@ -83,9 +83,10 @@ class JpegInfo(C.Structure):
 
 
 class DecodeOpts(C.Structure):
-    """mjh_decode_opts: what djpeg's -grayscale / -rgb / -nosmooth / -scale and the extended pixel layouts choose"""
+    """mjh_decode_opts: what djpeg's -grayscale / -rgb / -nosmooth / -scale / -dct and the extended pixel layouts choose, TurboJPEG's
+    bottom-up rows, and the raw sample planes instead of pixels"""
     _fields_ = [("out_color_space", C.c_int), ("pixel_size", C.c_int), ("rgb_offset", C.c_int * 3), ("fancy_upsampling", C.c_int),
-                ("scale_num", C.c_int), ("scale_denom", C.c_int)]
+                ("scale_num", C.c_int), ("scale_denom", C.c_int), ("dct_method", C.c_int), ("bottom_up", C.c_int), ("raw_planes", C.c_int)]
 
 
 class Result(C.Structure):
@@ -174,6 +175,9 @@ def lib():
             L.mjh_get_pixels_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
             L.mjh_decode_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float)]
             L.mjh_decode_wait.argtypes = [C.c_void_p]
+            L.mjh_get_plane.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int]
+            L.mjh_get_planes_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                                C.POINTER(C.c_int), C.POINTER(C.c_int)]
             L.mjh_transcode_batch_size.argtypes = [C.c_void_p]
         if hasattr(L, "mjh_enc_onepass_stats"):       # (absent from a MOZJPEG_AMD_LIB variant built from an older tree: A/B runs against it)
             L.mjh_enc_onepass_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
@@ -484,11 +488,16 @@ def _parse_scale(scale):
     return num, denom
 
 
-def decode_opts(color=None, layout=None, pixel_size=0, rgb_offset=None, fancy_upsampling=True, scale=None):
+DCT_METHODS = {None: 0, "int": 0, "islow": 0, "fast": 1, "ifast": 1}     # djpeg -dct int / fast -> mjh_decode_opts.dct_method
+
+
+def decode_opts(color=None, layout=None, pixel_size=0, rgb_offset=None, fancy_upsampling=True, scale=None, dct=None, bottom_up=False,
+                raw_planes=False):
     """DecodeOpts from djpeg's vocabulary.  color: None (the file's default: gray stays gray, everything else RGB), "gray" /
     "grayscale" (-grayscale), "rgb" (-rgb) or a CS_* number; layout: a name out of PIXEL_LAYOUTS, or pixel_size and rgb_offset;
     fancy_upsampling=False: -nosmooth; scale: -scale, a pair (num, denom) or a string "M/N" that resolves to 1/8, 2/8, 4/8 or
-    8/8 as djpeg resolves it (scale_idct_size)."""
+    8/8 as djpeg resolves it (scale_idct_size); dct: "int" (the default) or "fast" (-dct fast, TurboJPEG's FASTDCT);
+    bottom_up=True: the rows last to first (TurboJPEG's BOTTOMUP); raw_planes=True: no pixels, the sample planes (decode_planes)."""
     o = DecodeOpts()
     lib().mjh_decode_opts_defaults(C.byref(o))
     if isinstance(color, str):
@@ -507,7 +516,17 @@ def decode_opts(color=None, layout=None, pixel_size=0, rgb_offset=None, fancy_up
         o.rgb_offset[:] = [int(v) for v in rgb_offset]
     o.fancy_upsampling = int(bool(fancy_upsampling))
     o.scale_num, o.scale_denom = _parse_scale(scale)
+    if isinstance(dct, int) and not isinstance(dct, bool):
+        o.dct_method = dct
+    elif dct in DCT_METHODS:
+        o.dct_method = DCT_METHODS[dct]
+    else:
+        raise MjhError(EINVAL, "dct %r (None, 'int' or 'fast')" % (dct,))
+    o.bottom_up = int(bool(bottom_up))
+    o.raw_planes = int(bool(raw_planes))
     # the library's own checks (plan_pixels), made here as well so that decode() can refuse its options before it groups files
+    if o.dct_method not in (0, 1):
+        raise MjhError(EINVAL, "dct_method %d of a decode call (0 = JDCT_ISLOW, 1 = JDCT_IFAST)" % o.dct_method)
     if o.out_color_space not in (0, CS_GRAYSCALE, CS_RGB):
         raise MjhError(EINVAL, "out_color_space %d (0, CS_GRAYSCALE or CS_RGB)" % o.out_color_space)
     if o.out_color_space == CS_GRAYSCALE:
@@ -527,15 +546,39 @@ _decode_encoders = {}
 
 
 def decode(files, *, max_batch=64, device=0, **opts):
-    """Decode JPEG files to pixels on the GPU: the bytes `djpeg` (+ -grayscale / -rgb / -nosmooth / -scale, see decode_opts) writes
-    for each of them, as numpy arrays [H, W, C] ([H, W] for gray) in input order; with scale=, [ceil(H k / 8), ceil(W k / 8), C].
+    """Decode JPEG files to pixels on the GPU: the bytes `djpeg` (+ -grayscale / -rgb / -nosmooth / -scale / -dct fast, see
+    decode_opts) writes for each of them, as numpy arrays [H, W, C] ([H, W] for gray) in input order; with scale=,
+    [ceil(H k / 8), ceil(W k / 8), C]; with bottom_up=True, the rows last to first.
     The files are grouped by what a batch must have in common, which the scale is not part of; one encoder per group is kept for
     later calls.  A file that cannot be decoded (unsupported type, malformed headers,
     damaged entropy-coded data) gets the MjhError in its slot; the others are unaffected."""
+    return _decode_grouped(files, max_batch, device, decode_opts(**opts))
+
+
+def yuv_plane_size(info, comp, k=8):
+    """(height, width) of plane `comp` of a file decoded at IDCT size k to planar output: TurboJPEG's tj3YUVPlaneWidth / Height of
+    the scaled image (turbojpeg.c) restated with the file's own factors -- the scaled size padded to whole MCUs of the full-size
+    samples (hmax x vmax), times the component's share: pad(ceil(W k / 8), hmax) * h / hmax."""
+    nc = info.num_components
+    maxh = max(info.h_samp_factor[c] for c in range(nc))
+    maxv = max(info.v_samp_factor[c] for c in range(nc))
+    w, h = -(-info.image_width * k // 8), -(-info.image_height * k // 8)
+    pw, ph = -(-w // maxh) * maxh, -(-h // maxv) * maxv
+    return ph * info.v_samp_factor[comp] // maxv, pw * info.h_samp_factor[comp] // maxh
+
+
+def decode_planes(files, scale=None, dct=None, *, max_batch=64, device=0):
+    """Decode JPEG files to their sample planes on the GPU, without upsampling or colour conversion (TurboJPEG's
+    tj3DecompressToYUVPlanes8): per file a list of uint8 arrays [h, w], one per component, of yuv_plane_size(), or the MjhError.
+    Every component is transformed at the scale's own size (mjh_decode_opts.raw_planes), so the planes keep the file's
+    subsampling at every scale."""
+    return _decode_grouped(files, max_batch, device, decode_opts(scale=scale, dct=dct, raw_planes=True))
+
+
+def _decode_grouped(files, max_batch, device, o):
     files = [bytes(f) for f in files]
     out = [None] * len(files)
     groups = {}
-    o = decode_opts(**opts)
     for i, f in enumerate(files):
         try:
             info = jpeg_info(f)
@@ -859,13 +902,35 @@ class Encoder:
         _chk(lib().mjh_get_pixels_device(self._h, C.byref(base), C.byref(pitch), C.byref(stride)))
         return base.value, pitch.value, stride.value, self.decode_stats()
 
+    def get_planes(self, i, info, k):
+        """the sample planes of image i of the last batch, decoded with raw_planes at IDCT size k: a list of uint8 [h, w] arrays of
+        yuv_plane_size(info, c, k) (mjh_get_plane); info: the JpegInfo of the file"""
+        out = []
+        for c in range(info.num_components):
+            a = np.empty(yuv_plane_size(info, c, k), np.uint8)
+            _chk(lib().mjh_get_plane(self._h, i, c, a.ctypes.data, a.strides[0], a.shape[1], a.shape[0]))
+            out.append(a)
+        return out
+
+    def planes_device(self, comp):
+        """(device pointer, row pitch, image stride, width, height) of component comp's plane of the last raw_planes batch
+        (mjh_get_planes_device); wait_decode() first"""
+        base, pitch, stride, w, h = C.c_void_p(), C.c_size_t(), C.c_size_t(), C.c_int(), C.c_int()
+        _chk(lib().mjh_get_planes_device(self._h, comp, C.byref(base), C.byref(pitch), C.byref(stride), C.byref(w), C.byref(h)))
+        return base.value, pitch.value, stride.value, w.value, h.value
+
     def decode_host(self, files, errors="raise", opts=None, **kw):
         """files: JPEG byte strings that agree with the encoder's parameters (params_from_jpeg).  Returns their pixels, a list of
-        numpy arrays.  errors="return": no exception for a batch with damaged files -- their slots hold the MjhError, the slots
-        of the good files None (nothing of such a batch is handed out: submit the good ones again)."""
+        numpy arrays -- or, with raw_planes, per file the list of its sample planes (get_planes).  errors="return": no exception
+        for a batch with damaged files -- their slots hold the MjhError, the slots of the good files None (nothing of such a
+        batch is handed out: submit the good ones again)."""
         n = len(files)
+        o = opts if opts is not None else decode_opts(**kw)
         try:
-            self.submit_decode(files, opts=opts, **kw)
+            self.submit_decode(files, opts=o)
+            if o.raw_planes:
+                k = 8 if o.scale_num == 0 and o.scale_denom == 0 else scale_idct_size(o.scale_num, o.scale_denom)
+                return [self.get_planes(i, jpeg_info(files[i]), k) for i in range(n)]
             return [self.get_pixels(i) for i in range(n)]
         except MjhError:
             if errors != "return":

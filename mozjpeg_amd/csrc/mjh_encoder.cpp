@@ -436,9 +436,19 @@ struct mjh_encoder {
   bool dp_waited = false;               // ... and has been waited for (the guard check runs once per batch)
   bool dp_queued = false;               // the last batch of files went through mjh_decode_host and got as far as its kernels
   int dp_n = 0;
+  // raw_planes: the batch stopped after K-I1; its sample planes in d_planes (component c: rp_w[c] x rp_h[c] samples of real blocks
+  // at plane_off, rows rp_pitch[c] apart)
+  bool dp_raw = false;
+  int rp_ncomp = 0, rp_w[MJH_MAXC] = {}, rp_h[MJH_MAXC] = {}, rp_pitch[MJH_MAXC] = {};
 };
 
 static long div_round_up(long a, long b) { return (a + b - 1) / b; }
+
+// the AA&N scale factors of every position (natural order) scaled up by 14 bits: aanscales of jcdctmgr.c:291-345 and jddctmgr.c:284-316
+static const int kAanScales[64] = { 16384, 22725, 21407, 19266, 16384, 12873, 8867, 4520, 22725, 31521, 29692, 26722, 22725, 17855, 12299, 6270,
+                                    21407, 29692, 27969, 25172, 21407, 16819, 11585, 5906, 19266, 26722, 25172, 22654, 19266, 15137, 10426, 5315,
+                                    16384, 22725, 21407, 19266, 16384, 12873, 8867, 4520, 12873, 17855, 16819, 15137, 12873, 10114, 6967, 3552,
+                                    8867, 12299, 11585, 10426, 8867, 6967, 4799, 2446, 4520, 6270, 5906, 5315, 4520, 3552, 2446, 1247 };
 
 // trellis_q_opt with the arithmetic coder.  The coder's trellis passes all select component 0 (no statistics pass sits between
 // them and prepare_for_pass's trellis_pass case does not re-select the scan: jcmaster.c:686-702, :1001-1005); they are passes
@@ -1188,11 +1198,7 @@ extern "C" int mjh_encoder_create(const mjh_params *p, int max_batch, int device
       hq.lambda_tbl[t][k] = (float)(1.0 / (double)(q * q));   // jcdctmgr.c:1017-1021
       {   // the conventional quantizer's divisor: a UINT16 argument in the reference's 8-bit build (see MjhQuant)
         // JDCT_IFAST: quantval x the AA&N scale factors of the position (natural order) x 8, rounded at 11 bits (jcdctmgr.c:291-345)
-        static const int aan[64] = { 16384, 22725, 21407, 19266, 16384, 12873, 8867, 4520, 22725, 31521, 29692, 26722, 22725, 17855, 12299, 6270,
-                                     21407, 29692, 27969, 25172, 21407, 16819, 11585, 5906, 19266, 26722, 25172, 22654, 19266, 15137, 10426, 5315,
-                                     16384, 22725, 21407, 19266, 16384, 12873, 8867, 4520, 12873, 17855, 16819, 15137, 12873, 10114, 6967, 3552,
-                                     8867, 12299, 11585, 10426, 8867, 6967, 4799, 2446, 4520, 6270, 5906, 5315, 4520, 3552, 2446, 1247 };
-        const int dc = p->dct_method == 1 ? (C.precision == 12 ? (int)(((long)q * aan[kZZ[k]] + 1024L) >> 11) : (int)((((long)q * aan[kZZ[k]] + 1024L) >> 11) & 0xFFFF))
+        const int dc = p->dct_method == 1 ? (C.precision == 12 ? (int)(((long)q * kAanScales[kZZ[k]] + 1024L) >> 11) : (int)((((long)q * kAanScales[kZZ[k]] + 1024L) >> 11) & 0xFFFF))
                                           : C.precision == 12 ? 8 * q : (int)((8u * (unsigned)q) & 0xFFFFu);
         if (dc == 0)      // q = 8192, 16384, 24576: compute_reciprocal(0) divides by zero -- the reference dies
           for (int i = 0; i < C.ncomp; i++) if (p->quant_tbl_no[i] == t) e->fdct_div_zero = true;
@@ -3234,17 +3240,33 @@ extern "C" int mjh_decode_host(mjh_encoder *e, const void *const jpegs[], const 
   if (e->xf_on) return fail(MJH_EUNSUPPORTED, "a lossless transform (mjh_encoder_set_transform) together with decoding to pixels");
   mjh_decode_opts o;
   if (opts) o = *opts; else mjh_decode_opts_defaults(&o);
+  if (o.dct_method != 0 && o.dct_method != 1) return fail(MJH_EINVAL, "dct_method %d of a decode call (0 = JDCT_ISLOW, 1 = JDCT_IFAST)", o.dct_method);
+  const bool ifast = o.dct_method == 1, raw = o.raw_planes != 0;
   int k = 8, ssize[3] = { 8, 8, 8 };
   int rc = resolve_scale(&o, &k);
   if (rc) return rc;
   MjhPixOut P;
-  rc = plan_pixels(e, &o, k, &P, ssize);
-  if (rc) return rc;
+  if (raw) {
+    // the planes alone: every component at the scale's own size (what TurboJPEG forces for planar output, turbojpeg.c:2151-2167),
+    // so that they keep the file's subsampling at every scale; nothing of the pixel options is looked at
+    const MjhConst &C0 = e->C;
+    if (C0.ncomp != 1 && C0.ncomp != 3) return fail(MJH_EUNSUPPORTED, "decoding files of %d components", C0.ncomp);
+    if (C0.precision != 8) return fail(MJH_EUNSUPPORTED, "decoding %d-bit files", C0.precision);
+    memset(&P, 0, sizeof(P));
+    P.W = (int)div_round_up((long)C0.W * k, 8); P.H = (int)div_round_up((long)C0.H * k, 8);
+    P.ncomp = C0.ncomp;
+    P.planes_per_image = C0.planes_per_image;
+    for (int c = 0; c < P.ncomp; c++) { ssize[c] = k; P.c[c].pw = k == 8 ? C0.c[c].pw : (C0.c[c].wib * k + 3) & ~3; }
+  } else {
+    rc = plan_pixels(e, &o, k, &P, ssize);
+    if (rc) return rc;
+    P.bottom_up = o.bottom_up != 0;
+  }
   size_t o_jfif = 0;
   rc = decode_front(e, jpegs, sizes, n, true, &o_jfif);
   if (rc) return rc;
   const MjhConst &C = e->C;
-  const size_t need = (size_t)e->max_batch * (size_t)P.image_stride;
+  const size_t need = raw ? 0 : (size_t)e->max_batch * (size_t)P.image_stride;
   if (need > e->pixout_cap) {
     HIPCHK(hipStreamSynchronize(e->stream));
     if (e->d_pixout) { (void)mjh_guard_free(e->d_pixout); e->d_pixout = nullptr; }
@@ -3257,33 +3279,55 @@ extern "C" int mjh_decode_host(mjh_encoder *e, const void *const jpegs[], const 
     for (hipEvent_t &ev : e->dp_ev) HIPCHK(hipEventCreate(&ev));
     HIPCHK(hipEventCreateWithFlags(&e->dp_done, hipEventDisableTiming));
   }
-  MjhIdctQ Q;
+  // the multipliers: quantval (jidctint.c, jidctred.c) and, for the fast method, DESCALE(quantval * aanscales, CONST_BITS 14 -
+  // IFAST_SCALE_BITS 2) with rounding, kept as int (jddctmgr.c:284-316)
+  MjhIdctQ Q, QF;
   memset(&Q, 0, sizeof(Q));
+  memset(&QF, 0, sizeof(QF));
   for (int c = 0; c < C.ncomp; c++)
-    for (int k = 0; k < 64; k++) Q.q[c][k] = (int)e->p_created.quantval[e->p_created.quant_tbl_no[c]][k];
+    for (int k = 0; k < 64; k++) {
+      const long long qv = (long long)e->p_created.quantval[e->p_created.quant_tbl_no[c]][k];
+      Q.q[c][k] = (int)qv;
+      QF.q[c][k] = (int)((qv * kAanScales[k] + 2048) >> 12);
+    }
   hipStream_t s = e->stream;
   const bool timed = e->profiling != 0;
-  e->dp = P; e->dp_n = n;
+  e->dp = P; e->dp_n = n; e->dp_raw = raw;
   e->last_n = n; e->compact_last = false; e->last = nullptr;      // (mjh_read_tap: d_q holds this batch's plain planes, d_planes its samples)
   if (timed) HIPCHK(hipEventRecord(e->dp_ev[0], s));
-  if (k == 8) mjh_launch_idct(C, Q, P.ncomp, e->d_q, e->d_planes, e->d_tstat, n, s);
+  if (k == 8) (ifast ? mjh_launch_idct_ifast : mjh_launch_idct)(C, ifast ? QF : Q, P.ncomp, e->d_q, e->d_planes, e->d_tstat, n, s);
   else {
     // a scaled call: the reduced transforms component by component; the components the ratios leave at size 8 (chroma of a
-    // 4:2:0 file at 1/2) go through k_idct, handed a descriptor that lists them alone
+    // 4:2:0 file at 1/2) go through k_idct or k_idct_ifast -- only they have a method to choose (jddctmgr.c start_pass) --
+    // handed a descriptor that lists them alone
     MjhConst C8 = C;
     MjhIdctQ Q8;
     memset(&Q8, 0, sizeof(Q8));
     int n8 = 0;
+    // raw_planes with the fast method: a component jdmaster.c would have left at size 8 got its AA&N multiplier table from
+    // jddctmgr.c start_pass BEFORE TurboJPEG forced the reduced transform on it (turbojpeg.c:2151-2167 swaps the function and
+    // leaves dct_table alone), so the reference runs jidctred.c on those multipliers (chroma of a 4:2:0 file at 1/2).  Its bytes
+    // are the contract: the same table goes to k_idct_scaled here.
+    MjhIdctQ QS = Q;
+    if (raw && ifast)
+      for (int c = 0; c < P.ncomp; c++) {
+        int ss = k;
+        while (ss < 8 && (C.maxh * k) % (C.c[c].h * ss * 2) == 0 && (C.maxv * k) % (C.c[c].v * ss * 2) == 0) ss *= 2;
+        if (ss == 8) memcpy(QS.q[c], QF.q[c], sizeof(QS.q[c]));
+      }
     for (int c = 0; c < P.ncomp; c++) {
-      if (ssize[c] != 8) { mjh_launch_idct_scaled(C, Q, c, ssize[c], P.c[c].pw, e->d_q, e->d_planes, e->d_tstat, n, s); continue; }
+      if (ssize[c] != 8) { mjh_launch_idct_scaled(C, QS, c, ssize[c], P.c[c].pw, e->d_q, e->d_planes, e->d_tstat, n, s); continue; }
       C8.c[n8] = C.c[c];
-      memcpy(Q8.q[n8], Q.q[c], sizeof(Q8.q[n8]));
+      memcpy(Q8.q[n8], (ifast ? QF : Q).q[c], sizeof(Q8.q[n8]));
       n8++;
     }
-    if (n8) mjh_launch_idct(C8, Q8, n8, e->d_q, e->d_planes, e->d_tstat, n, s);
+    if (n8) (ifast ? mjh_launch_idct_ifast : mjh_launch_idct)(C8, Q8, n8, e->d_q, e->d_planes, e->d_tstat, n, s);
   }
   if (timed) HIPCHK(hipEventRecord(e->dp_ev[1], s));
-  mjh_launch_upcolor(P, e->d_planes, e->d_pixout, e->d_tstat, n, s);
+  if (raw) {
+    e->rp_ncomp = P.ncomp;
+    for (int c = 0; c < P.ncomp; c++) { e->rp_w[c] = C.c[c].wib * k; e->rp_h[c] = C.c[c].hib * k; e->rp_pitch[c] = P.c[c].pw; }
+  } else mjh_launch_upcolor(P, e->d_planes, e->d_pixout, e->d_tstat, n, s);
   if (timed) HIPCHK(hipEventRecord(e->dp_ev[2], s));
   e->dp_timed = timed;
   HIPCHK(hipGetLastError());
@@ -3323,6 +3367,7 @@ extern "C" int mjh_get_pixels(mjh_encoder *e, int i, void *dst, size_t row_pitch
   if (!e || !dst) return fail(MJH_EINVAL, "bad arguments");
   int rc = wait_pixels(e);
   if (rc) return rc;
+  if (e->dp_raw) return fail(MJH_EINVAL, "the last batch was decoded with raw_planes: it has sample planes (mjh_get_plane), no pixels");
   if (i < 0 || i >= e->dp_n) return fail(MJH_EINVAL, "image %d of a batch of %d", i, e->dp_n);
   const size_t row_bytes = (size_t)e->dp.W * (size_t)e->dp.px_size;
   if (row_pitch < row_bytes) return fail(MJH_EINVAL, "row_pitch %zu is smaller than a row (%zu bytes)", row_pitch, row_bytes);
@@ -3334,9 +3379,39 @@ extern "C" int mjh_get_pixels_device(mjh_encoder *e, void **d_base, size_t *row_
 {
   if (!e) return fail(MJH_EINVAL, "null encoder");
   if (!e->dp_queued) return fail(MJH_EINVAL, "the last batch was not decoded through mjh_decode_host");
+  if (e->dp_raw) return fail(MJH_EINVAL, "the last batch was decoded with raw_planes: it has sample planes (mjh_get_planes_device), no pixels");
   if (d_base) *d_base = e->d_pixout;
   if (row_pitch) *row_pitch = (size_t)e->dp.row_pitch;
   if (image_stride) *image_stride = (size_t)e->dp.image_stride;
+  return MJH_OK;
+}
+
+extern "C" int mjh_get_plane(mjh_encoder *e, int i, int comp, void *dst, size_t row_pitch, int width, int height)
+{
+  if (!e || !dst) return fail(MJH_EINVAL, "bad arguments");
+  if (e->dp_queued && !e->dp_raw) return fail(MJH_EINVAL, "the last batch was not decoded with raw_planes");
+  int rc = wait_pixels(e);
+  if (rc) return rc;
+  if (i < 0 || i >= e->dp_n) return fail(MJH_EINVAL, "image %d of a batch of %d", i, e->dp_n);
+  if (comp < 0 || comp >= e->rp_ncomp) return fail(MJH_EINVAL, "component %d of %d", comp, e->rp_ncomp);
+  if (width < 1 || height < 1 || width > e->rp_w[comp] || height > e->rp_h[comp])
+    return fail(MJH_EINVAL, "%d x %d samples of component %d, whose plane holds %d x %d", width, height, comp, e->rp_w[comp], e->rp_h[comp]);
+  if (row_pitch < (size_t)width) return fail(MJH_EINVAL, "row_pitch %zu is smaller than a row (%d bytes)", row_pitch, width);
+  HIPCHK(hipMemcpy2D(dst, row_pitch, e->d_planes + (size_t)i * (size_t)e->C.planes_per_image + (size_t)e->C.c[comp].plane_off, (size_t)e->rp_pitch[comp],
+                     (size_t)width, (size_t)height, hipMemcpyDeviceToHost));
+  return MJH_OK;
+}
+
+extern "C" int mjh_get_planes_device(mjh_encoder *e, int comp, void **d_base, size_t *row_pitch, size_t *image_stride, int *width, int *height)
+{
+  if (!e) return fail(MJH_EINVAL, "null encoder");
+  if (!e->dp_queued || !e->dp_raw) return fail(MJH_EINVAL, "the last batch was not decoded with raw_planes");
+  if (comp < 0 || comp >= e->rp_ncomp) return fail(MJH_EINVAL, "component %d of %d", comp, e->rp_ncomp);
+  if (d_base) *d_base = e->d_planes + (size_t)e->C.c[comp].plane_off;
+  if (row_pitch) *row_pitch = (size_t)e->rp_pitch[comp];
+  if (image_stride) *image_stride = (size_t)e->C.planes_per_image;
+  if (width) *width = e->rp_w[comp];
+  if (height) *height = e->rp_h[comp];
   return MJH_OK;
 }
 

@@ -6,6 +6,7 @@
 
 // the multipliers of the inverse transform: quantval of every component's table, natural order, as 32-bit words (the reference
 // built without SIMD keeps them as int: MULTIPLIER, jmorecfg.h:367-372; wave-uniform reads become scalar loads)
+// For k_idct_ifast the same struct holds the AA&N multipliers of jddctmgr.c:284-316 instead (mjh_decode_host makes both).
 struct MjhIdctQ { int q[MJH_MAXC][64]; };
 
 // how one component reaches full size (jinit_upsampler jdsample.c:444-525)
@@ -33,6 +34,7 @@ struct MjhPixOut {
   int ncomp;                 // components the conversion reads (1 or 3)
   int px_size;               // bytes per output pixel: 1, 3 or 4
   int off_r, off_g, off_b;   // byte of every colour inside a pixel; the fourth byte of a 4-byte pixel is 0xFF
+  int bottom_up;             // image row y is stored at output row H - 1 - y (0: at row y)
   long long row_pitch, image_stride;      // of the output, bytes; rows hold whole groups of 4 pixels
   long long planes_per_image;
   MjhUpComp c[3];
@@ -41,6 +43,9 @@ struct MjhPixOut {
 // K-I1: coefficient planes (what k_dec_store / k_dec_dc leave) -> 8-bit sample planes, real blocks only; comps: the first
 // `comps` components.  status != 0: that image is skipped.
 void mjh_launch_idct(const MjhConst &C, const MjhIdctQ &Q, int comps, const int16_t *coef_q, uint8_t *planes, const unsigned *status, int n, hipStream_t s);
+// K-I1 with the fast integer method (jpeg_idct_ifast, djpeg -dct fast): the same launch, Q holding the AA&N multipliers
+// DESCALE(quantval * aanscales, 12) with rounding.  Only components at DCT_scaled_size 8 have such a method.
+void mjh_launch_idct_ifast(const MjhConst &C, const MjhIdctQ &Q, int comps, const int16_t *coef_q, uint8_t *planes, const unsigned *status, int n, hipStream_t s);
 // K-I1 at a reduced size (djpeg -scale): component ci alone at DCT_scaled_size N of 1, 2 or 4 (jpeg_idct_1x1 / 2x2 / 4x4 of
 // jidctred.c), its N x N samples per block into a plane at the component's plane_off whose rows are `pitch` samples apart (a
 // multiple of 4, at least wib * N; never more than the full-size plane holds).  Components left at size 8: mjh_launch_idct.

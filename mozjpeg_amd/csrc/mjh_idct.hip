@@ -12,9 +12,12 @@
 //   leave as eight 8-byte vector stores, one per sample row: the lanes of a wave hold horizontally adjacent blocks, so every
 //   store instruction writes one contiguous 512-byte run of a sample row.  The rows wait in registers; a pass through LDS would
 //   add a write and a read per sample and change nothing about the shape of the stores.
+// K-I1f k_idct_ifast: the same grid, loads and stores with the arithmetic of jpeg_idct_ifast (jidctfst.c), for djpeg -dct fast
+//   and TurboJPEG's FASTDCT; see the kernel.
 // K-I1s k_idct_scaled<N>: the same at DCT_scaled_size N = 1, 2, 4 (jidctred.c), one component per launch, for djpeg -scale.
 //   Fewer coefficient planes read, N x N samples per block written; see the kernel.  Components a scaled decode leaves at
-//   size 8 (and every component of an unscaled call) go through k_idct.
+//   size 8 (and every component of an unscaled call) go through k_idct, or k_idct_ifast when the call asks for the fast method
+//   (jddctmgr.c start_pass consults dct_method at size 8 only).
 // K-I2 k_upcolor: one lane per 4 output pixels of a row.  Per component the upsampler jinit_upsampler picks (jdsample.c:444-525),
 //   evaluated per output sample from the samples it reads, then the colour conversion of jdcolor.c / jdcolext.c, then one 4-byte,
 //   three 4-byte (12 contiguous bytes) or one 16-byte store (rows of the output hold whole groups of 4 pixels).
@@ -107,6 +110,78 @@ k_idct(MjhConst C, MjhIdctQ Q, const int16_t *__restrict__ coef_q, uint8_t *__re
     unsigned s[8];
 #pragma unroll
     for (int c = 0; c < 8; c++) s[c] = idct_range_limit((int)((o[c] + (1 << 17)) >> 18));
+    uint2 v;
+    v.x = s[0] | (s[1] << 8) | (s[2] << 16) | (s[3] << 24);
+    v.y = s[4] | (s[5] << 8) | (s[6] << 16) | (s[7] << 24);
+    *reinterpret_cast<uint2 *>(out + (size_t)r * cc.pw) = v;
+  }
+}
+
+// ---- K-I1 with the fast integer method (djpeg -dct fast, JDCT_IFAST): jpeg_idct_ifast jidctfst.c:170-368 --------------------------
+// As the reference built for 8-bit samples without SIMD has it: DCTELEM and the multipliers are int, CONST_BITS 8, PASS1_BITS 2.
+// MULTIPLY is a 64-bit product (its constant is a JLONG) shifted right by 8 WITHOUT rounding and cast back to int; every sum
+// and the dequantizing product are int.  Where those overflow (absurd quantization tables only: real files stay far inside)
+// the reference's behaviour is undefined; here they wrap in two's complement -- the sums are unsigned arithmetic.
+__device__ __forceinline__ unsigned ifast_mul(unsigned v, int c) { return (unsigned)(int)(((long long)(int)v * c) >> 8); }
+
+// the 1-D transform of both passes: eight inputs -> the eight sums in front of the final shift (pass 1 has none)
+__device__ __forceinline__ void idct8_ifast(const unsigned (&x)[8], unsigned (&o)[8])
+{
+  unsigned tmp10 = x[0] + x[4], tmp11 = x[0] - x[4];
+  const unsigned tmp13 = x[2] + x[6];
+  unsigned tmp12 = ifast_mul(x[2] - x[6], 362) - tmp13;          // FIX_1_414213562
+  const unsigned tmp0 = tmp10 + tmp13, tmp3 = tmp10 - tmp13, tmp1 = tmp11 + tmp12, tmp2 = tmp11 - tmp12;
+  const unsigned z13 = x[5] + x[3], z10 = x[5] - x[3], z11 = x[1] + x[7], z12 = x[1] - x[7];
+  const unsigned tmp7 = z11 + z13;
+  tmp11 = ifast_mul(z11 - z13, 362);
+  const unsigned z5 = ifast_mul(z10 + z12, 473);                 // FIX_1_847759065
+  tmp10 = ifast_mul(z12, 277) - z5;                              // FIX_1_082392200
+  tmp12 = ifast_mul(z10, -669) + z5;                             // -FIX_2_613125930
+  const unsigned tmp6 = tmp12 - tmp7, tmp5 = tmp11 - tmp6, tmp4 = tmp10 + tmp5;
+  o[0] = tmp0 + tmp7; o[7] = tmp0 - tmp7;
+  o[1] = tmp1 + tmp6; o[6] = tmp1 - tmp6;
+  o[2] = tmp2 + tmp5; o[5] = tmp2 - tmp5;
+  o[4] = tmp3 + tmp4; o[3] = tmp3 - tmp4;
+}
+
+// One lane per real block: the grid, the loads and the eight 8-byte row stores of k_idct.  Q holds the AA&N multipliers the
+// host made (mjh_idct.h), not quantval.  The reference's zero-AC shortcuts are no branches here: a column whose AC terms are
+// zero leaves MULTIPLY(0, c) = 0 everywhere, so every output of the general path is the dequantized DC, which is what the
+// shortcut stores (jidctfst.c:205-228); a workspace row with zero AC terms gives IDESCALE(ws[0], 5) eight times on either
+// path (:284-304).
+__global__ void __launch_bounds__(256)
+k_idct_ifast(MjhConst C, MjhIdctQ Q, const int16_t *__restrict__ coef_q, uint8_t *__restrict__ planes, const unsigned *__restrict__ status)
+{
+  const int img = blockIdx.z, ci = blockIdx.y;
+  const MjhComp &cc = C.c[ci];
+  const int b = (int)(blockIdx.x * 256u + threadIdx.x);
+  if (b >= cc.nblk) return;
+  if (status[img] != 0u) return;
+  const int16_t *in = coef_q + (size_t)img * C.coefs_per_image + cc.coef_off + b;
+  const int *q = Q.q[ci];
+  unsigned ws[64];
+  // pass 1: columns; the multipliers carry the 2^PASS1_BITS the workspace is scaled up by
+#pragma unroll
+  for (int c = 0; c < 8; c++) {
+    unsigned x[8], o[8];
+#pragma unroll
+    for (int r = 0; r < 8; r++) x[r] = (unsigned)(int)in[(size_t)kZigOfNat[r * 8 + c] * cc.kstride] * (unsigned)q[r * 8 + c];
+    idct8_ifast(x, o);
+#pragma unroll
+    for (int r = 0; r < 8; r++) ws[r * 8 + c] = o[r];
+  }
+  // pass 2: rows; a plain shift by PASS1_BITS + 3, then the range limit with the sample's centre added
+  const int by = b / cc.wib, bx = b - by * cc.wib;
+  uint8_t *out = planes + (size_t)img * C.planes_per_image + cc.plane_off + (size_t)(by * 8) * cc.pw + (size_t)bx * 8;
+#pragma unroll
+  for (int r = 0; r < 8; r++) {
+    unsigned x[8], o[8];
+#pragma unroll
+    for (int c = 0; c < 8; c++) x[c] = ws[r * 8 + c];
+    idct8_ifast(x, o);
+    unsigned s[8];
+#pragma unroll
+    for (int c = 0; c < 8; c++) s[c] = idct_range_limit((int)o[c] >> 5);
     uint2 v;
     v.x = s[0] | (s[1] << 8) | (s[2] << 16) | (s[3] << 24);
     v.y = s[4] | (s[5] << 8) | (s[6] << 16) | (s[7] << 24);
@@ -247,6 +322,7 @@ k_upcolor(MjhPixOut P, const uint8_t *__restrict__ planes, uint8_t *__restrict__
   if (x0 >= P.W) return;
   if (status[img] != 0u) return;
   const uint8_t *pl = planes + (size_t)img * P.planes_per_image;
+  const int yo = P.bottom_up ? P.H - 1 - y : y;          // the output row image row y goes to
   unsigned px[4][3];
 #pragma unroll
   for (int i = 0; i < 4; i++) {
@@ -266,7 +342,7 @@ k_upcolor(MjhPixOut P, const uint8_t *__restrict__ planes, uint8_t *__restrict__
     }
     px[i][0] = (unsigned)r; px[i][1] = (unsigned)g; px[i][2] = (unsigned)b;
   }
-  uint8_t *out = pixels + (size_t)img * P.image_stride + (size_t)y * P.row_pitch + (size_t)x0 * P.px_size;
+  uint8_t *out = pixels + (size_t)img * P.image_stride + (size_t)yo * P.row_pitch + (size_t)x0 * P.px_size;
   if (P.px_size == 1) {
     *reinterpret_cast<unsigned *>(out) = px[0][0] | (px[1][0] << 8) | (px[2][0] << 16) | (px[3][0] << 24);
   } else if (P.px_size == 4) {
@@ -296,6 +372,13 @@ void mjh_launch_idct(const MjhConst &C, const MjhIdctQ &Q, int comps, const int1
   int nblk = 1;
   for (int c = 0; c < comps; c++) if (C.c[c].nblk > nblk) nblk = C.c[c].nblk;
   hipLaunchKernelGGL(k_idct, dim3((nblk + 255) / 256, comps, n), dim3(256), 0, s, C, Q, coef_q, planes, status);
+}
+
+void mjh_launch_idct_ifast(const MjhConst &C, const MjhIdctQ &Q, int comps, const int16_t *coef_q, uint8_t *planes, const unsigned *status, int n, hipStream_t s)
+{
+  int nblk = 1;
+  for (int c = 0; c < comps; c++) if (C.c[c].nblk > nblk) nblk = C.c[c].nblk;
+  hipLaunchKernelGGL(k_idct_ifast, dim3((nblk + 255) / 256, comps, n), dim3(256), 0, s, C, Q, coef_q, planes, status);
 }
 
 void mjh_launch_upcolor(const MjhPixOut &P, const uint8_t *planes, uint8_t *pixels, const unsigned *status, int n, hipStream_t s)

@@ -4,8 +4,14 @@
  * A stock libturbojpeg carries a PRIVATE libjpeg (CMakeLists.txt:684-707), so the libjpeg drop-in cannot get in front of
  * it; this library interposes the TurboJPEG compress entry points themselves (turbojpeg.c:1169 tjCompress2,
  * turbojpeg-mp.c:69 tj3Compress8, turbojpeg.c:1222 tj3CompressFromYUVPlanes8 and their legacy wrappers).  Placed in front
- * of a libturbojpeg (LD_PRELOAD / link order) it serves compress handles on the GPU and forwards every handle it did not
- * create (decompress / transform instances) to the library behind it; used alone it is a compress-only TurboJPEG.
+ * of a libturbojpeg (LD_PRELOAD / link order) it serves compress and decompress handles on the GPU and forwards every handle
+ * it did not create (transform instances) to the library behind it; used alone it is a TurboJPEG without tj3Transform and
+ * tj3DecodeYUV*.
+ *
+ * Decompress instances (tj3Init(TJINIT_DECOMPRESS), tjInitDecompress) are this library's by default: headers through
+ * mjh_jpeg_probe, packed pixels through mjh_decode_host / mjh_get_pixels, planar YUV through mjh_decode_opts.raw_planes /
+ * mjh_get_plane (see the second half of this file).  With MOZJPEG_HIP_TJ_DECOMPRESS=0 in the environment they are forwarded
+ * to the library behind, as before this library had a decoder (NULL when there is none).
  *
  * What TurboJPEG asks of the codec (setCompDefaults turbojpeg.c:316-390): the JCP_FASTEST profile (turbojpeg.c:336) --
  * Annex K tables scaled by jpeg_set_quality(q, TRUE), standard Huffman tables unless TJPARAM_OPTIMIZE / progressive /
@@ -36,6 +42,9 @@ typedef struct tjs {
   int quality, subsamp, bottom_up, no_realloc, fast_dct, optimize, progressive, arithmetic, lossless, lossless_psv, lossless_pt, colorspace;
   int restart_blocks, restart_rows, xdensity, ydensity, density_units, stop_on_warning, precision;
   int jpeg_width, jpeg_height;
+  /* decompress instances: TJPARAM_FASTUPSAMPLE / SCANLIMIT / MAXMEMORY / MAXPIXELS and tj3SetScalingFactor */
+  int decompress, fast_upsample, scan_limit, max_memory, max_pixels;
+  tjscalingfactor sf;
   /* one cached encoder (a handle is used by one thread at a time, like a tjinstance) */
   mjh_encoder *enc;
   mjh_params enc_params;
@@ -69,6 +78,14 @@ static void defaults(tjs *t)
   t->lossless_psv = 1; t->lossless_pt = 0;   /* turbojpeg.c:560 */
   t->xdensity = 1; t->ydensity = 1; t->density_units = 0;
   t->jpeg_width = t->jpeg_height = -1;
+  t->sf.num = t->sf.denom = 1;
+}
+
+/* MOZJPEG_HIP_TJ_DECOMPRESS=0: decompress instances belong to the library behind this one */
+static int serve_decompress(void)
+{
+  const char *v = getenv("MOZJPEG_HIP_TJ_DECOMPRESS");
+  return !(v && v[0] == '0' && v[1] == 0);
 }
 
 static int pick_device(void)
@@ -84,21 +101,24 @@ static int pick_device(void)
 DLLEXPORT tjhandle tj3Init(int initType)
 {
   tjs *t;
-  if (initType != TJINIT_COMPRESS) {
+  if (initType != TJINIT_COMPRESS && !(initType == TJINIT_DECOMPRESS && serve_decompress())) {
     tjhandle (*f)(int) = (tjhandle (*)(int))next_sym("tj3Init");
     if (f) return f(initType);
-    snprintf(g_err, sizeof(g_err), "tj3Init(): this library serves compress instances only");
+    snprintf(g_err, sizeof(g_err), initType == TJINIT_DECOMPRESS ? "tj3Init(): MOZJPEG_HIP_TJ_DECOMPRESS=0 and no library behind this one"
+                                                                 : "tj3Init(): this library serves compress and decompress instances only");
     return NULL;
   }
   t = (tjs *)calloc(1, sizeof(*t));
   if (!t) { snprintf(g_err, sizeof(g_err), "tj3Init(): Memory allocation failure"); return NULL; }
   t->magic = TJS_MAGIC; t->self = t;
   defaults(t);
+  t->decompress = initType == TJINIT_DECOMPRESS;
   t->device = pick_device();
   snprintf(t->err, sizeof(t->err), "No error");
   return (tjhandle)t;
 }
 DLLEXPORT tjhandle tjInitCompress(void) { return tj3Init(TJINIT_COMPRESS); }
+DLLEXPORT tjhandle tjInitDecompress(void) { return tj3Init(TJINIT_DECOMPRESS); }
 
 DLLEXPORT void tj3Destroy(tjhandle handle)
 {
@@ -204,6 +224,25 @@ DLLEXPORT int tj3Set(tjhandle handle, int param, int value)
   tjs *t = ours(handle);
   if (!t) { int (*f)(tjhandle, int, int) = (int (*)(tjhandle, int, int))next_sym("tj3Set"); return f && handle ? f(handle, param, value) : fail(NULL, "tj3Set", "Invalid handle"); }
 #define RANGE(lo, hi) do { if (value < (lo) || value > (hi)) return fail(t, "tj3Set", "Parameter value out of range"); } while (0)
+  if (t->decompress) {   /* the same switch for an instance without COMPRESS (turbojpeg.c:686-790) */
+    switch (param) {
+    case TJPARAM_STOPONWARNING: RANGE(0, 1); t->stop_on_warning = value; return 0;
+    case TJPARAM_BOTTOMUP: RANGE(0, 1); t->bottom_up = value; return 0;
+    case TJPARAM_SUBSAMP: RANGE(0, TJ_NUMSAMP - 1); t->subsamp = value; return 0;
+    case TJPARAM_FASTUPSAMPLE: RANGE(0, 1); t->fast_upsample = value; return 0;
+    case TJPARAM_FASTDCT: RANGE(0, 1); t->fast_dct = value; return 0;
+    case TJPARAM_SCANLIMIT: RANGE(0, INT_MAX); t->scan_limit = value; return 0;
+    case TJPARAM_MAXMEMORY: RANGE(0, INT_MAX); t->max_memory = value; return 0;
+    case TJPARAM_MAXPIXELS: RANGE(0, INT_MAX); t->max_pixels = value; return 0;
+    case TJPARAM_NOREALLOC: case TJPARAM_QUALITY: case TJPARAM_OPTIMIZE: case TJPARAM_RESTARTBLOCKS: case TJPARAM_RESTARTROWS:
+      return fail(t, "tj3Set", "Parameter is not applicable to decompression instances");
+    case TJPARAM_JPEGWIDTH: case TJPARAM_JPEGHEIGHT: case TJPARAM_PRECISION: case TJPARAM_COLORSPACE: case TJPARAM_PROGRESSIVE:
+    case TJPARAM_ARITHMETIC: case TJPARAM_LOSSLESS: case TJPARAM_LOSSLESSPSV: case TJPARAM_LOSSLESSPT: case TJPARAM_XDENSITY:
+    case TJPARAM_YDENSITY: case TJPARAM_DENSITYUNITS:
+      return fail(t, "tj3Set", "Parameter is read-only in decompression instances");
+    default: return fail(t, "tj3Set", "Invalid parameter");
+    }
+  }
   switch (param) {
   case TJPARAM_STOPONWARNING: RANGE(0, 1); t->stop_on_warning = value; break;
   case TJPARAM_BOTTOMUP: RANGE(0, 1); t->bottom_up = value; break;
@@ -261,6 +300,13 @@ DLLEXPORT int tj3Get(tjhandle handle, int param)
   case TJPARAM_YDENSITY: return t->ydensity;
   case TJPARAM_DENSITYUNITS: return t->density_units;
   }
+  if (t->decompress)
+    switch (param) {
+    case TJPARAM_FASTUPSAMPLE: return t->fast_upsample;
+    case TJPARAM_SCANLIMIT: return t->scan_limit;
+    case TJPARAM_MAXMEMORY: return t->max_memory;
+    case TJPARAM_MAXPIXELS: return t->max_pixels;
+    }
   return -1;
 }
 
@@ -374,6 +420,7 @@ static int compress_pixels(tjs *t, const char *fn, const void *srcBuf, int width
   int y;
   if (srcBuf == NULL || width <= 0 || pitch < 0 || height <= 0 || pixelFormat < 0 || pixelFormat >= TJ_NUMPF || jpegBuf == NULL || jpegSize == NULL)
     return fail(t, fn, "Invalid argument");
+  if (t->decompress) return fail(t, fn, "Instance has not been initialized for compression");
   if (!t->lossless && t->quality == -1) return fail(t, fn, "TJPARAM_QUALITY must be specified");       /* turbojpeg-mp.c:89-92 */
   if (!t->lossless && t->subsamp == TJSAMP_UNKNOWN) return fail(t, fn, "TJPARAM_SUBSAMP must be specified");
   if (build_params(t, fn, width, height, pixelFormat, precision, &p) || get_encoder(t, fn, &p)) return -1;
@@ -477,6 +524,7 @@ static int compress_planes(tjs *t, const char *fn, const unsigned char *const *s
   size_t pitch[MJH_MAX_COMPS] = { 0, 0, 0, 0 };
   int pw[MJH_MAX_COMPS] = { 0, 0, 0, 0 }, ph[MJH_MAX_COMPS] = { 0, 0, 0, 0 }, nc, i;
   if (!srcPlanes || !srcPlanes[0] || width <= 0 || height <= 0 || jpegBuf == NULL || jpegSize == NULL) return fail(t, fn, "Invalid argument");
+  if (t->decompress) return fail(t, fn, "Instance has not been initialized for compression");
   if (t->quality == -1) return fail(t, fn, "TJPARAM_QUALITY must be specified");
   if (t->subsamp == TJSAMP_UNKNOWN) return fail(t, fn, "TJPARAM_SUBSAMP must be specified");
   if (t->subsamp != TJSAMP_GRAY && (!srcPlanes[1] || !srcPlanes[2])) return fail(t, fn, "Invalid argument");
@@ -576,4 +624,337 @@ DLLEXPORT int tjCompressFromYUV(tjhandle handle, const unsigned char *srcBuf, in
   rc = compress_planes(t, "tjCompressFromYUV", planes, width, strides, height, jpegBuf, &size);
   *jpegSize = (unsigned long)size;
   return rc;
+}
+
+
+/* ==== decompress instances ==========================================================================================================
+ * The rule of the compress half holds: the reference's bytes or an error, never a CPU fallback and never a different picture.
+ * - A file mjh_jpeg_probe refuses (progressive, arithmetic, 12-bit, lossless, four components, DNL) fails at the header or the
+ *   decompress call with the probe's text.
+ * - All 16 scaling factors of the reference are accepted and chosen (tjDecompress2) as there; a decompress call at a factor other
+ *   than 1/1, 1/2, 1/4, 1/8 fails with a text naming the factor.
+ * - Damaged entropy-coded data is a FATAL error and the destination is left untouched (the reference: a warning and a partial
+ *   image).  Cropping regions other than TJUNCROPPED, TJPF_CMYK and 12- / 16-bit output are refused.
+ * A handle keeps one mjh_encoder made from mjh_params_from_jpeg (the 'revert' profile, one file per call) and remakes it when
+ * a file's parameters differ, as the compress half does. */
+#define NUMSF 16
+static const tjscalingfactor kSf[NUMSF] = { { 2, 1 }, { 15, 8 }, { 7, 4 }, { 13, 8 }, { 3, 2 }, { 11, 8 }, { 5, 4 }, { 9, 8 }, { 1, 1 }, { 7, 8 },
+                                            { 3, 4 }, { 5, 8 }, { 1, 2 }, { 3, 8 }, { 1, 4 }, { 1, 8 } };
+
+DLLEXPORT tjscalingfactor *tj3GetScalingFactors(int *numScalingFactors)
+{
+  if (numScalingFactors == NULL) { snprintf(g_err, sizeof(g_err), "tj3GetScalingFactors(): Invalid argument"); return NULL; }
+  *numScalingFactors = NUMSF;
+  return (tjscalingfactor *)kSf;
+}
+DLLEXPORT tjscalingfactor *tjGetScalingFactors(int *numScalingFactors) { return tj3GetScalingFactors(numScalingFactors); }
+
+/* our decompress handle, or NULL with *fwd = the library behind's entry point (NULL and an error left when there is none) */
+static tjs *dinstance(tjhandle handle, const char *fn, void **fwd)
+{
+  tjs *t = ours(handle);
+  *fwd = NULL;
+  if (!t) {
+    if (handle) *fwd = next_sym(fn);
+    if (!*fwd) fail(NULL, fn, "Invalid handle");
+    return NULL;
+  }
+  if (!t->decompress) { fail(t, fn, "Instance has not been initialized for decompression"); return NULL; }
+  return t;
+}
+
+DLLEXPORT int tj3SetScalingFactor(tjhandle handle, tjscalingfactor scalingFactor)
+{
+  void *f;
+  tjs *t = dinstance(handle, "tj3SetScalingFactor", &f);
+  int i;
+  if (!t) return f ? ((int (*)(tjhandle, tjscalingfactor))f)(handle, scalingFactor) : -1;
+  for (i = 0; i < NUMSF; i++) if (scalingFactor.num == kSf[i].num && scalingFactor.denom == kSf[i].denom) break;
+  if (i >= NUMSF) return fail(t, "tj3SetScalingFactor", "Unsupported scaling factor");
+  t->sf = scalingFactor;
+  return 0;
+}
+
+DLLEXPORT int tj3SetCroppingRegion(tjhandle handle, tjregion croppingRegion)
+{
+  void *f;
+  tjs *t = dinstance(handle, "tj3SetCroppingRegion", &f);
+  if (!t) return f ? ((int (*)(tjhandle, tjregion))f)(handle, croppingRegion) : -1;
+  if (croppingRegion.x == 0 && croppingRegion.y == 0 && croppingRegion.w == 0 && croppingRegion.h == 0) return 0;
+  return fail(t, "tj3SetCroppingRegion", "partial decompression (a cropping region other than TJUNCROPPED) is not built on the GPU path");
+}
+
+/* getSubsamp turbojpeg.c:400-478 for the files that get this far (one or three components) */
+static int subsamp_of(const mjh_jpeg_info *in)
+{
+  int i, k;
+  const int *h = in->h_samp_factor, *v = in->v_samp_factor;
+  if (in->num_components == 1 && in->jpeg_color_space == MJH_CS_GRAYSCALE) return TJSAMP_GRAY;
+  if (in->num_components != 3) return TJSAMP_UNKNOWN;
+  for (i = 0; i < TJ_NUMSAMP; i++) {
+    int match;
+    if (i == TJSAMP_GRAY) continue;
+    if (h[0] == kMcuW[i] / 8 && v[0] == kMcuH[i] / 8) {               /* the standard way: luma carries the factors, chroma 1x1 */
+      for (match = 0, k = 1; k < 3; k++) if (h[k] == 1 && v[k] == 1) match++;
+      if (match == 2) return i;
+    }
+    if (h[0] == 2 && v[0] == 2 && (i == TJSAMP_422 || i == TJSAMP_440)) {       /* 4:2:2 and 4:4:0 under a 2x2 luma */
+      for (match = 0, k = 1; k < 3; k++) if (h[k] == kMcuH[i] / 8 && v[k] == kMcuW[i] / 8) match++;
+      if (match == 2) return i;
+    }
+    if (h[0] * v[0] <= 10 / 3 && i == TJSAMP_444) {                   /* 4:4:4 with equal factors above 1 (D_MAX_BLOCKS_IN_MCU / 3) */
+      for (match = 0, k = 1; k < 3; k++) if (h[k] == h[0] && v[k] == v[0]) match++;
+      if (match == 2) return i;
+    }
+  }
+  return TJSAMP_UNKNOWN;
+}
+
+/* jpeg_read_header + setDecompParameters (turbojpeg.c:482-504) */
+static int read_header(tjs *t, const char *fn, const unsigned char *jpegBuf, size_t jpegSize, mjh_jpeg_info *in)
+{
+  if (mjh_jpeg_probe(jpegBuf, jpegSize, in) != MJH_OK) return fail(t, fn, mjh_last_error());
+  t->subsamp = subsamp_of(in);
+  t->jpeg_width = in->image_width; t->jpeg_height = in->image_height;
+  t->precision = in->data_precision;
+  t->colorspace = in->jpeg_color_space == MJH_CS_GRAYSCALE ? TJCS_GRAY : in->jpeg_color_space == MJH_CS_RGB ? TJCS_RGB : in->jpeg_color_space == MJH_CS_YCbCr ? TJCS_YCbCr : -1;
+  t->progressive = t->arithmetic = t->lossless = 0;          /* (such files do not get this far) */
+  t->lossless_psv = 0; t->lossless_pt = 0;                   /* Ss and Al of a sequential scan */
+  if (in->saw_JFIF_marker) { t->xdensity = in->X_density; t->ydensity = in->Y_density; t->density_units = in->density_unit; }
+  else { t->xdensity = t->ydensity = 1; t->density_units = 0; }        /* (what the marker reader starts from, jdmarker.c) */
+  return 0;
+}
+
+DLLEXPORT int tj3DecompressHeader(tjhandle handle, const unsigned char *jpegBuf, size_t jpegSize)
+{
+  void *f;
+  mjh_jpeg_info in;
+  tjs *t = dinstance(handle, "tj3DecompressHeader", &f);
+  if (!t) return f ? ((int (*)(tjhandle, const unsigned char *, size_t))f)(handle, jpegBuf, jpegSize) : -1;
+  if (jpegBuf == NULL || jpegSize <= 0) return fail(t, "tj3DecompressHeader", "Invalid argument");
+  if (read_header(t, "tj3DecompressHeader", jpegBuf, jpegSize, &in)) return -1;
+  if (t->colorspace < 0) return fail(t, "tj3DecompressHeader", "Could not determine colorspace of JPEG image");
+  if (t->jpeg_width < 1 || t->jpeg_height < 1) return fail(t, "tj3DecompressHeader", "Invalid data returned in header");
+  return 0;
+}
+
+DLLEXPORT int tjDecompressHeader3(tjhandle handle, const unsigned char *jpegBuf, unsigned long jpegSize, int *width, int *height, int *jpegSubsamp, int *jpegColorspace)
+{
+  void *f;
+  int rc;
+  tjs *t = dinstance(handle, "tjDecompressHeader3", &f);
+  if (!t) return f ? ((int (*)(tjhandle, const unsigned char *, unsigned long, int *, int *, int *, int *))f)(handle, jpegBuf, jpegSize, width, height, jpegSubsamp, jpegColorspace) : -1;
+  if (width == NULL || height == NULL || jpegSubsamp == NULL || jpegColorspace == NULL) return fail(t, "tjDecompressHeader3", "Invalid argument");
+  rc = tj3DecompressHeader(handle, jpegBuf, (size_t)jpegSize);
+  *width = t->jpeg_width; *height = t->jpeg_height; *jpegSubsamp = t->subsamp; *jpegColorspace = t->colorspace;
+  if (*jpegSubsamp == TJSAMP_UNKNOWN) return fail(t, "tjDecompressHeader3", "Could not determine subsampling level of JPEG image");
+  return rc;
+}
+DLLEXPORT int tjDecompressHeader2(tjhandle handle, unsigned char *jpegBuf, unsigned long jpegSize, int *width, int *height, int *jpegSubsamp)
+{
+  int cs;
+  return tjDecompressHeader3(handle, jpegBuf, jpegSize, width, height, jpegSubsamp, &cs);
+}
+DLLEXPORT int tjDecompressHeader(tjhandle handle, unsigned char *jpegBuf, unsigned long jpegSize, int *width, int *height)
+{
+  int ss;
+  return tjDecompressHeader2(handle, jpegBuf, jpegSize, width, height, &ss);
+}
+
+/* the header, the limits, the encoder for this file and the options every decode call shares; *W, *H: the scaled size */
+static int decode_setup(tjs *t, const char *fn, const unsigned char *jpegBuf, size_t jpegSize, mjh_jpeg_info *in, mjh_decode_opts *o, int *W, int *H)
+{
+  mjh_params p;
+  char msg[160];
+  if (read_header(t, fn, jpegBuf, jpegSize, in)) return -1;
+  if (t->max_pixels && (unsigned long long)t->jpeg_width * (unsigned long long)t->jpeg_height > (unsigned long long)t->max_pixels) return fail(t, fn, "Image is too large");
+  if (!(t->sf.num == 1 && (t->sf.denom == 1 || t->sf.denom == 2 || t->sf.denom == 4 || t->sf.denom == 8))) {
+    snprintf(msg, sizeof(msg), "scaling factor %d/%d is not built on the GPU path (1/1, 1/2, 1/4 and 1/8 are; no CPU fallback)", t->sf.num, t->sf.denom);
+    return fail(t, fn, msg);
+  }
+  if (mjh_params_from_jpeg(in, MJH_PROFILE_FASTEST, &p) != MJH_OK) return fail(t, fn, mjh_last_error());
+  if (get_encoder(t, fn, &p)) return -1;
+  mjh_decode_opts_defaults(o);
+  o->scale_num = t->sf.num; o->scale_denom = t->sf.denom;
+  o->fancy_upsampling = !t->fast_upsample;
+  o->dct_method = t->fast_dct ? 1 : 0;                       /* JDCT_FASTEST = JDCT_IFAST / JDCT_ISLOW, turbojpeg-mp.c:191 */
+  *W = TJSCALED(t->jpeg_width, t->sf); *H = TJSCALED(t->jpeg_height, t->sf);
+  return 0;
+}
+
+static int decompress_pixels(tjs *t, const char *fn, const unsigned char *jpegBuf, size_t jpegSize, unsigned char *dstBuf, int pitch, int pixelFormat)
+{ /* tj3Decompress8 turbojpeg-mp.c:141-280 */
+  mjh_jpeg_info in;
+  mjh_decode_opts o;
+  const void *files[1];
+  int W, H;
+  if (jpegBuf == NULL || jpegSize <= 0 || dstBuf == NULL || pitch < 0 || pixelFormat < 0 || pixelFormat >= TJ_NUMPF) return fail(t, fn, "Invalid argument");
+  if (decode_setup(t, fn, jpegBuf, jpegSize, &in, &o, &W, &H)) return -1;
+  if (pixelFormat == TJPF_CMYK) return fail(t, fn, "CMYK / YCCK are outside the GPU path (no CPU fallback)");
+  if (pixelFormat == TJPF_GRAY) { o.out_color_space = MJH_CS_GRAYSCALE; o.pixel_size = 1; }
+  else {
+    o.out_color_space = MJH_CS_RGB; o.pixel_size = kPixelSize[pixelFormat];
+    o.rgb_offset[0] = kRed[pixelFormat]; o.rgb_offset[1] = kGreen[pixelFormat]; o.rgb_offset[2] = kBlue[pixelFormat];
+  }
+  o.bottom_up = t->bottom_up;
+  files[0] = jpegBuf;
+  if (mjh_decode_host(t->enc, files, &jpegSize, 1, &o) != MJH_OK) return fail(t, fn, mjh_last_error());
+  /* (waits, and fails on damaged data before a byte of dstBuf is written; only the pixels' bytes of every row are written) */
+  if (mjh_get_pixels(t->enc, 0, dstBuf, pitch ? (size_t)pitch : (size_t)W * (size_t)kPixelSize[pixelFormat]) != MJH_OK) return fail(t, fn, mjh_last_error());
+  return 0;
+}
+
+DLLEXPORT int tj3Decompress8(tjhandle handle, const unsigned char *jpegBuf, size_t jpegSize, unsigned char *dstBuf, int pitch, int pixelFormat)
+{
+  void *f;
+  tjs *t = dinstance(handle, "tj3Decompress8", &f);
+  if (!t) return f ? ((int (*)(tjhandle, const unsigned char *, size_t, unsigned char *, int, int))f)(handle, jpegBuf, jpegSize, dstBuf, pitch, pixelFormat) : -1;
+  return decompress_pixels(t, "tj3Decompress8", jpegBuf, jpegSize, dstBuf, pitch, pixelFormat);
+}
+DLLEXPORT int tj3Decompress12(tjhandle handle, const unsigned char *jpegBuf, size_t jpegSize, short *dstBuf, int pitch, int pixelFormat)
+{
+  void *f;
+  tjs *t = dinstance(handle, "tj3Decompress12", &f);
+  if (!t) return f ? ((int (*)(tjhandle, const unsigned char *, size_t, short *, int, int))f)(handle, jpegBuf, jpegSize, dstBuf, pitch, pixelFormat) : -1;
+  return fail(t, "tj3Decompress12", "12-bit files are outside the GPU decoder (no CPU fallback)");
+}
+DLLEXPORT int tj3Decompress16(tjhandle handle, const unsigned char *jpegBuf, size_t jpegSize, unsigned short *dstBuf, int pitch, int pixelFormat)
+{
+  void *f;
+  tjs *t = dinstance(handle, "tj3Decompress16", &f);
+  if (!t) return f ? ((int (*)(tjhandle, const unsigned char *, size_t, unsigned short *, int, int))f)(handle, jpegBuf, jpegSize, dstBuf, pitch, pixelFormat) : -1;
+  return fail(t, "tj3Decompress16", "16-bit (lossless) files are outside the GPU decoder (no CPU fallback)");
+}
+
+static void legacy_dflags(tjs *t, int flags)
+{ /* processFlags turbojpeg.c:507-534, DECOMPRESS */
+  t->bottom_up = !!(flags & TJFLAG_BOTTOMUP);
+  t->fast_upsample = !!(flags & TJFLAG_FASTUPSAMPLE);
+  t->no_realloc = !!(flags & TJFLAG_NOREALLOC);
+  t->fast_dct = !!(flags & TJFLAG_FASTDCT);
+  t->stop_on_warning = !!(flags & TJFLAG_STOPONWARNING);
+  if (flags & TJFLAG_LIMITSCANS) t->scan_limit = 500;
+}
+
+/* the legacy calls' choice of a factor (turbojpeg.c:1994-2001): the first of the 16 whose scaled size fits width x height */
+static int legacy_scale(tjs *t, const char *fn, const unsigned char *jpegBuf, unsigned long jpegSize, int width, int height)
+{
+  mjh_jpeg_info in;
+  int i;
+  if (jpegBuf == NULL || jpegSize <= 0 || width < 0 || height < 0) return fail(t, fn, "Invalid argument");
+  if (read_header(t, fn, jpegBuf, (size_t)jpegSize, &in)) return -1;
+  if (width == 0) width = t->jpeg_width;
+  if (height == 0) height = t->jpeg_height;
+  for (i = 0; i < NUMSF; i++) if (TJSCALED(t->jpeg_width, kSf[i]) <= width && TJSCALED(t->jpeg_height, kSf[i]) <= height) break;
+  if (i >= NUMSF) return fail(t, fn, "Could not scale down to desired image dimensions");
+  t->sf = kSf[i];
+  return 0;
+}
+
+DLLEXPORT int tjDecompress2(tjhandle handle, const unsigned char *jpegBuf, unsigned long jpegSize, unsigned char *dstBuf, int width, int pitch, int height, int pixelFormat, int flags)
+{
+  void *f;
+  tjs *t = dinstance(handle, "tjDecompress2", &f);
+  if (!t) return f ? ((int (*)(tjhandle, const unsigned char *, unsigned long, unsigned char *, int, int, int, int, int))f)(handle, jpegBuf, jpegSize, dstBuf, width, pitch, height, pixelFormat, flags) : -1;
+  if (legacy_scale(t, "tjDecompress2", jpegBuf, jpegSize, width, height)) return -1;
+  legacy_dflags(t, flags);
+  return decompress_pixels(t, "tjDecompress2", jpegBuf, (size_t)jpegSize, dstBuf, pitch, pixelFormat);
+}
+
+/* ---- planar YUV output (tj3DecompressToYUVPlanes8 turbojpeg.c:2046-2208): jpeg_read_raw_data for whole images ---- */
+static int decompress_planes(tjs *t, const char *fn, const unsigned char *jpegBuf, size_t jpegSize, unsigned char **dstPlanes, int *strides)
+{
+  mjh_jpeg_info in;
+  mjh_decode_opts o;
+  const void *files[1];
+  int W, H, i, nc, pw[3], ph[3];
+  if (jpegBuf == NULL || jpegSize <= 0 || !dstPlanes || !dstPlanes[0]) return fail(t, fn, "Invalid argument");
+  if (decode_setup(t, fn, jpegBuf, jpegSize, &in, &o, &W, &H)) return -1;
+  if (t->subsamp == TJSAMP_UNKNOWN) return fail(t, fn, "Could not determine subsampling level of JPEG image");
+  if (t->subsamp != TJSAMP_GRAY && (!dstPlanes[1] || !dstPlanes[2])) return fail(t, fn, "Invalid argument");
+  nc = t->subsamp == TJSAMP_GRAY ? 1 : 3;
+  for (i = 0; i < nc; i++) {
+    pw[i] = tj3YUVPlaneWidth(i, W, t->subsamp); ph[i] = tj3YUVPlaneHeight(i, H, t->subsamp);
+    if (strides && strides[i] < 0) return fail(t, fn, "negative plane strides are outside the GPU path");
+  }
+  o.raw_planes = 1;
+  files[0] = jpegBuf;
+  if (mjh_decode_host(t->enc, files, &jpegSize, 1, &o) != MJH_OK) return fail(t, fn, mjh_last_error());
+  if (mjh_decode_wait(t->enc) != MJH_OK) return fail(t, fn, mjh_last_error());           /* damaged data: before any plane is written */
+  for (i = 0; i < nc; i++)
+    if (mjh_get_plane(t->enc, 0, i, dstPlanes[i], (size_t)(strides && strides[i] != 0 ? strides[i] : pw[i]), pw[i], ph[i]) != MJH_OK) return fail(t, fn, mjh_last_error());
+  return 0;
+}
+
+DLLEXPORT int tj3DecompressToYUVPlanes8(tjhandle handle, const unsigned char *jpegBuf, size_t jpegSize, unsigned char **dstPlanes, int *strides)
+{
+  void *f;
+  tjs *t = dinstance(handle, "tj3DecompressToYUVPlanes8", &f);
+  if (!t) return f ? ((int (*)(tjhandle, const unsigned char *, size_t, unsigned char **, int *))f)(handle, jpegBuf, jpegSize, dstPlanes, strides) : -1;
+  return decompress_planes(t, "tj3DecompressToYUVPlanes8", jpegBuf, jpegSize, dstPlanes, strides);
+}
+
+static int decompress_yuv(tjs *t, const char *fn, const unsigned char *jpegBuf, size_t jpegSize, unsigned char *dstBuf, int align)
+{ /* tj3DecompressToYUV8 turbojpeg.c:2262-2320: one buffer, planes back to back, rows padded to `align` */
+  mjh_jpeg_info in;
+  unsigned char *planes[3];
+  int strides[3], W, H, pw0, ph0;
+  if (jpegBuf == NULL || jpegSize <= 0 || dstBuf == NULL || align < 1 || (align & (align - 1)) != 0) return fail(t, fn, "Invalid argument");
+  if (read_header(t, fn, jpegBuf, jpegSize, &in)) return -1;
+  if (t->subsamp == TJSAMP_UNKNOWN) return fail(t, fn, "Could not determine subsampling level of JPEG image");
+  W = TJSCALED(t->jpeg_width, t->sf); H = TJSCALED(t->jpeg_height, t->sf);
+  pw0 = tj3YUVPlaneWidth(0, W, t->subsamp); ph0 = tj3YUVPlaneHeight(0, H, t->subsamp);
+  planes[0] = dstBuf; strides[0] = PAD(pw0, align);
+  if (t->subsamp == TJSAMP_GRAY) { strides[1] = strides[2] = 0; planes[1] = planes[2] = NULL; }
+  else {
+    const int pw1 = tj3YUVPlaneWidth(1, W, t->subsamp), ph1 = tj3YUVPlaneHeight(1, H, t->subsamp);
+    strides[1] = strides[2] = PAD(pw1, align);
+    if ((unsigned long long)strides[0] * (unsigned long long)ph0 > (unsigned long long)INT_MAX || (unsigned long long)strides[1] * (unsigned long long)ph1 > (unsigned long long)INT_MAX)
+      return fail(t, fn, "Image or row alignment is too large");
+    planes[1] = planes[0] + (size_t)strides[0] * ph0;
+    planes[2] = planes[1] + (size_t)strides[1] * ph1;
+  }
+  return decompress_planes(t, fn, jpegBuf, jpegSize, planes, strides);
+}
+
+DLLEXPORT int tj3DecompressToYUV8(tjhandle handle, const unsigned char *jpegBuf, size_t jpegSize, unsigned char *dstBuf, int align)
+{
+  void *f;
+  tjs *t = dinstance(handle, "tj3DecompressToYUV8", &f);
+  if (!t) return f ? ((int (*)(tjhandle, const unsigned char *, size_t, unsigned char *, int))f)(handle, jpegBuf, jpegSize, dstBuf, align) : -1;
+  return decompress_yuv(t, "tj3DecompressToYUV8", jpegBuf, jpegSize, dstBuf, align);
+}
+
+DLLEXPORT int tjDecompressToYUVPlanes(tjhandle handle, const unsigned char *jpegBuf, unsigned long jpegSize, unsigned char **dstPlanes, int width, int *strides, int height, int flags)
+{
+  void *f;
+  tjs *t = dinstance(handle, "tjDecompressToYUVPlanes", &f);
+  if (!t) return f ? ((int (*)(tjhandle, const unsigned char *, unsigned long, unsigned char **, int, int *, int, int))f)(handle, jpegBuf, jpegSize, dstPlanes, width, strides, height, flags) : -1;
+  if (legacy_scale(t, "tjDecompressToYUVPlanes", jpegBuf, jpegSize, width, height)) return -1;
+  legacy_dflags(t, flags);
+  return decompress_planes(t, "tjDecompressToYUVPlanes", jpegBuf, (size_t)jpegSize, dstPlanes, strides);
+}
+
+DLLEXPORT int tjDecompressToYUV2(tjhandle handle, const unsigned char *jpegBuf, unsigned long jpegSize, unsigned char *dstBuf, int width, int align, int height, int flags)
+{
+  void *f;
+  tjs *t = dinstance(handle, "tjDecompressToYUV2", &f);
+  if (!t) return f ? ((int (*)(tjhandle, const unsigned char *, unsigned long, unsigned char *, int, int, int, int))f)(handle, jpegBuf, jpegSize, dstBuf, width, align, height, flags) : -1;
+  if (legacy_scale(t, "tjDecompressToYUV2", jpegBuf, jpegSize, width, height)) return -1;
+  legacy_dflags(t, flags);
+  return decompress_yuv(t, "tjDecompressToYUV2", jpegBuf, (size_t)jpegSize, dstBuf, align);
+}
+DLLEXPORT int tjDecompressToYUV(tjhandle handle, unsigned char *jpegBuf, unsigned long jpegSize, unsigned char *dstBuf, int flags)
+{
+  return tjDecompressToYUV2(handle, jpegBuf, jpegSize, dstBuf, 0, 4, 0, flags);
+}
+
+DLLEXPORT int tjDecompress(tjhandle handle, unsigned char *jpegBuf, unsigned long jpegSize, unsigned char *dstBuf, int width, int pitch, int height, int pixelSize, int flags)
+{ /* turbojpeg.c:2022-2033 */
+  int pf = -1;
+  if (flags & TJ_YUV) return tjDecompressToYUV(handle, jpegBuf, jpegSize, dstBuf, flags);
+  if (pixelSize == 1) pf = TJPF_GRAY;
+  else if (pixelSize == 3) pf = (flags & TJ_BGR) ? TJPF_BGR : TJPF_RGB;
+  else if (pixelSize == 4) pf = (flags & TJ_ALPHAFIRST) ? ((flags & TJ_BGR) ? TJPF_XBGR : TJPF_XRGB) : ((flags & TJ_BGR) ? TJPF_BGRX : TJPF_RGBX);
+  return tjDecompress2(handle, jpegBuf, jpegSize, dstBuf, width, pitch, height, pf, flags);
 }

@@ -10,7 +10,12 @@ after a warm-up) with the run-to-run spread; the phase times of the Huffman deco
 yardstick: oracle/_ref/djpeg -pnm over the same files, 16 processes at a time, input on a RAM disk and output discarded (that
 figure includes process start and PPM formatting).  The first call's pixels are compared with djpeg's before anything is timed.
 --scale M/N: both workloads decoded at that scale (1/2, 1/4, 1/8: the reduced inverse DCTs), the reference being djpeg -scale M/N.
-usage: python tools/bench_decode.py [--workloads A,B] [--scale 1/1] [--seconds 2] [--repeats 3] [--out profiles/decode_bench]"""
+--dct fast: instead of the above, the K-I1 time of k_idct_ifast (mjh_decode_opts.dct_method 1) next to k_idct's on the same batch of
+workload A, alternating calls under mjh_set_profiling(1); the fast pixels of the first call are compared with djpeg -dct fast.
+--tj: instead of the above, files/s of tj3Decompress8 (TJPF_RGB, full size) through mozjpeg_amd/libmozjpeg_hip_turbojpeg.so on 8 files
+of workload A from one thread -- one image per call, each call synchronises -- next to the reference's oracle/_ref/libturbojpeg.so.0
+in the same process, alternating rounds; the two libraries' pixels are compared first.
+usage: python tools/bench_decode.py [--workloads A,B] [--scale 1/1] [--dct fast] [--tj] [--seconds 2] [--repeats 3] [--out profiles/decode_bench]"""
 import argparse
 import json
 import os
@@ -64,6 +69,86 @@ def timed(enc, files, seconds, host, opts):
             return calls * len(files) / dt
 
 
+def median(v):
+    return sorted(v)[len(v) // 2]
+
+
+def bench_dct_fast(a, isa):
+    """K-I1 of both IDCT methods on the 64 x 4K batch: ms per call (median of `rounds` alternating calls, device events)"""
+    files = sources("A")
+    n = len(files)
+    info = M.jpeg_info(files[0])
+    enc = M.Encoder(M.params_from_jpeg(files[0], revert=True), max_batch=n)
+    opts = {"int": M.decode_opts(dct="int"), "fast": M.decode_opts(dct="fast")}
+    outs = enc.decode_host(files[:n], opts=opts["fast"])
+    with ThreadPoolExecutor(16) as ex:
+        same = list(ex.map(lambda i: bool(np.array_equal(outs[i], DC.djpeg(files[i], ["-dct", "fast"]))), range(n)))
+    del outs
+    enc.set_profiling(1)
+    ms = {"int": [], "fast": []}
+    up = {"int": [], "fast": []}
+    rounds = 11
+    for r in range(rounds + 2):
+        for name in ("int", "fast"):
+            enc.submit_decode(files, opts=opts[name])
+            enc.sync()
+            st = enc.decode_stats()["ms"]
+            if r >= 2:                                  # (two warm-up rounds)
+                ms[name].append(st["idct"])
+                up[name].append(st["upcolor"])
+    enc.close()
+    w, h = info.image_width, info.image_height
+    traffic = n * w * h * 1.5 * 3                       # coefficients read (2 bytes a sample) + samples written
+    res = {"files": n, "width": w, "height": h, "rounds": rounds, "identical_to_djpeg_dct_fast": all(same),
+           "kernel_sha": {k: isa[k]["sha"] for k in ("k_idct", "k_idct_ifast")}, "vgpr": {k: isa[k]["vgpr"] for k in ("k_idct", "k_idct_ifast")},
+           "k_idct_ms": median(ms["int"]), "k_idct_ifast_ms": median(ms["fast"]), "k_idct_ms_all": ms["int"], "k_idct_ifast_ms_all": ms["fast"],
+           "k_upcolor_ms": median(up["int"] + up["fast"]),
+           "k_idct_gbytes_per_s": traffic / median(ms["int"]) / 1e6, "k_idct_ifast_gbytes_per_s": traffic / median(ms["fast"]) / 1e6}
+    res["ifast_over_islow"] = res["k_idct_ifast_ms"] / res["k_idct_ms"]
+    return res
+
+
+def bench_tj(a, isa):
+    """tj3Decompress8, one image per call from one thread: the shipped TurboJPEG-signature library against the reference's"""
+    import ctypes as C
+    import tj_decompress_cases as TD
+    files = sources("A")[:8]
+    info = M.jpeg_info(files[0])
+    w, h = info.image_width, info.image_height
+    libs = {"mozjpeg_hip_turbojpeg": TD.load(TD.TJSHIM), "reference_libturbojpeg": TD.load(TD.TJLIB)}
+    handles = {k: L.tj3Init(TD.TJINIT_DECOMPRESS) for k, L in libs.items()}
+    bufs = {k: np.zeros((h, w, 3), np.uint8) for k in libs}
+
+    def one(k, f):
+        rc = libs[k].tj3Decompress8(handles[k], f, len(f), bufs[k].ctypes.data, 0, TD.PF_RGB)
+        assert rc == 0, libs[k].tj3GetErrorStr(handles[k])
+
+    same = []
+    for f in files:
+        for k in libs:
+            one(k, f)
+        same.append(bool(np.array_equal(*bufs.values())))
+    rates = {k: [] for k in libs}
+    for _ in range(a.repeats):
+        for k in libs:
+            calls, t0 = 0, time.perf_counter()
+            while True:
+                one(k, files[calls % len(files)])
+                calls += 1
+                dt = time.perf_counter() - t0
+                if dt >= a.seconds:
+                    break
+            rates[k].append(calls / dt)
+    for k, L in libs.items():
+        L.tj3Destroy(handles[k])
+    res = {"files": len(files), "width": w, "height": h, "identical_to_reference": all(same), "threads": 1,
+           "kernel_sha": {k: isa[k]["sha"] for k in ("k_dec_sync", "k_dec_store", "k_idct", "k_upcolor")}}
+    for k, v in rates.items():
+        res[k] = {"files_per_s": v, "median_files_per_s": median(v), "median_mpixels_per_s": median(v) * w * h / 1e6, "spread": (max(v) - min(v)) / median(v)}
+    res["ratio_to_reference"] = res["mozjpeg_hip_turbojpeg"]["median_files_per_s"] / res["reference_libturbojpeg"]["median_files_per_s"]
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", default="A,B")
@@ -71,7 +156,22 @@ def main():
     ap.add_argument("--seconds", type=float, default=2.0)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--dct", default=None, choices=["fast"])
+    ap.add_argument("--tj", action="store_true")
     a = ap.parse_args()
+    if a.dct or a.tj:
+        isa = json.load(open(os.path.join(ROOT, "mozjpeg_amd", "kernel_isa.json")))
+        result = {"source_stamp": isa.get("source_stamp")}
+        if a.dct:
+            result["dct_fast"] = bench_dct_fast(a, isa["kernels"])
+            print(json.dumps({"dct_fast": result["dct_fast"]}), flush=True)
+        if a.tj:
+            result["tj"] = bench_tj(a, isa["kernels"])
+            print(json.dumps({"tj": result["tj"]}), flush=True)
+        if a.out:
+            with open(a.out + ".json", "w") as f:
+                json.dump(result, f, indent=1)
+        return
     opts = M.decode_opts(scale=a.scale)
     k = M.scale_idct_size(opts.scale_num, opts.scale_denom)
     dj_args = ["-scale", a.scale] if k != 8 else []
