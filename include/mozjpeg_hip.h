@@ -325,6 +325,7 @@ int mjh_encoder_sync(mjh_encoder *e);
 #define MJH_CS_GRAYSCALE 1   /* J_COLOR_SPACE values (jpeglib.h:232-234) */
 #define MJH_CS_RGB       2
 #define MJH_CS_YCbCr     3
+#define MJH_CS_RGB565    16  /* JCS_RGB565: an output of mjh_decode_host only */
 typedef struct {
   int comps_in_scan;
   int component_index[MJH_MAX_COMPS];               /* frame index of every component of the scan */
@@ -439,6 +440,12 @@ int mjh_encoder_set_transform(mjh_encoder *e, const mjh_transform *t);
  * pixel_size / rgb_offset: the layouts mjh_params.input_pixel_size / rgb_offset name for input -- 3 or 4 bytes per RGB pixel
  * (0 = 3), the byte of R, G and B inside it (all 0 = 0, 1, 2); the fourth byte of a 4-byte pixel is 0xFF.  Gray pixels are
  * one byte.  fancy_upsampling: 1 = djpeg's default, 0 = -nosmooth.
+ * MJH_CS_RGB565 (djpeg -rgb565, jdcol565.c): 16-bit pixels ((r << 8) & 0xF800) | ((g << 3) & 0x7E0) | (b >> 3), little-endian, of
+ * any file RGB output is made of.  pixel_size is 0 or 2, rgb_offset all 0 (mjh_decode_opts_defaults sets 0, 1, 2).  no_dither 0: the reference's ordered dither
+ * (dither_mode other than JDITHER_NONE, djpeg's default), added in front of the range limit -- byte x & 3 of
+ * dither_matrix[y & 3] (jdcolor.c:619) to red and blue, half of it to green, (x, y) the pixel's place in the (scaled) image:
+ * what the reference gives a client that reads one row per jpeg_read_scanlines call into 4-byte aligned rows, as djpeg does
+ * (it takes the matrix row from output_scanline at the time of the call).  no_dither 1: plain (-dither none).
  * scale_num / scale_denom: djpeg -scale M/N, decoding at a reduced size inside the inverse DCT (jidctred.c).  The fraction is
  * resolved as jpeg_core_output_dimensions does (jdmaster.c:105ff): to k / 8 with the smallest k in 1..16 for which
  * scale_num * 8 <= scale_denom * k, 16 if there is none -- 1/5 decodes at 2/8.  k = 1, 2, 4 and 8 are built; 8 is the
@@ -457,8 +464,8 @@ int mjh_encoder_set_transform(mjh_encoder *e, const mjh_transform *t);
  * the reference then runs the reduced transform of a component the pixel path would have left at size 8 -- chroma of a 4:2:0
  * file at 1/2 -- on the fast method's multiplier table; so does this call, for the reference's bytes.)  out_color_space,
  * pixel_size, rgb_offset, fancy_upsampling and bottom_up are ignored.
- * The three fields were appended; 0 in all of them is the behaviour of the struct without them.
- * MJH_EINVAL: an unknown colour space, pixel size, offsets or dct_method; a scale_num or scale_denom below 1 (other than 0/0).
+ * dct_method, bottom_up, raw_planes and no_dither were appended; 0 in all of them is the behaviour of the struct without them.
+ * MJH_EINVAL: an unknown colour space, pixel size, offsets or dct_method; a pixel size other than 0 or 2 or an offset with RGB565; a scale_num or scale_denom below 1 (other than 0/0).
  * MJH_EUNSUPPORTED: a lossless transform set on the encoder; a scale that resolves to an IDCT size of 3, 5, 6, 7 or 9 to 16;
  * the float IDCT, cropping and colour quantization have no option here. */
 typedef struct {
@@ -470,6 +477,7 @@ typedef struct {
   int dct_method;
   int bottom_up;
   int raw_planes;
+  int no_dither;
 } mjh_decode_opts;
 void mjh_decode_opts_defaults(mjh_decode_opts *o);
 /* Decodes n files (opts == NULL: the defaults).  Queued on the encoder's stream; the bytes need not stay valid after the call.

@@ -18,6 +18,7 @@ PROFILE_MAX_COMPRESSION = 0x5D083AAD
 PROFILE_FASTEST = 0x2AEA5CB4
 COLOR_YCC, COLOR_NONE, COLOR_YCC_IN = 0, 1, 2
 CS_GRAYSCALE, CS_RGB, CS_YCBCR = 1, 2, 3      # JpegInfo.jpeg_color_space
+CS_RGB565 = 16                                # JCS_RGB565: DecodeOpts.out_color_space only
 OK, EINVAL, EUNSUPPORTED, EHIP, ENOMEM, ETOOSMALL = 0, -1, -2, -3, -4, -5
 TAP_PLANE, TAP_COEF_UQ, TAP_COEF_Q, TAP_COEF_Q0, TAP_HUFF_BITS, TAP_HUFF_VALS, TAP_PROG_SCAN_US, TAP_LL_COUNTS = 1, 2, 3, 4, 5, 6, 7, 8
 
@@ -86,7 +87,8 @@ class DecodeOpts(C.Structure):
     """mjh_decode_opts: what djpeg's -grayscale / -rgb / -nosmooth / -scale / -dct and the extended pixel layouts choose, TurboJPEG's
     bottom-up rows, and the raw sample planes instead of pixels"""
     _fields_ = [("out_color_space", C.c_int), ("pixel_size", C.c_int), ("rgb_offset", C.c_int * 3), ("fancy_upsampling", C.c_int),
-                ("scale_num", C.c_int), ("scale_denom", C.c_int), ("dct_method", C.c_int), ("bottom_up", C.c_int), ("raw_planes", C.c_int)]
+                ("scale_num", C.c_int), ("scale_denom", C.c_int), ("dct_method", C.c_int), ("bottom_up", C.c_int), ("raw_planes", C.c_int),
+                ("no_dither", C.c_int)]
 
 
 class Result(C.Structure):
@@ -492,18 +494,18 @@ DCT_METHODS = {None: 0, "int": 0, "islow": 0, "fast": 1, "ifast": 1}     # djpeg
 
 
 def decode_opts(color=None, layout=None, pixel_size=0, rgb_offset=None, fancy_upsampling=True, scale=None, dct=None, bottom_up=False,
-                raw_planes=False):
+                raw_planes=False, dither=True):
     """DecodeOpts from djpeg's vocabulary.  color: None (the file's default: gray stays gray, everything else RGB), "gray" /
-    "grayscale" (-grayscale), "rgb" (-rgb) or a CS_* number; layout: a name out of PIXEL_LAYOUTS, or pixel_size and rgb_offset;
+    "grayscale" (-grayscale), "rgb" (-rgb), "rgb565" (-rgb565: 16-bit pixels, with dither=False -dither none) or a CS_* number; layout: a name out of PIXEL_LAYOUTS, or pixel_size and rgb_offset;
     fancy_upsampling=False: -nosmooth; scale: -scale, a pair (num, denom) or a string "M/N" that resolves to 1/8, 2/8, 4/8 or
     8/8 as djpeg resolves it (scale_idct_size); dct: "int" (the default) or "fast" (-dct fast, TurboJPEG's FASTDCT);
     bottom_up=True: the rows last to first (TurboJPEG's BOTTOMUP); raw_planes=True: no pixels, the sample planes (decode_planes)."""
     o = DecodeOpts()
     lib().mjh_decode_opts_defaults(C.byref(o))
     if isinstance(color, str):
-        names = {"gray": CS_GRAYSCALE, "grayscale": CS_GRAYSCALE, "rgb": CS_RGB}
+        names = {"gray": CS_GRAYSCALE, "grayscale": CS_GRAYSCALE, "rgb": CS_RGB, "rgb565": CS_RGB565}
         if color not in names:
-            raise MjhError(EINVAL, "color %r (None, 'gray' or 'rgb')" % (color,))
+            raise MjhError(EINVAL, "color %r (None, 'gray', 'rgb' or 'rgb565')" % (color,))
         o.out_color_space = names[color]
     elif color is not None:
         o.out_color_space = int(color)
@@ -514,6 +516,8 @@ def decode_opts(color=None, layout=None, pixel_size=0, rgb_offset=None, fancy_up
     o.pixel_size = int(pixel_size)
     if rgb_offset is not None:
         o.rgb_offset[:] = [int(v) for v in rgb_offset]
+    elif o.out_color_space == CS_RGB565:
+        o.rgb_offset[:] = [0, 0, 0]     # (the defaults name 0, 1, 2; a 16-bit pixel has no byte offsets)
     o.fancy_upsampling = int(bool(fancy_upsampling))
     o.scale_num, o.scale_denom = _parse_scale(scale)
     if isinstance(dct, int) and not isinstance(dct, bool):
@@ -524,11 +528,18 @@ def decode_opts(color=None, layout=None, pixel_size=0, rgb_offset=None, fancy_up
         raise MjhError(EINVAL, "dct %r (None, 'int' or 'fast')" % (dct,))
     o.bottom_up = int(bool(bottom_up))
     o.raw_planes = int(bool(raw_planes))
+    o.no_dither = int(not dither)
     # the library's own checks (plan_pixels), made here as well so that decode() can refuse its options before it groups files
     if o.dct_method not in (0, 1):
         raise MjhError(EINVAL, "dct_method %d of a decode call (0 = JDCT_ISLOW, 1 = JDCT_IFAST)" % o.dct_method)
-    if o.out_color_space not in (0, CS_GRAYSCALE, CS_RGB):
-        raise MjhError(EINVAL, "out_color_space %d (0, CS_GRAYSCALE or CS_RGB)" % o.out_color_space)
+    if o.out_color_space not in (0, CS_GRAYSCALE, CS_RGB, CS_RGB565):
+        raise MjhError(EINVAL, "out_color_space %d (0, CS_GRAYSCALE, CS_RGB or CS_RGB565)" % o.out_color_space)
+    if o.out_color_space == CS_RGB565:
+        if o.pixel_size not in (0, 2):
+            raise MjhError(EINVAL, "pixel_size %d of RGB565 output (0 or 2)" % o.pixel_size)
+        if list(o.rgb_offset) != [0, 0, 0]:
+            raise MjhError(EINVAL, "rgb_offset %d,%d,%d of RGB565 output (all 0)" % tuple(o.rgb_offset))
+        return o
     if o.out_color_space == CS_GRAYSCALE:
         if o.pixel_size not in (0, 1):
             raise MjhError(EINVAL, "pixel_size %d of grayscale output (0 or 1)" % o.pixel_size)
@@ -887,9 +898,15 @@ class Encoder:
         return dict(width=w.value, height=h.value, pixel_size=px.value, ms=dict(idct=float(ms[0]), upcolor=float(ms[1])))
 
     def get_pixels(self, i, out=None):
-        """image i of the last decoded batch: uint8 [H, W, C], [H, W] for gray (mjh_get_pixels); out: an array of that shape with
+        """image i of the last decoded batch: uint8 [H, W, C], [H, W] for gray, uint16 [H, W] for RGB565 (mjh_get_pixels); out: an array of that shape with
         contiguous rows to fill instead of a new one"""
         st = self.decode_stats()
+        if st["pixel_size"] == 2:       # RGB565: one uint16 per pixel
+            shape = (st["height"], st["width"])
+            a = np.empty(shape, np.uint16) if out is None else out
+            assert a.shape == shape and a.dtype == np.uint16 and a.strides[1] == 2, "expected uint16 %s" % (shape,)
+            _chk(lib().mjh_get_pixels(self._h, i, a.ctypes.data, a.strides[0]))
+            return a
         shape = (st["height"], st["width"]) + ((st["pixel_size"],) if st["pixel_size"] > 1 else ())
         a = np.empty(shape, np.uint8) if out is None else out
         assert a.shape == shape and a.dtype == np.uint8 and a.strides[1:] == np.empty(shape[1:], np.uint8).strides, "expected uint8 %s" % (shape,)

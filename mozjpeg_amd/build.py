@@ -88,10 +88,12 @@ def build_shim(force=False, verbose=False):
             print(" ".join(cmd))
         subprocess.check_call(cmd)
     api = os.path.join(CSRC, "jpeg_api.c")
-    if force or _newer(STANDALONE, [src, api, hdr, LIB, os.path.join(CSRC, "mjh_quant_presets.h")]):
-        # stand-alone flavour: a complete libjpeg.so.62 for the COMPRESS API, nothing of the reference at run time
+    dapi = os.path.join(CSRC, "jpeg_dapi.c")
+    if force or _newer(STANDALONE, [src, api, dapi, hdr, LIB, os.path.join(CSRC, "mjh_quant_presets.h")]):
+        # stand-alone flavour: a complete libjpeg.so.62 -- the compress API (jpeg_api.c) and the decompress API
+        # (jpeg_dapi.c) -- nothing of the reference at run time
         os.makedirs(os.path.dirname(STANDALONE), exist_ok=True)
-        cmd = ["gcc", "-O2", "-fPIC", "-shared", "-Wall", "-DMJH_STANDALONE"] + inc + ["-o", STANDALONE, src, api, "-L" + HERE,
+        cmd = ["gcc", "-O2", "-fPIC", "-shared", "-Wall", "-DMJH_STANDALONE"] + inc + ["-o", STANDALONE, src, api, dapi, "-L" + HERE,
                                                                                          "-l:libmozjpeg_hip.so", "-Wl,-soname,libjpeg.so.62",
                                                                                          "-Wl,-rpath,$ORIGIN/..", "-lpthread"]
         if verbose:

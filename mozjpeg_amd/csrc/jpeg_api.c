@@ -1,16 +1,15 @@
 /*
  * jpeg_api.c -- the rest of the libjpeg COMPRESS API around the MI355X hot path: together with
- * jpeg_shim.c (-DMJH_STANDALONE) this file is a libjpeg.so.62 an unchanged client such as cjpeg can run against without
- * any code of the reference in the process.  What is restated here is host-side bookkeeping only -- object life cycle,
+ * jpeg_shim.c (-DMJH_STANDALONE) and jpeg_dapi.c (the decompress API) this file is a libjpeg.so.62 an unchanged client such as
+ * cjpeg or djpeg can run against without any code of the reference in the process.  What is restated here is host-side bookkeeping only -- object life cycle,
  * parameter setters, memory / error / destination managers, marker helpers; the pixel -> bytes path is the GPU's.
  *
  * Compiled against the libjpeg headers of the tree it replaces (struct jpeg_compress_struct, jpeg_memory_mgr,
  * jpeg_error_mgr ... are ABI; the message texts come from that tree's jerror.h the way its own jerror.c gets them).
  * Each entry point cites the reference function whose behaviour it keeps.
  *
- * Not provided (this is the compress half): the decompressor, backing-store files
- * of the memory manager (virtual arrays always live in memory).  The decompress symbols an unchanged cjpeg binary
- * references (it can read JPEG input files) exist as stubs that raise JERR_NOT_COMPILED.
+ * Not provided: backing-store files of the memory manager (virtual arrays always live in memory), jpeg_read_coefficients
+ * (a stub that raises JERR_NOT_COMPILED).  The objects, error and memory managers here serve both halves.
  */
 #define JPEG_INTERNALS
 #include <stdio.h>
@@ -331,6 +330,7 @@ void jpeg_abort(j_common_ptr cinfo)
 { /* jcomapi.c:30-55 */
   mjh_shim_drop(cinfo);
   if (cinfo->mem == NULL) return;
+  if (cinfo->is_decompressor) mjh_dapi_drop(cinfo);
   (*cinfo->mem->free_pool) (cinfo, JPOOL_IMAGE);
   if (cinfo->is_decompressor) { cinfo->global_state = DSTATE_START; ((j_decompress_ptr)cinfo)->marker_list = NULL; }
   else cinfo->global_state = CSTATE_START;
@@ -339,6 +339,7 @@ void jpeg_abort(j_common_ptr cinfo)
 void jpeg_destroy(j_common_ptr cinfo)
 { /* jcomapi.c:70-80 */
   mjh_shim_drop(cinfo);
+  if (cinfo->mem != NULL && cinfo->is_decompressor) mjh_dapi_drop(cinfo);
   if (cinfo->mem != NULL) (*cinfo->mem->self_destruct) (cinfo);
   cinfo->mem = NULL;
   cinfo->global_state = 0;
@@ -1015,25 +1016,14 @@ void jpeg_copy_critical_parameters(const j_decompress_ptr srcinfo, j_compress_pt
 }
 
 /* =====================================================================================================================
- * what this library does not do.  An unchanged cjpeg is linked with immediate binding, so every symbol it names must
- * exist; the ones of the decompressor (cjpeg can take a JPEG file as input) raise
- * JERR_NOT_COMPILED when they are actually called.
+ * what this library does not do.  The decompress API is jpeg_dapi.c's; reading a file's coefficient arrays (an unchanged
+ * jpegtran on this library alone) is not built and raises JERR_NOT_COMPILED when it is called.
  * ===================================================================================================================== */
 #ifdef MJH_STANDALONE
 static void not_here(j_common_ptr cinfo, const char *what)
 {
-  fprintf(stderr, "mozjpeg_hip: %s is not part of this library (compress API only)\n", what);
+  fprintf(stderr, "mozjpeg_hip: %s is not part of this library (the GPU decoder delivers pixels and sample planes)\n", what);
   ERREXIT(cinfo, JERR_NOT_COMPILED);
 }
-void jpeg_CreateDecompress(j_decompress_ptr cinfo, int version, size_t structsize) { (void)version; (void)structsize; cinfo->mem = NULL; not_here((j_common_ptr)cinfo, "jpeg_CreateDecompress"); }
-void jpeg_destroy_decompress(j_decompress_ptr cinfo) { jpeg_destroy((j_common_ptr)cinfo); }
-void jpeg_abort_decompress(j_decompress_ptr cinfo) { jpeg_abort((j_common_ptr)cinfo); }
-boolean jpeg_finish_decompress(j_decompress_ptr cinfo) { not_here((j_common_ptr)cinfo, "jpeg_finish_decompress"); return FALSE; }
-int jpeg_read_header(j_decompress_ptr cinfo, boolean require_image) { (void)require_image; not_here((j_common_ptr)cinfo, "jpeg_read_header"); return 0; }
-JDIMENSION jpeg_read_scanlines(j_decompress_ptr cinfo, JSAMPARRAY scanlines, JDIMENSION max_lines) { (void)scanlines; (void)max_lines; not_here((j_common_ptr)cinfo, "jpeg_read_scanlines"); return 0; }
-boolean jpeg_start_decompress(j_decompress_ptr cinfo) { not_here((j_common_ptr)cinfo, "jpeg_start_decompress"); return FALSE; }
-void jpeg_save_markers(j_decompress_ptr cinfo, int marker_code, unsigned int length_limit) { (void)marker_code; (void)length_limit; not_here((j_common_ptr)cinfo, "jpeg_save_markers"); }
-void jpeg_stdio_src(j_decompress_ptr cinfo, FILE *infile) { (void)infile; not_here((j_common_ptr)cinfo, "jpeg_stdio_src"); }
-void jpeg_mem_src(j_decompress_ptr cinfo, const unsigned char *inbuffer, unsigned long insize) { (void)inbuffer; (void)insize; not_here((j_common_ptr)cinfo, "jpeg_mem_src"); }
 jvirt_barray_ptr *jpeg_read_coefficients(j_decompress_ptr cinfo) { not_here((j_common_ptr)cinfo, "jpeg_read_coefficients"); return NULL; }
 #endif

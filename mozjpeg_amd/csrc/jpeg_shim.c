@@ -127,6 +127,11 @@ static void cache_release(mjh_encoder *enc)
   pthread_mutex_unlock(&g_lock);
 }
 
+#ifdef MJH_STANDALONE
+mjh_encoder *mjh_shim_cache_acquire(const void *params) { return cache_acquire((const mjh_params *)params, pick_device()); }
+void mjh_shim_cache_release(mjh_encoder *enc) { cache_release(enc); }
+#endif
+
 /* ---- coalescing of concurrent clients --------------------------------------------------------------------------------
  * libjpeg hands the library ONE image per compress object, and a single-image schedule leaves most of the device idle
  * (measured, 16 client threads with an encoder each: 979 4K images/s, every image waiting 6.6 ms for its ~25 small

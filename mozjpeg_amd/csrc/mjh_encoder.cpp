@@ -3189,9 +3189,16 @@ static int plan_pixels(const mjh_encoder *e, const mjh_decode_opts *o, int k, Mj
   const bool src_gray = C.ncomp == 1, src_rgb = C.ncomp == 3 && e->p_created.color_transform == MJH_COLOR_NONE;
   int cs = o->out_color_space;
   if (cs == 0) cs = src_gray ? MJH_CS_GRAYSCALE : MJH_CS_RGB;
-  if (cs != MJH_CS_GRAYSCALE && cs != MJH_CS_RGB) return fail(MJH_EINVAL, "out_color_space %d (0, MJH_CS_GRAYSCALE or MJH_CS_RGB)", o->out_color_space);
+  if (cs != MJH_CS_GRAYSCALE && cs != MJH_CS_RGB && cs != MJH_CS_RGB565)
+    return fail(MJH_EINVAL, "out_color_space %d (0, MJH_CS_GRAYSCALE, MJH_CS_RGB or MJH_CS_RGB565)", o->out_color_space);
   int px = o->pixel_size;
-  if (cs == MJH_CS_GRAYSCALE) {
+  if (cs == MJH_CS_RGB565) {
+    // jdcol565.c: 16-bit pixels, one layout; k_upcolor_565 reads no offsets
+    if (px != 0 && px != 2) return fail(MJH_EINVAL, "pixel_size %d of RGB565 output (0 or 2)", px);
+    if (o->rgb_offset[0] || o->rgb_offset[1] || o->rgb_offset[2]) return fail(MJH_EINVAL, "rgb_offset %d,%d,%d of RGB565 output (all 0)", o->rgb_offset[0], o->rgb_offset[1], o->rgb_offset[2]);
+    px = 2;
+    P->conv = src_gray ? MJH_CC_GRAY_RGB : (src_rgb ? MJH_CC_RGB_RGB : MJH_CC_YCC_RGB);
+  } else if (cs == MJH_CS_GRAYSCALE) {
     if (px != 0 && px != 1) return fail(MJH_EINVAL, "pixel_size %d of grayscale output (0 or 1)", px);
     px = 1;
     P->conv = src_rgb ? MJH_CC_RGB_GRAY : MJH_CC_GRAY;
@@ -3327,7 +3334,8 @@ extern "C" int mjh_decode_host(mjh_encoder *e, const void *const jpegs[], const 
   if (raw) {
     e->rp_ncomp = P.ncomp;
     for (int c = 0; c < P.ncomp; c++) { e->rp_w[c] = C.c[c].wib * k; e->rp_h[c] = C.c[c].hib * k; e->rp_pitch[c] = P.c[c].pw; }
-  } else mjh_launch_upcolor(P, e->d_planes, e->d_pixout, e->d_tstat, n, s);
+  } else if (P.px_size == 2) mjh_launch_upcolor_565(P, o.no_dither == 0, e->d_planes, e->d_pixout, e->d_tstat, n, s);
+  else mjh_launch_upcolor(P, e->d_planes, e->d_pixout, e->d_tstat, n, s);
   if (timed) HIPCHK(hipEventRecord(e->dp_ev[2], s));
   e->dp_timed = timed;
   HIPCHK(hipGetLastError());

@@ -32,7 +32,7 @@ struct MjhPixOut {
   int W, H;
   int conv;                  // MJH_CC_*
   int ncomp;                 // components the conversion reads (1 or 3)
-  int px_size;               // bytes per output pixel: 1, 3 or 4
+  int px_size;               // bytes per output pixel: 1, 3 or 4 (2: k_upcolor_565)
   int off_r, off_g, off_b;   // byte of every colour inside a pixel; the fourth byte of a 4-byte pixel is 0xFF
   int bottom_up;             // image row y is stored at output row H - 1 - y (0: at row y)
   long long row_pitch, image_stride;      // of the output, bytes; rows hold whole groups of 4 pixels
@@ -53,4 +53,7 @@ void mjh_launch_idct_scaled(const MjhConst &C, const MjhIdctQ &Q, int ci, int N,
 // K-I2: sample planes -> interleaved pixels.  Everything it knows of the planes and the image comes from P, so a scaled decode
 // is the same kernel given the reduced planes (dw, dh, pw), the group ratios of jdsample.c:454-459 and the scaled W x H.
 void mjh_launch_upcolor(const MjhPixOut &P, const uint8_t *planes, uint8_t *pixels, const unsigned *status, int n, hipStream_t s);
+// K-I2 for JCS_RGB565: P.px_size 2, P.conv one of MJH_CC_GRAY_RGB / MJH_CC_YCC_RGB / MJH_CC_RGB_RGB; 16-bit little-endian pixels,
+// dither != 0: the ordered dither of jdcol565.c by image row and column, 0: plain (JDITHER_NONE)
+void mjh_launch_upcolor_565(const MjhPixOut &P, int dither, const uint8_t *planes, uint8_t *pixels, const unsigned *status, int n, hipStream_t s);
 #endif

@@ -24,6 +24,8 @@
 //   Edges: neighbours are clamped to [0, downsampled_width) x [0, downsampled_height), which is what the special
 //   first / last column cases of the fancy upsamplers (jdsample.c:289-303, :386-404) and the duplicated context rows of the main
 //   controller (jdmainct.c make_funny_pointers / set_bottom_pointers) amount to; samples beyond are never read.
+// K-I2' k_upcolor_565: the same lanes for JCS_RGB565 (djpeg -rgb565): 4 packed 16-bit pixels, one 8-byte store, with or without
+//   the reference's ordered dither; see the kernel.
 #include <hip/hip_runtime.h>
 #include "mjh_device.h"
 #include "mjh_idct.h"
@@ -367,6 +369,51 @@ k_upcolor(MjhPixOut P, const uint8_t *__restrict__ planes, uint8_t *__restrict__
   }
 }
 
+// ---- K-I2 for JCS_RGB565 (djpeg -rgb565): jdcol565.c / jdmrg565.c, little-endian ------------------------------------------------
+// d: byte x & 3 of dither_matrix[y & 3] (jdcolor.c:619), y the row of the (scaled) image -- what a client that reads one row
+// per jpeg_read_scanlines call, as djpeg does, gets from the reference (it takes the matrix row from output_scanline at the time
+// of the call); a row whose pointer is 4-byte aligned (PACK_NEED_ALIGNMENT = 0).
+__constant__ unsigned kDither565[4] = { 0x0008020Au, 0x0C040E06u, 0x030B0109u, 0x0F070D05u };
+
+// The grid, the planes and the MjhPixOut of k_upcolor (px_size 2; the offsets are not read); one lane's 4 pixels are 8 bytes
+// and one store.  The dither goes in BEFORE the range limit (range_limit[y + Crrtab[cr] + d], jdcol565.c:136): red and blue
+// get d, green d >> 1; a gray file gets d on its one sample, which is then packed three times (gray_rgb565D_convert).
+// dither 0 (dither_mode = JDITHER_NONE, djpeg -dither none): d = 0, which is ycc_rgb565_convert / rgb_rgb565_convert /
+// gray_rgb565_convert.  The sums stay inside the part of the reference's table that is a plain clamp (-256 .. 639).
+__global__ void __launch_bounds__(256)
+k_upcolor_565(MjhPixOut P, int dither, const uint8_t *__restrict__ planes, uint8_t *__restrict__ pixels, const unsigned *__restrict__ status)
+{
+  const int img = blockIdx.z, y = blockIdx.y;
+  const int x0 = (int)(blockIdx.x * 256u + threadIdx.x) * 4;
+  if (x0 >= P.W) return;
+  if (status[img] != 0u) return;
+  const uint8_t *pl = planes + (size_t)img * P.planes_per_image;
+  const int yo = P.bottom_up ? P.H - 1 - y : y;
+  const unsigned dm = dither ? kDither565[y & 3] : 0u;
+  unsigned p16[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const int x = x0 + i < P.W ? x0 + i : P.W - 1;      // (the pad of the last group, as in k_upcolor)
+    const int d = (int)((dm >> (8 * i)) & 0xFFu);       // x0 is a multiple of 4: x & 3 = i
+    const int a = up_sample(P.c[0], pl + P.c[0].plane_off, x, y);
+    int r, g, b;
+    if (P.ncomp == 3) {
+      const int c1 = up_sample(P.c[1], pl + P.c[1].plane_off, x, y), c2 = up_sample(P.c[2], pl + P.c[2].plane_off, x, y);
+      if (P.conv == MJH_CC_YCC_RGB) {                  // the tables of build_ycc_rgb_table, as k_upcolor
+        const int cb = c1 - 128, cr = c2 - 128;
+        r = a + ((91881 * cr + 32768) >> 16);
+        g = a + ((-22554 * cb + 32768 - 46802 * cr) >> 16);
+        b = a + ((116130 * cb + 32768) >> 16);
+      } else { r = a; g = c1; b = c2; }                // rgb_rgb565(D)_convert
+      r = clamp255(r + d); g = clamp255(g + (d >> 1)); b = clamp255(b + d);
+    } else r = g = b = clamp255(a + d);                // gray_rgb565(D)_convert
+    p16[i] = (((unsigned)r << 8) & 0xF800u) | (((unsigned)g << 3) & 0x7E0u) | ((unsigned)b >> 3);      // PACK_SHORT_565_LE
+  }
+  uint2 v;
+  v.x = p16[0] | (p16[1] << 16); v.y = p16[2] | (p16[3] << 16);
+  *reinterpret_cast<uint2 *>(pixels + (size_t)img * P.image_stride + (size_t)yo * P.row_pitch + (size_t)x0 * 2) = v;
+}
+
 void mjh_launch_idct(const MjhConst &C, const MjhIdctQ &Q, int comps, const int16_t *coef_q, uint8_t *planes, const unsigned *status, int n, hipStream_t s)
 {
   int nblk = 1;
@@ -385,6 +432,12 @@ void mjh_launch_upcolor(const MjhPixOut &P, const uint8_t *planes, uint8_t *pixe
 {
   const int groups = (P.W + 3) / 4;
   hipLaunchKernelGGL(k_upcolor, dim3((groups + 255) / 256, P.H, n), dim3(256), 0, s, P, planes, pixels, status);
+}
+
+void mjh_launch_upcolor_565(const MjhPixOut &P, int dither, const uint8_t *planes, uint8_t *pixels, const unsigned *status, int n, hipStream_t s)
+{
+  const int groups = (P.W + 3) / 4;
+  hipLaunchKernelGGL(k_upcolor_565, dim3((groups + 255) / 256, P.H, n), dim3(256), 0, s, P, dither, planes, pixels, status);
 }
 
 void mjh_launch_idct_scaled(const MjhConst &C, const MjhIdctQ &Q, int ci, int N, int pitch, const int16_t *coef_q, uint8_t *planes, const unsigned *status, int n, hipStream_t s)

@@ -12,10 +12,13 @@ figure includes process start and PPM formatting).  The first call's pixels are 
 --scale M/N: both workloads decoded at that scale (1/2, 1/4, 1/8: the reduced inverse DCTs), the reference being djpeg -scale M/N.
 --dct fast: instead of the above, the K-I1 time of k_idct_ifast (mjh_decode_opts.dct_method 1) next to k_idct's on the same batch of
 workload A, alternating calls under mjh_set_profiling(1); the fast pixels of the first call are compared with djpeg -dct fast.
+--color rgb565: instead of the above, the K-I2 time of k_upcolor_565 (16-bit pixels, ordered dither and plain) next to k_upcolor's
+(3-byte RGB) on the same batch of workload A, alternating calls under mjh_set_profiling(1); the 565 pixels of the first call are
+compared with djpeg -rgb565 -bmp.
 --tj: instead of the above, files/s of tj3Decompress8 (TJPF_RGB, full size) through mozjpeg_amd/libmozjpeg_hip_turbojpeg.so on 8 files
 of workload A from one thread -- one image per call, each call synchronises -- next to the reference's oracle/_ref/libturbojpeg.so.0
 in the same process, alternating rounds; the two libraries' pixels are compared first.
-usage: python tools/bench_decode.py [--workloads A,B] [--scale 1/1] [--dct fast] [--tj] [--seconds 2] [--repeats 3] [--out profiles/decode_bench]"""
+usage: python tools/bench_decode.py [--workloads A,B] [--scale 1/1] [--dct fast] [--color rgb565] [--tj] [--seconds 2] [--repeats 3] [--out profiles/decode_bench]"""
 import argparse
 import json
 import os
@@ -108,6 +111,40 @@ def bench_dct_fast(a, isa):
     return res
 
 
+def bench_rgb565(a, isa):
+    """K-I2 of the 3-byte and the 565 kernels on the 64 x 4K batch: ms per call (median of `rounds` alternating calls, device events)"""
+    import djpeg_cases as DJ
+    files = sources("A")
+    n = len(files)
+    info = M.jpeg_info(files[0])
+    enc = M.Encoder(M.params_from_jpeg(files[0], revert=True), max_batch=n)
+    opts = {"rgb": M.decode_opts(color="rgb"), "rgb565": M.decode_opts(color="rgb565"), "rgb565_plain": M.decode_opts(color="rgb565", dither=False)}
+    outs = enc.decode_host(files[:n], opts=opts["rgb565"])
+    with ThreadPoolExecutor(16) as ex:
+        same = list(ex.map(lambda i: bool(DJ.same565(outs[i], DJ.djpeg565(files[i]))), range(n)))
+    del outs
+    enc.set_profiling(1)
+    ms = {k: [] for k in opts}
+    rounds = 11
+    for r in range(rounds + 2):
+        for name in opts:
+            enc.submit_decode(files, opts=opts[name])
+            enc.sync()
+            if r >= 2:                                  # (two warm-up rounds)
+                ms[name].append(enc.decode_stats()["ms"]["upcolor"])
+    enc.close()
+    w, h = info.image_width, info.image_height
+    planes = n * w * h * 1.5                            # 4:2:0: 1.5 samples a pixel read
+    res = {"files": n, "width": w, "height": h, "rounds": rounds, "identical_to_djpeg_rgb565": all(same),
+           "kernel_sha": {k: isa[k]["sha"] for k in ("k_upcolor", "k_upcolor_565")}, "vgpr": {k: isa[k]["vgpr"] for k in ("k_upcolor", "k_upcolor_565")},
+           "k_upcolor_ms": median(ms["rgb"]), "k_upcolor_565_ms": median(ms["rgb565"]), "k_upcolor_565_plain_ms": median(ms["rgb565_plain"]),
+           "ms_all": ms,
+           "k_upcolor_gbytes_per_s": (planes + n * w * h * 3) / median(ms["rgb"]) / 1e6,
+           "k_upcolor_565_gbytes_per_s": (planes + n * w * h * 2) / median(ms["rgb565"]) / 1e6}
+    res["rgb565_over_rgb"] = res["k_upcolor_565_ms"] / res["k_upcolor_ms"]
+    return res
+
+
 def bench_tj(a, isa):
     """tj3Decompress8, one image per call from one thread: the shipped TurboJPEG-signature library against the reference's"""
     import ctypes as C
@@ -158,13 +195,17 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--dct", default=None, choices=["fast"])
     ap.add_argument("--tj", action="store_true")
+    ap.add_argument("--color", default=None, choices=["rgb565"])
     a = ap.parse_args()
-    if a.dct or a.tj:
+    if a.dct or a.tj or a.color:
         isa = json.load(open(os.path.join(ROOT, "mozjpeg_amd", "kernel_isa.json")))
         result = {"source_stamp": isa.get("source_stamp")}
         if a.dct:
             result["dct_fast"] = bench_dct_fast(a, isa["kernels"])
             print(json.dumps({"dct_fast": result["dct_fast"]}), flush=True)
+        if a.color:
+            result["rgb565"] = bench_rgb565(a, isa["kernels"])
+            print(json.dumps({"rgb565": result["rgb565"]}), flush=True)
         if a.tj:
             result["tj"] = bench_tj(a, isa["kernels"])
             print(json.dumps({"tj": result["tj"]}), flush=True)
