@@ -515,6 +515,9 @@ int mjh_decode_stats(mjh_encoder *e, int *width, int *height, int *pixel_size, f
  * groups of 256 blocks whose bits outgrew their window (64 Kbit) and were coded by the direct path -- both counted since
  * the encoder was made.  Any pointer may be NULL.  Synchronises with the device. */
 int mjh_enc_onepass_stats(mjh_encoder *e, int *enabled, unsigned long long *long_blocks, unsigned long long *big_groups);
+/* Which DC trellis kernels the latest call launched: 0 none, 1 one lane per chain (MJH_DC_LANES), 2 the sliding-window kernel,
+ * 3 the general kernel, 4 the speculative pair of one- and two-frame calls. */
+int mjh_get_dc_path(mjh_encoder *e, int *path);
 
 /* Size in bytes of JPEG i of the last batch (synchronises). */
 int mjh_get_jpeg_size(mjh_encoder *e, int i, size_t *size);

@@ -181,6 +181,8 @@ def lib():
             L.mjh_get_planes_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                                 C.POINTER(C.c_int), C.POINTER(C.c_int)]
             L.mjh_transcode_batch_size.argtypes = [C.c_void_p]
+        if hasattr(L, "mjh_get_dc_path"):
+            L.mjh_get_dc_path.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         if hasattr(L, "mjh_enc_onepass_stats"):       # (absent from a MOZJPEG_AMD_LIB variant built from an older tree: A/B runs against it)
             L.mjh_enc_onepass_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
         _lib = L
@@ -845,6 +847,12 @@ class Encoder:
         on, a, b = C.c_int(), C.c_ulonglong(), C.c_ulonglong()
         _chk(lib().mjh_enc_onepass_stats(self._h, C.byref(on), C.byref(a), C.byref(b)))
         return dict(enabled=bool(on.value), long_blocks=a.value, big_groups=b.value)
+
+    def dc_path(self):
+        """the DC trellis kernels of the latest call: None (no DC trellis), "lane" (one lane per chain, MJH_DC_LANES), "dc3", "dc2" or "speculative"""
+        v = C.c_int()
+        _chk(lib().mjh_get_dc_path(self._h, C.byref(v)))
+        return (None, "lane", "dc3", "dc2", "speculative")[v.value]
 
     def transcode_host(self, files, errors="raise", **transform):
         """files: JPEG byte strings that agree with the encoder's parameters (params_from_jpeg).  Returns the re-coded files.

@@ -304,6 +304,9 @@ struct mjh_encoder {
   int dc_mode = 0;
   int dc_late = 1;                   // large sequential batches: the DC chains of components >= dc_late (1: both chroma components, 2: Cr only) run behind the AC kernel, under the tail of small kernels (MJH_DC_LATE=0: all next to it)
   int dc_stats_side = 1;             // the final DC statistics run on the side stream behind the DC trellis (MJH_DC_STATS_SIDE=0: main stream)
+  int dc_lanes = 12000;              // MJH_DC_LANES: the DC trellis runs one lane per chain (k_trellis_dc_lane) in a call with at least this many chains per component (frames x iMCU rows) that meets dc_window_ok's conditions (0: never, 1: whenever they hold; the default: profiles/dc_lanes_ab.md)
+  int dc_lanes_set = 0;              // MJH_DC_LANES was given: only then may the lane kernel take a call of one or two frames from the speculative pair
+  int dc_path = 0;                   // the DC kernel family of the latest call (MJH_DC_PATH_*; mjh_get_dc_path)
   int dc_window_ok = 0;              // every component's DC quantizer step 8q >= 40: the DC trellis may use its sliding-window kernel
   int trellis_chunks = 0;            // image ranges of the tile-sorted first tier (MJH_TRELLIS_CHUNKS; 0 = by batch size): the general tiers of range c run next to the first tier of range c + 1
   hipEvent_t ev_chunk[4] = { nullptr, nullptr, nullptr, nullptr };
@@ -958,6 +961,7 @@ static int mjh_streams_overlap(hipStream_t a, hipStream_t b)
 
 static thread_local bool g_create_twin = false;
 static thread_local int g_twin_onepass = 1;     // the twin takes the primary's setting (the environment is read once, for the primary)
+static thread_local int g_twin_dc_lanes = 0, g_twin_dc_lanes_set = 0;    // (the same for MJH_DC_LANES)
 static thread_local hipStream_t g_twin_avoid[2] = { nullptr, nullptr };   // make_twin: the primary's main and side stream     // mjh_encoder_create is making the second buffer set of an encoder (make_twin)
 
 // The encoder's main and side stream (every encoder kind).
@@ -1132,6 +1136,8 @@ extern "C" int mjh_encoder_create(const mjh_params *p, int max_batch, int device
   if (const char *v = getenv("MJH_TRELLIS_CHUNKS")) { e->trellis_chunks = atoi(v); if (e->trellis_chunks < 0 || e->trellis_chunks > 4) e->trellis_chunks = 0; }
   for (int i = 0; i < 4; i++) HIPCHK_E(hipEventCreateWithFlags(&e->ev_chunk[i], hipEventDisableTiming));
   if (const char *v = getenv("MJH_DC_LATE")) { e->dc_late = atoi(v); if (e->dc_late < 0 || e->dc_late > 2) e->dc_late = 1; }   // A/B knob
+  if (g_create_twin) { e->dc_lanes = g_twin_dc_lanes; e->dc_lanes_set = g_twin_dc_lanes_set; }
+  else if (const char *v = getenv("MJH_DC_LANES")) { e->dc_lanes = atoi(v); if (e->dc_lanes < 0) e->dc_lanes = 0; e->dc_lanes_set = 1; }   // A/B knob
   e->dc_window_ok = 1;
   for (int i = 0; i < C.ncomp; i++) if (p->quantval[p->quant_tbl_no[i]][0] < 5) e->dc_window_ok = 0;
   if (const char *v = getenv("MJH_DC_SPEC")) e->dc_spec = atoi(v);
@@ -1629,6 +1635,7 @@ static int run_pipeline(mjh_encoder *e, const void *d_pixels, size_t row_pitch, 
   const int spi = e->spi;
   e->sizes_valid = false;
   e->last_n = n;
+  e->dc_path = MJH_DC_PATH_NONE;
   e->res_buf = -1;
   e->coef_input = coef_src != nullptr;
   e->last_stream = s;
@@ -1841,7 +1848,7 @@ static int run_pipeline(mjh_encoder *e, const void *d_pixels, size_t row_pitch, 
     const int dc_mode = e->dc_mode;   // experiments (MJH_DC_MODE): 1 = DC trellis on the main stream, before the AC kernel
     if (p.trellis_quant_dc && dc_mode == 1) {
       pr.mark("trellis_dc(serial)");
-      mjh_launch_trellis_dc(dc_chain_view(e, CV), e->d_quant, e->d_uq, e->d_q, e->d_tabs, spi, sl_dc, e->d_lambda, e->d_back, n, s, e->dc_window_ok);
+      e->dc_path = mjh_launch_trellis_dc(dc_chain_view(e, CV), e->d_quant, e->d_uq, e->d_q, e->d_tabs, spi, sl_dc, e->d_lambda, e->d_back, n, s, e->dc_window_ok, 0, -1, e->dc_lanes);
     } else if (p.trellis_quant_dc) {
       HIPCHK(hipEventRecord(e->ev_fork, s));
       HIPCHK(hipStreamWaitEvent(e->side_stream, e->ev_fork, 0));
@@ -1853,7 +1860,8 @@ static int run_pipeline(mjh_encoder *e, const void *d_pixels, size_t row_pitch, 
       // row one after the other): every block row is walked for every value the row above can end on, in parallel, and a second
       // kernel back-tracks the walks whose hypothesis held (mjh_kernels.hip, K6 speculative)
       const size_t spec_bytes = 2 * (size_t)C.total_real_blocks * 9 * 16;
-      const bool spec = e->dc_spec && n <= 2 && qstride == 0 && spec_bytes <= ((size_t)256 << 20) && mjh_trellis_dc_speculative_ok(CV, e->dc_window_ok);
+      const bool spec = e->dc_spec && n <= 2 && qstride == 0 && spec_bytes <= ((size_t)256 << 20) && mjh_trellis_dc_speculative_ok(CV, e->dc_window_ok) &&
+                        !(e->dc_lanes_set && mjh_trellis_dc_lanes_ok(dc_chain_view(e, CV), e->dc_window_ok, n, e->dc_lanes));   // (MJH_DC_LANES set and reached by two frames: asked for; the default never takes these calls)
       if (spec && !e->d_back9) {
         int rows = 0;
         for (int c = 0; c < C.ncomp; c++) rows += C.c[c].hib;
@@ -1871,10 +1879,10 @@ static int run_pipeline(mjh_encoder *e, const void *d_pixels, size_t row_pitch, 
       // every chain starts here, the older schedule)
       const bool sorted_tier = nzm && e->d_nq8 && e->trellis_v3 > 0 && e->trellis_variant <= 4;
       dc_late = e->dc_late > 0 && sorted_tier && !spec && final_dc_here && nloops == 1 && CV.ncomp == 3 && !e->debug_taps && (size_t)n * C.total_real_blocks >= e->small_batch;
-      if (spec) mjh_launch_trellis_dc_speculative(CV, e->d_quant, e->d_uq, e->d_q, e->d_tabs, spi, sl_dc, e->d_lambda, e->d_back9, e->d_jfin, e->d_qspec, n, e->side_stream);
+      if (spec) { mjh_launch_trellis_dc_speculative(CV, e->d_quant, e->d_uq, e->d_q, e->d_tabs, spi, sl_dc, e->d_lambda, e->d_back9, e->d_jfin, e->d_qspec, n, e->side_stream); e->dc_path = MJH_DC_PATH_SPEC; }
       else
-      mjh_launch_trellis_dc(dc_chain_view(e, CV), e->d_quant, e->d_uq, e->d_q, e->d_tabs, spi, sl_dc, e->d_lambda, e->d_back, n, e->side_stream, e->dc_window_ok,
-                            0, dc_late ? e->dc_late * CV.mcu_rows : -1);   // (the DC entries never change: image 0's tables serve all)
+      e->dc_path = mjh_launch_trellis_dc(dc_chain_view(e, CV), e->d_quant, e->d_uq, e->d_q, e->d_tabs, spi, sl_dc, e->d_lambda, e->d_back, n, e->side_stream, e->dc_window_ok,
+                            0, dc_late ? e->dc_late * CV.mcu_rows : -1, e->dc_lanes);   // (the DC entries never change: image 0's tables serve all)
       if (pr.enabled && e->profiling == 1) { HIPCHK(hipEventRecord(e->side_events[2 * e->prof_calls + 1], e->side_stream)); e->side_timed = true; }
       if (final_dc_here && !dc_late) {
         // the final DC statistics need nothing but the DC trellis's result: counted here, they cost no time of their own
@@ -1909,7 +1917,7 @@ static int run_pipeline(mjh_encoder *e, const void *d_pixels, size_t row_pitch, 
     if (dc_late) {
       if (!v3) return fail(MJH_EINVAL, "internal: the late DC chains need the tile-sorted trellis' event");
       HIPCHK(hipStreamWaitEvent(e->side_stream, e->ev_side0, 0));
-      mjh_launch_trellis_dc(CV, e->d_quant, e->d_uq, e->d_q, e->d_tabs, spi, sl_dc, e->d_lambda, e->d_back, n, e->side_stream, e->dc_window_ok, e->dc_late * CV.mcu_rows, -1);
+      mjh_launch_trellis_dc(CV, e->d_quant, e->d_uq, e->d_q, e->d_tabs, spi, sl_dc, e->d_lambda, e->d_back, n, e->side_stream, e->dc_window_ok, e->dc_late * CV.mcu_rows, -1, e->dc_lanes);
       mjh_launch_stats_dc(C, e->d_q, e->d_tabs, spi, fin_dc, 1, zero4, n, e->side_stream);
       final_dc_counted = true;
       HIPCHK(hipEventRecord(e->ev_join, e->side_stream));
@@ -2121,6 +2129,7 @@ static int make_twin(mjh_encoder *e)
   mjh_encoder *t = nullptr;
   g_create_twin = true;
   g_twin_onepass = e->enc_onepass;
+  g_twin_dc_lanes = e->dc_lanes; g_twin_dc_lanes_set = e->dc_lanes_set;
   g_twin_avoid[0] = e->stream; g_twin_avoid[1] = e->side_stream;
   const int rc = mjh_encoder_create(&e->p_created, e->max_batch, e->device, &t);
   g_create_twin = false;
@@ -3438,6 +3447,16 @@ extern "C" int mjh_decode_stats(mjh_encoder *e, int *width, int *height, int *pi
       for (int k = 0; k < 2; k++) HIPCHK(hipEventElapsedTime(&ms[k], e->dp_ev[k], e->dp_ev[k + 1]));
     }
   }
+  return MJH_OK;
+}
+
+// Which DC trellis kernels the latest call launched: 0 none (no DC trellis), 1 one lane per chain (k_trellis_dc_lane), 2 k_trellis_dc3,
+// 3 k_trellis_dc2, 4 the speculative pair.  (The call may have been run by the second buffer set.)
+extern "C" int mjh_get_dc_path(mjh_encoder *e, int *path)
+{
+  if (!e || !path) return fail(MJH_EINVAL, "null argument");
+  const mjh_encoder *x = e->last ? e->last : e;
+  *path = x->dc_path;
   return MJH_OK;
 }
 

@@ -1608,6 +1608,206 @@ k_trellis_dc3(MjhConst C, const MjhQuant *__restrict__ Q, const int16_t *__restr
 }
 
 // ---------------------------------------------------------------------------------------------
+// K6 for large batches: ONE LANE PER CHAIN.  k_trellis_dc3 fills 9 of the 16 lanes of a DPP row and spends about 45 of its
+// ~111 wave instructions per block step on moving the nine predecessors between lanes.  With tens of thousands of chains in a
+// launch a lane can own a whole chain instead: it keeps the NC costs of the predecessor block in registers, evaluates the
+// 2 NC - 1 distinct rates once and does the NC x NC step itself; all 64 lanes work and nothing crosses lanes (plain C++: no
+// DPP, no LDS, no inline assembly).  The same float operations on the same values as dc3: cost = prev + (rate + dist),
+// dist = (float)(delta * delta) * (lambda * lambda_tbl[0]).
+// Orientation: the costs of a block are kept in its own CANDIDATE order (index kk, value sign * (qv - h + kk)), so that the
+// reference's "first minimum" over the predecessor's candidates (:1100-1106) is the lowest index.  A step runs in the
+// predecessor's orientation R (R = 1: its raw DC was negative, its values fall with the index): slot a holds the current
+// block's value c0 + (R ? NC - 1 - a : a), so the difference to predecessor i is D + (R ? -1 : 1) * (a - i) and its rate is
+// rate[a - i + NC - 1] of |(R ? -D : D) + t - (NC - 1)|, t = 0 .. 2 NC - 2 -- static register indices throughout.  The
+// new costs are then turned into the block's own order (`flip`: its sign differs from the predecessor's).
+// The first block of a row has one pseudo-predecessor: value lastDC at index 0 with cost 0.0 (0.0 + x == x), the others 3e38.
+// Back pointers: per block one 8-byte word, packed into the first half of the component's 16-byte slots of `back`: nibble a =
+// the predecessor's candidate index, bit 36 flip, bit 37 negative, bits 48..63 qv - h; the back-track reads nothing else (its
+// loads do not depend on the path).
+// Lanes are the chains of ONE component over the whole batch, image-major: every lane of a launch has the same chain length.
+// ---------------------------------------------------------------------------------------------
+#ifndef DCL_BLOCK
+#define DCL_BLOCK 128    // lanes per workgroup (no lane needs another; measured 64 / 128: profiles/dc_lanes_ab.md)
+#endif
+#ifndef DCL_G
+#define DCL_G 8      // blocks per group (even): their inputs (forward) / words (back-track) are one load per lane, issued a group ahead
+#endif
+template <int NC> __device__ __forceinline__ float dc_lane_min(const float (&c)[NC])       // a tree of three-way minima (costs are never NaN)
+{
+  float m = fminf(fminf(c[0], c[1]), c[2]);
+  if constexpr (NC == 5) m = fminf(fminf(m, c[3]), c[4]);
+  if constexpr (NC >= 7) {
+    const float m1 = fminf(fminf(c[3], c[4]), c[5]);
+    if constexpr (NC == 7) m = fminf(fminf(m, m1), c[6]);
+    else m = fminf(fminf(m, m1), fminf(fminf(c[6], c[7]), c[8]));
+  }
+  return m;
+}
+template <int NC>
+__device__ __forceinline__ void dc_lane_chain(const MjhComp &cc, int imcu, unsigned long long rsi, int dq, float rcp, float lt0,
+                                              const int16_t *__restrict__ uq0, int16_t *__restrict__ qo0, const float *__restrict__ lam, uint4 *__restrict__ bk)
+{
+  constexpr int N1 = NC - 1, H = NC / 2;
+  int last_dc = 0;
+  for (int sub = 0; sub < cc.v; sub++) {
+    const int br = imcu * cc.v + sub;
+    if (br >= cc.hib) break;      // (the last iMCU row of an odd block-row count)
+    const int row0 = br * cc.wib;
+    float pc[NC];                 // the predecessor's costs, in its candidate order
+    pc[0] = 0.0f;
+#pragma unroll
+    for (int i = 1; i < NC; i++) pc[i] = 3e38f;
+    int prev_c0 = last_dc, R = 0;
+    // The raw DC and lambda of DCL_G blocks come in ONE load each per lane, a group ahead of their use, and the group's back-pointer
+    // words leave in 16-byte stores: every lane's addresses are its own row's, so each access of the wave touches 64 cache lines, and
+    // with three such accesses per block the step was bound by them, not by its arithmetic (2.7 instead of 1.8 us; profiles/dc_lanes_ab.md).
+    // (a row that starts on an odd block is 2-byte aligned only, a lambda row 4-byte: the wide loads and stores below rely on the
+    // target's unaligned access mode for global memory, as every amdhsa target has it)
+    struct alignas(2) XsG { int16_t v[DCL_G]; };
+    struct alignas(4) LamG { float v[DCL_G]; };
+    struct alignas(8) BackG { uint2 v[DCL_G]; };
+    uint2 *bk8 = reinterpret_cast<uint2 *>(bk);          // one 8-byte word per block, packed (the first half of the component's slots)
+    auto fetch = [&](int g, XsG &xo, LamG &lo) {
+      if (g + DCL_G <= cc.wib) {
+        __builtin_memcpy(&xo, uq0 + row0 + g, sizeof(XsG));
+        __builtin_memcpy(&lo, lam + row0 + g, sizeof(LamG));
+      } else {
+#pragma unroll
+        for (int s = 0; s < DCL_G; s++) { const int b = min(g + s, cc.wib - 1); xo.v[s] = uq0[row0 + b]; lo.v[s] = lam[row0 + b]; }
+      }
+    };
+    XsG xs_c, xs_n;
+    LamG lam_c, lam_n;
+    fetch(0, xs_c, lam_c);
+    for (int g = 0; g < cc.wib; g += DCL_G) {
+      fetch(g + DCL_G, xs_n, lam_n);      // in flight while these are walked
+      BackG bw;
+#pragma unroll
+      for (int s = 0; s < DCL_G; s++) {
+        bw.v[s] = make_uint2(0, 0);
+        if (g + s < cc.wib) {
+          const int xs = xs_c.v[s];
+          const float lambda_dc = lam_c.v[s] * lt0;
+          const int x = xs < 0 ? -xs : xs, neg = xs < 0 ? 1 : 0;
+          const int qv = udiv_exact(x + (dq >> 1), dq, rcp);
+          const int c0 = neg ? -(qv + H) : qv - H;           // the lowest candidate value
+          const int D = c0 - prev_c0, Dp = R ? -D : D;
+          const int flip = neg ^ R;
+          float rt[2 * NC - 1];
+#pragma unroll
+          for (int t = 0; t < 2 * NC - 1; t++) rt[t] = dc_rate(rsi, Dp + t - N1);
+          // slot a = candidate kk = flip ? N1 - a : a
+          const int dA = mul24(qv - H + (flip ? N1 : 0), dq) - x, stq = flip ? -dq : dq;
+          float best[NC];
+          unsigned lo = 0, hi = 0;
+#pragma unroll
+          for (int a = 0; a < NC; a++) {
+            const int delta = dA + mul24(a, stq);
+            const float dist = (float)mul24(delta, delta) * lambda_dc;
+            float c[NC];
+#pragma unroll
+            for (int i = 0; i < NC; i++) c[i] = pc[i] + (rt[a - i + N1] + dist);
+            const float m = dc_lane_min<NC>(c);
+            int bb = N1;
+#pragma unroll
+            for (int i = N1 - 1; i >= 0; i--) bb = c[i] == m ? i : bb;       // the first minimum, as the reference's strict '<' scan keeps it
+            best[a] = m;
+            if (a < 8) lo |= (unsigned)bb << (4 * a); else hi = (unsigned)bb;
+          }
+#pragma unroll
+          for (int k = 0; k < NC; k++) pc[k] = flip ? best[N1 - k] : best[k];
+          prev_c0 = c0;
+          R = neg;
+          hi |= (unsigned)flip << 4 | (unsigned)neg << 5 | (unsigned)((qv - H) & 0xFFFF) << 16;
+          bw.v[s] = make_uint2(lo, hi);
+        }
+      }
+      if (g + DCL_G <= cc.wib && ((row0 + g) & 1) == 0) {      // (16-byte aligned: whole 16-byte stores)
+#pragma unroll
+        for (int s = 0; s < DCL_G; s += 2) *reinterpret_cast<uint4 *>(bk8 + row0 + g + s) = make_uint4(bw.v[s].x, bw.v[s].y, bw.v[s + 1].x, bw.v[s + 1].y);
+      } else
+#pragma unroll
+        for (int s = 0; s < DCL_G; s++) if (g + s < cc.wib) bk8[row0 + g + s] = bw.v[s];
+      xs_c = xs_n; lam_c = lam_n;
+    }
+    // first minimum over the candidates of the last block, in candidate order (:1309-1313)
+    int j = N1;
+    {
+      const float m = dc_lane_min<NC>(pc);
+#pragma unroll
+      for (int i = N1 - 1; i >= 0; i--) j = pc[i] == m ? i : j;
+    }
+    __threadfence_block();
+    // back-track: the words of DCL_G blocks in one load, a group ahead (they do not depend on the path); their values in one store
+    auto fetch_back = [&](int top, BackG &wo) {
+      if (top - (DCL_G - 1) >= 0 && ((row0 + top - (DCL_G - 1)) & 1) == 0) {
+#pragma unroll
+        for (int s = 0; s < DCL_G; s += 2) {
+          const uint4 q = *reinterpret_cast<const uint4 *>(bk8 + row0 + top - (DCL_G - 1) + s);
+          wo.v[s] = make_uint2(q.x, q.y); wo.v[s + 1] = make_uint2(q.z, q.w);
+        }
+      } else
+#pragma unroll
+        for (int s = 0; s < DCL_G; s++) wo.v[s] = bk8[row0 + max(top - (DCL_G - 1) + s, 0)];
+    };
+    BackG w_c, w_n;
+    fetch_back(cc.wib - 1, w_c);
+    for (int top = cc.wib - 1; top >= 0; top -= DCL_G) {
+      fetch_back(top - DCL_G, w_n);
+      XsG out;
+#pragma unroll
+      for (int s = DCL_G - 1; s >= 0; s--) {           // block top - (DCL_G - 1) + s
+        out.v[s] = 0;
+        if (top - (DCL_G - 1) + s >= 0) {
+          const uint2 w = w_c.v[s];
+          int cnd = (int)(short)(w.y >> 16) + j;
+          if (w.y & 32u) cnd = -cnd;
+          out.v[s] = (int16_t)cnd;
+          if (s == DCL_G - 1 && top == cc.wib - 1) last_dc = cnd;
+          const int a = (w.y & 16u) ? N1 - j : j;
+          j = (int)(((((unsigned long long)w.y) << 32 | w.x) >> (4 * a)) & 15u);
+        }
+      }
+      if (top - (DCL_G - 1) >= 0) __builtin_memcpy(qo0 + row0 + top - (DCL_G - 1), &out, sizeof(XsG));
+      else
+#pragma unroll
+        for (int s = 0; s < DCL_G; s++) if (top - (DCL_G - 1) + s >= 0) qo0[row0 + top - (DCL_G - 1) + s] = out.v[s];
+      w_c = w_n;
+    }
+  }
+}
+
+// chains [imcu0, imcu0 + cnt) of component `comp` of every image: lane t = image t / cnt, iMCU row imcu0 + t % cnt
+__global__ void __launch_bounds__(DCL_BLOCK)
+k_trellis_dc_lane(MjhConst C, const MjhQuant *__restrict__ Q, const int16_t *__restrict__ coef_uq,
+                  int16_t *__restrict__ coef_q, const MjhHuffTable *__restrict__ tabs, int slots_per_image,
+                  int slot, const float *__restrict__ lambda_in, uint8_t *__restrict__ back, int comp, int imcu0, int cnt, int total)
+{
+  const int t = blockIdx.x * DCL_BLOCK + threadIdx.x;
+  if (t >= total) return;       // (no lane needs another: the last wave may be short)
+  const int img = t / cnt, imcu = imcu0 + (t - img * cnt);
+  const MjhComp cc = C.c[comp];
+  const MjhHuffTable *T = tabs + (size_t)img * slots_per_image + slot;
+  unsigned long long rsi = 0;   // 12 x 5 bits: category + its code length
+  for (int s = 0; s < 12; s++) rsi |= (unsigned long long)((T->ehufsi[s] + s) & 31) << (5 * s);
+  const int q0 = Q->q[cc.qtbl][0];
+  const int dq = 8 * q0;
+  const float rcp = Q->rcp8q[cc.qtbl][0];
+  const float lt0 = Q->lambda_tbl[cc.qtbl][0];
+  int ncand = (2 + 60 / q0) | 1;                 // get_num_dc_trellis_candidates :930-933
+  if (ncand > 9) ncand = 9;
+  const int16_t *uq0 = coef_uq + (size_t)img * C.coefs_per_image + cc.coef_off;  // plane k = 0
+  int16_t *qo0 = coef_q + (size_t)img * C.coefs_per_image + cc.coef_off;
+  const float *lam = lambda_in + (size_t)img * C.total_real_blocks + cc.blk_off;
+  uint4 *bk = reinterpret_cast<uint4 *>(back) + ((size_t)img * C.total_real_blocks + cc.blk_off);
+  // (one quantizer step per launch: the whole wave takes one of these)
+  if (ncand == 9) dc_lane_chain<9>(cc, imcu, rsi, dq, rcp, lt0, uq0, qo0, lam, bk);
+  else if (ncand == 7) dc_lane_chain<7>(cc, imcu, rsi, dq, rcp, lt0, uq0, qo0, lam, bk);
+  else if (ncand == 5) dc_lane_chain<5>(cc, imcu, rsi, dq, rcp, lt0, uq0, qo0, lam, bk);
+  else dc_lane_chain<3>(cc, imcu, rsi, dq, rcp, lt0, uq0, qo0, lam, bk);
+}
+
+// ---------------------------------------------------------------------------------------------
 // K6 for one or two frames: block rows walked SPECULATIVELY (round 4).  With a single 4K frame on the chip the DC trellis is
 // the critical path of the whole encode (402 of 690 us): a luma chain is the 2 block rows of an iMCU row walked one after the
 // other, because the first block of the second row is rated against the FINAL last value of the first row (lastDC,
@@ -2684,17 +2884,40 @@ void mjh_launch_trellis_dc_speculative(const MjhConst &C, const MjhQuant *Q, con
   hipLaunchKernelGGL(k_trellis_dc3_resolve, dim3(C.ncomp * C.mcu_rows, n), dim3(64), 0, s, C, (int16_t *)q, (const int *)jfin, (const int16_t *)qspec, rows);
 }
 
-void mjh_launch_trellis_dc(const MjhConst &C, const MjhQuant *Q, const void *uq, void *q, const MjhHuffTable *tabs, int spi, const int dc_slot[4], const float *lambda, void *back, int n, hipStream_t s,
-                           int window_ok, int chain0, int chain1)
+// one lane per chain: the window kernel's conditions, and at least lanes_min chains PER COMPONENT in the call (frames x iMCU rows; 0:
+// never).  What has to be hidden is one luma chain next to the AC trellis of the whole batch, so the criterion counts what grows with
+// the batch and does not depend on how the call splits its chains into launches (MJH_DC_LATE).
+bool mjh_trellis_dc_lanes_ok(const MjhConst &C, int window_ok, int n, int lanes_min)
+{
+  return window_ok && C.delta_dc_weight <= 0.0f && lanes_min > 0 && (long long)n * C.mcu_rows >= lanes_min;
+}
+
+int mjh_launch_trellis_dc(const MjhConst &C, const MjhQuant *Q, const void *uq, void *q, const MjhHuffTable *tabs, int spi, const int dc_slot[4], const float *lambda, void *back, int n, hipStream_t s,
+                          int window_ok, int chain0, int chain1, int lanes_min)
 {
   const int nchains = C.ncomp * C.mcu_rows;
   if (chain1 < 0 || chain1 > nchains) chain1 = nchains;      // (default: every chain)
-  if (chain0 >= chain1) return;
+  if (chain0 >= chain1) return MJH_DC_PATH_NONE;
+  // one lane per chain when the launch has enough chains to fill waves with them: one launch per component, so that every
+  // lane of a wave walks the same number of blocks
+  if (mjh_trellis_dc_lanes_ok(C, window_ok, n, lanes_min)) {
+    for (int c = 0; c < C.ncomp; c++) {
+      const int lo = chain0 > c * C.mcu_rows ? chain0 : c * C.mcu_rows, hi = chain1 < (c + 1) * C.mcu_rows ? chain1 : (c + 1) * C.mcu_rows;
+      if (lo >= hi) continue;
+      const int cnt = hi - lo, total = n * cnt;
+      hipLaunchKernelGGL(k_trellis_dc_lane, dim3((total + DCL_BLOCK - 1) / DCL_BLOCK), dim3(DCL_BLOCK), 0, s, C, Q, (const int16_t *)uq, (int16_t *)q, tabs, spi, dc_slot[c], lambda, (uint8_t *)back,
+                         c, lo - c * C.mcu_rows, cnt, total);
+    }
+    return MJH_DC_PATH_LANE;
+  }
   dim3 grid((chain1 - chain0 + 3) / 4, n);
   // the sliding-window kernel when every DC quantizer step 8q is >= 40 and the vertical-gradient term is off; the general DPP kernel otherwise
-  if (window_ok && C.delta_dc_weight <= 0.0f)
+  if (window_ok && C.delta_dc_weight <= 0.0f) {
     hipLaunchKernelGGL(k_trellis_dc3, grid, dim3(64), 0, s, C, Q, (const int16_t *)uq, (int16_t *)q, tabs, spi, make_int4(dc_slot[0], dc_slot[1], dc_slot[2], dc_slot[3]), lambda, (uint8_t *)back, chain0, chain1);
-  else hipLaunchKernelGGL(k_trellis_dc2, grid, dim3(64), 0, s, C, Q, (const int16_t *)uq, (int16_t *)q, tabs, spi, make_int4(dc_slot[0], dc_slot[1], dc_slot[2], dc_slot[3]), lambda, (uint8_t *)back, chain0, chain1);
+    return MJH_DC_PATH_DC3;
+  }
+  hipLaunchKernelGGL(k_trellis_dc2, grid, dim3(64), 0, s, C, Q, (const int16_t *)uq, (int16_t *)q, tabs, spi, make_int4(dc_slot[0], dc_slot[1], dc_slot[2], dc_slot[3]), lambda, (uint8_t *)back, chain0, chain1);
+  return MJH_DC_PATH_DC2;
 }
 
 void mjh_launch_encode(const MjhConst &C, const void *q, const unsigned long long *nzmask, const MjhHuffTable *tabs, int spi, const int dc_slot[4], const int ac_slot[4],

@@ -30,8 +30,12 @@ void mjh_launch_qopt_update(void *sums, MjhQuant *Q, int n, hipStream_t s);   //
 void mjh_launch_qopt_fix(const MjhQuant *Q, void *out, size_t out_stride, unsigned *sizes, int dqt_start, int sof_off, const int *tabs, int ntab,
                          int multi, int baseline_capable, int n, hipStream_t s);
 // window_ok: every component's DC quantizer step 8q is >= 40 (candidate values are then never clamped: the sliding-window kernel applies)
-void mjh_launch_trellis_dc(const MjhConst &C, const MjhQuant *Q, const void *uq, void *q, const MjhHuffTable *tabs, int spi, const int dc_slot[4], const float *lambda, void *back, int n, hipStream_t s,
-                           int window_ok = 0, int chain0 = 0, int chain1 = -1);   // chains [chain0, chain1) of every image (component-major, one per iMCU row); -1: all
+// lanes_min > 0: a call with at least that many chains per component (n x iMCU rows) that meets the window kernel's conditions runs one
+// lane per chain (k_trellis_dc_lane), whatever range of its chains this launch takes.  Returns the kernel family that was launched (mjh_get_dc_path).
+enum { MJH_DC_PATH_NONE = 0, MJH_DC_PATH_LANE = 1, MJH_DC_PATH_DC3 = 2, MJH_DC_PATH_DC2 = 3, MJH_DC_PATH_SPEC = 4 };
+bool mjh_trellis_dc_lanes_ok(const MjhConst &C, int window_ok, int n, int lanes_min);
+int mjh_launch_trellis_dc(const MjhConst &C, const MjhQuant *Q, const void *uq, void *q, const MjhHuffTable *tabs, int spi, const int dc_slot[4], const float *lambda, void *back, int n, hipStream_t s,
+                          int window_ok = 0, int chain0 = 0, int chain1 = -1, int lanes_min = 0);   // chains [chain0, chain1) of every image (component-major, one per iMCU row); -1: all
 void mjh_launch_encode(const MjhConst &C, const void *q, const unsigned long long *nzmask, const MjhHuffTable *tabs, int spi, const int dc_slot[4], const int ac_slot[4],
                        void *len16, void *off32, unsigned *sums, int chunks_per_image, unsigned *totals,
                        unsigned *stream, size_t stream_words_per_image, void *meta,
