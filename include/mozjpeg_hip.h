@@ -464,7 +464,13 @@ int mjh_encoder_set_transform(mjh_encoder *e, const mjh_transform *t);
  * the reference then runs the reduced transform of a component the pixel path would have left at size 8 -- chroma of a 4:2:0
  * file at 1/2 -- on the fast method's multiplier table; so does this call, for the reference's bytes.)  out_color_space,
  * pixel_size, rgb_offset, fancy_upsampling and bottom_up are ignored.
- * dct_method, bottom_up, raw_planes and no_dither were appended; 0 in all of them is the behaviour of the struct without them.
+ * raw_coefs: the call stops after the Huffman decoder (its DC sums and the scrub of damaged files included) and produces neither
+ * pixels nor planes: the files' quantized DCT coefficients (jpeg_read_coefficients, jdtrans.c), through mjh_get_coefs /
+ * mjh_get_coefs_device -- per component [height_in_blocks][blocks_per_row][64] int16, block-major, natural order: the arrays
+ * mjh_encode_coefficients_host / _device read.  The values are the 16 bits the reference's JCOEF holds; no +-1023 limit is
+ * applied (that is the entropy coder's: a file with a larger value decodes here and is refused when it is coded again).  Every
+ * other field of the struct is ignored, raw_planes too.  The files accepted are those of mjh_transcode_host.
+ * dct_method, bottom_up, raw_planes, no_dither and raw_coefs were appended; 0 in all of them is the behaviour of the struct without them.
  * MJH_EINVAL: an unknown colour space, pixel size, offsets or dct_method; a pixel size other than 0 or 2 or an offset with RGB565; a scale_num or scale_denom below 1 (other than 0/0).
  * MJH_EUNSUPPORTED: a lossless transform set on the encoder; a scale that resolves to an IDCT size of 3, 5, 6, 7 or 9 to 16;
  * the float IDCT, cropping and colour quantization have no option here. */
@@ -478,6 +484,7 @@ typedef struct {
   int bottom_up;
   int raw_planes;
   int no_dither;
+  int raw_coefs;
 } mjh_decode_opts;
 void mjh_decode_opts_defaults(mjh_decode_opts *o);
 /* Decodes n files (opts == NULL: the defaults).  Queued on the encoder's stream; the bytes need not stay valid after the call.
@@ -499,12 +506,30 @@ int mjh_get_pixels_device(mjh_encoder *e, void **d_base, size_t *row_pitch, size
 /* After a raw_planes call: copies the top-left width x height samples of component comp of image i to host memory, row_pitch
  * bytes between rows (synchronises).  The plane holds the component's real blocks at the call's IDCT size k: (blocks across * k)
  * x (blocks down * k) samples, never fewer than ceil(W h k / (8 hmax)) x ceil(H v k / (8 vmax)); more than that is MJH_EINVAL.
- * After a call that made pixels: MJH_EINVAL (and mjh_get_pixels after a raw_planes call likewise). */
+ * After a call that made pixels or coefficients: MJH_EINVAL (and mjh_get_pixels after a raw_planes or raw_coefs call likewise). */
 int mjh_get_plane(mjh_encoder *e, int i, int comp, void *dst, size_t row_pitch, int width, int height);
 /* The device view of the same planes: sample (x, y) of component comp of image i is at base + i * image_stride + y * row_pitch
  * + x, for x < width and y < height.  Does not wait (see mjh_get_pixels_device).  Any pointer may be NULL. */
 int mjh_get_planes_device(mjh_encoder *e, int comp, void **d_base, size_t *row_pitch, size_t *image_stride, int *width, int *height);
-/* Size (the scaled one) and pixel size of the last decoded batch (0 after a raw_planes call) and, with mjh_set_profiling(e, 1), the milliseconds of its two pixel kernels:
+/* After a raw_coefs call: the device arrays of component comp.  Coefficient k (natural order) of block (row, col) of image i is
+ * the int16 at base + i * image_stride + ((row * blocks_per_row + col) * 64 + k) * 2, for row < height_in_blocks and
+ * col < blocks_per_row; the columns from width_in_blocks on are padding (the width the reference rounds its arrays up to) and
+ * hold zeros, as every block of a damaged file does.  image_stride = height_in_blocks * blocks_per_row * 128: the batch is one
+ * contiguous [n][height_in_blocks][blocks_per_row][64] array, which mjh_encode_coefficients_device takes as it is.  Does not wait
+ * (see mjh_get_pixels_device): mjh_decode_wait waits and reports damaged files.  The buffer is made by the first raw_coefs call
+ * and reused by the next.  Any pointer may be NULL.  After a call that made pixels or planes: MJH_EINVAL. */
+int mjh_get_coefs_device(mjh_encoder *e, int comp, void **d_base, size_t *image_stride, int *blocks_per_row, int *height_in_blocks, int *width_in_blocks);
+/* Copies the height_in_blocks x width_in_blocks real blocks of component comp of image i to host memory, dst_blocks_per_row
+ * blocks (of 64 int16) between rows, at least width_in_blocks (synchronises).  MJH_EINVAL after a call that made pixels or planes,
+ * and for a batch with a damaged file (mjh_transcode_status tells which). */
+int mjh_get_coefs(mjh_encoder *e, int i, int comp, void *dst, size_t dst_blocks_per_row);
+/* With mjh_set_profiling(e, 1): the milliseconds of the last raw_coefs call's export kernel (0 without profiling), the phase
+ * behind the four of the Huffman decoder that mjh_transcode_stats reports for the same call.  It is a call of its own because
+ * mjh_transcode_stats and mjh_decode_stats write into arrays of 4 and 2 floats that their callers own: a fifth value there
+ * would overrun every caller built against the header as it was.  The Python binding appends it to transcode_stats()["ms"] as
+ * "export".  ms may be NULL.  After a call that made pixels or planes: MJH_EINVAL. */
+int mjh_get_coefs_ms(mjh_encoder *e, float *ms);
+/* Size (the scaled one) and pixel size of the last decoded batch (0 after a raw_planes or raw_coefs call) and, with mjh_set_profiling(e, 1), the milliseconds of its two pixel kernels:
  * [0] dequantization + inverse DCT, [1] upsampling + colour conversion (the Huffman decoder's phases: mjh_transcode_stats).
  * Any pointer may be NULL. */
 int mjh_decode_stats(mjh_encoder *e, int *width, int *height, int *pixel_size, float ms[2]);

@@ -85,10 +85,10 @@ class JpegInfo(C.Structure):
 
 class DecodeOpts(C.Structure):
     """mjh_decode_opts: what djpeg's -grayscale / -rgb / -nosmooth / -scale / -dct and the extended pixel layouts choose, TurboJPEG's
-    bottom-up rows, and the raw sample planes instead of pixels"""
+    bottom-up rows, and the raw sample planes or the DCT coefficients instead of pixels"""
     _fields_ = [("out_color_space", C.c_int), ("pixel_size", C.c_int), ("rgb_offset", C.c_int * 3), ("fancy_upsampling", C.c_int),
                 ("scale_num", C.c_int), ("scale_denom", C.c_int), ("dct_method", C.c_int), ("bottom_up", C.c_int), ("raw_planes", C.c_int),
-                ("no_dither", C.c_int)]
+                ("no_dither", C.c_int), ("raw_coefs", C.c_int)]
 
 
 class Result(C.Structure):
@@ -181,6 +181,10 @@ def lib():
             L.mjh_get_planes_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                                 C.POINTER(C.c_int), C.POINTER(C.c_int)]
             L.mjh_transcode_batch_size.argtypes = [C.c_void_p]
+        if hasattr(L, "mjh_get_coefs"):
+            L.mjh_get_coefs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+            L.mjh_get_coefs_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)] + [C.POINTER(C.c_int)] * 3
+            L.mjh_get_coefs_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         if hasattr(L, "mjh_get_dc_path"):
             L.mjh_get_dc_path.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         if hasattr(L, "mjh_enc_onepass_stats"):       # (absent from a MOZJPEG_AMD_LIB variant built from an older tree: A/B runs against it)
@@ -496,12 +500,13 @@ DCT_METHODS = {None: 0, "int": 0, "islow": 0, "fast": 1, "ifast": 1}     # djpeg
 
 
 def decode_opts(color=None, layout=None, pixel_size=0, rgb_offset=None, fancy_upsampling=True, scale=None, dct=None, bottom_up=False,
-                raw_planes=False, dither=True):
+                raw_planes=False, dither=True, raw_coefs=False):
     """DecodeOpts from djpeg's vocabulary.  color: None (the file's default: gray stays gray, everything else RGB), "gray" /
     "grayscale" (-grayscale), "rgb" (-rgb), "rgb565" (-rgb565: 16-bit pixels, with dither=False -dither none) or a CS_* number; layout: a name out of PIXEL_LAYOUTS, or pixel_size and rgb_offset;
     fancy_upsampling=False: -nosmooth; scale: -scale, a pair (num, denom) or a string "M/N" that resolves to 1/8, 2/8, 4/8 or
     8/8 as djpeg resolves it (scale_idct_size); dct: "int" (the default) or "fast" (-dct fast, TurboJPEG's FASTDCT);
-    bottom_up=True: the rows last to first (TurboJPEG's BOTTOMUP); raw_planes=True: no pixels, the sample planes (decode_planes)."""
+    bottom_up=True: the rows last to first (TurboJPEG's BOTTOMUP); raw_planes=True: no pixels, the sample planes (decode_planes);
+    raw_coefs=True: nothing of the above, the quantized DCT coefficients (decode_coefficients)."""
     o = DecodeOpts()
     lib().mjh_decode_opts_defaults(C.byref(o))
     if isinstance(color, str):
@@ -531,6 +536,7 @@ def decode_opts(color=None, layout=None, pixel_size=0, rgb_offset=None, fancy_up
     o.bottom_up = int(bool(bottom_up))
     o.raw_planes = int(bool(raw_planes))
     o.no_dither = int(not dither)
+    o.raw_coefs = int(bool(raw_coefs))
     # the library's own checks (plan_pixels), made here as well so that decode() can refuse its options before it groups files
     if o.dct_method not in (0, 1):
         raise MjhError(EINVAL, "dct_method %d of a decode call (0 = JDCT_ISLOW, 1 = JDCT_IFAST)" % o.dct_method)
@@ -586,6 +592,14 @@ def decode_planes(files, scale=None, dct=None, *, max_batch=64, device=0):
     Every component is transformed at the scale's own size (mjh_decode_opts.raw_planes), so the planes keep the file's
     subsampling at every scale."""
     return _decode_grouped(files, max_batch, device, decode_opts(scale=scale, dct=dct, raw_planes=True))
+
+
+def decode_coefficients(files, *, max_batch=64, device=0):
+    """Decode JPEG files to their quantized DCT coefficients on the GPU (jpeg_read_coefficients): per file a list of int16 arrays
+    [height_in_blocks, width_in_blocks, 64], one per component, block-major and in natural order -- what
+    Encoder.encode_coefficients_host takes -- or the MjhError in its slot.  The values are the file's own (no limit of +-1023 is
+    applied; the entropy coder refuses what it cannot code).  The quantization tables they belong to: jpeg_info(f).quantval."""
+    return _decode_grouped(files, max_batch, device, decode_opts(raw_coefs=True))
 
 
 def _decode_grouped(files, max_batch, device, o):
@@ -837,10 +851,15 @@ class Encoder:
         return rc, (t.value or b"").decode()
 
     def transcode_stats(self):
-        """subsequence bytes, synchronisation rounds, host synchronisations and decoder phase times (ms, with profiling) of the last transcode call"""
+        """subsequence bytes, synchronisation rounds, host synchronisations and decoder phase times (ms, with profiling) of the last transcode call;
+        after a batch decoded with coefficients=True the times end with "export", the export kernel's"""
         a, b, c, ms = C.c_int(), C.c_int(), C.c_int(), (C.c_float * 4)()
         _chk(lib().mjh_transcode_stats(self._h, C.byref(a), C.byref(b), C.byref(c), ms))
-        return dict(subseq=a.value, rounds=b.value, host_syncs=c.value, ms=dict(zip(("sync", "prefix", "store", "dc"), [float(x) for x in ms])))
+        phases = dict(zip(("sync", "prefix", "store", "dc"), [float(x) for x in ms]))
+        x = C.c_float()
+        if hasattr(lib(), "mjh_get_coefs_ms") and lib().mjh_get_coefs_ms(self._h, C.byref(x)) == OK:
+            phases["export"] = float(x.value)       # the last batch was decoded with coefficients=True: k_export_coefs behind the decoder
+        return dict(subseq=a.value, rounds=b.value, host_syncs=c.value, ms=phases)
 
     def enc_onepass_stats(self):
         """the one-walk Huffman coder (MJH_ENC_ONEPASS): whether it is on, and how often its two slower paths ran since the encoder was made"""
@@ -874,12 +893,12 @@ class Encoder:
             return res
 
     # existing files in, pixels out (djpeg): Huffman decoding, inverse DCT, upsampling and colour conversion on the device
-    def submit_decode(self, files, opts=None, **kw):
+    def submit_decode(self, files, opts=None, coefficients=False, **kw):
         """Asynchronous mjh_decode_host (opts: a DecodeOpts, or decode_opts()' keywords); results through get_pixels() /
-        pixels_device()."""
+        pixels_device() -- with coefficients=True (raw_coefs) through get_coefficients() / coefficients_device()."""
         files = [bytes(f) for f in files]
         n = len(files)
-        o = opts if opts is not None else decode_opts(**kw)
+        o = opts if opts is not None else decode_opts(raw_coefs=coefficients, **kw)
         _chk(lib().mjh_decode_host(self._h, (C.c_char_p * n)(*files), (C.c_size_t * n)(*[len(f) for f in files]), n, C.byref(o)))
         return n
 
@@ -944,15 +963,37 @@ class Encoder:
         _chk(lib().mjh_get_planes_device(self._h, comp, C.byref(base), C.byref(pitch), C.byref(stride), C.byref(w), C.byref(h)))
         return base.value, pitch.value, stride.value, w.value, h.value
 
-    def decode_host(self, files, errors="raise", opts=None, **kw):
+    def get_coefficients(self, i):
+        """the coefficients of image i of the last batch decoded with coefficients=True: one int16 array [height_in_blocks,
+        width_in_blocks, 64] per component (mjh_get_coefs)"""
+        out = []
+        for c in range(self.params.num_components):
+            wib, hib = self.geometry(c)[:2]
+            a = np.empty((hib, wib, 64), np.int16)
+            _chk(lib().mjh_get_coefs(self._h, i, c, a.ctypes.data, wib))
+            out.append(a)
+        return out
+
+    def coefficients_device(self, comp):
+        """(device pointer, image stride in bytes, blocks per row, height in blocks, width in blocks) of component comp's arrays of
+        the last batch decoded with coefficients=True (mjh_get_coefs_device): int16 [n, height, blocks per row, 64], contiguous;
+        wait_decode() first"""
+        base, stride, bpr, hib, wib = C.c_void_p(), C.c_size_t(), C.c_int(), C.c_int(), C.c_int()
+        _chk(lib().mjh_get_coefs_device(self._h, comp, C.byref(base), C.byref(stride), C.byref(bpr), C.byref(hib), C.byref(wib)))
+        return base.value, stride.value, bpr.value, hib.value, wib.value
+
+    def decode_host(self, files, errors="raise", opts=None, coefficients=False, **kw):
         """files: JPEG byte strings that agree with the encoder's parameters (params_from_jpeg).  Returns their pixels, a list of
-        numpy arrays -- or, with raw_planes, per file the list of its sample planes (get_planes).  errors="return": no exception
+        numpy arrays -- or, with raw_planes, per file the list of its sample planes (get_planes), with coefficients=True the list
+        of its coefficient arrays (get_coefficients).  errors="return": no exception
         for a batch with damaged files -- their slots hold the MjhError, the slots of the good files None (nothing of such a
         batch is handed out: submit the good ones again)."""
         n = len(files)
-        o = opts if opts is not None else decode_opts(**kw)
+        o = opts if opts is not None else decode_opts(raw_coefs=coefficients, **kw)
         try:
             self.submit_decode(files, opts=o)
+            if o.raw_coefs:
+                return [self.get_coefficients(i) for i in range(n)]
             if o.raw_planes:
                 k = 8 if o.scale_num == 0 and o.scale_denom == 0 else scale_idct_size(o.scale_num, o.scale_denom)
                 return [self.get_planes(i, jpeg_info(files[i]), k) for i in range(n)]

@@ -8,8 +8,8 @@
  * jpeg_error_mgr ... are ABI; the message texts come from that tree's jerror.h the way its own jerror.c gets them).
  * Each entry point cites the reference function whose behaviour it keeps.
  *
- * Not provided: backing-store files of the memory manager (virtual arrays always live in memory), jpeg_read_coefficients
- * (a stub that raises JERR_NOT_COMPILED).  The objects, error and memory managers here serve both halves.
+ * Not provided: backing-store files of the memory manager (virtual arrays always live in memory).  The objects, error and
+ * memory managers here serve both halves (jpeg_read_coefficients is jpeg_dapi.c's).
  */
 #define JPEG_INTERNALS
 #include <stdio.h>
@@ -1014,16 +1014,3 @@ void jpeg_copy_critical_parameters(const j_decompress_ptr srcinfo, j_compress_pt
     dstinfo->Y_density = srcinfo->Y_density;
   }
 }
-
-/* =====================================================================================================================
- * what this library does not do.  The decompress API is jpeg_dapi.c's; reading a file's coefficient arrays (an unchanged
- * jpegtran on this library alone) is not built and raises JERR_NOT_COMPILED when it is called.
- * ===================================================================================================================== */
-#ifdef MJH_STANDALONE
-static void not_here(j_common_ptr cinfo, const char *what)
-{
-  fprintf(stderr, "mozjpeg_hip: %s is not part of this library (the GPU decoder delivers pixels and sample planes)\n", what);
-  ERREXIT(cinfo, JERR_NOT_COMPILED);
-}
-jvirt_barray_ptr *jpeg_read_coefficients(j_decompress_ptr cinfo) { not_here((j_common_ptr)cinfo, "jpeg_read_coefficients"); return NULL; }
-#endif

@@ -8,9 +8,13 @@
  * jdapimin.c / jdmaster.c.  Everything after the first SOS header is the device's: jpeg_start_decompress reads the rest of the
  * datastream through the client's source manager, hands ONE file to an encoder made from mjh_params_from_jpeg (leased from
  * the cache of the compress half), waits, and keeps the pixels in host memory; jpeg_read_scanlines copies rows out.
+ * jpeg_read_coefficients (jdtrans.c) does the same with mjh_decode_opts.raw_coefs and hands out the quantized coefficients in
+ * virtual arrays of the object's memory manager: an unchanged jpegtran runs on this library alone.  The arrays have the
+ * reference's padded dimensions and hold the reference's real blocks; their PADDING blocks are zero, where the reference keeps
+ * whatever an interleaved scan coded for its dummy blocks (jpeg_write_coefficients and transupp.c read real blocks only).
  *
  * Not built (JERR_NOT_COMPILED with one line on stderr): suspension (a source that returns FALSE: JERR_CANT_SUSPEND), buffered-image
- * mode, colour quantization, the float IDCT, IDCT sizes other than 1, 2, 4, 8, cropping / skipping scanlines, jpeg_read_coefficients,
+ * mode, colour quantization, the float IDCT, IDCT sizes other than 1, 2, 4, 8, cropping / skipping scanlines,
  * and every source mjh_jpeg_probe refuses.  Damaged entropy-coded data is FATAL at jpeg_start_decompress (the reference warns and
  * delivers a partial image): JERR_INPUT_EOF when the source ran dry (it said JWRN_JPEG_EOF), else JWRN_HUFF_BAD_CODE's text
  * as an error.
@@ -93,7 +97,9 @@ typedef struct {
   size_t row_bytes;
   unsigned char *planes[MAX_COMPONENTS];   /* raw_data_out: the components' real blocks */
   size_t plane_w[MAX_COMPONENTS], plane_h[MAX_COMPONENTS];
-  mjh_encoder *enc;            /* leased only inside jpeg_start_decompress */
+  mjh_encoder *enc;            /* leased only inside jpeg_start_decompress / jpeg_read_coefficients */
+  jvirt_barray_ptr *coef_arrays;   /* jpeg_read_coefficients: one array per component (JPOOL_IMAGE: gone with jpeg_abort) */
+  int latching;                /* jpeg_read_coefficients: every scan's components get their quant_table as the scan starts */
 } d_master;
 
 #define DM(cinfo) ((d_master *)(cinfo)->master)
@@ -116,6 +122,7 @@ void mjh_dapi_drop(void *obj)
   free(m->pixels); m->pixels = NULL;
   for (ci = 0; ci < MAX_COMPONENTS; ci++) { free(m->planes[ci]); m->planes[ci] = NULL; }
   if (m->enc) { mjh_shim_cache_release(m->enc); m->enc = NULL; }
+  m->coef_arrays = NULL; m->latching = 0;
 }
 
 /* =====================================================================================================================
@@ -984,6 +991,20 @@ static void put_kept_tables(j_decompress_ptr cinfo, unsigned char *dst, size_t *
   *n = p;
 }
 
+/* latch_quant_tables jdinput.c:233-260: the components of the scan that starts keep a copy of their table as it is NOW */
+static void latch_quant_tables(j_decompress_ptr cinfo)
+{
+  int ci;
+  for (ci = 0; ci < cinfo->comps_in_scan; ci++) {
+    jpeg_component_info *comp = cinfo->cur_comp_info[ci];
+    const int qn = comp->quant_tbl_no;
+    if (comp->quant_table != NULL) continue;
+    if (qn < 0 || qn >= NUM_QUANT_TBLS || cinfo->quant_tbl_ptrs[qn] == NULL) ERREXIT1(cinfo, JERR_NO_QUANT_TABLE, qn);
+    comp->quant_table = (JQUANT_TBL *)(*cinfo->mem->alloc_small) ((j_common_ptr)cinfo, JPOOL_IMAGE, sizeof(JQUANT_TBL));
+    memcpy(comp->quant_table, cinfo->quant_tbl_ptrs[qn], sizeof(JQUANT_TBL));
+  }
+}
+
 /* from behind an SOS header to EOI: entropy-coded data in whole runs, the segments between scans through read_markers */
 static void read_to_eoi(j_decompress_ptr cinfo)
 {
@@ -1006,6 +1027,7 @@ static void read_to_eoi(j_decompress_ptr cinfo)
     cinfo->unread_marker = c;
     if (read_markers(cinfo) == JPEG_REACHED_EOI) break;
     cinfo->inputctl->has_multiple_scans = TRUE;
+    if (DM(cinfo)->latching) latch_quant_tables(cinfo);
   }
   file_put1(cinfo, 0xFF); file_put1(cinfo, M_EOI);
   cinfo->inputctl->eoi_reached = TRUE;
@@ -1023,46 +1045,16 @@ static void decoder_failed(j_decompress_ptr cinfo, int rc, int damaged)
   ERREXIT1(cinfo, JERR_OUT_OF_MEMORY, 0);
 }
 
-boolean jpeg_start_decompress(j_decompress_ptr cinfo)
+/* What jpeg_start_decompress and jpeg_read_coefficients share: the tables the file may leave out, the rest of the datastream
+ * through the source manager, an encoder leased for the frame, ONE file decoded with the call's options and waited for.  The
+ * lease (DM(cinfo)->enc) is the caller's to end. */
+static void decode_file(j_decompress_ptr cinfo, const mjh_decode_opts *opts)
 {
   d_master *m = DM(cinfo);
-  mjh_decode_opts o;
   mjh_jpeg_info *info;
   mjh_params *p;
-  int ci, k, rc, off[3], px;
+  int ci, rc;
   double t0 = 0.0, t1;
-  if (cinfo->global_state != DSTATE_READY) ERREXIT1(cinfo, JERR_BAD_STATE, cinfo->global_state);
-  if (cinfo->buffered_image) refuse(cinfo, "buffered-image mode is not built (the GPU path decodes a whole file at once)");
-  if (cinfo->quantize_colors) refuse(cinfo, "colour quantization (djpeg -gif / -colors / -map) is not built on the GPU path (no CPU fallback)");
-  if (cinfo->dct_method != JDCT_ISLOW && cinfo->dct_method != JDCT_IFAST) refuse(cinfo, "the float inverse DCT (djpeg -dct float) is not built on the GPU path (no CPU fallback)");
-  calc_output_dimensions(cinfo);
-  k = cinfo->min_DCT_scaled_size;
-  if (k != 1 && k != 2 && k != 4 && k != 8) {
-    char why[160];
-    snprintf(why, sizeof(why), "scale %u/%u decodes with the %dx%d inverse DCT; the sizes built on the GPU path are 1x1, 2x2, 4x4 and 8x8", cinfo->scale_num, cinfo->scale_denom, k, k);
-    refuse(cinfo, why);
-  }
-  mjh_decode_opts_defaults(&o);
-  o.scale_num = k; o.scale_denom = 8;
-  o.dct_method = cinfo->dct_method == JDCT_IFAST ? 1 : 0;
-  o.fancy_upsampling = cinfo->do_fancy_upsampling ? 1 : 0;
-  px = 0;
-  if (cinfo->raw_data_out) {
-    for (ci = 0; ci < cinfo->num_components; ci++)
-      if (cinfo->comp_info[ci].DCT_scaled_size != k) refuse(cinfo, "raw_data_out with a scale at which the components are transformed at different sizes is not built on the GPU path");
-    o.raw_planes = 1;
-  } else if (cinfo->out_color_space == JCS_GRAYSCALE) {
-    if (cinfo->jpeg_color_space != JCS_GRAYSCALE && cinfo->jpeg_color_space != JCS_YCbCr && cinfo->jpeg_color_space != JCS_RGB) ERREXIT(cinfo, JERR_CONVERSION_NOTIMPL);
-    o.out_color_space = MJH_CS_GRAYSCALE; px = 1;
-  } else if (cinfo->out_color_space == JCS_RGB565) {
-    o.out_color_space = MJH_CS_RGB565; px = 2;
-    o.rgb_offset[0] = o.rgb_offset[1] = o.rgb_offset[2] = 0;
-    o.no_dither = cinfo->dither_mode == JDITHER_NONE;
-  } else if ((px = rgb_layout(cinfo->out_color_space, off)) != 0) {
-    o.out_color_space = MJH_CS_RGB; o.pixel_size = px;
-    o.rgb_offset[0] = off[0]; o.rgb_offset[1] = off[1]; o.rgb_offset[2] = off[2];
-  } else
-    ERREXIT(cinfo, JERR_CONVERSION_NOTIMPL);              /* JCS_YCbCr, JCS_CMYK, JCS_YCCK */
   /* slots 0 and 1 without a table get the standard ones (std_huff_tables from jinit_huff_decoder jdhuff.c:816-823: Motion JPEG
    * frames come without DHT); an abbreviated image then carries them like every other kept table */
   for (ci = 0; ci < 4; ci++) {
@@ -1112,12 +1104,54 @@ boolean jpeg_start_decompress(j_decompress_ptr cinfo)
     const void *files[1];
     size_t sizes[1];
     files[0] = m->file; sizes[0] = m->file_len;
-    rc = mjh_decode_host(m->enc, files, sizes, 1, &o);
+    rc = mjh_decode_host(m->enc, files, sizes, 1, opts);
     if (rc != MJH_OK) decoder_failed(cinfo, rc, 0);
     rc = mjh_decode_wait(m->enc);
     if (rc != MJH_OK) decoder_failed(cinfo, rc, 1);
   }
   if (d_timing) { t1 = d_now(); d_acc(2, t1 - t0, 0); t0 = t1; }
+}
+
+boolean jpeg_start_decompress(j_decompress_ptr cinfo)
+{
+  d_master *m = DM(cinfo);
+  mjh_decode_opts o;
+  int ci, k, rc, off[3], px;
+  double t0 = 0.0;
+  if (cinfo->global_state != DSTATE_READY) ERREXIT1(cinfo, JERR_BAD_STATE, cinfo->global_state);
+  if (cinfo->buffered_image) refuse(cinfo, "buffered-image mode is not built (the GPU path decodes a whole file at once)");
+  if (cinfo->quantize_colors) refuse(cinfo, "colour quantization (djpeg -gif / -colors / -map) is not built on the GPU path (no CPU fallback)");
+  if (cinfo->dct_method != JDCT_ISLOW && cinfo->dct_method != JDCT_IFAST) refuse(cinfo, "the float inverse DCT (djpeg -dct float) is not built on the GPU path (no CPU fallback)");
+  calc_output_dimensions(cinfo);
+  k = cinfo->min_DCT_scaled_size;
+  if (k != 1 && k != 2 && k != 4 && k != 8) {
+    char why[160];
+    snprintf(why, sizeof(why), "scale %u/%u decodes with the %dx%d inverse DCT; the sizes built on the GPU path are 1x1, 2x2, 4x4 and 8x8", cinfo->scale_num, cinfo->scale_denom, k, k);
+    refuse(cinfo, why);
+  }
+  mjh_decode_opts_defaults(&o);
+  o.scale_num = k; o.scale_denom = 8;
+  o.dct_method = cinfo->dct_method == JDCT_IFAST ? 1 : 0;
+  o.fancy_upsampling = cinfo->do_fancy_upsampling ? 1 : 0;
+  px = 0;
+  if (cinfo->raw_data_out) {
+    for (ci = 0; ci < cinfo->num_components; ci++)
+      if (cinfo->comp_info[ci].DCT_scaled_size != k) refuse(cinfo, "raw_data_out with a scale at which the components are transformed at different sizes is not built on the GPU path");
+    o.raw_planes = 1;
+  } else if (cinfo->out_color_space == JCS_GRAYSCALE) {
+    if (cinfo->jpeg_color_space != JCS_GRAYSCALE && cinfo->jpeg_color_space != JCS_YCbCr && cinfo->jpeg_color_space != JCS_RGB) ERREXIT(cinfo, JERR_CONVERSION_NOTIMPL);
+    o.out_color_space = MJH_CS_GRAYSCALE; px = 1;
+  } else if (cinfo->out_color_space == JCS_RGB565) {
+    o.out_color_space = MJH_CS_RGB565; px = 2;
+    o.rgb_offset[0] = o.rgb_offset[1] = o.rgb_offset[2] = 0;
+    o.no_dither = cinfo->dither_mode == JDITHER_NONE;
+  } else if ((px = rgb_layout(cinfo->out_color_space, off)) != 0) {
+    o.out_color_space = MJH_CS_RGB; o.pixel_size = px;
+    o.rgb_offset[0] = off[0]; o.rgb_offset[1] = off[1]; o.rgb_offset[2] = off[2];
+  } else
+    ERREXIT(cinfo, JERR_CONVERSION_NOTIMPL);              /* JCS_YCbCr, JCS_CMYK, JCS_YCCK */
+  decode_file(cinfo, &o);
+  if (d_timing) t0 = d_now();
   if (cinfo->raw_data_out) {
     for (ci = 0; ci < cinfo->num_components; ci++) {
       m->plane_w[ci] = (size_t)cinfo->comp_info[ci].width_in_blocks * (size_t)k;
@@ -1193,6 +1227,66 @@ JDIMENSION jpeg_read_raw_data(j_decompress_ptr cinfo, JSAMPIMAGE data, JDIMENSIO
   }
   cinfo->output_scanline += lines;
   return lines;
+}
+
+/* =====================================================================================================================
+ * jpeg_read_coefficients -- jdtrans.c: the same call of the device decoder, stopped after the Huffman decoder
+ * ===================================================================================================================== */
+jvirt_barray_ptr *jpeg_read_coefficients(j_decompress_ptr cinfo)
+{ /* jdtrans.c:48-95 + transdecode_master_selection :103-161; the full-buffer case of jinit_d_coef_controller jdcoefct.c:834-860 */
+  d_master *m = DM(cinfo);
+  if (cinfo->master->lossless) ERREXIT(cinfo, JERR_NOTIMPL);
+  if (cinfo->global_state == DSTATE_READY) {
+    mjh_decode_opts o;
+    jpeg_component_info *comp;
+    int ci, rc;
+    cinfo->buffered_image = TRUE;               /* "this is effectively a buffered-image operation" */
+    m->coef_arrays = (jvirt_barray_ptr *)(*cinfo->mem->alloc_small) ((j_common_ptr)cinfo, JPOOL_IMAGE, sizeof(jvirt_barray_ptr) * MAX_COMPONENTS);
+    for (ci = 0, comp = cinfo->comp_info; ci < cinfo->num_components; ci++, comp++)
+      m->coef_arrays[ci] = (*cinfo->mem->request_virt_barray) ((j_common_ptr)cinfo, JPOOL_IMAGE, TRUE,
+                                                               (JDIMENSION)jround_up((long)comp->width_in_blocks, (long)comp->h_samp_factor),
+                                                               (JDIMENSION)jround_up((long)comp->height_in_blocks, (long)comp->v_samp_factor),
+                                                               (JDIMENSION)comp->v_samp_factor);
+    (*cinfo->mem->realize_virt_arrays) ((j_common_ptr)cinfo);     /* these and the client's own (jtransform_request_workspace) */
+    if (cinfo->progress != NULL) {
+      cinfo->progress->pass_counter = 0L;
+      cinfo->progress->pass_limit = (long)cinfo->total_iMCU_rows * (cinfo->inputctl->has_multiple_scans ? cinfo->num_components : 1);
+      cinfo->progress->completed_passes = 0;
+      cinfo->progress->total_passes = 1;
+      (*cinfo->progress->progress_monitor) ((j_common_ptr)cinfo);
+    }
+    m->latching = 1;
+    latch_quant_tables(cinfo);                  /* the first scan's header was read by jpeg_read_header */
+    mjh_decode_opts_defaults(&o);
+    o.raw_coefs = 1;
+    decode_file(cinfo, &o);
+    m->latching = 0;
+    for (ci = 0, comp = cinfo->comp_info; ci < cinfo->num_components; ci++, comp++) {
+      /* the real blocks row by row; the rows and columns of padding are the pre-zeroed array's */
+      const size_t row_bytes = (size_t)comp->width_in_blocks * sizeof(JBLOCK);
+      JDIMENSION r;
+      unsigned char *tmp = (unsigned char *)malloc(row_bytes * comp->height_in_blocks);
+      if (tmp == NULL) { mjh_dapi_drop(cinfo); ERREXIT1(cinfo, JERR_OUT_OF_MEMORY, 11); }
+      rc = mjh_get_coefs(m->enc, 0, ci, tmp, comp->width_in_blocks);
+      if (rc != MJH_OK) { free(tmp); decoder_failed(cinfo, rc, 0); }
+      for (r = 0; r < (JDIMENSION)jround_up((long)comp->height_in_blocks, (long)comp->v_samp_factor); r++) {
+        JBLOCKARRAY ba = (*cinfo->mem->access_virt_barray) ((j_common_ptr)cinfo, m->coef_arrays[ci], r, 1, TRUE);
+        if (r < comp->height_in_blocks) memcpy(ba[0], tmp + (size_t)r * row_bytes, row_bytes);
+      }
+      free(tmp);
+    }
+    mjh_shim_cache_release(m->enc);
+    m->enc = NULL;
+    free(m->file); m->file = NULL; m->file_len = m->file_cap = 0;
+    if (cinfo->progress != NULL) {
+      cinfo->progress->pass_counter = cinfo->progress->pass_limit;
+      (*cinfo->progress->progress_monitor) ((j_common_ptr)cinfo);
+    }
+    cinfo->global_state = DSTATE_STOPPING;      /* so that jpeg_finish_decompress does the right thing */
+  }
+  if (cinfo->global_state == DSTATE_STOPPING && cinfo->buffered_image && m->coef_arrays != NULL) return m->coef_arrays;
+  ERREXIT1(cinfo, JERR_BAD_STATE, cinfo->global_state);
+  return NULL;
 }
 
 boolean jpeg_finish_decompress(j_decompress_ptr cinfo)

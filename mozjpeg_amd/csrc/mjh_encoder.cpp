@@ -443,6 +443,13 @@ struct mjh_encoder {
   // at plane_off, rows rp_pitch[c] apart)
   bool dp_raw = false;
   int rp_ncomp = 0, rp_w[MJH_MAXC] = {}, rp_h[MJH_MAXC] = {}, rp_pitch[MJH_MAXC] = {};
+  // raw_coefs: the batch stopped after K-D; k_export_coefs put its coefficients into d_coefx as block-major natural-order arrays
+  // (cx: component c's array of image 0, its row pitch in blocks, the bytes between images).  The buffer is made by the first
+  // raw_coefs call.
+  bool dp_coefs = false;
+  uint8_t *d_coefx = nullptr;
+  MjhCoefDst cx{};
+  hipEvent_t cx_ev[2] = { nullptr, nullptr }; bool cx_timed = false;
 };
 
 static long div_round_up(long a, long b) { return (a + b - 1) / b; }
@@ -897,6 +904,8 @@ static void free_all(mjh_encoder *e)
   for (void *q : { (void *)e->h_tc, (void *)e->h_tdesc, (void *)e->h_tstat[0], (void *)e->h_tstat[1], (void *)e->h_tflag }) if (q) (void)hipHostFree(q);
   for (hipEvent_t ev : e->tc_ev) if (ev) (void)hipEventDestroy(ev);
   if (e->d_pixout) (void)mjh_guard_free(e->d_pixout);
+  if (e->d_coefx) (void)mjh_guard_free(e->d_coefx);
+  for (hipEvent_t ev : e->cx_ev) if (ev) (void)hipEventDestroy(ev);
   if (e->h_dstat) (void)hipHostFree(e->h_dstat);
   for (hipEvent_t ev : { e->dp_ev[0], e->dp_ev[1], e->dp_ev[2], e->dp_done }) if (ev) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : e->prof_events) (void)hipEventDestroy(ev);
@@ -3249,6 +3258,61 @@ static int plan_pixels(const mjh_encoder *e, const mjh_decode_opts *o, int k, Mj
   return MJH_OK;
 }
 
+// the host-side pieces every mjh_decode_host batch needs: its status words and the events behind it (made by the first call)
+static int decode_host_state(mjh_encoder *e)
+{
+  if (e->h_dstat) return MJH_OK;
+  HIPCHK(mjh_numa_host_alloc((void **)&e->h_dstat, (size_t)e->max_batch * 4, hipHostMallocDefault, e->device));
+  for (hipEvent_t &ev : e->dp_ev) HIPCHK(hipEventCreate(&ev));
+  HIPCHK(hipEventCreateWithFlags(&e->dp_done, hipEventDisableTiming));
+  return MJH_OK;
+}
+
+// mjh_decode_opts.raw_coefs: the front half, then k_export_coefs instead of the pixel kernels.  Nothing of the pixel options is
+// looked at; the files accepted are the front half's (any number of components it decodes).
+static int decode_coefs(mjh_encoder *e, const void *const jpegs[], const size_t sizes[], int n)
+{
+  size_t o_jfif = 0;
+  int rc = decode_front(e, jpegs, sizes, n, true, &o_jfif);
+  if (rc) return rc;
+  const MjhConst &C = e->C;
+  if (!e->d_coefx) {
+    // component c: max_batch arrays of [hib][wpad][64], the width the reference pads its arrays to (jinit_d_coef_controller
+    // jdcoefct.c:852-858), so that the arrays go into mjh_encode_coefficients_device as they are; the padding columns are zeros
+    size_t total = 0;
+    for (int c = 0; c < C.ncomp; c++) total += (size_t)e->max_batch * (size_t)C.c[c].hib * (size_t)C.c[c].wpad * 128;
+    HIPCHK(mjh_dmalloc((void **)&e->d_coefx, total));
+    size_t off = 0;
+    for (int c = 0; c < C.ncomp; c++) {
+      e->cx.base[c] = e->d_coefx + off;
+      e->cx.blocks_per_row[c] = C.c[c].wpad;
+      e->cx.blocks[c] = (long long)C.c[c].hib * C.c[c].wpad;
+      e->cx.stride[c] = e->cx.blocks[c] * 128;
+      off += (size_t)e->max_batch * (size_t)e->cx.stride[c];
+    }
+    for (hipEvent_t &ev : e->cx_ev) HIPCHK(hipEventCreate(&ev));
+  }
+  rc = decode_host_state(e);
+  if (rc) return rc;
+  hipStream_t s = e->stream;
+  const bool timed = e->profiling != 0;
+  memset(&e->dp, 0, sizeof(e->dp));
+  e->dp.W = C.W; e->dp.H = C.H;
+  e->dp_n = n; e->dp_raw = false; e->dp_coefs = true; e->dp_timed = false;
+  e->last_n = n; e->compact_last = false; e->last = nullptr;
+  if (timed) HIPCHK(hipEventRecord(e->cx_ev[0], s));
+  mjh_launch_export_coefs(C, e->cx, e->d_q, e->d_tstat, n, s);
+  if (timed) HIPCHK(hipEventRecord(e->cx_ev[1], s));
+  e->cx_timed = timed;
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(e->h_dstat, e->d_tstat, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipEventRecord(e->dp_done, s));
+  e->last_stream = s;
+  e->dp_queued = true;
+  e->dp_waited = false;
+  return MJH_OK;
+}
+
 extern "C" int mjh_decode_host(mjh_encoder *e, const void *const jpegs[], const size_t sizes[], int n, const mjh_decode_opts *opts)
 {
   if (!e) return fail(MJH_EINVAL, "null encoder");
@@ -3256,6 +3320,7 @@ extern "C" int mjh_decode_host(mjh_encoder *e, const void *const jpegs[], const 
   if (e->xf_on) return fail(MJH_EUNSUPPORTED, "a lossless transform (mjh_encoder_set_transform) together with decoding to pixels");
   mjh_decode_opts o;
   if (opts) o = *opts; else mjh_decode_opts_defaults(&o);
+  if (o.raw_coefs) return decode_coefs(e, jpegs, sizes, n);
   if (o.dct_method != 0 && o.dct_method != 1) return fail(MJH_EINVAL, "dct_method %d of a decode call (0 = JDCT_ISLOW, 1 = JDCT_IFAST)", o.dct_method);
   const bool ifast = o.dct_method == 1, raw = o.raw_planes != 0;
   int k = 8, ssize[3] = { 8, 8, 8 };
@@ -3290,11 +3355,8 @@ extern "C" int mjh_decode_host(mjh_encoder *e, const void *const jpegs[], const 
     HIPCHK(mjh_dmalloc((void **)&e->d_pixout, need));
     e->pixout_cap = need;
   }
-  if (!e->h_dstat) {
-    HIPCHK(mjh_numa_host_alloc((void **)&e->h_dstat, (size_t)e->max_batch * 4, hipHostMallocDefault, e->device));
-    for (hipEvent_t &ev : e->dp_ev) HIPCHK(hipEventCreate(&ev));
-    HIPCHK(hipEventCreateWithFlags(&e->dp_done, hipEventDisableTiming));
-  }
+  rc = decode_host_state(e);
+  if (rc) return rc;
   // the multipliers: quantval (jidctint.c, jidctred.c) and, for the fast method, DESCALE(quantval * aanscales, CONST_BITS 14 -
   // IFAST_SCALE_BITS 2) with rounding, kept as int (jddctmgr.c:284-316)
   MjhIdctQ Q, QF;
@@ -3308,7 +3370,7 @@ extern "C" int mjh_decode_host(mjh_encoder *e, const void *const jpegs[], const 
     }
   hipStream_t s = e->stream;
   const bool timed = e->profiling != 0;
-  e->dp = P; e->dp_n = n; e->dp_raw = raw;
+  e->dp = P; e->dp_n = n; e->dp_raw = raw; e->dp_coefs = false;
   e->last_n = n; e->compact_last = false; e->last = nullptr;      // (mjh_read_tap: d_q holds this batch's plain planes, d_planes its samples)
   if (timed) HIPCHK(hipEventRecord(e->dp_ev[0], s));
   if (k == 8) (ifast ? mjh_launch_idct_ifast : mjh_launch_idct)(C, ifast ? QF : Q, P.ncomp, e->d_q, e->d_planes, e->d_tstat, n, s);
@@ -3385,6 +3447,7 @@ extern "C" int mjh_get_pixels(mjh_encoder *e, int i, void *dst, size_t row_pitch
   int rc = wait_pixels(e);
   if (rc) return rc;
   if (e->dp_raw) return fail(MJH_EINVAL, "the last batch was decoded with raw_planes: it has sample planes (mjh_get_plane), no pixels");
+  if (e->dp_coefs) return fail(MJH_EINVAL, "the last batch was decoded with raw_coefs: it has coefficients (mjh_get_coefs), no pixels");
   if (i < 0 || i >= e->dp_n) return fail(MJH_EINVAL, "image %d of a batch of %d", i, e->dp_n);
   const size_t row_bytes = (size_t)e->dp.W * (size_t)e->dp.px_size;
   if (row_pitch < row_bytes) return fail(MJH_EINVAL, "row_pitch %zu is smaller than a row (%zu bytes)", row_pitch, row_bytes);
@@ -3397,6 +3460,7 @@ extern "C" int mjh_get_pixels_device(mjh_encoder *e, void **d_base, size_t *row_
   if (!e) return fail(MJH_EINVAL, "null encoder");
   if (!e->dp_queued) return fail(MJH_EINVAL, "the last batch was not decoded through mjh_decode_host");
   if (e->dp_raw) return fail(MJH_EINVAL, "the last batch was decoded with raw_planes: it has sample planes (mjh_get_planes_device), no pixels");
+  if (e->dp_coefs) return fail(MJH_EINVAL, "the last batch was decoded with raw_coefs: it has coefficients (mjh_get_coefs_device), no pixels");
   if (d_base) *d_base = e->d_pixout;
   if (row_pitch) *row_pitch = (size_t)e->dp.row_pitch;
   if (image_stride) *image_stride = (size_t)e->dp.image_stride;
@@ -3429,6 +3493,49 @@ extern "C" int mjh_get_planes_device(mjh_encoder *e, int comp, void **d_base, si
   if (image_stride) *image_stride = (size_t)e->C.planes_per_image;
   if (width) *width = e->rp_w[comp];
   if (height) *height = e->rp_h[comp];
+  return MJH_OK;
+}
+
+extern "C" int mjh_get_coefs_device(mjh_encoder *e, int comp, void **d_base, size_t *image_stride, int *blocks_per_row, int *height_in_blocks, int *width_in_blocks)
+{
+  if (!e) return fail(MJH_EINVAL, "null encoder");
+  if (!e->dp_queued || !e->dp_coefs) return fail(MJH_EINVAL, "the last batch was not decoded with raw_coefs");
+  if (comp < 0 || comp >= e->C.ncomp) return fail(MJH_EINVAL, "component %d of %d", comp, e->C.ncomp);
+  if (d_base) *d_base = e->cx.base[comp];
+  if (image_stride) *image_stride = (size_t)e->cx.stride[comp];
+  if (blocks_per_row) *blocks_per_row = (int)e->cx.blocks_per_row[comp];
+  if (height_in_blocks) *height_in_blocks = e->C.c[comp].hib;
+  if (width_in_blocks) *width_in_blocks = e->C.c[comp].wib;
+  return MJH_OK;
+}
+
+extern "C" int mjh_get_coefs(mjh_encoder *e, int i, int comp, void *dst, size_t dst_blocks_per_row)
+{
+  if (!e || !dst) return fail(MJH_EINVAL, "bad arguments");
+  if (e->dp_queued && !e->dp_coefs) return fail(MJH_EINVAL, "the last batch was not decoded with raw_coefs");
+  int rc = wait_pixels(e);
+  if (rc) return rc;
+  if (i < 0 || i >= e->dp_n) return fail(MJH_EINVAL, "image %d of a batch of %d", i, e->dp_n);
+  if (comp < 0 || comp >= e->C.ncomp) return fail(MJH_EINVAL, "component %d of %d", comp, e->C.ncomp);
+  const MjhComp &cc = e->C.c[comp];
+  if (dst_blocks_per_row < (size_t)cc.wib) return fail(MJH_EINVAL, "dst_blocks_per_row %zu is smaller than a row (%d blocks)", dst_blocks_per_row, cc.wib);
+  HIPCHK(hipMemcpy2D(dst, dst_blocks_per_row * 128, (const uint8_t *)e->cx.base[comp] + (size_t)i * (size_t)e->cx.stride[comp], (size_t)e->cx.blocks_per_row[comp] * 128,
+                     (size_t)cc.wib * 128, (size_t)cc.hib, hipMemcpyDeviceToHost));
+  return MJH_OK;
+}
+
+extern "C" int mjh_get_coefs_ms(mjh_encoder *e, float *ms)
+{
+  if (!e) return fail(MJH_EINVAL, "null encoder");
+  if (!e->dp_queued || !e->dp_coefs) return fail(MJH_EINVAL, "the last batch was not decoded with raw_coefs");
+  if (ms) {
+    *ms = 0.f;
+    if (e->cx_timed) {
+      HIPCHK(hipSetDevice(e->device));
+      HIPCHK(hipEventSynchronize(e->cx_ev[1]));
+      HIPCHK(hipEventElapsedTime(ms, e->cx_ev[0], e->cx_ev[1]));
+    }
+  }
   return MJH_OK;
 }
 

@@ -83,6 +83,14 @@ struct MjhCoefSrc {
   long long stride[MJH_MAXC];        // bytes between images
 };
 
+// where k_export_coefs puts the coefficients of a decoded batch (mjh_decode_opts.raw_coefs): the layout MjhCoefSrc describes
+struct MjhCoefDst {
+  void *base[MJH_MAXC];              // first block of image 0: [height_in_blocks][blocks_per_row][64] int16, natural order
+  long long blocks_per_row[MJH_MAXC];
+  long long stride[MJH_MAXC];        // bytes between images
+  long long blocks[MJH_MAXC];        // blocks of one image the destination holds: no store goes beyond them
+};
+
 // What jtransform_request_workspace decides for one source file and one mjh_transform (mjh_transform_plan, mjh_jpeg_parse.cpp):
 // every operation is "transpose or not, then mirror the whole iMCUs in x and / or y, then cut".  Coordinates are the
 // DESTINATION's (after the transposition).

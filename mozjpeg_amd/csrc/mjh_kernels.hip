@@ -767,6 +767,54 @@ k_import_coefs(MjhConst C, MjhCoefSrc S, int16_t *__restrict__ coef_q, MjhImageM
   for (int k = 0; k < 64; k++) qo[(size_t)k * cc.kstride] = (int16_t)v[kZZ.v[k]];
 }
 // =============================================================================================
+// K2c  coefficient export: K2b turned round (jpeg_read_coefficients jdtrans.c:47 hands out what the Huffman decoder left;
+// mjh_decode_opts.raw_coefs).  The planes K-D stored (coefficient-major, zig-zag order, real blocks only) become the caller's
+// arrays: block-major, natural order, [height_in_blocks][blocks_per_row][64].  One lane = one block of the DESTINATION, padding
+// columns (blocks_per_row > wib) included: 64 coalesced plane loads bounded by the component's block count -- a padding block and
+// every block of a file whose status is set load nothing and are zeros -- so every byte of the destination is written by the
+// batch that owns it.  Values are the planes' 16 bits as they are (no +-1023 limit: that is the entropy coder's, K2b).
+// A lane's block is 128 contiguous bytes, 64 lanes' blocks 8 KiB: the wave puts its 64 blocks into LDS (row pitch 33 words: the
+// 32 word stores of a lane and the word loads below are free of bank conflicts) and stores them row-wise, a lane 16 bytes and
+// the wave 1 KiB = 8 whole cache lines per store instruction.  (Every lane storing its own block with 8 x 16 bytes -- 64 lines
+// touched per store instruction -- was built and measured 1.6 % slower: DESIGN section 4 K-X.)
+// No store goes beyond D.blocks[comp] blocks of an image, whatever the geometry says.
+// =============================================================================================
+__global__ void __launch_bounds__(64)
+k_export_coefs(MjhConst C, MjhCoefDst D, const int16_t *__restrict__ coef_q, const unsigned *__restrict__ status)
+{
+  const int comp = blockIdx.y, img = blockIdx.z, lane = threadIdx.x;
+  const MjhComp cc = C.c[comp];
+  const long long bpr = D.blocks_per_row[comp];
+  const long long want = (long long)cc.hib * bpr;
+  const long long ndst = want < D.blocks[comp] ? want : D.blocks[comp];
+  const long long d0 = (long long)blockIdx.x * 64, d = d0 + lane;
+  bool real = false;
+  int blk = 0;
+  if (d < ndst && status[img] == 0u) {
+    const long long br = d / bpr, bc = d - br * bpr;
+    if (bc < cc.wib) { blk = (int)(br * cc.wib + bc); real = blk < cc.nblk; }
+  }
+  const int16_t *qi = coef_q + (size_t)img * C.coefs_per_image + cc.coef_off + blk;
+  int v[64];
+#pragma unroll
+  for (int k = 0; k < 64; k++) v[kZZ.v[k]] = real ? (int)qi[(size_t)k * cc.kstride] : 0;
+  unsigned w[32];
+#pragma unroll
+  for (int j = 0; j < 32; j++) w[j] = ((unsigned)v[2 * j] & 0xFFFFu) | ((unsigned)v[2 * j + 1] << 16);
+  uint8_t *out = reinterpret_cast<uint8_t *>(D.base[comp]) + (size_t)img * (size_t)D.stride[comp];
+  __shared__ unsigned tile[64 * 33];
+#pragma unroll
+  for (int j = 0; j < 32; j++) tile[lane * 33 + j] = w[j];
+  __syncthreads();
+  const int c4 = (lane & 7) * 4;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const int b = i * 8 + (lane >> 3);
+    const unsigned *t = tile + b * 33 + c4;
+    if (d0 + b < ndst) *reinterpret_cast<uint4 *>(out + (size_t)(d0 + b) * 128 + (size_t)c4 * 4) = make_uint4(t[0], t[1], t[2], t[3]);
+  }
+}
+// =============================================================================================
 // Dummy-block resolution (compress_first_pass jccoefct.c:312-345, compress_trellis_pass
 // :443-476): dummy blocks are never stored.  A padded position (r,c) of a component maps to
 // the real block whose DC it copies; its AC coefficients are zero.
@@ -2751,6 +2799,14 @@ void mjh_launch_import_coefs(const MjhConst &C, const MjhCoefSrc &S, void *coef_
   for (int i = 0; i < C.ncomp; i++) m = C.c[i].nblk > m ? C.c[i].nblk : m;
   dim3 grid((m + 63) / 64, C.ncomp, n);
   hipLaunchKernelGGL(k_import_coefs, grid, dim3(64), 0, s, C, S, (int16_t *)coef_q, (MjhImageMeta *)meta);
+}
+
+void mjh_launch_export_coefs(const MjhConst &C, const MjhCoefDst &D, const void *coef_q, const unsigned *status, int n, hipStream_t s)
+{
+  long long m = 0;
+  for (int i = 0; i < C.ncomp; i++) { const long long b = (long long)C.c[i].hib * D.blocks_per_row[i]; m = b > m ? b : m; }
+  dim3 grid((unsigned)((m + 63) / 64), C.ncomp, n);
+  hipLaunchKernelGGL(k_export_coefs, grid, dim3(64), 0, s, C, D, (const int16_t *)coef_q, status);
 }
 
 void mjh_launch_import_planes(const MjhConst &C, const MjhPlaneSrc &S, void *planes, int n, hipStream_t s)

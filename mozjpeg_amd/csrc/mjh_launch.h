@@ -5,6 +5,8 @@
 #include "mjh_internal.h"
 
 void mjh_launch_import_coefs(const MjhConst &C, const MjhCoefSrc &S, void *coef_q, void *meta, int n, hipStream_t s);
+// the planes of a decoded batch -> block-major natural-order arrays (k_export_coefs)
+void mjh_launch_export_coefs(const MjhConst &C, const MjhCoefDst &D, const void *coef_q, const unsigned *status, int n, hipStream_t s);
 void mjh_launch_import_planes(const MjhConst &C, const MjhPlaneSrc &S, void *planes, int n, hipStream_t s);
 void mjh_launch_color(const MjhConst &C, const void *pix, size_t row_pitch, size_t img_stride, void *planes, int n, hipStream_t s);
 void mjh_launch_dct(const MjhConst &C, const MjhQuant *Q, const void *planes, void *uq, void *q, float *lambda,
