@@ -319,8 +319,8 @@ int mjh_encoder_sync(mjh_encoder *e);
  * JPEG bytes in, JPEG bytes out.  The host reads marker segments only; every Huffman symbol is decoded by kernels
  * (mjh_decode.hip), whose output feeds the entropy-coding passes of mjh_encode_coefficients_*.
  * Accepted: Huffman-coded sequential DCT files (SOF0, SOF1), 8-bit, 1 or 3 components, one interleaved scan or several
- * scans (every component in exactly one), any restart intervals.  MJH_EUNSUPPORTED: progressive, arithmetic, lossless,
- * 12-bit, 2 or 4 components, DNL.  COM / APPn markers are not copied (-copy none). */
+ * scans (every component in exactly one), any restart intervals.  MJH_EUNSUPPORTED: progressive (unless asked for, see
+ * mjh_encoder_set_sources below), arithmetic, lossless, 12-bit, 2 or 4 components, DNL.  COM / APPn markers are not copied (-copy none). */
 #define MJH_MAX_FILE_SCANS 4
 #define MJH_CS_GRAYSCALE 1   /* J_COLOR_SPACE values (jpeglib.h:232-234) */
 #define MJH_CS_RGB       2
@@ -339,7 +339,7 @@ typedef struct {
   uint8_t huff_vals[8][256];
 } mjh_jpeg_scan;
 typedef struct {
-  int sof_type;                                     /* 0 = SOF0 (baseline), 1 = SOF1 (extended sequential) */
+  int sof_type;                                     /* 0 = SOF0 (baseline), 1 = SOF1 (extended sequential), 2 = SOF2 (mjh_jpeg_probe_ex only) */
   int data_precision;
   int image_width, image_height;
   int num_components;
@@ -356,6 +356,45 @@ typedef struct {
  * ends; decodes nothing.  MJH_EINVAL with the reference's reason for malformed headers, MJH_EUNSUPPORTED for file
  * types outside the list above. */
 int mjh_jpeg_probe(const void *jpeg, size_t size, mjh_jpeg_info *info);
+/* ---- progressive source files (SOF2, Huffman-coded), opt-in ----
+ * With nothing set every entry point refuses a progressive file as the list above says.  mjh_jpeg_probe_ex with
+ * MJH_SRC_PROGRESSIVE in `accept`, and the calls of an encoder that mjh_encoder_set_sources(e, MJH_SRC_PROGRESSIVE) was called on
+ * (mjh_transcode_host, mjh_decode_host with and without raw_coefs), accept 8-bit SOF2 files of 1 or 3 components; SOF9 / SOF10,
+ * 12-bit, lossless, four components and DNL stay refused in the same words.
+ * A progressive file has more scans than mjh_jpeg_info holds: info->sof_type is 2, info->num_scans is 0 and the scans go to
+ * scans[0 .. *num_scans), each with its spectral selection (Ss, Se), its successive approximation (Ah, Al) and the Huffman tables
+ * and restart interval in force at its SOS (DHT and DRI between scans are normal in these files).  More than
+ * min(cap, MJH_MAX_SRC_SCANS) scans: MJH_EUNSUPPORTED with the count.  Every scan is validated as start_pass_phuff_decoder does
+ * (jdphuff.c:91-121; a violation is MJH_EINVAL, JERR_BAD_PROGRESSION), and the progression as jdphuff.c:126-144 tracks it in
+ * coef_bits: where the reference only warns (JWRN_BOGUS_PROGRESSION: an AC scan before the component's DC scan, a first scan of
+ * a coefficient already coded, a refinement whose Ah is not the Al before it), the file is refused with MJH_EUNSUPPORTED.
+ * accept = 0: mjh_jpeg_probe (scans, cap, num_scans may be NULL / 0).  A sequential file gives the same info with either flag. */
+#define MJH_SRC_PROGRESSIVE 1u
+#define MJH_MAX_SRC_SCANS 64     /* the cap on the scans of one progressive file */
+typedef struct {
+  int comps_in_scan;                                /* the fields of mjh_jpeg_scan, in its order */
+  int component_index[MJH_MAX_COMPS];
+  int dc_tbl_no[MJH_MAX_COMPS], ac_tbl_no[MJH_MAX_COMPS];
+  unsigned restart_interval;
+  size_t data_offset, data_size;
+  unsigned restart_markers;
+  int huff_defined;
+  uint8_t huff_bits[8][17];
+  uint8_t huff_vals[8][256];
+  int Ss, Se, Ah, Al;                               /* of the SOS: coefficients Ss..Se (0, 0 = a DC scan), Ah = 0 a first scan, else a refinement to bit Al */
+} mjh_jpeg_scan_ex;
+int mjh_jpeg_probe_ex(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_info *info, mjh_jpeg_scan_ex *scans, int cap, int *num_scans);
+/* The kinds of source file the encoder's mjh_transcode_host / mjh_decode_host calls take beyond the sequential ones: 0 (the state
+ * of a new encoder) or MJH_SRC_PROGRESSIVE.  Files of one call may differ in scan script, and progressive and sequential files of
+ * one geometry may share a call.  Refused with a progressive file in the call (MJH_EUNSUPPORTED): a lossless transform
+ * (mjh_encoder_set_transform), and -- on the way to pixels or planes only -- a file at whose end the reference would smooth blocks
+ * (jdcoefct.c smoothing_ok: some AC coefficient of positions 1..9 never sent or not refined to the last bit). */
+int mjh_encoder_set_sources(mjh_encoder *e, unsigned accept);
+/* The refinement scans of the last call's progressive files: how many levels of scans there were (first scans are level 0 and
+ * count; a scan's level is 1 + the highest level among the earlier scans of its file that share a component and overlap its
+ * coefficient range; 0 = no progressive file in the call) and, with mjh_set_profiling(e, 1), the milliseconds the levels above 0
+ * took together.  The four phases of mjh_transcode_stats cover the first scans.  Any pointer may be NULL. */
+int mjh_decode_prog_stats(mjh_encoder *e, int *levels, float *ms);
 /* What jpeg_copy_critical_parameters (jctrans.c:75-171) leaves in the destination object: the profile's defaults
  * (the max-compression profile: optimal tables, progressive with scan search), trellis_quant = 0, and the source's size,
  * colour space, precision, component ids, sampling factors, quantization-table numbers and tables -- not its Huffman tables,

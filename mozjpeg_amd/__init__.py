@@ -64,6 +64,16 @@ class JpegScan(C.Structure):
                 ("huff_vals", (C.c_uint8 * 256) * 8)]
 
 
+class JpegScanEx(C.Structure):
+    """mjh_jpeg_scan_ex: one scan of a progressive source file (mjh_jpeg_probe_ex): the fields of JpegScan, then its spectral
+    selection Ss..Se and successive approximation Ah, Al"""
+    _fields_ = JpegScan._fields_ + [("Ss", C.c_int), ("Se", C.c_int), ("Ah", C.c_int), ("Al", C.c_int)]
+
+
+SRC_PROGRESSIVE = 1         # MJH_SRC_PROGRESSIVE
+MAX_SRC_SCANS = 64          # MJH_MAX_SRC_SCANS: the cap on the scans of one progressive file
+
+
 class Transform(C.Structure):
     """mjh_transform: a lossless transform of the re-compression path (jpegtran -rotate / -flip / -transpose / -transverse,
     -trim, -perfect, -crop, -grayscale); make one with transform_spec()"""
@@ -162,6 +172,10 @@ def lib():
         L.mjh_get_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_char_p)),
                                            C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int)]
         L.mjh_jpeg_probe.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(JpegInfo)]
+        if hasattr(L, "mjh_jpeg_probe_ex"):
+            L.mjh_jpeg_probe_ex.argtypes = [C.c_char_p, C.c_size_t, C.c_uint, C.POINTER(JpegInfo), C.POINTER(JpegScanEx), C.c_int, C.POINTER(C.c_int)]
+            L.mjh_encoder_set_sources.argtypes = [C.c_void_p, C.c_uint]
+            L.mjh_decode_prog_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float)]
         L.mjh_params_from_jpeg.argtypes = [C.POINTER(JpegInfo), C.c_int, C.POINTER(Params)]
         L.mjh_transform_parse_crop.argtypes = [C.POINTER(Transform), C.c_char_p]
         L.mjh_params_from_jpeg_transform.argtypes = [C.POINTER(JpegInfo), C.POINTER(Transform), C.c_int, C.POINTER(Params)]
@@ -326,13 +340,21 @@ def make_params(width, height, *, quality=75, baseline=False, revert=False, opti
     return p
 
 
-def jpeg_info(data):
+def jpeg_info(data, progressive_sources=False):
     """The marker segments of a JPEG file (mjh_jpeg_probe): frame, tables, colour space, JFIF / Adobe fields, and per scan its
     components, Huffman tables, restart interval and the byte range of its entropy-coded data.  Raises MjhError (EUNSUPPORTED:
-    progressive, arithmetic, lossless, 12-bit, 4 components; EINVAL: malformed)."""
+    progressive, arithmetic, lossless, 12-bit, 4 components; EINVAL: malformed).
+    progressive_sources=True (mjh_jpeg_probe_ex with MJH_SRC_PROGRESSIVE): a Huffman-coded progressive file is accepted; its
+    JpegInfo has sof_type 2 and num_scans 0, and its scans are the list `prog_scans` of JpegScanEx (empty for a sequential file)."""
     info = JpegInfo()
     data = bytes(data)
-    _chk(lib().mjh_jpeg_probe(data, len(data), C.byref(info)))
+    if not progressive_sources:
+        _chk(lib().mjh_jpeg_probe(data, len(data), C.byref(info)))
+        return info
+    scans, n = (JpegScanEx * MAX_SRC_SCANS)(), C.c_int()
+    _chk(lib().mjh_jpeg_probe_ex(data, len(data), SRC_PROGRESSIVE, C.byref(info), scans, MAX_SRC_SCANS, C.byref(n)))
+    info.prog_scans = [scans[i] for i in range(n.value)]
+    info._prog_keep = scans         # (the list's entries are views of this array)
     return info
 
 
@@ -358,13 +380,14 @@ def transform_spec(transform=None, trim=False, perfect=False, crop=None, graysca
 
 
 def params_from_jpeg(data, *, revert=False, optimize=False, progressive=None, fastcrush=False, restart=0,
-                     transform=None, trim=False, perfect=False, crop=None, grayscale=False):
+                     transform=None, trim=False, perfect=False, crop=None, grayscale=False, progressive_sources=False):
     """Parameters of a `jpegtran -copy none` run on this file (mjh_params_from_jpeg = jpeg_copy_critical_parameters) plus
     jpegtran's switches in make_params' vocabulary.  `data`: the file's bytes or a JpegInfo.
     transform / trim / perfect / crop / grayscale (transform_spec): the parameters of the DESTINATION of that lossless transform
     (mjh_params_from_jpeg_transform); the Transform rides along as `.transform`, and an Encoder made from these parameters
-    applies it in transcode_host."""
-    info = data if isinstance(data, JpegInfo) else jpeg_info(data)
+    applies it in transcode_host.  progressive_sources=True: bytes of a progressive file are accepted (jpeg_info); jpegtran copies
+    no scan script, so its parameters are those of a sequential file of the same frame."""
+    info = data if isinstance(data, JpegInfo) else jpeg_info(data, progressive_sources)
     p = Params()
     L = lib()
     t = transform_spec(transform, trim, perfect, crop, grayscale)
@@ -401,7 +424,7 @@ def _signature(info):
 _recompress_encoders = {}
 
 
-def recompress(files, *, max_batch=64, device=0, **switches):
+def recompress(files, *, max_batch=64, device=0, progressive_sources=False, **switches):
     """Re-compress JPEG files on the GPU: what `jpegtran -copy none` + the switches (revert, optimize, progressive, fastcrush,
     restart) writes for each of them, in input order.  The files are grouped by what a batch must have in common; one encoder
     per group is kept for later calls.  In the max-compression profile without `revert` / `progressive` a source that is
@@ -409,13 +432,15 @@ def recompress(files, *, max_batch=64, device=0, **switches):
     (unsupported type, malformed headers, damaged entropy-coded data) gets the MjhError in its slot; the others are unaffected.
     transform / trim / perfect / crop / grayscale (transform_spec): jpegtran's lossless transforms in the same pass; with any of
     them but `perfect` a source is never returned in place of its result (jpegtran clears prefer_smallest), and a file whose
-    geometry refuses the request (not perfect, a crop outside the image) gets that MjhError in its slot."""
+    geometry refuses the request (not perfect, a crop outside the image) gets that MjhError in its slot.
+    progressive_sources=True: progressive files are decoded too (Encoder.set_sources); they share batches with sequential files
+    of the same frame."""
     files = [bytes(f) for f in files]
     out = [None] * len(files)
     groups = {}
     for i, f in enumerate(files):
         try:
-            info = jpeg_info(f)
+            info = jpeg_info(f, progressive_sources)
         except MjhError as exc:
             out[i] = exc
             continue
@@ -429,11 +454,14 @@ def recompress(files, *, max_batch=64, device=0, **switches):
     for sig, (info, idx) in groups.items():
         key = (sig, key_sw, device, LIB_PATH)
         enc = _recompress_encoders.get(key)
+        if enc is not None:
+            enc.set_sources(progressive=progressive_sources)
         if enc is None or enc.max_batch < min(max_batch, len(idx)):
             if enc is not None:
                 enc.close()
             try:
                 enc = _recompress_encoders[key] = Encoder(params_from_jpeg(info, **switches), max_batch=min(max_batch, len(idx)), device=device)
+                enc.set_sources(progressive=progressive_sources)
             except MjhError as exc:         # a transform this group's geometry refuses (perfect, a crop outside the image, ...)
                 _recompress_encoders.pop(key, None)
                 if not (transforming or switches.get("perfect") or exc.code == EUNSUPPORTED):      # (a frame no encoder exists for)
@@ -564,14 +592,16 @@ def decode_opts(color=None, layout=None, pixel_size=0, rgb_offset=None, fancy_up
 _decode_encoders = {}
 
 
-def decode(files, *, max_batch=64, device=0, **opts):
+def decode(files, *, max_batch=64, device=0, progressive_sources=False, **opts):
     """Decode JPEG files to pixels on the GPU: the bytes `djpeg` (+ -grayscale / -rgb / -nosmooth / -scale / -dct fast, see
     decode_opts) writes for each of them, as numpy arrays [H, W, C] ([H, W] for gray) in input order; with scale=,
     [ceil(H k / 8), ceil(W k / 8), C]; with bottom_up=True, the rows last to first.
     The files are grouped by what a batch must have in common, which the scale is not part of; one encoder per group is kept for
     later calls.  A file that cannot be decoded (unsupported type, malformed headers,
-    damaged entropy-coded data) gets the MjhError in its slot; the others are unaffected."""
-    return _decode_grouped(files, max_batch, device, decode_opts(**opts))
+    damaged entropy-coded data) gets the MjhError in its slot; the others are unaffected.
+    progressive_sources=True: progressive files are decoded too, except those whose blocks djpeg would smooth (an AC coefficient
+    of positions 1..9 never sent or not fully refined): EUNSUPPORTED naming block smoothing."""
+    return _decode_grouped(files, max_batch, device, decode_opts(**opts), progressive_sources)
 
 
 def yuv_plane_size(info, comp, k=8):
@@ -586,29 +616,29 @@ def yuv_plane_size(info, comp, k=8):
     return ph * info.v_samp_factor[comp] // maxv, pw * info.h_samp_factor[comp] // maxh
 
 
-def decode_planes(files, scale=None, dct=None, *, max_batch=64, device=0):
+def decode_planes(files, scale=None, dct=None, *, max_batch=64, device=0, progressive_sources=False):
     """Decode JPEG files to their sample planes on the GPU, without upsampling or colour conversion (TurboJPEG's
     tj3DecompressToYUVPlanes8): per file a list of uint8 arrays [h, w], one per component, of yuv_plane_size(), or the MjhError.
     Every component is transformed at the scale's own size (mjh_decode_opts.raw_planes), so the planes keep the file's
     subsampling at every scale."""
-    return _decode_grouped(files, max_batch, device, decode_opts(scale=scale, dct=dct, raw_planes=True))
+    return _decode_grouped(files, max_batch, device, decode_opts(scale=scale, dct=dct, raw_planes=True), progressive_sources)
 
 
-def decode_coefficients(files, *, max_batch=64, device=0):
+def decode_coefficients(files, *, max_batch=64, device=0, progressive_sources=False):
     """Decode JPEG files to their quantized DCT coefficients on the GPU (jpeg_read_coefficients): per file a list of int16 arrays
     [height_in_blocks, width_in_blocks, 64], one per component, block-major and in natural order -- what
     Encoder.encode_coefficients_host takes -- or the MjhError in its slot.  The values are the file's own (no limit of +-1023 is
     applied; the entropy coder refuses what it cannot code).  The quantization tables they belong to: jpeg_info(f).quantval."""
-    return _decode_grouped(files, max_batch, device, decode_opts(raw_coefs=True))
+    return _decode_grouped(files, max_batch, device, decode_opts(raw_coefs=True), progressive_sources)
 
 
-def _decode_grouped(files, max_batch, device, o):
+def _decode_grouped(files, max_batch, device, o, progressive_sources=False):
     files = [bytes(f) for f in files]
     out = [None] * len(files)
     groups = {}
     for i, f in enumerate(files):
         try:
-            info = jpeg_info(f)
+            info = jpeg_info(f, progressive_sources)
         except MjhError as exc:
             out[i] = exc
             continue
@@ -616,11 +646,14 @@ def _decode_grouped(files, max_batch, device, o):
     for sig, (info, idx) in groups.items():
         key = (sig, device, LIB_PATH)
         enc = _decode_encoders.get(key)
+        if enc is not None:
+            enc.set_sources(progressive=progressive_sources)
         if enc is None or enc.max_batch < min(max_batch, len(idx)):
             if enc is not None:
                 enc.close()
             try:
                 enc = _decode_encoders[key] = Encoder(params_from_jpeg(info, revert=True), max_batch=min(max_batch, len(idx)), device=device)
+                enc.set_sources(progressive=progressive_sources)
             except MjhError as exc:         # a frame no encoder exists for (fractional sampling ratios): this group's files alone
                 _decode_encoders.pop(key, None)
                 if exc.code != EUNSUPPORTED:
@@ -721,6 +754,19 @@ class Encoder:
         keywords, or None for none.  The encoder's parameters must be the transform's destination (params_from_jpeg)."""
         t = transform_spec(transform, **spec)
         _chk(lib().mjh_encoder_set_transform(self._h, C.byref(t) if t is not None else None))
+
+    def set_sources(self, progressive=True):
+        """The kinds of source file the following transcode / decode calls take beyond the sequential ones
+        (mjh_encoder_set_sources): progressive=True accepts Huffman-coded progressive files, False is the state of a new encoder."""
+        self._progressive = bool(progressive)
+        _chk(lib().mjh_encoder_set_sources(self._h, SRC_PROGRESSIVE if progressive else 0))
+
+    def prog_stats(self):
+        """levels of scans in the last call's progressive files (first scans are level 0 and count; 0: no progressive file) and the
+        milliseconds their refinement levels took (with profiling) (mjh_decode_prog_stats)"""
+        lv, ms = C.c_int(), C.c_float()
+        _chk(lib().mjh_decode_prog_stats(self._h, C.byref(lv), C.byref(ms)))
+        return dict(levels=lv.value, ms=float(ms.value))
 
     def close(self):
         if self._h:
@@ -996,7 +1042,7 @@ class Encoder:
                 return [self.get_coefficients(i) for i in range(n)]
             if o.raw_planes:
                 k = 8 if o.scale_num == 0 and o.scale_denom == 0 else scale_idct_size(o.scale_num, o.scale_denom)
-                return [self.get_planes(i, jpeg_info(files[i]), k) for i in range(n)]
+                return [self.get_planes(i, jpeg_info(files[i], getattr(self, "_progressive", False)), k) for i in range(n)]
             return [self.get_pixels(i) for i in range(n)]
         except MjhError:
             if errors != "return":

@@ -68,6 +68,12 @@ struct MjhDecBatch {
                                    // symbol for more), 32767 = never on the way to pixels (the decompressor takes any amplitude a symbol exists for)
 };
 
+// What a scan of a progressive file adds to MjhDecScan: entry i of a parallel array belongs to scan i of the same batch (MjhDecScan
+// keeps its layout: the kernels of mjh_decode.hip copy it into LDS word by word).  Ss..Se: the coefficient positions the scan codes
+// (0..0: a DC scan, then ncomp may be > 1; else one component and diff_off is unused); Ah = 0: a first scan, values << Al; else a
+// refinement of bit Al
+struct MjhDecProg { int Ss, Se, Ah, Al; };
+
 // A lossless transform fused into the two places that store coefficients (mjh_encoder_set_transform): the kernels decode in the
 // SOURCE frame's geometry (the MjhConst they get is the source's) and store into the DESTINATION frame's planes.  Every operation
 // of transupp.c is: transpose or not; mirror the whole iMCUs in x and / or y (a partial iMCU at that edge stays in place); cut.
@@ -97,6 +103,14 @@ void mjh_launch_dec_dc(const MjhConst &C, const MjhDecBatch &B, int16_t *coef_q,
 // the storing pass and the DC sums with a transform: Cs = the SOURCE frame's geometry, X (device memory) = where things go
 void mjh_launch_dec_store_x(const MjhConst &Cs, const MjhDecBatch &B, int16_t *coef_q, const MjhXform *X, hipStream_t s);
 void mjh_launch_dec_dc_x(const MjhConst &Cs, const MjhDecBatch &B, int16_t *coef_q, const MjhXform *X, hipStream_t s);
+// progressive files (mjh_decode_prog.hip).  First scans: the same phases with a batch of their own (B.scans / PS in step; k_dec_prefix
+// serves both).  Refinement scans: B.segs[0 .. B.nseg) are the restart segments of ONE level's DC (dc_refine) or AC (ac_refine)
+// refinement scans; sub_seg / state / carry / ord / diff are not looked at.
+void mjh_launch_pdec_sync(const MjhConst &C, const MjhDecBatch &B, const MjhDecProg *PS, int q, int first, hipStream_t s);
+void mjh_launch_pdec_store(const MjhConst &C, const MjhDecBatch &B, const MjhDecProg *PS, int16_t *coef_q, hipStream_t s);
+void mjh_launch_pdec_dc(const MjhConst &C, const MjhDecBatch &B, const MjhDecProg *PS, int16_t *coef_q, hipStream_t s);
+void mjh_launch_pdec_dc_refine(const MjhConst &C, const MjhDecBatch &B, const MjhDecProg *PS, int16_t *coef_q, hipStream_t s);
+void mjh_launch_pdec_ac_refine(const MjhConst &C, const MjhDecBatch &B, const MjhDecProg *PS, int16_t *coef_q, hipStream_t s);
 void mjh_launch_dec_scrub(const MjhConst &C, const MjhDecBatch &B, int16_t *coef_q, void *meta, hipStream_t s);
 // after the encode: image i's JFIF version / density bytes (7 bytes at file offset 11) and its status from the encoder's own checks
 void mjh_launch_dec_finish(const uint8_t *jfif7, int patch, uint8_t *out, size_t out_stride, const void *meta, unsigned *status, int n, hipStream_t s);

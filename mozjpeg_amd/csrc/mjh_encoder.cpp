@@ -11,6 +11,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <array>
 #include <atomic>
 #include <condition_variable>
 #include <functional>
@@ -430,6 +431,10 @@ struct mjh_encoder {
   int tc_n = 0, tc_rounds = 0, tc_syncs = 0, tc_S = 0;
   bool tc_queued = false;               // the last mjh_transcode_host call got as far as queueing its batch (else only the host's findings exist)
   hipEvent_t tc_ev[5] = { nullptr, nullptr, nullptr, nullptr, nullptr }; bool tc_timed = false;
+  // mjh_encoder_set_sources: progressive files (mjh_decode_prog.hip).  The events are made by the first call that holds one.
+  unsigned src_accept = 0;
+  int pg_levels = 0;                    // levels of scans in the last call's progressive files (0: none in the call)
+  hipEvent_t pg_ev[2] = { nullptr, nullptr }; bool pg_timed = false;
   // mjh_decode_host (mjh_idct.hip): the interleaved pixels of the last decoded batch (made at the first call, grown when a later
   // call asks for larger pixels), its layout, its status words on the host and the event behind everything it queued
   uint8_t *d_pixout = nullptr; size_t pixout_cap = 0;
@@ -903,6 +908,7 @@ static void free_all(mjh_encoder *e)
   for (void *q : { (void *)e->d_tc, (void *)e->d_tdesc, e->d_tsub, (void *)e->d_tdiff, (void *)e->d_tdiff_x, (void *)e->d_tstat, (void *)e->d_tchanged }) if (q) (void)mjh_guard_free(q);
   for (void *q : { (void *)e->h_tc, (void *)e->h_tdesc, (void *)e->h_tstat[0], (void *)e->h_tstat[1], (void *)e->h_tflag }) if (q) (void)hipHostFree(q);
   for (hipEvent_t ev : e->tc_ev) if (ev) (void)hipEventDestroy(ev);
+  for (hipEvent_t ev : e->pg_ev) if (ev) (void)hipEventDestroy(ev);
   if (e->d_pixout) (void)mjh_guard_free(e->d_pixout);
   if (e->d_coefx) (void)mjh_guard_free(e->d_coefx);
   for (hipEvent_t ev : e->cx_ev) if (ev) (void)hipEventDestroy(ev);
@@ -2784,7 +2790,8 @@ static void build_xform(const MjhXformPlan &g, const MjhConst &Cd, MjhXform *X)
 // The front half both mjh_transcode_host and mjh_decode_host run: marker walk, agreement with the encoder, descriptors, staging and
 // the K-D kernels.  It leaves the batch's coefficient planes in d_q and its per-image status in d_tstat, both queued on e->stream.
 // pixels: the caller is mjh_decode_host (no result arenas are made); *o_jfif_out: where the files' APP0 fields lie in d_tdesc
-static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t sizes[], int n, bool pixels, size_t *o_jfif_out)
+// samples: the caller goes on to the inverse DCT (pixels or planes), where the reference would smooth the blocks of some progressive files
+static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t sizes[], int n, bool pixels, size_t *o_jfif_out, bool samples = false)
 {
   if (e) { e->tc_n = 0; e->tc_code.clear(); e->tc_text.clear(); e->tc_queued = false; e->dp_queued = false; }   // a call refused as a whole leaves no per-file status, and none of an earlier batch
   if (!e || !jpegs || !sizes || n < 1 || n > e->max_batch) return fail(MJH_EINVAL, "bad arguments (n=%d, max_batch=%d)", n, e ? e->max_batch : 0);
@@ -2800,8 +2807,41 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
   e->tc_S = e->dec_subseq;
   // ---- 1. marker segments of every file (a few worker threads; nothing is decoded) and the comparison with the encoder
   std::vector<mjh_jpeg_info> infos((size_t)n);
+  std::vector<std::vector<mjh_jpeg_scan_ex>> pscans((size_t)n);      // the scans of the call's progressive files
+  e->pg_levels = 0; e->pg_timed = false;
   CopyPool::get().run(n, [&](int i) {
-    int rc = (!jpegs[i] || !sizes[i]) ? fail(MJH_EINVAL, "empty file") : mjh_jpeg_probe(jpegs[i], sizes[i], &infos[i]);
+    int rc;
+    if (!jpegs[i] || !sizes[i]) rc = fail(MJH_EINVAL, "empty file");
+    else if (!e->src_accept) rc = mjh_jpeg_probe(jpegs[i], sizes[i], &infos[i]);
+    else {
+      static thread_local std::vector<mjh_jpeg_scan_ex> room;
+      room.resize(MJH_MAX_SRC_SCANS);
+      int ns = 0;
+      rc = mjh_jpeg_probe_ex(jpegs[i], sizes[i], e->src_accept, &infos[i], room.data(), MJH_MAX_SRC_SCANS, &ns);
+      if (rc == MJH_OK && infos[i].sof_type == 2) {
+        pscans[(size_t)i].assign(room.begin(), room.begin() + ns);
+        if (e->xf_on) rc = fail(MJH_EUNSUPPORTED, "a lossless transform (mjh_encoder_set_transform) together with a progressive source file");
+        else if (samples) {
+          // smoothing_ok (jdcoefct.c:360-421) at the end of the file: the DC of every component sent, the ten quantizers nonzero,
+          // and some AC coefficient of positions 1..9 never sent or not refined to its last bit
+          const mjh_jpeg_info &f = infos[i];
+          int bits[MJH_MAX_COMPS][10];
+          for (int c = 0; c < MJH_MAX_COMPS; c++) for (int k = 0; k < 10; k++) bits[c][k] = -1;
+          for (const mjh_jpeg_scan_ex &x : pscans[(size_t)i])
+            for (int j = 0; j < x.comps_in_scan; j++)
+              for (int k = x.Ss; k <= x.Se && k < 10; k++) bits[x.component_index[j]][k] = x.Al;
+          bool ok = true, useful = false;
+          for (int c = 0; c < f.num_components; c++) {
+            for (int k = 0; k < 10; k++) if (f.quantval[f.quant_tbl_no[c]][kZZ[k]] == 0) ok = false;
+            if (bits[c][0] < 0) ok = false;
+            for (int k = 1; k < 10; k++) if (bits[c][k] != 0) useful = true;
+          }
+          if (ok && useful)
+            rc = fail(MJH_EUNSUPPORTED, "the reference would apply block smoothing to this progressive file (jdcoefct.c smoothing_ok: an AC coefficient of positions "
+                                        "1..9 was never sent or not refined to its last bit), which is not built: its coefficients can be read and re-coded");
+        }
+      }
+    }
     if (rc == MJH_OK) {
       const mjh_jpeg_info &f = infos[i];
       const mjh_params &p = e->p_created;
@@ -2857,52 +2897,109 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
     }
   }
   const MjhConst &G = xf ? Cs : C;          // the geometry the entropy-coded data is laid out in
-  // ---- 2. descriptors: scans, restart segments (RSTn positions: a byte search), subsequences, derived Huffman tables
+  // ---- 2. descriptors: scans, restart segments (RSTn positions: a byte search), subsequences, derived Huffman tables.
+  // One set of descriptor arrays per group of scans that is launched together: [0] the scans of the sequential files, [1] the first
+  // scans (Ah = 0) of the progressive files, then per level of refinement scans l >= 1 its DC refinements [2 l] and its AC refinements
+  // [2 l + 1].  A scan's level is 1 + the highest level among the earlier scans of its file that share a component and overlap
+  // its coefficient range; first scans are level 0.  Only sets 0 and 1 have subsequences.
   const int S = e->dec_subseq;
   const int frame_mcus = G.mcus_per_row * G.mcu_rows;
-  std::vector<MjhDecScan> scans;
-  std::vector<MjhDecSeg> segs;
-  std::vector<unsigned> sub_seg;
+  struct DescSet {
+    std::vector<MjhDecScan> scans;
+    std::vector<MjhDecProg> ps;
+    std::vector<MjhDecSeg> segs;
+    std::vector<unsigned> sub_seg;
+    int max_nsub = 1;
+    size_t o_scans = 0, o_ps = 0, o_segs = 0, o_subs = 0, sub_base = 0;      // where the arrays lie in d_tdesc / d_tsub
+  };
+  std::vector<DescSet> sets(2);
   std::vector<MjhDecTable> tables;
   std::vector<size_t> file_off((size_t)n);
   size_t total_bytes = 0;
-  int max_nsub = 1;
+  int levels = 0;
   for (int i = 0; i < n; i++) { file_off[(size_t)i] = total_bytes; total_bytes += up16(sizes[i]); }
   for (int i = 0; i < n; i++) {
     if (e->tc_code[(size_t)i] != MJH_OK) continue;
     const mjh_jpeg_info &f = infos[(size_t)i];
+    const std::vector<mjh_jpeg_scan_ex> &px = pscans[(size_t)i];
+    const bool prog = f.sof_type == 2;
     const uint8_t *d = (const uint8_t *)jpegs[i];
-    const size_t scans0 = scans.size(), segs0 = segs.size(), subs0 = sub_seg.size(), tabs0 = tables.size();
+    std::vector<std::array<size_t, 4>> saved;
+    for (const DescSet &t : sets) saved.push_back(std::array<size_t, 4>{ { t.scans.size(), t.segs.size(), t.sub_seg.size(), (size_t)t.max_nsub } });
+    const size_t tabs0 = tables.size();
     const char *why = nullptr;
     long long diff_off = 0;
-    for (int k = 0; k < f.num_scans && !why; k++) {
-      const mjh_jpeg_scan &fs = f.scans[k];
+    int level_of[MJH_MAX_SRC_SCANS];
+    int file_levels = 0;
+    const int nscans = prog ? (int)px.size() : f.num_scans;
+    for (int k = 0; k < nscans && !why; k++) {
+      // the fields both kinds of scan record share, and the progression parameters (a sequential scan: everything at once)
+      MjhDecProg pp = { 0, 63, 0, 0 };
+      int ncs, tbl_dc[MJH_MAX_COMPS], tbl_ac[MJH_MAX_COMPS], cidx[MJH_MAX_COMPS];
+      unsigned ri_file, nrst;
+      size_t data_offset, data_size;
+      const uint8_t (*hbits)[17];
+      const uint8_t (*hvals)[256];
+      auto take = [&](const auto &fs) {
+        ncs = fs.comps_in_scan;
+        for (int j = 0; j < MJH_MAX_COMPS; j++) { cidx[j] = fs.component_index[j]; tbl_dc[j] = fs.dc_tbl_no[j]; tbl_ac[j] = fs.ac_tbl_no[j]; }
+        ri_file = fs.restart_interval; nrst = fs.restart_markers; data_offset = fs.data_offset; data_size = fs.data_size;
+        hbits = fs.huff_bits; hvals = fs.huff_vals;
+      };
+      int set_idx = 0;
+      if (prog) {
+        const mjh_jpeg_scan_ex &x = px[(size_t)k];
+        take(x);
+        pp.Ss = x.Ss; pp.Se = x.Se; pp.Ah = x.Ah; pp.Al = x.Al;
+        int lv = 0;
+        if (x.Ah)
+          for (int t = 0; t < k; t++) {
+            const mjh_jpeg_scan_ex &y = px[(size_t)t];
+            bool shares = false;
+            for (int a = 0; a < x.comps_in_scan; a++) for (int b = 0; b < y.comps_in_scan; b++) shares = shares || x.component_index[a] == y.component_index[b];
+            if (shares && y.Ss <= x.Se && x.Ss <= y.Se && level_of[t] + 1 > lv) lv = level_of[t] + 1;
+          }
+        level_of[k] = lv;
+        if (lv + 1 > file_levels) file_levels = lv + 1;
+        set_idx = lv == 0 ? 1 : 2 * lv + (x.Ss == 0 ? 0 : 1);
+        if ((size_t)set_idx >= sets.size()) sets.resize((size_t)set_idx + 1);
+      } else take(f.scans[k]);
+      DescSet &D = sets[(size_t)set_idx];
+      const bool need_dc = pp.Ss == 0 && pp.Ah == 0, need_ac = pp.Se != 0;      // the tables the scan decodes with (DC refinement: none)
       if (xf) {      // a scan that holds only dropped components (grayscale on a non-interleaved file) is not decoded
         bool kept = false;
-        for (int j = 0; j < fs.comps_in_scan; j++) kept = kept || fs.component_index[j] < plan.num_components;
+        for (int j = 0; j < ncs; j++) kept = kept || cidx[j] < plan.num_components;
         if (!kept) continue;
       }
       MjhDecScan sc;
       memset(&sc, 0, sizeof(sc));
       sc.image = i;
-      sc.ncomp = fs.comps_in_scan;
+      sc.ncomp = ncs;
       sc.bpm = 0;
       for (int j = 0; j < sc.ncomp; j++) {
-        const int ci = fs.component_index[j];
+        const int ci = cidx[j];
         sc.comp[j] = ci;
         sc.nb[j] = sc.ncomp == 1 ? 1 : G.c[ci].h * G.c[ci].v;
         sc.bpm += sc.nb[j];
         MjhDecTable T;
-        if (!make_dec_table(fs.huff_bits[2 * fs.dc_tbl_no[j]], fs.huff_vals[2 * fs.dc_tbl_no[j]], true, &T)) { why = "Bogus Huffman table definition (JERR_BAD_HUFF_TABLE)"; break; }
-        sc.dctab[j] = (int)tables.size(); tables.push_back(T);
-        if (!make_dec_table(fs.huff_bits[2 * fs.ac_tbl_no[j] + 1], fs.huff_vals[2 * fs.ac_tbl_no[j] + 1], false, &T)) { why = "Bogus Huffman table definition (JERR_BAD_HUFF_TABLE)"; break; }
-        sc.actab[j] = (int)tables.size(); tables.push_back(T);
+        int idx_dc = -1, idx_ac = -1;
+        if (need_dc) {
+          if (!make_dec_table(hbits[2 * tbl_dc[j]], hvals[2 * tbl_dc[j]], true, &T)) { why = "Bogus Huffman table definition (JERR_BAD_HUFF_TABLE)"; break; }
+          idx_dc = (int)tables.size(); tables.push_back(T);
+        }
+        if (need_ac) {
+          if (!make_dec_table(hbits[2 * tbl_ac[j] + 1], hvals[2 * tbl_ac[j] + 1], false, &T)) { why = "Bogus Huffman table definition (JERR_BAD_HUFF_TABLE)"; break; }
+          idx_ac = (int)tables.size(); tables.push_back(T);
+        }
+        // (a kernel that loads the scan loads both tables of every component: the one a progressive scan has stands for the other)
+        sc.dctab[j] = idx_dc >= 0 ? idx_dc : idx_ac >= 0 ? idx_ac : 0;
+        sc.actab[j] = idx_ac >= 0 ? idx_ac : sc.dctab[j];
       }
       if (why) break;
       if (sc.bpm > 10) { why = "Sampling factors too large for interleaved scan (JERR_BAD_MCU_SIZE)"; break; }
       {
         int pair[10], nbk = 0;
-        for (int j = 0; j < sc.ncomp; j++) for (int t = 0; t < sc.nb[j]; t++) pair[nbk++] = fs.dc_tbl_no[j] * 4 + fs.ac_tbl_no[j];
+        for (int j = 0; j < sc.ncomp; j++) for (int t = 0; t < sc.nb[j]; t++) pair[nbk++] = (need_dc ? tbl_dc[j] : 0) * 4 + (need_ac ? tbl_ac[j] : 0);
         for (int b = 0; b < sc.bpm; b++) {
           sc.canon[b] = b;
           for (int c = 0; c < b; c++) {
@@ -2914,34 +3011,39 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
       }
       sc.mcus = sc.ncomp == 1 ? G.c[sc.comp[0]].nblk : frame_mcus;
       sc.mcus_per_row = sc.ncomp == 1 ? G.c[sc.comp[0]].wib : G.mcus_per_row;
-      sc.ri = (fs.restart_interval && (long long)fs.restart_interval < sc.mcus) ? (int)fs.restart_interval : sc.mcus;
-      sc.diff_off = diff_off;
-      diff_off += (long long)sc.mcus * sc.bpm;
-      if (diff_off > G.total_mcu_blocks) { why = "internal: DC difference array too small"; break; }
-      if (fs.data_size >= ((size_t)1 << 28)) { why = "a scan of 256 MB or more (bit positions inside a restart segment are 32-bit)"; break; }
+      sc.ri = (ri_file && (long long)ri_file < sc.mcus) ? (int)ri_file : sc.mcus;
+      if (need_dc) {       // (the scan-order array holds DC differences: a sequential scan's, a DC first scan's)
+        sc.diff_off = diff_off;
+        diff_off += (long long)sc.mcus * sc.bpm;
+        if (diff_off > G.total_mcu_blocks) { why = "internal: DC difference array too small"; break; }
+      }
+      if (data_size >= ((size_t)1 << 28)) { why = "a scan of 256 MB or more (bit positions inside a restart segment are 32-bit)"; break; }
       // restart segments: RSTn markers are the only 0xFF not followed by 0x00 inside the range (mjh_jpeg_probe)
+      const bool subs = set_idx < 2;
       const int nseg_expected = (sc.mcus + sc.ri - 1) / sc.ri;
-      const size_t a = fs.data_offset, b = a + fs.data_size;
+      const size_t a = data_offset, b = a + data_size;
       size_t seg_start = a, q = a;
       int k_seg = 0;
-      const size_t sub_first = sub_seg.size();
+      const size_t sub_first = D.sub_seg.size();
       auto close_seg = [&](size_t end) {
         MjhDecSeg sg;
         memset(&sg, 0, sizeof(sg));
         sg.off = file_off[(size_t)i] + seg_start;
         sg.len = (unsigned)(end - seg_start);
-        sg.scan = (int)scans.size();
+        sg.scan = (int)D.scans.size();
         sg.mcu0 = k_seg * sc.ri;
         sg.nmcu = sc.mcus - sg.mcu0 < sc.ri ? sc.mcus - sg.mcu0 : sc.ri;
-        sg.sub0 = (int)sub_seg.size();
-        sg.nsub = S > 0 ? (int)((sg.len + (unsigned)S - 1) / (unsigned)S) : 1;
-        if (sg.nsub < 1) sg.nsub = 1;
-        if (sg.nsub > max_nsub) max_nsub = sg.nsub;
-        for (int t = 0; t < sg.nsub; t++) sub_seg.push_back((unsigned)segs.size());
-        segs.push_back(sg);
+        if (subs) {
+          sg.sub0 = (int)D.sub_seg.size();
+          sg.nsub = S > 0 ? (int)((sg.len + (unsigned)S - 1) / (unsigned)S) : 1;
+          if (sg.nsub < 1) sg.nsub = 1;
+          if (sg.nsub > D.max_nsub) D.max_nsub = sg.nsub;
+          for (int t = 0; t < sg.nsub; t++) D.sub_seg.push_back((unsigned)D.segs.size());
+        }
+        D.segs.push_back(sg);
         k_seg++;
       };
-      while (fs.restart_markers && q < b && !why) {      // (a scan without RSTn markers -- the probe counted them -- is one segment: no second search)
+      while (nrst && q < b && !why) {      // (a scan without RSTn markers -- the probe counted them -- is one segment: no second search)
         const uint8_t *ff = (const uint8_t *)memchr(d + q, 0xFF, b - q);
         if (!ff) break;
         q = (size_t)(ff - d);
@@ -2958,24 +3060,40 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
       if (why) break;
       close_seg(b);
       if (k_seg != nseg_expected) { why = "Corrupt JPEG data: restart markers missing in the entropy-coded data (JWRN_HIT_MARKER)"; break; }
-      while ((sub_seg.size() - sub_first) % MJH_DEC_WG) sub_seg.push_back(0xFFFFFFFFu);   // a workgroup serves one (image, scan)
-      scans.push_back(sc);
+      if (subs) while ((D.sub_seg.size() - sub_first) % MJH_DEC_WG) D.sub_seg.push_back(0xFFFFFFFFu);   // a workgroup serves one (image, scan)
+      D.scans.push_back(sc);
+      D.ps.push_back(pp);
     }
     if (why) {
-      scans.resize(scans0); segs.resize(segs0); sub_seg.resize(subs0); tables.resize(tabs0);
+      for (size_t t = 0; t < sets.size(); t++) {
+        const std::array<size_t, 4> z = t < saved.size() ? saved[t] : std::array<size_t, 4>{ { 0, 0, 0, 1 } };
+        sets[t].scans.resize(z[0]); sets[t].ps.resize(z[0]); sets[t].segs.resize(z[1]); sets[t].sub_seg.resize(z[2]); sets[t].max_nsub = (int)z[3];
+      }
+      tables.resize(tabs0);
       e->tc_code[(size_t)i] = MJH_EINVAL; e->tc_text[(size_t)i] = why;
-    }
+    } else if (file_levels > levels) levels = file_levels;
   }
   for (int i = 0; i < n; i++)
     if (e->tc_code[(size_t)i] != MJH_OK) return fail(e->tc_code[(size_t)i], "file %d: %s", i, e->tc_text[(size_t)i].c_str());
+  const bool has_prog = levels > 0;
+  e->pg_levels = levels;
   // ---- 3. staging: the files as they are + one descriptor block, two host->device copies
   int rc = pixels ? MJH_OK : host_buffers(e);
   if (rc) return rc;
   HIPCHK(hipStreamSynchronize(e->stream));   // the staging buffers may still feed the previous batch
   e->tc_syncs++;
-  const size_t nsubp = sub_seg.size();
-  const size_t o_scans = 0, o_segs = up16(o_scans + scans.size() * sizeof(MjhDecScan)), o_subs = up16(o_segs + segs.size() * sizeof(MjhDecSeg)),
-               o_tabs = up16(o_subs + nsubp * 4), o_jfif = up16(o_tabs + tables.size() * sizeof(MjhDecTable)), o_xf = up16(o_jfif + (size_t)n * 8),
+  size_t o_end = 0, nsubp = 0;
+  const size_t per_sub = sizeof(MjhDecState) + sizeof(MjhDecCarry) + sizeof(unsigned);
+  for (DescSet &D : sets) {
+    D.o_scans = o_end;
+    D.o_ps = up16(D.o_scans + D.scans.size() * sizeof(MjhDecScan));
+    D.o_segs = up16(D.o_ps + D.ps.size() * sizeof(MjhDecProg));
+    D.o_subs = up16(D.o_segs + D.segs.size() * sizeof(MjhDecSeg));
+    o_end = up16(D.o_subs + D.sub_seg.size() * 4);
+    D.sub_base = nsubp * per_sub;            // (a set's subsequence count is a multiple of the workgroup size: its arrays stay aligned)
+    nsubp += D.sub_seg.size();
+  }
+  const size_t o_tabs = o_end, o_jfif = up16(o_tabs + tables.size() * sizeof(MjhDecTable)), o_xf = up16(o_jfif + (size_t)n * 8),
                desc_bytes = xf ? up16(o_xf + sizeof(MjhXform)) : o_xf;
   if (total_bytes > e->tc_cap) {
     if (e->d_tc) { (void)mjh_guard_free(e->d_tc); e->d_tc = nullptr; }
@@ -2995,7 +3113,6 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
     HIPCHK(mjh_numa_host_alloc((void **)&e->h_tdesc, cap, hipHostMallocDefault, e->device));
     e->tdesc_cap = cap;
   }
-  const size_t per_sub = sizeof(MjhDecState) + sizeof(MjhDecCarry) + sizeof(unsigned);
   if (nsubp * per_sub > e->tsub_cap) {
     if (e->d_tsub) { (void)mjh_guard_free(e->d_tsub); e->d_tsub = nullptr; }
     e->tsub_cap = 0;
@@ -3011,6 +3128,8 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
     HIPCHK(mjh_numa_host_alloc((void **)&e->h_tflag, 64, hipHostMallocDefault, e->device));
     for (hipEvent_t &ev : e->tc_ev) HIPCHK(hipEventCreate(&ev));
   }
+  if (has_prog && !e->pg_ev[0])
+    for (hipEvent_t &ev : e->pg_ev) HIPCHK(hipEventCreate(&ev));
   if (xf) {
     const size_t need = (size_t)e->max_batch * (size_t)G.total_mcu_blocks * 2;
     if (need > e->tdiff_x_cap) {
@@ -3022,9 +3141,12 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
     memcpy(e->h_tdesc + o_xf, &X, sizeof(X));
   }
   CopyPool::get().run(n, [&](int i) { memcpy(e->h_tc + file_off[(size_t)i], jpegs[i], sizes[i]); });
-  memcpy(e->h_tdesc + o_scans, scans.data(), scans.size() * sizeof(MjhDecScan));
-  memcpy(e->h_tdesc + o_segs, segs.data(), segs.size() * sizeof(MjhDecSeg));
-  memcpy(e->h_tdesc + o_subs, sub_seg.data(), nsubp * 4);
+  for (const DescSet &D : sets) {
+    memcpy(e->h_tdesc + D.o_scans, D.scans.data(), D.scans.size() * sizeof(MjhDecScan));
+    memcpy(e->h_tdesc + D.o_ps, D.ps.data(), D.ps.size() * sizeof(MjhDecProg));
+    memcpy(e->h_tdesc + D.o_segs, D.segs.data(), D.segs.size() * sizeof(MjhDecSeg));
+    memcpy(e->h_tdesc + D.o_subs, D.sub_seg.data(), D.sub_seg.size() * 4);
+  }
   memcpy(e->h_tdesc + o_tabs, tables.data(), tables.size() * sizeof(MjhDecTable));
   for (int i = 0; i < n; i++) {       // this file's APP0 fields (jctrans.c:162-170): version only from a 1.x file, density whenever JFIF was seen
     const mjh_jpeg_info &f = infos[(size_t)i];
@@ -3039,56 +3161,90 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
   HIPCHK(hipMemcpyAsync(e->d_tc, e->h_tc, total_bytes, hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(e->d_tdesc, e->h_tdesc, desc_bytes, hipMemcpyHostToDevice, s));
   // ---- 4. the decoder
-  MjhDecBatch B;
-  memset(&B, 0, sizeof(B));
-  B.bytes = e->d_tc;
-  B.scans = (const MjhDecScan *)(e->d_tdesc + o_scans);
-  B.segs = (const MjhDecSeg *)(e->d_tdesc + o_segs);
-  B.sub_seg = (const unsigned *)(e->d_tdesc + o_subs);
-  B.tables = (const MjhDecTable *)(e->d_tdesc + o_tabs);
-  B.state = (MjhDecState *)e->d_tsub;
-  B.carry = (MjhDecCarry *)((uint8_t *)e->d_tsub + nsubp * sizeof(MjhDecState));
-  B.ord = (unsigned *)((uint8_t *)e->d_tsub + nsubp * (sizeof(MjhDecState) + sizeof(MjhDecCarry)));
-  B.changed = e->d_tchanged;
-  B.status = e->d_tstat;
-  B.diff = xf ? e->d_tdiff_x : e->d_tdiff;
-  B.nsub_padded = (int)nsubp; B.nseg = (int)segs.size(); B.nscan = (int)scans.size(); B.n = n;
-  B.S = S > 0 ? S : 1;
-  B.coef_limit = pixels ? 32767 : 1023;     // jchuff.c:596,624 refuses what it cannot code (JERR_BAD_DCT_COEF); jdhuff.c / jidctint.c take every amplitude
+  int16_t *const d_diff = xf ? e->d_tdiff_x : e->d_tdiff;
+  auto batch_of = [&](const DescSet &D) {
+    MjhDecBatch B;
+    memset(&B, 0, sizeof(B));
+    const size_t ns = D.sub_seg.size();
+    uint8_t *sub = (uint8_t *)e->d_tsub + D.sub_base;
+    B.bytes = e->d_tc;
+    B.scans = (const MjhDecScan *)(e->d_tdesc + D.o_scans);
+    B.segs = (const MjhDecSeg *)(e->d_tdesc + D.o_segs);
+    B.sub_seg = (const unsigned *)(e->d_tdesc + D.o_subs);
+    B.tables = (const MjhDecTable *)(e->d_tdesc + o_tabs);
+    B.state = (MjhDecState *)sub;
+    B.carry = (MjhDecCarry *)(sub + ns * sizeof(MjhDecState));
+    B.ord = (unsigned *)(sub + ns * (sizeof(MjhDecState) + sizeof(MjhDecCarry)));
+    B.changed = e->d_tchanged;
+    B.status = e->d_tstat;
+    B.diff = d_diff;
+    B.nsub_padded = (int)ns; B.nseg = (int)D.segs.size(); B.nscan = (int)D.scans.size(); B.n = n;
+    B.S = S > 0 ? S : 1;
+    B.coef_limit = pixels ? 32767 : 1023;     // jchuff.c:596,624 refuses what it cannot code (JERR_BAD_DCT_COEF); jdhuff.c / jidctint.c take every amplitude
+    return B;
+  };
+  auto ps_of = [&](const DescSet &D) { return (const MjhDecProg *)(e->d_tdesc + D.o_ps); };
+  const MjhDecBatch B = batch_of(sets[0]), BP = batch_of(sets[1]);      // sequential scans / first scans of progressive files
+  const MjhDecProg *const PS = ps_of(sets[1]);
   const bool timed = e->profiling != 0;
   HIPCHK(hipMemsetAsync(e->d_q, 0, (size_t)n * C.coefs_per_image * 2, s));
-  HIPCHK(hipMemsetAsync(B.diff, 0, (size_t)n * (size_t)G.total_mcu_blocks * 2, s));
+  HIPCHK(hipMemsetAsync(d_diff, 0, (size_t)n * (size_t)G.total_mcu_blocks * 2, s));
   HIPCHK(hipMemsetAsync(e->d_tstat, 0, (size_t)n * 4, s));
   HIPCHK(hipMemsetAsync(e->d_meta, 0, (size_t)n * sizeof(MjhImageMeta), s));
   if (timed) HIPCHK(hipEventRecord(e->tc_ev[0], s));
-  mjh_launch_dec_sync(G, B, 0, 1, s);
-  // Synchronisation rounds in groups of launches: the rounds of a group run back to back (a round that finds the one before it
-  // unchanged returns at once), the host reads the group's last flag and launches the next group only when it was set.  A round
-  // extends the true prefix of every segment by one subsequence at least: max_nsub - 1 rounds always suffice.
-  for (int done = 0, group = 3; done < max_nsub - 1;) {
-    const int g = group < max_nsub - 1 - done ? group : max_nsub - 1 - done;
-    HIPCHK(hipMemsetAsync(e->d_tchanged, 0, 64 * 4, s));
-    for (int q = 0; q < g; q++) mjh_launch_dec_sync(G, B, q, 0, s);
-    done += g;
-    e->tc_rounds += g;
-    if (done >= max_nsub - 1) break;
-    HIPCHK(hipMemcpyAsync(e->h_tflag, e->d_tchanged + (g - 1), 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    e->tc_syncs++;
-    if (!*(volatile unsigned *)e->h_tflag) break;
-    group = group * 2 < 64 ? group * 2 : 64;
-  }
+  // First pass, then synchronisation rounds in groups of launches: the rounds of a group run back to back (a round that finds the
+  // one before it unchanged returns at once), the host reads the group's last flag and launches the next group only when it was
+  // set.  A round extends the true prefix of every segment by one subsequence at least: max_nsub - 1 rounds always suffice.
+  auto sync_rounds = [&](const MjhDecBatch &Bx, const MjhDecProg *ps, int max_nsub) -> int {
+    auto launch = [&](int q, int first) { if (ps) mjh_launch_pdec_sync(G, Bx, ps, q, first, s); else mjh_launch_dec_sync(G, Bx, q, first, s); };
+    launch(0, 1);
+    for (int done = 0, group = 3; done < max_nsub - 1;) {
+      const int g = group < max_nsub - 1 - done ? group : max_nsub - 1 - done;
+      HIPCHK(hipMemsetAsync(e->d_tchanged, 0, 64 * 4, s));
+      for (int q = 0; q < g; q++) launch(q, 0);
+      done += g;
+      e->tc_rounds += g;
+      if (done >= max_nsub - 1) break;
+      HIPCHK(hipMemcpyAsync(e->h_tflag, e->d_tchanged + (g - 1), 4, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+      e->tc_syncs++;
+      if (!*(volatile unsigned *)e->h_tflag) break;
+      group = group * 2 < 64 ? group * 2 : 64;
+    }
+    return MJH_OK;
+  };
+  if (B.nscan) { rc = sync_rounds(B, nullptr, sets[0].max_nsub); if (rc) return rc; }
+  if (BP.nscan) { rc = sync_rounds(BP, PS, sets[1].max_nsub); if (rc) return rc; }
   if (timed) HIPCHK(hipEventRecord(e->tc_ev[1], s));
-  mjh_launch_dec_prefix(B, s);
+  if (B.nscan) mjh_launch_dec_prefix(B, s);
+  if (BP.nscan) mjh_launch_dec_prefix(BP, s);
   if (timed) HIPCHK(hipEventRecord(e->tc_ev[2], s));
   const MjhXform *d_X = (const MjhXform *)(e->d_tdesc + o_xf);
-  if (xf) mjh_launch_dec_store_x(G, B, e->d_q, d_X, s);
-  else mjh_launch_dec_store(C, B, e->d_q, s);
+  if (B.nscan) {
+    if (xf) mjh_launch_dec_store_x(G, B, e->d_q, d_X, s);
+    else mjh_launch_dec_store(C, B, e->d_q, s);
+  }
+  if (BP.nscan) mjh_launch_pdec_store(C, BP, PS, e->d_q, s);
   if (timed) HIPCHK(hipEventRecord(e->tc_ev[3], s));
-  if (xf) mjh_launch_dec_dc_x(G, B, e->d_q, d_X, s);
-  else mjh_launch_dec_dc(C, B, e->d_q, s);
-  mjh_launch_dec_scrub(C, B, e->d_q, e->d_meta, s);
+  if (B.nscan) {
+    if (xf) mjh_launch_dec_dc_x(G, B, e->d_q, d_X, s);
+    else mjh_launch_dec_dc(C, B, e->d_q, s);
+  }
+  if (BP.nscan) mjh_launch_pdec_dc(C, BP, PS, e->d_q, s);
+  if (!has_prog) mjh_launch_dec_scrub(C, B, e->d_q, e->d_meta, s);
   if (timed) { HIPCHK(hipEventRecord(e->tc_ev[4], s)); e->tc_timed = true; }
+  if (has_prog) {
+    // the refinement scans, level by level in stream order, for all images of the batch; then the scrub, which their status feeds too
+    if (timed) HIPCHK(hipEventRecord(e->pg_ev[0], s));
+    for (size_t t = 2; t < sets.size(); t++) {
+      if (sets[t].segs.empty()) continue;
+      const MjhDecBatch BR = batch_of(sets[t]);
+      if (t & 1) mjh_launch_pdec_ac_refine(C, BR, ps_of(sets[t]), e->d_q, s);
+      else mjh_launch_pdec_dc_refine(C, BR, ps_of(sets[t]), e->d_q, s);
+    }
+    if (timed) { HIPCHK(hipEventRecord(e->pg_ev[1], s)); e->pg_timed = true; }
+    mjh_launch_dec_scrub(C, BP, e->d_q, e->d_meta, s);
+  }
   HIPCHK(hipGetLastError());
   *o_jfif_out = o_jfif;
   return MJH_OK;
@@ -3115,6 +3271,29 @@ extern "C" int mjh_transcode_host(mjh_encoder *e, const void *const jpegs[], con
   if (rc) return rc;
   e->tc_batch[b] = true;
   e->tc_queued = true;
+  return MJH_OK;
+}
+
+extern "C" int mjh_encoder_set_sources(mjh_encoder *e, unsigned accept)
+{
+  if (!e) return fail(MJH_EINVAL, "null encoder");
+  if (accept & ~MJH_SRC_PROGRESSIVE) return fail(MJH_EINVAL, "unknown source kinds 0x%x (MJH_SRC_PROGRESSIVE)", accept);
+  e->src_accept = accept;
+  return MJH_OK;
+}
+
+extern "C" int mjh_decode_prog_stats(mjh_encoder *e, int *levels, float *ms)
+{
+  if (!e) return fail(MJH_EINVAL, "null encoder");
+  if (levels) *levels = e->pg_levels;
+  if (ms) {
+    *ms = 0.f;
+    if (e->pg_timed) {
+      HIPCHK(hipSetDevice(e->device));
+      HIPCHK(hipEventSynchronize(e->pg_ev[1]));
+      HIPCHK(hipEventElapsedTime(ms, e->pg_ev[0], e->pg_ev[1]));
+    }
+  }
   return MJH_OK;
 }
 
@@ -3344,7 +3523,7 @@ extern "C" int mjh_decode_host(mjh_encoder *e, const void *const jpegs[], const 
     P.bottom_up = o.bottom_up != 0;
   }
   size_t o_jfif = 0;
-  rc = decode_front(e, jpegs, sizes, n, true, &o_jfif);
+  rc = decode_front(e, jpegs, sizes, n, true, &o_jfif, true);
   if (rc) return rc;
   const MjhConst &C = e->C;
   const size_t need = raw ? 0 : (size_t)e->max_batch * (size_t)P.image_stride;

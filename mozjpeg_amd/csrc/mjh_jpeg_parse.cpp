@@ -3,6 +3,7 @@
 // a Huffman symbol: the entropy-coded data is only searched for 0xFF to find where a scan ends.
 #include <initializer_list>
 #include <stdarg.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <string.h>
 
@@ -28,11 +29,20 @@ static const int kNatural[64] = {
   35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
   58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63 };
 
-extern "C" int mjh_jpeg_probe(const void *jpeg, size_t size, mjh_jpeg_info *info)
+// The marker walk behind mjh_jpeg_probe (accept = 0, ex = nullptr) and mjh_jpeg_probe_ex.  A progressive file (SOF2, accepted with
+// MJH_SRC_PROGRESSIVE) leaves its scans in ex[] and info->num_scans at 0; its scan script is checked as start_pass_phuff_decoder
+// checks it (jdphuff.c:91-144), except that what the reference only warns about (JWRN_BOGUS_PROGRESSION) refuses the file: the
+// device decoder then never meets a refinement of something that was not sent.
+static_assert(offsetof(mjh_jpeg_scan_ex, Ss) == sizeof(mjh_jpeg_scan), "mjh_jpeg_scan_ex begins with the fields of mjh_jpeg_scan");
+static int probe_walk(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_info *info, mjh_jpeg_scan_ex *ex, int cap, int *num_ex)
 {
-  if (!jpeg || !info) return pfail(MJH_EINVAL, "bad arguments");
   const uint8_t *d = (const uint8_t *)jpeg;
   memset(info, 0, sizeof(*info));
+  if (num_ex) *num_ex = 0;
+  bool prog = false;
+  int nex = 0;
+  int coef_bits[MJH_MAX_COMPS][64];
+  for (int c = 0; c < MJH_MAX_COMPS; c++) for (int k = 0; k < 64; k++) coef_bits[c][k] = -1;
   if (size < 4 || d[0] != 0xFF || d[1] != 0xD8) return pfail(MJH_EINVAL, "Not a JPEG file: no SOI marker (JERR_NO_SOI)");
   // the tables in force (DHT segments redefine them between scans)
   static thread_local uint8_t hbits[8][17], hvals[8][256];
@@ -62,10 +72,12 @@ extern "C" int mjh_jpeg_probe(const void *jpeg, size_t size, mjh_jpeg_info *info
     switch (m) {
     case 0xC0: case 0xC1: case 0xC2: case 0xC3: case 0xC9: case 0xCA: case 0xCB:
     case 0xC5: case 0xC6: case 0xC7: case 0xCD: case 0xCE: case 0xCF: {
-      if (m == 0xC2) return pfail(MJH_EUNSUPPORTED, "progressive source file (SOF2): only sequential Huffman-coded files are decoded on the device");
+      if (m == 0xC2 && !(accept & MJH_SRC_PROGRESSIVE))
+        return pfail(MJH_EUNSUPPORTED, "progressive source file (SOF2): only sequential Huffman-coded files are decoded on the device");
       if (m == 0xC3) return pfail(MJH_EUNSUPPORTED, "lossless source file (SOF3): jpeg_copy_critical_parameters refuses it as well (JERR_NOTIMPL, jctrans.c:83)");
       if (m == 0xC9 || m == 0xCA || m == 0xCB) return pfail(MJH_EUNSUPPORTED, "arithmetic-coded source file (SOF%d)", m - 0xC0);
-      if (m != 0xC0 && m != 0xC1) return pfail(MJH_EUNSUPPORTED, "Unsupported JPEG process: SOF type 0x%02x (JERR_SOF_UNSUPPORTED)", m);
+      if (m != 0xC0 && m != 0xC1 && m != 0xC2) return pfail(MJH_EUNSUPPORTED, "Unsupported JPEG process: SOF type 0x%02x (JERR_SOF_UNSUPPORTED)", m);
+      prog = m == 0xC2;
       if (saw_sof) return pfail(MJH_EINVAL, "Invalid JPEG file structure: two SOF markers (JERR_SOF_DUPLICATE)");
       if (n < 6) return pfail(MJH_EINVAL, "Bogus marker length (JERR_BAD_LENGTH)");
       info->sof_type = m - 0xC0;
@@ -120,7 +132,7 @@ extern "C" int mjh_jpeg_probe(const void *jpeg, size_t size, mjh_jpeg_info *info
         if (n - o - 1 < need) return pfail(MJH_EINVAL, "Bogus marker length (JERR_BAD_LENGTH)");
         uint16_t q[64];
         for (int i = 0; i < 64; i++) q[kNatural[i]] = pq ? (uint16_t)((s[o + 1 + 2 * i] << 8) | s[o + 2 + 2 * i]) : s[o + 1 + i];
-        if (info->num_scans > 0 && ((info->quant_defined >> t) & 1) && memcmp(q, info->quantval[t], sizeof(q)) != 0)
+        if (info->num_scans + nex > 0 && ((info->quant_defined >> t) & 1) && memcmp(q, info->quantval[t], sizeof(q)) != 0)
           return pfail(MJH_EINVAL, "Cannot transcode due to multiple use of quantization table %d (JERR_MISMATCHED_QUANT_TABLE)", t);
         memcpy(info->quantval[t], q, sizeof(q));
         info->quant_defined |= 1 << t;
@@ -154,8 +166,22 @@ extern "C" int mjh_jpeg_probe(const void *jpeg, size_t size, mjh_jpeg_info *info
       if (n < 1) return pfail(MJH_EINVAL, "Bogus marker length (JERR_BAD_LENGTH)");
       const int nc = s[0];
       if (n != (size_t)(2 * nc + 4) || nc < 1 || nc > MJH_MAX_COMPS) return pfail(MJH_EINVAL, "Bogus marker length (JERR_BAD_LENGTH)");
-      if (info->num_scans >= MJH_MAX_FILE_SCANS) return pfail(MJH_EINVAL, "more than %d scans in a sequential file", MJH_MAX_FILE_SCANS);
-      mjh_jpeg_scan *sc = &info->scans[info->num_scans];
+      if (!prog && info->num_scans >= MJH_MAX_FILE_SCANS) return pfail(MJH_EINVAL, "more than %d scans in a sequential file", MJH_MAX_FILE_SCANS);
+      // a progressive file's scan is built in a scratch record and copied into ex[] (mjh_jpeg_scan_ex begins with the fields of
+      // mjh_jpeg_scan); scans beyond the room the caller gave are walked and checked all the same, for the count in the refusal
+      static thread_local mjh_jpeg_scan scratch;
+      if (prog) memset(&scratch, 0, sizeof(scratch));
+      mjh_jpeg_scan *sc = prog ? &scratch : &info->scans[info->num_scans];
+      const uint8_t *t = s + 1 + 2 * nc;
+      const int Ss = t[0], Se = t[1], Ah = t[2] >> 4, Al = t[2] & 15;
+      if (prog) {                      // start_pass_phuff_decoder (jdphuff.c:91-121)
+        bool bad = false;
+        if (Ss == 0) { if (Se != 0) bad = true; }
+        else if (Ss > Se || Se >= 64 || nc != 1) bad = true;
+        if (Ah != 0 && Al != Ah - 1) bad = true;
+        if (Al > 13) bad = true;
+        if (bad) return pfail(MJH_EINVAL, "Invalid progressive/lossless parameters Ss=%d Se=%d Ah=%d Al=%d (JERR_BAD_PROGRESSION)", Ss, Se, Ah, Al);
+      }
       sc->comps_in_scan = nc;
       for (int i = 0; i < nc; i++) {
         const int id = s[1 + 2 * i];
@@ -163,17 +189,32 @@ extern "C" int mjh_jpeg_probe(const void *jpeg, size_t size, mjh_jpeg_info *info
         for (int c = 0; c < info->num_components; c++) if (info->component_id[c] == id) { ci = c; break; }
         if (ci < 0) return pfail(MJH_EINVAL, "Invalid component ID %d in SOS (JERR_BAD_COMPONENT_ID)", id);
         if (i > 0 && ci <= sc->component_index[i - 1]) return pfail(MJH_EINVAL, "Invalid component ID %d in SOS (JERR_BAD_COMPONENT_ID)", id);
-        if (comp_scans[ci]++) return pfail(MJH_EINVAL, "component %d is coded by two scans of a sequential file (JERR_BAD_SCAN_SCRIPT)", ci);
+        if (comp_scans[ci]++ && !prog) return pfail(MJH_EINVAL, "component %d is coded by two scans of a sequential file (JERR_BAD_SCAN_SCRIPT)", ci);
         sc->component_index[i] = ci;
         sc->dc_tbl_no[i] = s[2 + 2 * i] >> 4;
         sc->ac_tbl_no[i] = s[2 + 2 * i] & 15;
+        if (prog) {
+          // jdphuff.c:126-144: where the reference warns, the file is refused
+          if (Ss != 0 && coef_bits[ci][0] < 0)
+            return pfail(MJH_EUNSUPPORTED, "Inconsistent progression sequence for component %d coefficient %d (JWRN_BOGUS_PROGRESSION): an AC scan before the component's DC scan", ci, 0);
+          for (int k = Ss; k <= Se; k++) {
+            const int expected = coef_bits[ci][k] < 0 ? 0 : coef_bits[ci][k];
+            if (Ah != expected || (Ah == 0 && coef_bits[ci][k] >= 0))
+              return pfail(MJH_EUNSUPPORTED, "Inconsistent progression sequence for component %d coefficient %d (JWRN_BOGUS_PROGRESSION): %s", ci, k,
+                           Ah == 0 ? "a first scan of a coefficient already coded" : coef_bits[ci][k] < 0 ? "a refinement of a coefficient not yet coded" : "a refinement whose Ah is not the Al before it");
+            coef_bits[ci][k] = Al;
+          }
+          // only the table the scan decodes with (jdphuff.c:159-176): DC first its DC table, an AC scan its AC table, DC refinement none
+          const bool need_dc = Ss == 0 && Ah == 0, need_ac = Ss != 0;
+          if ((need_dc && (sc->dc_tbl_no[i] > 3 || !((hdef >> (2 * sc->dc_tbl_no[i])) & 1))) || (need_ac && (sc->ac_tbl_no[i] > 3 || !((hdef >> (2 * sc->ac_tbl_no[i] + 1)) & 1))))
+            return pfail(MJH_EINVAL, "Huffman table 0x%02x was not defined (JERR_NO_HUFF_TABLE)", s[2 + 2 * i]);
+        } else
         if (sc->dc_tbl_no[i] > 3 || sc->ac_tbl_no[i] > 3 || !((hdef >> (2 * sc->dc_tbl_no[i])) & 1) || !((hdef >> (2 * sc->ac_tbl_no[i] + 1)) & 1))
           return pfail(MJH_EINVAL, "Huffman table 0x%02x was not defined (JERR_NO_HUFF_TABLE)", s[2 + 2 * i]);
         if (!((info->quant_defined >> info->quant_tbl_no[ci]) & 1))
           return pfail(MJH_EINVAL, "Quantization table 0x%02x was not defined (JERR_NO_QUANT_TABLE)", info->quant_tbl_no[ci]);
       }
-      const uint8_t *t = s + 1 + 2 * nc;
-      if (t[0] != 0 || t[1] != 63 || t[2] != 0)
+      if (!prog && (t[0] != 0 || t[1] != 63 || t[2] != 0))
         return pfail(MJH_EINVAL, "Invalid progressive parameters Ss=%d Se=%d Ah=%d Al=%d in a sequential file (JERR_BAD_PROGRESSION)", t[0], t[1], t[2] >> 4, t[2] & 15);
       sc->restart_interval = ri;
       sc->huff_defined = hdef;
@@ -200,7 +241,15 @@ extern "C" int mjh_jpeg_probe(const void *jpeg, size_t size, mjh_jpeg_info *info
       sc->data_size = q - pos;
       sc->restart_markers = nrst;
       pos = q;
-      info->num_scans++;
+      if (!prog) info->num_scans++;
+      else {
+        if (nex < cap) {
+          mjh_jpeg_scan_ex *xs = &ex[nex];
+          memcpy(xs, sc, sizeof(*sc));
+          xs->Ss = Ss; xs->Se = Se; xs->Ah = Ah; xs->Al = Al;
+        }
+        nex++;
+      }
       break;
     }
     default:              // APPn, COM and the rest: skipped (-copy none)
@@ -208,15 +257,32 @@ extern "C" int mjh_jpeg_probe(const void *jpeg, size_t size, mjh_jpeg_info *info
     }
   }
   if (!saw_sof) return pfail(MJH_EINVAL, "Invalid JPEG file structure: missing SOF marker (JERR_NO_IMAGE)");
-  if (info->num_scans == 0) return pfail(MJH_EINVAL, "JPEG datastream contains no image (JERR_NO_IMAGE)");
+  if (info->num_scans + nex == 0) return pfail(MJH_EINVAL, "JPEG datastream contains no image (JERR_NO_IMAGE)");
   for (int c = 0; c < info->num_components; c++)
     if (!comp_scans[c]) return pfail(MJH_EINVAL, "component %d of the source file is in no scan (JERR_MISSING_DATA)", c);
+  if (prog && nex > cap) return pfail(MJH_EUNSUPPORTED, "%d scans in a progressive file: at most %d are decoded (MJH_MAX_SRC_SCANS = %d)", nex, cap, MJH_MAX_SRC_SCANS);
+  if (num_ex) *num_ex = nex;
   // default_decompress_parms (jdapimin.c:130-205)
   if (info->num_components == 1) info->jpeg_color_space = MJH_CS_GRAYSCALE;
   else if (info->saw_JFIF_marker) info->jpeg_color_space = MJH_CS_YCbCr;
   else if (info->saw_Adobe_marker) info->jpeg_color_space = info->Adobe_transform == 0 ? MJH_CS_RGB : MJH_CS_YCbCr;
   else info->jpeg_color_space = (info->component_id[0] == 82 && info->component_id[1] == 71 && info->component_id[2] == 66) ? MJH_CS_RGB : MJH_CS_YCbCr;
   return MJH_OK;
+}
+
+extern "C" int mjh_jpeg_probe(const void *jpeg, size_t size, mjh_jpeg_info *info)
+{
+  if (!jpeg || !info) return pfail(MJH_EINVAL, "bad arguments");
+  return probe_walk(jpeg, size, 0u, info, nullptr, 0, nullptr);
+}
+
+extern "C" int mjh_jpeg_probe_ex(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_info *info, mjh_jpeg_scan_ex *scans, int cap, int *num_scans)
+{
+  if (!jpeg || !info) return pfail(MJH_EINVAL, "bad arguments");
+  if (accept & ~MJH_SRC_PROGRESSIVE) return pfail(MJH_EINVAL, "unknown source kinds 0x%x (MJH_SRC_PROGRESSIVE)", accept);
+  if (!(accept & MJH_SRC_PROGRESSIVE)) { if (num_scans) *num_scans = 0; return probe_walk(jpeg, size, 0u, info, nullptr, 0, nullptr); }
+  if (!scans || !num_scans || cap < 1) return pfail(MJH_EINVAL, "bad arguments: MJH_SRC_PROGRESSIVE needs room for the scans");
+  return probe_walk(jpeg, size, accept, info, scans, cap < MJH_MAX_SRC_SCANS ? cap : MJH_MAX_SRC_SCANS, num_scans);
 }
 
 extern "C" int mjh_params_from_jpeg(const mjh_jpeg_info *info, int compress_profile, mjh_params *p)

@@ -17,7 +17,10 @@ processes at a time for each, input and output on a RAM disk; this process opens
 files/s of re-compression to host memory (mjh_transcode_host, -revert -optimize) -- on this tree's library and on LIB, a
 libmozjpeg_hip.so built from the parent commit (python -m mozjpeg_amd.build in a checkout of it): one child process per library and
 round (MOZJPEG_AMD_LIB), alternating, the same files; the two must agree within the run-to-run spread.
-usage: python tools/bench_coefs.py [--jpegtran | --against LIB] [--seconds 2] [--repeats 3] [--rounds 11] [--out profiles/coef_bench]"""
+--progressive default|simple [--workload A|B]: the first mode on the same images as progressive files (the reference's cjpeg with its
+default switches, or with -revert -progressive), decoded with Encoder.set_sources(progressive=True); the phase times then hold
+"refinement", the milliseconds of the refinement levels.
+usage: python tools/bench_coefs.py [--jpegtran | --against LIB | --progressive default|simple [--workload B]] [--seconds 2] [--repeats 3] [--rounds 11] [--out profiles/coef_bench]"""
 import argparse
 import json
 import os
@@ -69,16 +72,18 @@ def timed(enc, files, seconds, what, host):
 
 def bench_gpu(a, isa):
     torch.cuda.init()                                  # torch's runtime before the library's (tests/conftest.py has the reason)
-    files = sources("A")
+    prog = a.progressive is not None
+    files = sources(a.workload, a.progressive)
     n = len(files)
-    info = M.jpeg_info(files[0])
-    enc = M.Encoder(M.params_from_jpeg(files[0], revert=True), max_batch=n)
+    info = M.jpeg_info(files[0], prog)
+    enc = M.Encoder(M.params_from_jpeg(files[0], revert=True, progressive_sources=prog), max_batch=n)
+    enc.set_sources(progressive=prog)
     # ---- the arrays are the reference's (8 of the files through coef_dump)
     outs = enc.decode_host(files, coefficients=True)
     with ThreadPoolExecutor(8) as ex:
         same = all(ex.map(lambda i: CC.same_arrays(outs[i], CC.parse_dump(CC.dump_files(O.REF_DIR, "dump", [files[i]])[2])), range(0, n, 8)))
     del outs
-    res = {"files": n, "width": info.image_width, "height": info.image_height, "source_bytes": sum(len(f) for f in files),
+    res = {"progressive_sources": a.progressive, "files": n, "width": info.image_width, "height": info.image_height, "source_bytes": sum(len(f) for f in files),
            "identical_to_reference": same, "kernel_sha": {k: isa[k]["sha"] for k in KERNELS}, "vgpr": {"k_export_coefs": isa["k_export_coefs"]["vgpr"]}}
     # ---- rates
     geo = [enc.coefficients_device(c) for c in range(info.num_components)]
@@ -109,9 +114,11 @@ def bench_gpu(a, isa):
         ev[1].record()
         torch.cuda.synchronize()
         if r >= 2:                                      # (two warm-up rounds)
-            phases.append(enc.transcode_stats()["ms"])
+            phases.append(dict(enc.transcode_stats()["ms"], **({"refinement": enc.prog_stats()["ms"]} if prog else {})))
             ms["export"].append(phases[-1]["export"])
             ms["copy"].append(ev[0].elapsed_time(ev[1]))
+    if prog:
+        res["levels"] = enc.prog_stats()["levels"]
     enc.close()
     res["export"] = {"bytes": nbytes, "rounds": a.rounds, "ms_all": ms}
     for k in ms:
@@ -204,6 +211,8 @@ def main():
     ap.add_argument("--jpegtran", action="store_true")
     ap.add_argument("--against", default=None)
     ap.add_argument("--existing-paths", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--progressive", default=None, choices=["default", "simple"])
+    ap.add_argument("--workload", default="A", choices=["A", "B"])
     ap.add_argument("--seconds", type=float, default=2.0)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=11)

@@ -18,7 +18,9 @@ compared with djpeg -rgb565 -bmp.
 --tj: instead of the above, files/s of tj3Decompress8 (TJPF_RGB, full size) through mozjpeg_amd/libmozjpeg_hip_turbojpeg.so on 8 files
 of workload A from one thread -- one image per call, each call synchronises -- next to the reference's oracle/_ref/libturbojpeg.so.0
 in the same process, alternating rounds; the two libraries' pixels are compared first.
-usage: python tools/bench_decode.py [--workloads A,B] [--scale 1/1] [--dct fast] [--color rgb565] [--tj] [--seconds 2] [--repeats 3] [--out profiles/decode_bench]"""
+--progressive default|simple: the workloads' images as progressive files (the reference's cjpeg with its default switches, or with
+-revert -progressive), decoded with Encoder.set_sources(progressive=True); phase_ms then holds "refinement", the refinement levels' time.
+usage: python tools/bench_decode.py [--progressive default|simple] [--workloads A,B] [--scale 1/1] [--dct fast] [--color rgb565] [--tj] [--seconds 2] [--repeats 3] [--out profiles/decode_bench]"""
 import argparse
 import json
 import os
@@ -196,7 +198,9 @@ def main():
     ap.add_argument("--dct", default=None, choices=["fast"])
     ap.add_argument("--tj", action="store_true")
     ap.add_argument("--color", default=None, choices=["rgb565"])
+    ap.add_argument("--progressive", default=None, choices=["default", "simple"])
     a = ap.parse_args()
+    prog = a.progressive is not None
     if a.dct or a.tj or a.color:
         isa = json.load(open(os.path.join(ROOT, "mozjpeg_amd", "kernel_isa.json")))
         result = {"source_stamp": isa.get("source_stamp")}
@@ -218,13 +222,14 @@ def main():
     dj_args = ["-scale", a.scale] if k != 8 else []
     isa = json.load(open(os.path.join(ROOT, "mozjpeg_amd", "kernel_isa.json")))["kernels"]
     result = {"kernel_sha": {k: isa[k]["sha"] for k in isa if k in ("k_dec_sync", "k_dec_prefix", "k_dec_store", "k_dec_dc", "k_idct", "k_upcolor") or k.startswith("k_idct_scaled")},
-              "scale": a.scale, "idct_size": k, "workloads": {}}
+              "scale": a.scale, "idct_size": k, "progressive_sources": a.progressive, "workloads": {}}
     for wl in a.workloads.split(","):
-        files = sources(wl)
+        files = sources(wl, a.progressive)
         n = len(files)
-        info = M.jpeg_info(files[0])
+        info = M.jpeg_info(files[0], prog)
         w, h = info.image_width, info.image_height
-        enc = M.Encoder(M.params_from_jpeg(files[0], revert=True), max_batch=n)
+        enc = M.Encoder(M.params_from_jpeg(files[0], revert=True, progressive_sources=prog), max_batch=n)
+        enc.set_sources(progressive=prog)
         outs = enc.decode_host(files, opts=opts)
         ow, oh = -(-w * k // 8), -(-h * k // 8)
         assert outs[0].shape == (oh, ow, 3)
@@ -255,6 +260,9 @@ def main():
             enc.submit_decode(files, opts=opts)
             enc.sync()
             ms.append(dict(enc.transcode_stats()["ms"], **enc.decode_stats()["ms"]))
+            if prog:
+                ms[-1]["refinement"] = enc.prog_stats()["ms"]
+                r["levels"] = enc.prog_stats()["levels"]
         enc.set_profiling(0)
         r["phase_ms"] = {k: sorted(m[k] for m in ms)[len(ms) // 2] for k in ms[0]}
         # byte counts of the pixel kernels: coefficients read + planes written; planes read + pixels written (4:2:0: 1.5 samples a pixel)

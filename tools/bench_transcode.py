@@ -11,7 +11,9 @@ and host synchronisations per call, the decoder's phase times and the per-kernel
 --transform NAME [--trim]: the same under a lossless transform (mozjpeg_amd.TRANSFORMS; the reference side runs jpegtran with the same
 switch), and next to the decoder's phase times what a plain device-to-device copy and a zeroing of the batch's coefficient planes take
 (the yardstick a separate permutation pass would have to be measured against).
-usage: python tools/bench_transcode.py [--workloads A,B] [--seconds 2] [--repeats 3] [--subseq 512,0] [--transform rot90 [--trim]]
+--progressive default|simple: the same images as progressive files, written by the reference's cjpeg with its default switches or with
+-revert -progressive, decoded with Encoder.set_sources(progressive=True); the refinement levels' time is reported next to the phases.
+usage: python tools/bench_transcode.py [--progressive default|simple] [--workloads A,B] [--seconds 2] [--repeats 3] [--subseq 512,0] [--transform rot90 [--trim]]
                                        [--out profiles/transcode_bench]"""
 import argparse
 import json
@@ -60,7 +62,12 @@ def plane_probe(p, n, rounds=5):
     return a.numel() * 2, best[0], best[1]
 
 
-def sources(workload):
+# --progressive: the sources as the reference's cjpeg writes them with its default switches (the max-compression profile: progressive
+# with scan search and trellis quantization, its own quantization tables) or with -revert -progressive (jpeg_simple_progression)
+PROGRESSIVE_ARGS = {None: ["-revert"], "default": [], "simple": ["-revert", "-progressive"]}
+
+
+def sources(workload, progressive=None):
     if workload == "A":
         imgs = [O.synthetic_frame(3840, 2160, seed=1234 + i) for i in range(64)]
     else:
@@ -68,7 +75,7 @@ def sources(workload):
         imgs = [big[i % 4][y:y + 240, x:x + 320] for i, (y, x) in enumerate((y, x) for y in range(0, 1920, 120) for x in range(0, 3520, 55))][:1024]
         assert len(imgs) == 1024
     with ThreadPoolExecutor(16) as ex:
-        return list(ex.map(lambda a: TC.cjpeg(a, ["-revert", "-quality", "75", "-sample", "2x2"]), imgs))
+        return list(ex.map(lambda a: TC.cjpeg(a, PROGRESSIVE_ARGS[progressive] + ["-quality", "75", "-sample", "2x2"]), imgs))
 
 
 def reference_rate(files, procs=16, switches=None):
@@ -109,19 +116,22 @@ def main():
     ap.add_argument("--subseq", default="512,0")
     ap.add_argument("--transform", default=None, choices=sorted(M.TRANSFORMS))
     ap.add_argument("--trim", action="store_true")
+    ap.add_argument("--progressive", default=None, choices=["default", "simple"])
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    prog = a.progressive is not None
     xf = dict(transform=a.transform, trim=a.trim) if a.transform else {}
     switches = SWITCHES[:2] + XC.jpegtran_args(**xf) + SWITCHES[2:]
-    result = {"switches": switches, "workloads": {}}
+    result = {"switches": switches, "progressive_sources": a.progressive, "workloads": {}}
     for wl in a.workloads.split(","):
-        files = sources(wl)
+        files = sources(wl, a.progressive)
         ref_rate, ref_outs, ramdisk = reference_rate(files, switches=switches)
         r = {"files": len(files), "source_bytes": sum(len(f) for f in files), "reference_files_per_s": ref_rate, "reference_on_ramdisk": ramdisk, "configs": {}}
         encs = {}
         for s in a.subseq.split(","):
             os.environ["MJH_DECODE_SUBSEQ"] = s
-            encs[s] = M.Encoder(M.params_from_jpeg(files[0], revert=True, optimize=True, **xf), max_batch=len(files))
+            encs[s] = M.Encoder(M.params_from_jpeg(files[0], revert=True, optimize=True, progressive_sources=prog, **xf), max_batch=len(files))
+            encs[s].set_sources(progressive=prog)
         os.environ.pop("MJH_DECODE_SUBSEQ", None)
         for s, enc in encs.items():
             outs = enc.transcode_host(files)
@@ -142,6 +152,8 @@ def main():
                 enc.submit_transcode(files)
                 enc.collect(0)
             c["decoder_ms"] = enc.transcode_stats()["ms"]
+            if prog:
+                c["refinement"] = enc.prog_stats()          # levels of scans, and the milliseconds of the levels above 0
             c["kernel_ms"] = enc.kernel_times()
             enc.set_profiling(0)
             enc.close()
