@@ -1,5 +1,5 @@
 // mjh_decode.h -- descriptors shared by the host side of mjh_transcode_host (mjh_encoder.cpp) and the Huffman decoder kernels
-// (mjh_decode.hip).  The host reads marker segments only (mjh_jpeg_probe); every Huffman symbol is decoded on the device.
+// (mjh_decode.hip, mjh_decode_prog.hip; their shared device code: mjh_decode_dev.h).  The host reads marker segments only (mjh_jpeg_probe); every Huffman symbol is decoded on the device.
 #ifndef MJH_DECODE_H
 #define MJH_DECODE_H
 #include <hip/hip_runtime.h>
@@ -69,7 +69,7 @@ struct MjhDecBatch {
 };
 
 // What a scan of a progressive file adds to MjhDecScan: entry i of a parallel array belongs to scan i of the same batch (MjhDecScan
-// keeps its layout: the kernels of mjh_decode.hip copy it into LDS word by word).  Ss..Se: the coefficient positions the scan codes
+// keeps its layout: dec_load_scan copies it into LDS word by word).  Ss..Se: the coefficient positions the scan codes
 // (0..0: a DC scan, then ncomp may be > 1; else one component and diff_off is unused); Ah = 0: a first scan, values << Al; else a
 // refinement of bit Al
 struct MjhDecProg { int Ss, Se, Ah, Al; };
@@ -94,21 +94,17 @@ struct MjhXform {
   uint8_t zz_t[64];
 };
 
-// phase 0: every lane decodes its own subsequence from the guessed state; q >= 1: one synchronisation round (exits at once when
-// round q - 1 of the group changed nothing); then block indices, the storing pass, the DC prefix sums and the scrub of damaged images
-void mjh_launch_dec_sync(const MjhConst &C, const MjhDecBatch &B, int q, int first, hipStream_t s);
+// phase 0 (first): every lane decodes its own subsequence from the guessed state; q >= 1: one synchronisation round (exits at once
+// when round q - 1 of the group changed nothing); then block indices, the storing pass, the DC running sums and the scrub of damaged
+// images.  PS == nullptr: B holds sequential scans; else the first scans of progressive files, PS[i] belonging to B.scans[i] (a batch
+// of their own; k_dec_prefix serves both).  X == nullptr: no transform; else C = the SOURCE frame's geometry and X (device memory) =
+// where things go.  PS and X together do not exist: the host refuses a transform of a progressive file.
+void mjh_launch_dec_sync(const MjhConst &C, const MjhDecBatch &B, const MjhDecProg *PS, int q, int first, hipStream_t s);
 void mjh_launch_dec_prefix(const MjhDecBatch &B, hipStream_t s);
-void mjh_launch_dec_store(const MjhConst &C, const MjhDecBatch &B, int16_t *coef_q, hipStream_t s);
-void mjh_launch_dec_dc(const MjhConst &C, const MjhDecBatch &B, int16_t *coef_q, hipStream_t s);
-// the storing pass and the DC sums with a transform: Cs = the SOURCE frame's geometry, X (device memory) = where things go
-void mjh_launch_dec_store_x(const MjhConst &Cs, const MjhDecBatch &B, int16_t *coef_q, const MjhXform *X, hipStream_t s);
-void mjh_launch_dec_dc_x(const MjhConst &Cs, const MjhDecBatch &B, int16_t *coef_q, const MjhXform *X, hipStream_t s);
-// progressive files (mjh_decode_prog.hip).  First scans: the same phases with a batch of their own (B.scans / PS in step; k_dec_prefix
-// serves both).  Refinement scans: B.segs[0 .. B.nseg) are the restart segments of ONE level's DC (dc_refine) or AC (ac_refine)
-// refinement scans; sub_seg / state / carry / ord / diff are not looked at.
-void mjh_launch_pdec_sync(const MjhConst &C, const MjhDecBatch &B, const MjhDecProg *PS, int q, int first, hipStream_t s);
-void mjh_launch_pdec_store(const MjhConst &C, const MjhDecBatch &B, const MjhDecProg *PS, int16_t *coef_q, hipStream_t s);
-void mjh_launch_pdec_dc(const MjhConst &C, const MjhDecBatch &B, const MjhDecProg *PS, int16_t *coef_q, hipStream_t s);
+void mjh_launch_dec_store(const MjhConst &C, const MjhDecBatch &B, const MjhDecProg *PS, const MjhXform *X, int16_t *coef_q, hipStream_t s);
+void mjh_launch_dec_dc(const MjhConst &C, const MjhDecBatch &B, const MjhDecProg *PS, const MjhXform *X, int16_t *coef_q, hipStream_t s);
+// refinement scans of progressive files (mjh_decode_prog.hip): B.segs[0 .. B.nseg) are the restart segments of ONE level's DC
+// (dc_refine) or AC (ac_refine) refinement scans; sub_seg / state / carry / ord / diff are not looked at.
 void mjh_launch_pdec_dc_refine(const MjhConst &C, const MjhDecBatch &B, const MjhDecProg *PS, int16_t *coef_q, hipStream_t s);
 void mjh_launch_pdec_ac_refine(const MjhConst &C, const MjhDecBatch &B, const MjhDecProg *PS, int16_t *coef_q, hipStream_t s);
 void mjh_launch_dec_scrub(const MjhConst &C, const MjhDecBatch &B, int16_t *coef_q, void *meta, hipStream_t s);

@@ -11,33 +11,20 @@
 //
 // Lossless transforms (transupp.c's flips, rotations, transpositions, trim, crop, grayscale) are fused into the stores: k_dec_store_x
 // and k_dec_dc_x decode in the source frame's geometry and write every coefficient to its place in the destination frame (MjhXform).
+//
+// This file: dec_run (one sequential block: DC symbol, then AC symbols), k_dec_prefix, the scrub and the finish, and the launchers of
+// all phases.  The phases themselves (first pass and sync rounds, storing pass, DC sums) are the bodies of mjh_decode_dev.h, which the
+// first scans of progressive files share (mjh_decode_prog.hip); k_dec_sync, k_dec_store[_x] and k_dec_dc[_x] instantiate them.
 #include <hip/hip_runtime.h>
 #include "mjh_device.h"
 #include "mjh_decode.h"
 #include "mjh_decode_dev.h"
 
-// Where block (row, col) of a source component goes in the destination frame (-1: trimmed or cropped away, or the component is
-// dropped) and, in cls, whether it was mirrored in x (1) / y (2).  The inverse of the do_* routines of transupp.c, which exists
-// because each of them permutes the blocks it keeps.  The result is checked against the destination's block grid whatever
-// the descriptors say.
-__device__ __forceinline__ int dec_xf_block(const MjhXform &X, const MjhXformComp &xc, int row, int col, unsigned &cls)
-{
-  int x = X.transpose ? row : col, y = X.transpose ? col : row;
-  cls = 0;
-  if (X.mirror_x && x < xc.cw) { x = xc.cw - 1 - x; cls |= 1u; }
-  if (X.mirror_y && y < xc.ch) { y = xc.ch - 1 - y; cls |= 2u; }
-  x -= xc.xcb; y -= xc.ycb;
-  if (x < 0 || y < 0 || x >= xc.wib || y >= xc.hib) return -1;
-  const int blk = y * xc.wib + x;
-  return blk < xc.nblk ? blk : -1;
-}
-
-// Decodes from (p, k, b) while the next code word starts in front of end_bits.  STORE: also while ord < total (the segment's
-// blocks), coefficients and DC differences written; returns true when the segment's last block was completed here.
-template <bool STORE, bool XF = false>
+// The run function of a sequential scan (declared in mjh_decode_dev.h).  XF: every store goes through *X.
+template <bool STORE, bool XF>
 __device__ __forceinline__ bool dec_run(const MjhComp *lc, const MjhDecScan &sc, const MjhDecTable *T, DecReader &R, unsigned end_bits,
                                         unsigned &p, int &k, int &b, unsigned &n, unsigned ord, unsigned total, int mcu,
-                                        int16_t *coef_img, int16_t *diff_img, unsigned &flags, int lim, const MjhXform *X = nullptr)
+                                        int16_t *coef_img, int16_t *diff_img, unsigned &flags, int lim, const MjhXform *X)
 {
   DecWhere wh{ 0, -1, 0 };
   unsigned cls = 0;
@@ -45,11 +32,7 @@ __device__ __forceinline__ bool dec_run(const MjhComp *lc, const MjhDecScan &sc,
   auto remap = [&]() {
     if (XF && wh.blk >= 0) { const int wib = lc[wh.j].wib, row = wh.blk / wib; wh.blk = dec_xf_block(*X, X->c[sc.comp[wh.j]], row, wh.blk - row * wib, cls); }
   };
-  int j = 0;
-  {
-    int t = b;
-    while (j < sc.ncomp - 1 && t >= sc.nb[j]) { t -= sc.nb[j]; j++; }
-  }
+  int j = dec_comp_of_block(sc, b);
   if (STORE) { wh = dec_locate(lc, sc, mcu, b); remap(); }
   bool bad = false;
   while (p < end_bits) {
@@ -59,14 +42,7 @@ __device__ __forceinline__ bool dec_run(const MjhComp *lc, const MjhDecScan &sc,
     bool done = false;
     if (k == 0) {
       const int s = dec_symbol(T[2 * j], w, nb, bad) & 15;
-      if (STORE) {
-        int diff = 0;
-        if (s) {
-          const int r = (int)((w << nb) >> (64 - s));
-          diff = r < (1 << (s - 1)) ? r - (1 << s) + 1 : r;       // HUFF_EXTEND
-        }
-        diff_img[wh.m] = (int16_t)diff;
-      }
+      if (STORE) diff_img[wh.m] = (int16_t)(s ? dec_extend(w, nb, s) : 0);
       p = R.advance(p, nb + s);
       k = 1;
     } else {
@@ -75,8 +51,7 @@ __device__ __forceinline__ bool dec_run(const MjhComp *lc, const MjhDecScan &sc,
       if (s) {
         k += r;
         if (STORE) {
-          const int v = (int)((w << nb) >> (64 - s));
-          const int val = v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
+          const int val = dec_extend(w, nb, s);
           if (val > lim || val < -lim) flags |= MJH_DEC_BADCOEF;
           // a run that passes position 63 lands in the spare entries of jpeg_natural_order, all 63 (jdhuff.c:619-628)
           if (XF) {
@@ -102,8 +77,8 @@ __device__ __forceinline__ bool dec_run(const MjhComp *lc, const MjhDecScan &sc,
       n++;
       k = 0;
       b++;
-      if (b >= sc.bpm) { b = 0; j = 0; mcu++; }
-      else { int t = b; j = 0; while (j < sc.ncomp - 1 && t >= sc.nb[j]) { t -= sc.nb[j]; j++; } }
+      if (b >= sc.bpm) { b = 0; mcu++; }
+      j = dec_comp_of_block(sc, b);
       if (STORE) {
         ord++;
         if (ord >= total) { if (bad) flags |= MJH_DEC_CORRUPT; return true; }
@@ -117,48 +92,7 @@ __device__ __forceinline__ bool dec_run(const MjhComp *lc, const MjhDecScan &sc,
 }
 
 __global__ void __launch_bounds__(MJH_DEC_WG)
-k_dec_sync(MjhConst C, MjhDecBatch B, int q, int first)
-{
-  __shared__ MjhDecScan sc;
-  __shared__ MjhDecTable T[2 * MJH_MAXC];
-  __shared__ MjhComp lc[MJH_MAXC];
-  if (!first && q > 0 && B.changed[q - 1] == 0u) return;      // (uniform: the round before this one changed nothing)
-  const unsigned g = blockIdx.x * MJH_DEC_WG + threadIdx.x;
-  const unsigned sg0 = B.sub_seg[blockIdx.x * MJH_DEC_WG];
-  dec_load_scan(C, B, B.segs[sg0].scan, &sc, T, lc);
-  const unsigned sg = B.sub_seg[g];
-  if (sg == 0xFFFFFFFFu) return;
-  const MjhDecSeg seg = B.segs[sg];
-  const unsigned i = g - (unsigned)seg.sub0, S = (unsigned)B.S;
-  DecReader R;
-  R.d = B.bytes + seg.off;
-  R.len = seg.len;
-  unsigned p, n = 0, flags = 0;
-  int k, b;
-  unsigned j;
-  if (first) {
-    p = dec_sub_start(R.d, R.len, i, S) * 8u;
-    k = 0; b = 0;
-    j = i;
-  } else {
-    const MjhDecCarry c = B.carry[g];
-    if (!c.active) return;
-    p = c.p; k = (int)(c.kb & 0xFFu); b = (int)(c.kb >> 8);
-    j = (unsigned)c.next;
-  }
-  (void)dec_run<false>(lc, sc, T, R, dec_sub_end_bits(R.len, j, (unsigned)seg.nsub, S), p, k, b, n, 0u, 0u, 0, nullptr, nullptr, flags, 0);
-  b = sc.canon[b];
-  const unsigned kb = (unsigned)k | ((unsigned)b << 8);
-  MjhDecState *st = B.state + seg.sub0 + j;
-  bool same = false;
-  if (!first) { const MjhDecState old = *st; same = old.p == p && old.kb == kb; }
-  st->p = p; st->kb = kb; st->n = n; st->pad = 0;          // (the lane that comes from further back knows the entry state better: its count stands)
-  MjhDecCarry c;
-  c.p = p; c.kb = kb; c.next = (int)j + 1;
-  c.active = (!same && j + 1 < (unsigned)seg.nsub) ? 1 : 0;
-  B.carry[g] = c;
-  if (!first && !same) B.changed[q] = 1u;
-}
+k_dec_sync(MjhConst C, MjhDecBatch B, int q, int first) { dec_sync_body<false>(C, B, nullptr, q, first); }
 
 // block index of every subsequence's first unfinished block: exclusive prefix sum of the counts over the segment
 __global__ void __launch_bounds__(64)
@@ -186,206 +120,15 @@ k_dec_prefix(MjhDecBatch B)
   }
 }
 
-// every subsequence again from its now known entry state, storing
+// the storing pass and the DC sums, plain and with a transform (C = the SOURCE frame's geometry, *X = where things go)
 __global__ void __launch_bounds__(MJH_DEC_WG)
-k_dec_store(MjhConst C, MjhDecBatch B, int16_t *__restrict__ coef_q)
-{
-  __shared__ MjhDecScan sc;
-  __shared__ MjhDecTable T[2 * MJH_MAXC];
-  __shared__ MjhComp lc[MJH_MAXC];
-  const unsigned g = blockIdx.x * MJH_DEC_WG + threadIdx.x;
-  const unsigned sg0 = B.sub_seg[blockIdx.x * MJH_DEC_WG];
-  dec_load_scan(C, B, B.segs[sg0].scan, &sc, T, lc);
-  const unsigned sg = B.sub_seg[g];
-  if (sg == 0xFFFFFFFFu) return;
-  const MjhDecSeg seg = B.segs[sg];
-  const unsigned i = g - (unsigned)seg.sub0, S = (unsigned)B.S;
-  DecReader R;
-  R.d = B.bytes + seg.off;
-  R.len = seg.len;
-  unsigned p = 0, n = 0, flags = 0;
-  int k = 0, b = 0;
-  if (i > 0) { const MjhDecState e = B.state[g - 1]; p = e.p; k = (int)(e.kb & 0xFFu); b = (int)(e.kb >> 8); }
-  const unsigned ord = B.ord[g], total = (unsigned)seg.nmcu * (unsigned)sc.bpm;
-  const bool last = i + 1 == (unsigned)seg.nsub;
-  if (ord < total) {
-    // (the entry state's b is ord mod bpm whenever the chain of states is the true one; a damaged stream may leave anything: the
-    //  block index decides where stores go, the state only how the bits are read)
-    b = (int)(ord % (unsigned)sc.bpm);
-    const int mcu = seg.mcu0 + (int)(ord / (unsigned)sc.bpm);
-    const bool fin = dec_run<true>(lc, sc, T, R, dec_sub_end_bits(R.len, i, (unsigned)seg.nsub, S), p, k, b, n, ord, total, mcu,
-                                   coef_q + (size_t)sc.image * C.coefs_per_image, B.diff + (size_t)sc.image * C.total_mcu_blocks, flags, B.coef_limit);
-    if (fin) {
-      // the last block ends here: nothing but the padding of its last byte may follow (jdmarker.c next_marker: "extraneous bytes"),
-      // and it must not have read past the end ("Premature end of JPEG file" / JWRN_HIT_MARKER)
-      unsigned nbp = p >> 3;
-      if (p & 7u) { const unsigned byte = nbp < R.len ? (unsigned)R.d[nbp] : 0u; nbp += 1u + (byte == 0xFFu ? 1u : 0u); }
-      if (p > R.len * 8u || nbp < R.len) flags |= MJH_DEC_CORRUPT;
-    } else if (last) flags |= MJH_DEC_CORRUPT;               // the data ends in front of the segment's last block
-  } else if (i == 0) flags |= MJH_DEC_CORRUPT;
-  if (flags) atomicOr(&B.status[sc.image], flags);
-}
-
-// the descriptor of the transform into LDS: lanes index its tables by their own k
-__device__ __forceinline__ void dec_load_xform(const MjhXform *Xg, MjhXform *X)
-{
-  const unsigned *src = reinterpret_cast<const unsigned *>(Xg);
-  unsigned *dst = reinterpret_cast<unsigned *>(X);
-  for (unsigned i = threadIdx.x; i < sizeof(MjhXform) / 4; i += MJH_DEC_WG) dst[i] = src[i];
-  __syncthreads();
-}
-
-// k_dec_store with a transform: C = the SOURCE frame's geometry, the stores go where *Xg says (the destination's planes)
+k_dec_store(MjhConst C, MjhDecBatch B, int16_t *__restrict__ coef_q) { dec_store_body<false, false>(C, B, nullptr, coef_q, nullptr); }
 __global__ void __launch_bounds__(MJH_DEC_WG)
-k_dec_store_x(MjhConst C, MjhDecBatch B, int16_t *__restrict__ coef_q, const MjhXform *__restrict__ Xg)
-{
-  __shared__ MjhDecScan sc;
-  __shared__ MjhDecTable T[2 * MJH_MAXC];
-  __shared__ MjhComp lc[MJH_MAXC];
-  __shared__ MjhXform X;
-  dec_load_xform(Xg, &X);
-  const unsigned g = blockIdx.x * MJH_DEC_WG + threadIdx.x;
-  const unsigned sg0 = B.sub_seg[blockIdx.x * MJH_DEC_WG];
-  dec_load_scan(C, B, B.segs[sg0].scan, &sc, T, lc);
-  const unsigned sg = B.sub_seg[g];
-  if (sg == 0xFFFFFFFFu) return;
-  const MjhDecSeg seg = B.segs[sg];
-  const unsigned i = g - (unsigned)seg.sub0, S = (unsigned)B.S;
-  DecReader R;
-  R.d = B.bytes + seg.off;
-  R.len = seg.len;
-  unsigned p = 0, n = 0, flags = 0;
-  int k = 0, b = 0;
-  if (i > 0) { const MjhDecState e = B.state[g - 1]; p = e.p; k = (int)(e.kb & 0xFFu); b = (int)(e.kb >> 8); }
-  const unsigned ord = B.ord[g], total = (unsigned)seg.nmcu * (unsigned)sc.bpm;
-  const bool last = i + 1 == (unsigned)seg.nsub;
-  if (ord < total) {
-    // (the entry state's b is ord mod bpm whenever the chain of states is the true one; a damaged stream may leave anything: the
-    //  block index decides where stores go, the state only how the bits are read)
-    b = (int)(ord % (unsigned)sc.bpm);
-    const int mcu = seg.mcu0 + (int)(ord / (unsigned)sc.bpm);
-    const bool fin = dec_run<true, true>(lc, sc, T, R, dec_sub_end_bits(R.len, i, (unsigned)seg.nsub, S), p, k, b, n, ord, total, mcu,
-                                   coef_q + (size_t)sc.image * X.coefs_per_image, B.diff + (size_t)sc.image * C.total_mcu_blocks, flags, B.coef_limit, &X);
-    if (fin) {
-      // the last block ends here: nothing but the padding of its last byte may follow (jdmarker.c next_marker: "extraneous bytes"),
-      // and it must not have read past the end ("Premature end of JPEG file" / JWRN_HIT_MARKER)
-      unsigned nbp = p >> 3;
-      if (p & 7u) { const unsigned byte = nbp < R.len ? (unsigned)R.d[nbp] : 0u; nbp += 1u + (byte == 0xFFu ? 1u : 0u); }
-      if (p > R.len * 8u || nbp < R.len) flags |= MJH_DEC_CORRUPT;
-    } else if (last) flags |= MJH_DEC_CORRUPT;               // the data ends in front of the segment's last block
-  } else if (i == 0) flags |= MJH_DEC_CORRUPT;
-  if (flags) atomicOr(&B.status[sc.image], flags);
-}
-
-// DC values = per component and restart segment the running sum of the stored differences (dummy blocks take part, jdhuff.c:588-592)
+k_dec_store_x(MjhConst C, MjhDecBatch B, int16_t *__restrict__ coef_q, const MjhXform *__restrict__ X) { dec_store_body<false, true>(C, B, nullptr, coef_q, X); }
 __global__ void __launch_bounds__(MJH_DEC_WG)
-k_dec_dc(MjhConst C, MjhDecBatch B, int16_t *__restrict__ coef_q)
-{
-  __shared__ int s_sum[MJH_DEC_WG];
-  __shared__ int s_rst[MJH_DEC_WG];
-  const MjhDecScan *scp = B.scans + blockIdx.y;        // (uniform: read through scalar loads, no private copy)
-  const int j = blockIdx.x, ncomp = scp->ncomp;
-  if (j >= ncomp) return;
-  const int mcus = scp->mcus, mpr = scp->mcus_per_row, image = scp->image;
-  long long doff = scp->diff_off;
-  for (int t = 0; t < j; t++) doff += (long long)scp->nb[t] * mcus;
-  const MjhComp cc = C.c[scp->comp[j]];
-  const int nbj = scp->nb[j];
-  const int N = mcus * nbj, L = scp->ri * nbj;     // blocks of the component in the scan / per restart segment
-  const int per = (N + MJH_DEC_WG - 1) / MJH_DEC_WG;
-  const int m0 = per * (int)threadIdx.x < N ? per * (int)threadIdx.x : N, m1 = m0 + per < N ? m0 + per : N;
-  const int16_t *diff = B.diff + (size_t)image * C.total_mcu_blocks + doff;
-  int sum = 0, rst = 0;
-  {
-    int ph = m0 % L;
-    for (int m = m0; m < m1; m++) {
-      if (ph == 0) { sum = 0; rst = 1; }
-      sum += diff[m];
-      if (++ph == L) ph = 0;
-    }
-  }
-  s_sum[threadIdx.x] = sum; s_rst[threadIdx.x] = rst;
-  __syncthreads();
-  int pred = 0;
-  for (int t = 0; t < (int)threadIdx.x; t++) pred = s_rst[t] ? s_sum[t] : pred + s_sum[t];
-  int16_t *dc = coef_q + (size_t)image * C.coefs_per_image + cc.coef_off;
-  int ph = m0 % L;
-  int mcu = m0 / nbj, t = m0 - mcu * nbj;
-  int my = mcu / mpr, mx = mcu - my * mpr;
-  for (int m = m0; m < m1; m++) {
-    if (ph == 0) pred = 0;
-    pred += diff[m];
-    int blk;
-    if (ncomp == 1) blk = m;
-    else {
-      const int by = t / cc.h, bx = t - by * cc.h;
-      const int row = my * cc.v + by, col = mx * cc.h + bx;
-      blk = (row < cc.hib && col < cc.wib) ? row * cc.wib + col : -1;
-    }
-    if (blk >= 0 && blk < cc.nblk) dc[blk] = (int16_t)pred;
-    if (++ph == L) ph = 0;
-    if (++t == nbj) { t = 0; if (++mx == mpr) { mx = 0; my++; } }
-  }
-}
-
-// k_dec_dc with a transform: C = the SOURCE frame's geometry (the prediction chain is the source's, dummy blocks included); only the
-// final store is mapped
+k_dec_dc(MjhConst C, MjhDecBatch B, int16_t *__restrict__ coef_q) { dec_dc_body<false, false>(C, B, nullptr, coef_q, nullptr); }
 __global__ void __launch_bounds__(MJH_DEC_WG)
-k_dec_dc_x(MjhConst C, MjhDecBatch B, int16_t *__restrict__ coef_q, const MjhXform *__restrict__ X)
-{
-  __shared__ int s_sum[MJH_DEC_WG];
-  __shared__ int s_rst[MJH_DEC_WG];
-  const MjhDecScan *scp = B.scans + blockIdx.y;        // (uniform: read through scalar loads, no private copy)
-  const int j = blockIdx.x, ncomp = scp->ncomp;
-  if (j >= ncomp) return;
-  const MjhXformComp xc = X->c[scp->comp[j]];
-  if (xc.nblk == 0) return;      // (uniform: a dropped component)
-  const int mcus = scp->mcus, mpr = scp->mcus_per_row, image = scp->image;
-  long long doff = scp->diff_off;
-  for (int t = 0; t < j; t++) doff += (long long)scp->nb[t] * mcus;
-  const MjhComp cc = C.c[scp->comp[j]];
-  const int nbj = scp->nb[j];
-  const int N = mcus * nbj, L = scp->ri * nbj;     // blocks of the component in the scan / per restart segment
-  const int per = (N + MJH_DEC_WG - 1) / MJH_DEC_WG;
-  const int m0 = per * (int)threadIdx.x < N ? per * (int)threadIdx.x : N, m1 = m0 + per < N ? m0 + per : N;
-  const int16_t *diff = B.diff + (size_t)image * C.total_mcu_blocks + doff;
-  int sum = 0, rst = 0;
-  {
-    int ph = m0 % L;
-    for (int m = m0; m < m1; m++) {
-      if (ph == 0) { sum = 0; rst = 1; }
-      sum += diff[m];
-      if (++ph == L) ph = 0;
-    }
-  }
-  s_sum[threadIdx.x] = sum; s_rst[threadIdx.x] = rst;
-  __syncthreads();
-  int pred = 0;
-  for (int t = 0; t < (int)threadIdx.x; t++) pred = s_rst[t] ? s_sum[t] : pred + s_sum[t];
-  int16_t *dc = coef_q + (size_t)image * X->coefs_per_image + xc.coef_off;
-  int ph = m0 % L;
-  int mcu = m0 / nbj, t = m0 - mcu * nbj;
-  int my = mcu / mpr, mx = mcu - my * mpr;
-  for (int m = m0; m < m1; m++) {
-    if (ph == 0) pred = 0;
-    pred += diff[m];
-    int blk;
-    if (ncomp == 1) blk = m;
-    else {
-      const int by = t / cc.h, bx = t - by * cc.h;
-      const int row = my * cc.v + by, col = mx * cc.h + bx;
-      blk = (row < cc.hib && col < cc.wib) ? row * cc.wib + col : -1;
-    }
-    if (blk >= 0 && blk < cc.nblk) {
-      unsigned cls;
-      const int row = blk / cc.wib;
-      blk = dec_xf_block(*X, xc, row, blk - row * cc.wib, cls);
-      if (blk >= 0) dc[blk] = (int16_t)pred;
-    }
-    if (++ph == L) ph = 0;
-    if (++t == nbj) { t = 0; if (++mx == mpr) { mx = 0; my++; } }
-  }
-}
+k_dec_dc_x(MjhConst C, MjhDecBatch B, int16_t *__restrict__ coef_q, const MjhXform *__restrict__ X) { dec_dc_body<false, true>(C, B, nullptr, coef_q, X); }
 
 // a damaged image continues through the schedule as zeroed blocks; its status goes where the coefficient checks report
 __global__ void __launch_bounds__(256)
@@ -409,29 +152,30 @@ k_dec_finish(const uint8_t *__restrict__ jfif7, int patch, uint8_t *__restrict__
     for (int i = 0; i < 7; i++) out[(size_t)img * out_stride + 11 + i] = jfif7[img * 8 + i];
 }
 
-void mjh_launch_dec_sync(const MjhConst &C, const MjhDecBatch &B, int q, int first, hipStream_t s)
+// PS != nullptr: the first scans of progressive files (the wrappers of mjh_decode_prog.hip); X != nullptr: a transform (sequential only)
+void mjh_launch_dec_sync(const MjhConst &C, const MjhDecBatch &B, const MjhDecProg *PS, int q, int first, hipStream_t s)
 {
-  hipLaunchKernelGGL(k_dec_sync, dim3(B.nsub_padded / MJH_DEC_WG), dim3(MJH_DEC_WG), 0, s, C, B, q, first);
+  const dim3 grid(B.nsub_padded / MJH_DEC_WG), wg(MJH_DEC_WG);
+  if (PS) hipLaunchKernelGGL(k_pdec_sync, grid, wg, 0, s, C, B, PS, q, first);
+  else hipLaunchKernelGGL(k_dec_sync, grid, wg, 0, s, C, B, q, first);
 }
 void mjh_launch_dec_prefix(const MjhDecBatch &B, hipStream_t s)
 {
   hipLaunchKernelGGL(k_dec_prefix, dim3(B.nseg), dim3(64), 0, s, B);
 }
-void mjh_launch_dec_store(const MjhConst &C, const MjhDecBatch &B, int16_t *coef_q, hipStream_t s)
+void mjh_launch_dec_store(const MjhConst &C, const MjhDecBatch &B, const MjhDecProg *PS, const MjhXform *X, int16_t *coef_q, hipStream_t s)
 {
-  hipLaunchKernelGGL(k_dec_store, dim3(B.nsub_padded / MJH_DEC_WG), dim3(MJH_DEC_WG), 0, s, C, B, coef_q);
+  const dim3 grid(B.nsub_padded / MJH_DEC_WG), wg(MJH_DEC_WG);
+  if (PS) hipLaunchKernelGGL(k_pdec_store, grid, wg, 0, s, C, B, PS, coef_q);
+  else if (X) hipLaunchKernelGGL(k_dec_store_x, grid, wg, 0, s, C, B, coef_q, X);
+  else hipLaunchKernelGGL(k_dec_store, grid, wg, 0, s, C, B, coef_q);
 }
-void mjh_launch_dec_dc(const MjhConst &C, const MjhDecBatch &B, int16_t *coef_q, hipStream_t s)
+void mjh_launch_dec_dc(const MjhConst &C, const MjhDecBatch &B, const MjhDecProg *PS, const MjhXform *X, int16_t *coef_q, hipStream_t s)
 {
-  hipLaunchKernelGGL(k_dec_dc, dim3(C.ncomp, B.nscan), dim3(MJH_DEC_WG), 0, s, C, B, coef_q);
-}
-void mjh_launch_dec_store_x(const MjhConst &Cs, const MjhDecBatch &B, int16_t *coef_q, const MjhXform *X, hipStream_t s)
-{
-  hipLaunchKernelGGL(k_dec_store_x, dim3(B.nsub_padded / MJH_DEC_WG), dim3(MJH_DEC_WG), 0, s, Cs, B, coef_q, X);
-}
-void mjh_launch_dec_dc_x(const MjhConst &Cs, const MjhDecBatch &B, int16_t *coef_q, const MjhXform *X, hipStream_t s)
-{
-  hipLaunchKernelGGL(k_dec_dc_x, dim3(Cs.ncomp, B.nscan), dim3(MJH_DEC_WG), 0, s, Cs, B, coef_q, X);
+  const dim3 grid(C.ncomp, B.nscan), wg(MJH_DEC_WG);
+  if (PS) hipLaunchKernelGGL(k_pdec_dc, grid, wg, 0, s, C, B, PS, coef_q);
+  else if (X) hipLaunchKernelGGL(k_dec_dc_x, grid, wg, 0, s, C, B, coef_q, X);
+  else hipLaunchKernelGGL(k_dec_dc, grid, wg, 0, s, C, B, coef_q);
 }
 void mjh_launch_dec_scrub(const MjhConst &C, const MjhDecBatch &B, int16_t *coef_q, void *meta, hipStream_t s)
 {

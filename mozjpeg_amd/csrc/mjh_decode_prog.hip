@@ -3,7 +3,8 @@
 // caller; every kernel here stores or changes only what its scan codes).
 //
 // First scans (Ah = 0) do not depend on one another and go through the scheme of mjh_decode.hip: restart segments x self-synchronising
-// subsequences, k_pdec_sync until the host reads "unchanged", k_dec_prefix, k_pdec_store, k_pdec_dc.
+// subsequences, k_pdec_sync until the host reads "unchanged", k_dec_prefix, k_pdec_store, k_pdec_dc.  The three are the phase bodies
+// of mjh_decode_dev.h instantiated with pdec_run, the run function of this file; the launchers of mjh_decode.hip start them.
 //   DC first (decode_mcu_DC_first): one symbol + its value bits per block, dummy blocks included; state = (bit position, block in MCU).
 //   AC first (decode_mcu_AC_first): one component, its own raster of real blocks; state = (bit position, k in Ss..Se).  An EOBn symbol
 //     ends the current block and R - 1 further ones without another bit, so it adds R to the lane's block count and leaves k = Ss:
@@ -34,26 +35,18 @@ __device__ __forceinline__ bool pdec_run(const MjhComp *lc, const MjhDecScan &sc
   bool bad = false;
   if (ps.Ss == 0) {
     // ---- DC first: (*block)[0] = (last_dc_val += diff) << Al; the differences go to the scan-order array, k_pdec_dc sums and shifts
-    int j = 0;
-    { int t = b; while (j < sc.ncomp - 1 && t >= sc.nb[j]) { t -= sc.nb[j]; j++; } }
+    int j = dec_comp_of_block(sc, b);
     while (p < end_bits) {
       if (STORE && ord >= total) break;
       const unsigned long long w = R.fetch(p);
       int nb;
       const int s = dec_symbol(T[2 * j], w, nb, bad) & 15;
-      if (STORE) {
-        int diff = 0;
-        if (s) {
-          const int r = (int)((w << nb) >> (64 - s));
-          diff = r < (1 << (s - 1)) ? r - (1 << s) + 1 : r;       // HUFF_EXTEND
-        }
-        diff_img[dec_locate(lc, sc, mcu, b).m] = (int16_t)diff;
-      }
+      if (STORE) diff_img[dec_locate(lc, sc, mcu, b).m] = (int16_t)(s ? dec_extend(w, nb, s) : 0);
       p = R.advance(p, nb + s);
       if (n <= total) n++;
       b++;
-      if (b >= sc.bpm) { b = 0; j = 0; mcu++; }
-      else { int t = b; j = 0; while (j < sc.ncomp - 1 && t >= sc.nb[j]) { t -= sc.nb[j]; j++; } }
+      if (b >= sc.bpm) { b = 0; mcu++; }
+      j = dec_comp_of_block(sc, b);
       if (STORE) {
         ord++;
         if (ord >= total) { if (bad) flags |= MJH_DEC_CORRUPT; return true; }
@@ -74,9 +67,7 @@ __device__ __forceinline__ bool pdec_run(const MjhComp *lc, const MjhDecScan &sc
     if (s) {
       k += r;
       if (STORE) {
-        const int v = (int)((w << nb) >> (64 - s));
-        const int ext = v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
-        const int val = (int)(int16_t)((unsigned)ext << ps.Al);           // (JCOEF)LEFT_SHIFT(s, Al)
+        const int val = (int)(int16_t)((unsigned)dec_extend(w, nb, s) << ps.Al);           // (JCOEF)LEFT_SHIFT(s, Al)
         if (val > lim || val < -lim) flags |= MJH_DEC_BADCOEF;
         // a run that passes Se lands where the reference puts it: position k, or 63 through the spare entries of jpeg_natural_order
         if (mcu >= 0 && mcu < cc.nblk) coef_img[cc.coef_off + (long long)(k > 63 ? 63 : k) * cc.kstride + mcu] = (int16_t)val;
@@ -110,160 +101,13 @@ __device__ __forceinline__ bool pdec_run(const MjhComp *lc, const MjhDecScan &sc
   return false;
 }
 
+// the phases of mjh_decode.hip for first scans: the shared bodies with pdec_run (launched by mjh_launch_dec_sync / _store / _dc)
 __global__ void __launch_bounds__(MJH_DEC_WG)
-k_pdec_sync(MjhConst C, MjhDecBatch B, const MjhDecProg *__restrict__ PS, int q, int first)
-{
-  __shared__ MjhDecScan sc;
-  __shared__ MjhDecTable T[2 * MJH_MAXC];
-  __shared__ MjhComp lc[MJH_MAXC];
-  if (!first && q > 0 && B.changed[q - 1] == 0u) return;      // (uniform: the round before this one changed nothing)
-  const unsigned g = blockIdx.x * MJH_DEC_WG + threadIdx.x;
-  const unsigned sg0 = B.sub_seg[blockIdx.x * MJH_DEC_WG];
-  const int scan = B.segs[sg0].scan;
-  dec_load_scan(C, B, scan, &sc, T, lc);
-  const MjhDecProg ps = PS[scan];
-  const unsigned sg = B.sub_seg[g];
-  if (sg == 0xFFFFFFFFu) return;
-  const MjhDecSeg seg = B.segs[sg];
-  const unsigned i = g - (unsigned)seg.sub0, S = (unsigned)B.S;
-  DecReader R;
-  R.d = B.bytes + seg.off;
-  R.len = seg.len;
-  unsigned p, n = 0, flags = 0;
-  int k, b;
-  unsigned j;
-  if (first) {
-    p = dec_sub_start(R.d, R.len, i, S) * 8u;
-    k = ps.Ss; b = 0;
-    j = i;
-  } else {
-    const MjhDecCarry c = B.carry[g];
-    if (!c.active) return;
-    p = c.p; k = (int)(c.kb & 0xFFu); b = (int)(c.kb >> 8);
-    j = (unsigned)c.next;
-  }
-  (void)pdec_run<false>(lc, sc, ps, T, R, dec_sub_end_bits(R.len, j, (unsigned)seg.nsub, S), p, k, b, n, 0u, (unsigned)seg.nmcu * (unsigned)sc.bpm, 0,
-                        nullptr, nullptr, flags, 0);
-  b = sc.canon[b];
-  const unsigned kb = (unsigned)k | ((unsigned)b << 8);
-  MjhDecState *st = B.state + seg.sub0 + j;
-  bool same = false;
-  if (!first) { const MjhDecState old = *st; same = old.p == p && old.kb == kb; }
-  st->p = p; st->kb = kb; st->n = n; st->pad = 0;
-  MjhDecCarry c;
-  c.p = p; c.kb = kb; c.next = (int)j + 1;
-  c.active = (!same && j + 1 < (unsigned)seg.nsub) ? 1 : 0;
-  B.carry[g] = c;
-  if (!first && !same) B.changed[q] = 1u;
-}
-
-// every subsequence again from its now known entry state and block index (k_dec_prefix), storing
+k_pdec_sync(MjhConst C, MjhDecBatch B, const MjhDecProg *__restrict__ PS, int q, int first) { dec_sync_body<true>(C, B, PS, q, first); }
 __global__ void __launch_bounds__(MJH_DEC_WG)
-k_pdec_store(MjhConst C, MjhDecBatch B, const MjhDecProg *__restrict__ PS, int16_t *__restrict__ coef_q)
-{
-  __shared__ MjhDecScan sc;
-  __shared__ MjhDecTable T[2 * MJH_MAXC];
-  __shared__ MjhComp lc[MJH_MAXC];
-  const unsigned g = blockIdx.x * MJH_DEC_WG + threadIdx.x;
-  const unsigned sg0 = B.sub_seg[blockIdx.x * MJH_DEC_WG];
-  const int scan = B.segs[sg0].scan;
-  dec_load_scan(C, B, scan, &sc, T, lc);
-  const MjhDecProg ps = PS[scan];
-  const unsigned sg = B.sub_seg[g];
-  if (sg == 0xFFFFFFFFu) return;
-  const MjhDecSeg seg = B.segs[sg];
-  const unsigned i = g - (unsigned)seg.sub0, S = (unsigned)B.S;
-  DecReader R;
-  R.d = B.bytes + seg.off;
-  R.len = seg.len;
-  unsigned p = 0, n = 0, flags = 0;
-  int k = ps.Ss, b = 0;
-  if (i > 0) { const MjhDecState e = B.state[g - 1]; p = e.p; k = (int)(e.kb & 0xFFu); b = (int)(e.kb >> 8); }
-  const unsigned ord = B.ord[g], total = (unsigned)seg.nmcu * (unsigned)sc.bpm;
-  const bool last = i + 1 == (unsigned)seg.nsub;
-  if (ord < total) {
-    // (the block index decides where stores go, the state only how the bits are read: see k_dec_store)
-    b = (int)(ord % (unsigned)sc.bpm);
-    const int mcu = seg.mcu0 + (int)(ord / (unsigned)sc.bpm);
-    const bool fin = pdec_run<true>(lc, sc, ps, T, R, dec_sub_end_bits(R.len, i, (unsigned)seg.nsub, S), p, k, b, n, ord, total, mcu,
-                                    coef_q + (size_t)sc.image * C.coefs_per_image, B.diff + (size_t)sc.image * C.total_mcu_blocks, flags, B.coef_limit);
-    if (fin) {
-      // the last block ends here: nothing but the padding of its last byte may follow, and it must not have read past the end
-      unsigned nbp = p >> 3;
-      if (p & 7u) { const unsigned byte = nbp < R.len ? (unsigned)R.d[nbp] : 0u; nbp += 1u + (byte == 0xFFu ? 1u : 0u); }
-      if (p > R.len * 8u || nbp < R.len) flags |= MJH_DEC_CORRUPT;
-    } else if (last) flags |= MJH_DEC_CORRUPT;               // the data ends in front of the segment's last block
-  } else if (i == 0) flags |= MJH_DEC_CORRUPT;
-  if (flags) atomicOr(&B.status[sc.image], flags);
-}
-
-// k_dec_dc for the DC first scans of the batch: the running sums of the differences, shifted left by the scan's Al, into plane 0
+k_pdec_store(MjhConst C, MjhDecBatch B, const MjhDecProg *__restrict__ PS, int16_t *__restrict__ coef_q) { dec_store_body<true, false>(C, B, PS, coef_q, nullptr); }
 __global__ void __launch_bounds__(MJH_DEC_WG)
-k_pdec_dc(MjhConst C, MjhDecBatch B, const MjhDecProg *__restrict__ PS, int16_t *__restrict__ coef_q)
-{
-  __shared__ int s_sum[MJH_DEC_WG];
-  __shared__ int s_rst[MJH_DEC_WG];
-  const MjhDecScan *scp = B.scans + blockIdx.y;        // (uniform: read through scalar loads, no private copy)
-  const int j = blockIdx.x, ncomp = scp->ncomp;
-  if (j >= ncomp || PS[blockIdx.y].Ss != 0) return;    // (uniform: an AC scan has no DC)
-  const int Al = PS[blockIdx.y].Al;
-  const int mcus = scp->mcus, mpr = scp->mcus_per_row, image = scp->image;
-  long long doff = scp->diff_off;
-  for (int t = 0; t < j; t++) doff += (long long)scp->nb[t] * mcus;
-  const MjhComp cc = C.c[scp->comp[j]];
-  const int nbj = scp->nb[j];
-  const int N = mcus * nbj, L = scp->ri * nbj;     // blocks of the component in the scan / per restart segment
-  const int per = (N + MJH_DEC_WG - 1) / MJH_DEC_WG;
-  const int m0 = per * (int)threadIdx.x < N ? per * (int)threadIdx.x : N, m1 = m0 + per < N ? m0 + per : N;
-  const int16_t *diff = B.diff + (size_t)image * C.total_mcu_blocks + doff;
-  int sum = 0, rst = 0;
-  {
-    int ph = m0 % L;
-    for (int m = m0; m < m1; m++) {
-      if (ph == 0) { sum = 0; rst = 1; }
-      sum += diff[m];
-      if (++ph == L) ph = 0;
-    }
-  }
-  s_sum[threadIdx.x] = sum; s_rst[threadIdx.x] = rst;
-  __syncthreads();
-  int pred = 0;
-  for (int t = 0; t < (int)threadIdx.x; t++) pred = s_rst[t] ? s_sum[t] : pred + s_sum[t];
-  int16_t *dc = coef_q + (size_t)image * C.coefs_per_image + cc.coef_off;
-  int ph = m0 % L;
-  int mcu = m0 / nbj, t = m0 - mcu * nbj;
-  int my = mcu / mpr, mx = mcu - my * mpr;
-  for (int m = m0; m < m1; m++) {
-    if (ph == 0) pred = 0;
-    pred += diff[m];
-    int blk;
-    if (ncomp == 1) blk = m;
-    else {
-      const int by = t / cc.h, bx = t - by * cc.h;
-      const int row = my * cc.v + by, col = mx * cc.h + bx;
-      blk = (row < cc.hib && col < cc.wib) ? row * cc.wib + col : -1;
-    }
-    if (blk >= 0 && blk < cc.nblk) dc[blk] = (int16_t)((unsigned)pred << Al);
-    if (++ph == L) ph = 0;
-    if (++t == nbj) { t = 0; if (++mx == mpr) { mx = 0; my++; } }
-  }
-}
-
-// the segment's scan and the geometry of its components into LDS (lanes index both by their own block)
-template <int WG>
-__device__ __forceinline__ void pdec_load_geom(const MjhConst &C, const MjhDecBatch &B, int scan, MjhDecScan *sc, MjhComp *lc)
-{
-  const unsigned *src = reinterpret_cast<const unsigned *>(B.scans + scan);
-  unsigned *dst = reinterpret_cast<unsigned *>(sc);
-  for (unsigned i = threadIdx.x; i < sizeof(MjhDecScan) / 4; i += WG) dst[i] = src[i];
-  __syncthreads();
-  for (int t = 0; t < sc->ncomp; t++) {
-    const unsigned *cs = reinterpret_cast<const unsigned *>(&C.c[sc->comp[t]]);
-    unsigned *cd = reinterpret_cast<unsigned *>(lc + t);
-    for (unsigned i = threadIdx.x; i < sizeof(MjhComp) / 4; i += WG) cd[i] = cs[i];
-  }
-  __syncthreads();
-}
+k_pdec_dc(MjhConst C, MjhDecBatch B, const MjhDecProg *__restrict__ PS, int16_t *__restrict__ coef_q) { dec_dc_body<true, false>(C, B, PS, coef_q, nullptr); }
 
 // DC refinement: one workgroup per restart segment.  Bit i of the segment's data (stuffed zeros skipped) belongs to block i of the
 // segment in MCU order, dummy blocks included; a set bit ORs 1 << Al into the block's DC value.
@@ -274,7 +118,7 @@ k_pdec_dc_refine(MjhConst C, MjhDecBatch B, const MjhDecProg *__restrict__ PS, i
   __shared__ MjhComp lc[MJH_MAXC];
   __shared__ unsigned s_cnt[MJH_DEC_WG];
   const MjhDecSeg seg = B.segs[blockIdx.x];
-  pdec_load_geom<MJH_DEC_WG>(C, B, seg.scan, &sc, lc);
+  dec_load_scan<MJH_DEC_WG, false>(C, B, seg.scan, &sc, nullptr, lc);
   const int p1 = 1 << PS[seg.scan].Al;
   const uint8_t *d = B.bytes + seg.off;
   const unsigned len = seg.len, total = (unsigned)seg.nmcu * (unsigned)sc.bpm;
@@ -354,7 +198,7 @@ k_pdec_ac_refine(MjhConst C, MjhDecBatch B, const MjhDecProg *__restrict__ PS, i
   __shared__ MjhComp lc[MJH_MAXC];
   __shared__ MjhDecTable T;
   const MjhDecSeg seg = B.segs[blockIdx.x];
-  pdec_load_geom<64>(C, B, seg.scan, &sc, lc);
+  dec_load_scan<64, false>(C, B, seg.scan, &sc, nullptr, lc);
   {
     const unsigned *ts = reinterpret_cast<const unsigned *>(B.tables + sc.actab[0]);
     unsigned *td = reinterpret_cast<unsigned *>(&T);
@@ -430,24 +274,10 @@ k_pdec_ac_refine(MjhConst C, MjhDecBatch B, const MjhDecProg *__restrict__ PS, i
   }
   // the segment's last block ends here: nothing but the padding of its last byte may follow, the cursor must not have passed the end,
   // and an EOB run must not reach beyond the segment
-  unsigned nbp = R.bp;
-  if (R.bit) { const unsigned byte = nbp < R.len ? (unsigned)R.d[nbp] : 0u; nbp += 1u + (byte == 0xFFu ? 1u : 0u); }
-  if (bad || eobrun > 0u || R.bp > R.len || (R.bp == R.len && R.bit) || nbp < R.len) flags |= MJH_DEC_CORRUPT;
+  if (bad || eobrun > 0u || dec_end_bad(R.d, R.len, R.bp, R.bit)) flags |= MJH_DEC_CORRUPT;
   if (flags && lane == 0) atomicOr(&B.status[sc.image], flags);
 }
 
-void mjh_launch_pdec_sync(const MjhConst &C, const MjhDecBatch &B, const MjhDecProg *PS, int q, int first, hipStream_t s)
-{
-  hipLaunchKernelGGL(k_pdec_sync, dim3(B.nsub_padded / MJH_DEC_WG), dim3(MJH_DEC_WG), 0, s, C, B, PS, q, first);
-}
-void mjh_launch_pdec_store(const MjhConst &C, const MjhDecBatch &B, const MjhDecProg *PS, int16_t *coef_q, hipStream_t s)
-{
-  hipLaunchKernelGGL(k_pdec_store, dim3(B.nsub_padded / MJH_DEC_WG), dim3(MJH_DEC_WG), 0, s, C, B, PS, coef_q);
-}
-void mjh_launch_pdec_dc(const MjhConst &C, const MjhDecBatch &B, const MjhDecProg *PS, int16_t *coef_q, hipStream_t s)
-{
-  hipLaunchKernelGGL(k_pdec_dc, dim3(C.ncomp, B.nscan), dim3(MJH_DEC_WG), 0, s, C, B, PS, coef_q);
-}
 void mjh_launch_pdec_dc_refine(const MjhConst &C, const MjhDecBatch &B, const MjhDecProg *PS, int16_t *coef_q, hipStream_t s)
 {
   hipLaunchKernelGGL(k_pdec_dc_refine, dim3(B.nseg), dim3(MJH_DEC_WG), 0, s, C, B, PS, coef_q);

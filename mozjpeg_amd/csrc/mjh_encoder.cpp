@@ -3196,12 +3196,11 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
   // one before it unchanged returns at once), the host reads the group's last flag and launches the next group only when it was
   // set.  A round extends the true prefix of every segment by one subsequence at least: max_nsub - 1 rounds always suffice.
   auto sync_rounds = [&](const MjhDecBatch &Bx, const MjhDecProg *ps, int max_nsub) -> int {
-    auto launch = [&](int q, int first) { if (ps) mjh_launch_pdec_sync(G, Bx, ps, q, first, s); else mjh_launch_dec_sync(G, Bx, q, first, s); };
-    launch(0, 1);
+    mjh_launch_dec_sync(G, Bx, ps, 0, 1, s);
     for (int done = 0, group = 3; done < max_nsub - 1;) {
       const int g = group < max_nsub - 1 - done ? group : max_nsub - 1 - done;
       HIPCHK(hipMemsetAsync(e->d_tchanged, 0, 64 * 4, s));
-      for (int q = 0; q < g; q++) launch(q, 0);
+      for (int q = 0; q < g; q++) mjh_launch_dec_sync(G, Bx, ps, q, 0, s);
       done += g;
       e->tc_rounds += g;
       if (done >= max_nsub - 1) break;
@@ -3219,18 +3218,12 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
   if (B.nscan) mjh_launch_dec_prefix(B, s);
   if (BP.nscan) mjh_launch_dec_prefix(BP, s);
   if (timed) HIPCHK(hipEventRecord(e->tc_ev[2], s));
-  const MjhXform *d_X = (const MjhXform *)(e->d_tdesc + o_xf);
-  if (B.nscan) {
-    if (xf) mjh_launch_dec_store_x(G, B, e->d_q, d_X, s);
-    else mjh_launch_dec_store(C, B, e->d_q, s);
-  }
-  if (BP.nscan) mjh_launch_pdec_store(C, BP, PS, e->d_q, s);
+  const MjhXform *d_X = xf ? (const MjhXform *)(e->d_tdesc + o_xf) : nullptr;      // (never with first scans: refused above)
+  if (B.nscan) mjh_launch_dec_store(G, B, nullptr, d_X, e->d_q, s);
+  if (BP.nscan) mjh_launch_dec_store(G, BP, PS, nullptr, e->d_q, s);
   if (timed) HIPCHK(hipEventRecord(e->tc_ev[3], s));
-  if (B.nscan) {
-    if (xf) mjh_launch_dec_dc_x(G, B, e->d_q, d_X, s);
-    else mjh_launch_dec_dc(C, B, e->d_q, s);
-  }
-  if (BP.nscan) mjh_launch_pdec_dc(C, BP, PS, e->d_q, s);
+  if (B.nscan) mjh_launch_dec_dc(G, B, nullptr, d_X, e->d_q, s);
+  if (BP.nscan) mjh_launch_dec_dc(G, BP, PS, nullptr, e->d_q, s);
   if (!has_prog) mjh_launch_dec_scrub(C, B, e->d_q, e->d_meta, s);
   if (timed) { HIPCHK(hipEventRecord(e->tc_ev[4], s)); e->tc_timed = true; }
   if (has_prog) {
