@@ -320,7 +320,8 @@ int mjh_encoder_sync(mjh_encoder *e);
  * (mjh_decode.hip), whose output feeds the entropy-coding passes of mjh_encode_coefficients_*.
  * Accepted: Huffman-coded sequential DCT files (SOF0, SOF1), 8-bit, 1 or 3 components, one interleaved scan or several
  * scans (every component in exactly one), any restart intervals.  MJH_EUNSUPPORTED: progressive (unless asked for, see
- * mjh_encoder_set_sources below), arithmetic, lossless, 12-bit, 2 or 4 components, DNL.  COM / APPn markers are not copied (-copy none). */
+ * mjh_encoder_set_sources below), arithmetic, lossless (decoded to samples when asked for, MJH_SRC_LOSSLESS below; never re-compressed),
+ * 12-bit, 2 or 4 components, DNL.  COM / APPn markers are not copied (-copy none). */
 #define MJH_MAX_FILE_SCANS 4
 #define MJH_CS_GRAYSCALE 1   /* J_COLOR_SPACE values (jpeglib.h:232-234) */
 #define MJH_CS_RGB       2
@@ -339,7 +340,7 @@ typedef struct {
   uint8_t huff_vals[8][256];
 } mjh_jpeg_scan;
 typedef struct {
-  int sof_type;                                     /* 0 = SOF0 (baseline), 1 = SOF1 (extended sequential), 2 = SOF2 (mjh_jpeg_probe_ex only) */
+  int sof_type;                                     /* 0 = SOF0 (baseline), 1 = SOF1 (extended sequential), 2 = SOF2, 3 = SOF3 (both mjh_jpeg_probe_ex only) */
   int data_precision;
   int image_width, image_height;
   int num_components;
@@ -351,6 +352,7 @@ typedef struct {
   int saw_Adobe_marker, Adobe_transform;
   int num_scans;
   mjh_jpeg_scan scans[MJH_MAX_FILE_SCANS];
+  int lossless_psv, lossless_pt;                    /* appended: a lossless file's first scan, its predictor (Ss) and point transform (Al); else 0 */
 } mjh_jpeg_info;
 /* Walks the marker segments of one file (jdmarker.c).  Searches the entropy-coded data for 0xFF to find where a scan
  * ends; decodes nothing.  MJH_EINVAL with the reference's reason for malformed headers, MJH_EUNSUPPORTED for file
@@ -371,6 +373,32 @@ int mjh_jpeg_probe(const void *jpeg, size_t size, mjh_jpeg_info *info);
  * accept = 0: mjh_jpeg_probe (scans, cap, num_scans may be NULL / 0).  A sequential file gives the same info with either flag. */
 #define MJH_SRC_PROGRESSIVE 1u
 #define MJH_MAX_SRC_SCANS 64     /* the cap on the scans of one progressive file */
+/* ---- lossless source files (SOF3, Huffman-coded), opt-in ----
+ * With MJH_SRC_LOSSLESS in `accept` (alone or OR-ed with MJH_SRC_PROGRESSIVE) mjh_jpeg_probe_ex accepts lossless files of
+ * data_precision 8, 12 or 16 (anything else: MJH_EINVAL, JERR_BAD_PRECISION), 1 or 3 components, every sampling factor 1, one
+ * interleaved scan or several scans with every component in exactly one, predictor Ss 1..7 and point transform Al 0..precision-1
+ * per scan (else MJH_EINVAL, JERR_BAD_PROGRESSION), tables in any of the four DC slots, and any restart interval that is a whole
+ * number of sample rows (else MJH_EINVAL, JERR_BAD_RESTART as jddiffct.c raises it).  It reports them the way it reports a
+ * progressive file: info->sof_type is 3, data_precision the file's, num_scans 0, the scans in scans[] with Ss = the predictor,
+ * Al = the point transform and Se = Ah = 0; info->lossless_psv / lossless_pt repeat those of the first scan.  Still
+ * MJH_EUNSUPPORTED, each naming its reason: arithmetic-coded lossless (SOF11), subsampled components, 2 or 4 components, DNL.
+ * mjh_params_from_jpeg on such an info gives the lossless parameters of the file -- mjh_params for an encoder that writes files of
+ * its size, precision, components, predictor and point transform with no colour conversion -- and an encoder made from them owns
+ * the geometry of mjh_decode_host calls on such files once mjh_encoder_set_sources(e, MJH_SRC_LOSSLESS) was called on it.  The
+ * files of one call must agree with it in size, component count and precision; they may differ in predictor, point transform,
+ * scan script, tables and restart interval.  mjh_decode_host on a lossless file (jdlhuff.c, jdlossls.c, jddiffct.c: the samples the
+ * reference's djpeg writes, which for a file of this library's encoder are the samples that went in, >> Pt << Pt):
+ *   out_color_space: 0 or the file's own (MJH_CS_GRAYSCALE for one component, MJH_CS_RGB for three).  There is no colour
+ *     conversion: MJH_CS_GRAYSCALE on a three-component file, MJH_CS_RGB on a gray file and MJH_CS_RGB565 are MJH_EUNSUPPORTED
+ *     ("Unsupported color conversion request" in the reference), and so are raw_planes and raw_coefs.
+ *   pixel_size / rgb_offset: as for DCT files but counted in SAMPLES -- 3 or 4 samples per RGB pixel, the sample of R, G and B
+ *     inside it; the fourth sample is the sample maximum 2^precision - 1 (the reference's JCS_EXT_* layouts, jdcolext.c).
+ *   bottom_up: honoured.  scale_*, fancy_upsampling, dct_method, no_dither: ignored, as the reference ignores them for these files.
+ * Samples are 1 byte (precision 8) or 2 bytes, little-endian (12, 16): mjh_decode_stats reports a pixel_size in BYTES of 1, 2, 3,
+ * 4, 6 or 8, and mjh_get_pixels / mjh_get_pixels_device address the image with it; rows hold whole groups of four pixels and are
+ * 16-byte aligned as ever.  Damaged entropy-coded data is fatal for that file alone, as on the other decode paths, and its pixels
+ * are zeros.  mjh_transcode_host refuses a lossless file whatever is set (jpegtran does: JERR_NOTIMPL, jctrans.c:83). */
+#define MJH_SRC_LOSSLESS 2u
 typedef struct {
   int comps_in_scan;                                /* the fields of mjh_jpeg_scan, in its order */
   int component_index[MJH_MAX_COMPS];
@@ -385,7 +413,7 @@ typedef struct {
 } mjh_jpeg_scan_ex;
 int mjh_jpeg_probe_ex(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_info *info, mjh_jpeg_scan_ex *scans, int cap, int *num_scans);
 /* The kinds of source file the encoder's mjh_transcode_host / mjh_decode_host calls take beyond the sequential ones: 0 (the state
- * of a new encoder) or MJH_SRC_PROGRESSIVE.  Files of one call may differ in scan script, and progressive and sequential files of
+ * of a new encoder), MJH_SRC_PROGRESSIVE, MJH_SRC_LOSSLESS or both.  Files of one call may differ in scan script, and progressive and sequential files of
  * one geometry may share a call.  Refused with a progressive file in the call (MJH_EUNSUPPORTED): a lossless transform
  * (mjh_encoder_set_transform), and -- on the way to pixels or planes only -- a file at whose end the reference would smooth blocks
  * (jdcoefct.c smoothing_ok: some AC coefficient of positions 1..9 never sent or not refined to the last bit). */
@@ -570,7 +598,8 @@ int mjh_get_coefs(mjh_encoder *e, int i, int comp, void *dst, size_t dst_blocks_
 int mjh_get_coefs_ms(mjh_encoder *e, float *ms);
 /* Size (the scaled one) and pixel size of the last decoded batch (0 after a raw_planes or raw_coefs call) and, with mjh_set_profiling(e, 1), the milliseconds of its two pixel kernels:
  * [0] dequantization + inverse DCT, [1] upsampling + colour conversion (the Huffman decoder's phases: mjh_transcode_stats).
- * Any pointer may be NULL. */
+ * After a batch of lossless files: pixel_size is in bytes (1, 2, 3, 4, 6 or 8), [0] is the undifferencing, [1] the samples into the
+ * pixel layout, and of mjh_transcode_stats' four phases the last (DC sums) is 0.  Any pointer may be NULL. */
 int mjh_decode_stats(mjh_encoder *e, int *width, int *height, int *pixel_size, float ms[2]);
 
 /* The sequential Huffman coder writes a scan without restart intervals in one walk over its blocks (MJH_ENC_ONEPASS=0 in

@@ -71,6 +71,7 @@ class JpegScanEx(C.Structure):
 
 
 SRC_PROGRESSIVE = 1         # MJH_SRC_PROGRESSIVE
+SRC_LOSSLESS = 2            # MJH_SRC_LOSSLESS
 MAX_SRC_SCANS = 64          # MJH_MAX_SRC_SCANS: the cap on the scans of one progressive file
 
 
@@ -90,7 +91,7 @@ class JpegInfo(C.Structure):
                 ("quantval", (C.c_uint16 * 64) * 4), ("jpeg_color_space", C.c_int), ("saw_JFIF_marker", C.c_int),
                 ("JFIF_major_version", C.c_int), ("JFIF_minor_version", C.c_int), ("density_unit", C.c_int),
                 ("X_density", C.c_int), ("Y_density", C.c_int), ("saw_Adobe_marker", C.c_int), ("Adobe_transform", C.c_int),
-                ("num_scans", C.c_int), ("scans", JpegScan * 4)]
+                ("num_scans", C.c_int), ("scans", JpegScan * 4), ("lossless_psv", C.c_int), ("lossless_pt", C.c_int)]
 
 
 class DecodeOpts(C.Structure):
@@ -340,20 +341,29 @@ def make_params(width, height, *, quality=75, baseline=False, revert=False, opti
     return p
 
 
-def jpeg_info(data, progressive_sources=False):
+def _src_accept(progressive_sources, lossless_sources):
+    return (SRC_PROGRESSIVE if progressive_sources else 0) | (SRC_LOSSLESS if lossless_sources else 0)
+
+
+def jpeg_info(data, progressive_sources=False, lossless_sources=False):
     """The marker segments of a JPEG file (mjh_jpeg_probe): frame, tables, colour space, JFIF / Adobe fields, and per scan its
     components, Huffman tables, restart interval and the byte range of its entropy-coded data.  Raises MjhError (EUNSUPPORTED:
     progressive, arithmetic, lossless, 12-bit, 4 components; EINVAL: malformed).
     progressive_sources=True (mjh_jpeg_probe_ex with MJH_SRC_PROGRESSIVE): a Huffman-coded progressive file is accepted; its
-    JpegInfo has sof_type 2 and num_scans 0, and its scans are the list `prog_scans` of JpegScanEx (empty for a sequential file)."""
+    JpegInfo has sof_type 2 and num_scans 0, and its scans are the list `prog_scans` of JpegScanEx (empty for a sequential file).
+    lossless_sources=True (MJH_SRC_LOSSLESS): a Huffman-coded lossless file of 8, 12 or 16 bits is accepted; its JpegInfo has
+    sof_type 3 and num_scans 0, and its scans are the list `lossless_scans` of JpegScanEx, Ss the predictor and Al the point
+    transform (empty for any other file)."""
     info = JpegInfo()
     data = bytes(data)
-    if not progressive_sources:
+    accept = _src_accept(progressive_sources, lossless_sources)
+    if not accept:
         _chk(lib().mjh_jpeg_probe(data, len(data), C.byref(info)))
         return info
     scans, n = (JpegScanEx * MAX_SRC_SCANS)(), C.c_int()
-    _chk(lib().mjh_jpeg_probe_ex(data, len(data), SRC_PROGRESSIVE, C.byref(info), scans, MAX_SRC_SCANS, C.byref(n)))
-    info.prog_scans = [scans[i] for i in range(n.value)]
+    _chk(lib().mjh_jpeg_probe_ex(data, len(data), accept, C.byref(info), scans, MAX_SRC_SCANS, C.byref(n)))
+    info.prog_scans = [scans[i] for i in range(n.value)] if info.sof_type == 2 else []
+    info.lossless_scans = [scans[i] for i in range(n.value)] if info.sof_type == 3 else []
     info._prog_keep = scans         # (the list's entries are views of this array)
     return info
 
@@ -380,14 +390,17 @@ def transform_spec(transform=None, trim=False, perfect=False, crop=None, graysca
 
 
 def params_from_jpeg(data, *, revert=False, optimize=False, progressive=None, fastcrush=False, restart=0,
-                     transform=None, trim=False, perfect=False, crop=None, grayscale=False, progressive_sources=False):
+                     transform=None, trim=False, perfect=False, crop=None, grayscale=False, progressive_sources=False,
+                     lossless_sources=False):
     """Parameters of a `jpegtran -copy none` run on this file (mjh_params_from_jpeg = jpeg_copy_critical_parameters) plus
     jpegtran's switches in make_params' vocabulary.  `data`: the file's bytes or a JpegInfo.
     transform / trim / perfect / crop / grayscale (transform_spec): the parameters of the DESTINATION of that lossless transform
     (mjh_params_from_jpeg_transform); the Transform rides along as `.transform`, and an Encoder made from these parameters
     applies it in transcode_host.  progressive_sources=True: bytes of a progressive file are accepted (jpeg_info); jpegtran copies
-    no scan script, so its parameters are those of a sequential file of the same frame."""
-    info = data if isinstance(data, JpegInfo) else jpeg_info(data, progressive_sources)
+    no scan script, so its parameters are those of a sequential file of the same frame.  lossless_sources=True: bytes of a
+    lossless file are accepted; its parameters are the lossless ones of the file (make_params(lossless=(psv, pt)) of its first
+    scan, its precision and components), for an Encoder that decodes such files -- jpegtran refuses them."""
+    info = data if isinstance(data, JpegInfo) else jpeg_info(data, progressive_sources, lossless_sources)
     p = Params()
     L = lib()
     t = transform_spec(transform, trim, perfect, crop, grayscale)
@@ -416,7 +429,7 @@ def _signature(info):
     """what the files of one mjh_transcode_host batch have in common (everything mjh_params_from_jpeg copies)"""
     nc = info.num_components
     used = sorted(set(info.quant_tbl_no[c] for c in range(nc)))
-    return (info.image_width, info.image_height, nc, info.jpeg_color_space,
+    return (info.image_width, info.image_height, nc, info.jpeg_color_space, info.sof_type == 3, info.data_precision,
             tuple((info.component_id[c], info.h_samp_factor[c], info.v_samp_factor[c], info.quant_tbl_no[c]) for c in range(nc)),
             tuple(bytes(info.quantval[t]) for t in used))
 
@@ -424,7 +437,10 @@ def _signature(info):
 _recompress_encoders = {}
 
 
-def recompress(files, *, max_batch=64, device=0, progressive_sources=False, **switches):
+_LOSSLESS_NO_COEFS = "lossless source file (SOF3): it has no DCT coefficients (jpeg_copy_critical_parameters refuses it as well: JERR_NOTIMPL, jctrans.c:83)"
+
+
+def recompress(files, *, max_batch=64, device=0, progressive_sources=False, lossless_sources=False, **switches):
     """Re-compress JPEG files on the GPU: what `jpegtran -copy none` + the switches (revert, optimize, progressive, fastcrush,
     restart) writes for each of them, in input order.  The files are grouped by what a batch must have in common; one encoder
     per group is kept for later calls.  In the max-compression profile without `revert` / `progressive` a source that is
@@ -434,15 +450,19 @@ def recompress(files, *, max_batch=64, device=0, progressive_sources=False, **sw
     them but `perfect` a source is never returned in place of its result (jpegtran clears prefer_smallest), and a file whose
     geometry refuses the request (not perfect, a crop outside the image) gets that MjhError in its slot.
     progressive_sources=True: progressive files are decoded too (Encoder.set_sources); they share batches with sequential files
-    of the same frame."""
+    of the same frame.  lossless_sources=True is accepted for symmetry with decode(): a lossless file is refused all the same
+    (EUNSUPPORTED in its slot), as jpegtran refuses it."""
     files = [bytes(f) for f in files]
     out = [None] * len(files)
     groups = {}
     for i, f in enumerate(files):
         try:
-            info = jpeg_info(f, progressive_sources)
+            info = jpeg_info(f, progressive_sources, lossless_sources)
         except MjhError as exc:
             out[i] = exc
+            continue
+        if info.sof_type == 3:
+            out[i] = MjhError(EUNSUPPORTED, _LOSSLESS_NO_COEFS)
             continue
         groups.setdefault(_signature(info), (info, []))[1].append(i)
     prefer_smallest = not (switches.get("revert") or switches.get("progressive"))
@@ -592,7 +612,7 @@ def decode_opts(color=None, layout=None, pixel_size=0, rgb_offset=None, fancy_up
 _decode_encoders = {}
 
 
-def decode(files, *, max_batch=64, device=0, progressive_sources=False, **opts):
+def decode(files, *, max_batch=64, device=0, progressive_sources=False, lossless_sources=False, **opts):
     """Decode JPEG files to pixels on the GPU: the bytes `djpeg` (+ -grayscale / -rgb / -nosmooth / -scale / -dct fast, see
     decode_opts) writes for each of them, as numpy arrays [H, W, C] ([H, W] for gray) in input order; with scale=,
     [ceil(H k / 8), ceil(W k / 8), C]; with bottom_up=True, the rows last to first.
@@ -600,8 +620,12 @@ def decode(files, *, max_batch=64, device=0, progressive_sources=False, **opts):
     later calls.  A file that cannot be decoded (unsupported type, malformed headers,
     damaged entropy-coded data) gets the MjhError in its slot; the others are unaffected.
     progressive_sources=True: progressive files are decoded too, except those whose blocks djpeg would smooth (an AC coefficient
-    of positions 1..9 never sent or not fully refined): EUNSUPPORTED naming block smoothing."""
-    return _decode_grouped(files, max_batch, device, decode_opts(**opts), progressive_sources)
+    of positions 1..9 never sent or not fully refined): EUNSUPPORTED naming block smoothing.
+    lossless_sources=True: lossless files (SOF3, 8 / 12 / 16 bits, predictors 1..7, any point transform) are decoded too, to the
+    samples djpeg writes: uint8 arrays for 8-bit files, uint16 for 12 and 16 bits, [H, W] or [H, W, 3] ([H, W, 4] for the
+    4-sample layouts, the fourth sample 2^precision - 1).  djpeg converts and scales nothing for these files: color= other than
+    the file's own is EUNSUPPORTED in the file's slot, scale / dct / fancy_upsampling are ignored."""
+    return _decode_grouped(files, max_batch, device, decode_opts(**opts), progressive_sources, lossless_sources)
 
 
 def yuv_plane_size(info, comp, k=8):
@@ -616,29 +640,30 @@ def yuv_plane_size(info, comp, k=8):
     return ph * info.v_samp_factor[comp] // maxv, pw * info.h_samp_factor[comp] // maxh
 
 
-def decode_planes(files, scale=None, dct=None, *, max_batch=64, device=0, progressive_sources=False):
+def decode_planes(files, scale=None, dct=None, *, max_batch=64, device=0, progressive_sources=False, lossless_sources=False):
     """Decode JPEG files to their sample planes on the GPU, without upsampling or colour conversion (TurboJPEG's
     tj3DecompressToYUVPlanes8): per file a list of uint8 arrays [h, w], one per component, of yuv_plane_size(), or the MjhError.
     Every component is transformed at the scale's own size (mjh_decode_opts.raw_planes), so the planes keep the file's
-    subsampling at every scale."""
-    return _decode_grouped(files, max_batch, device, decode_opts(scale=scale, dct=dct, raw_planes=True), progressive_sources)
+    subsampling at every scale.  A lossless file has no such planes: with lossless_sources=True, EUNSUPPORTED in its slot."""
+    return _decode_grouped(files, max_batch, device, decode_opts(scale=scale, dct=dct, raw_planes=True), progressive_sources, lossless_sources)
 
 
-def decode_coefficients(files, *, max_batch=64, device=0, progressive_sources=False):
+def decode_coefficients(files, *, max_batch=64, device=0, progressive_sources=False, lossless_sources=False):
     """Decode JPEG files to their quantized DCT coefficients on the GPU (jpeg_read_coefficients): per file a list of int16 arrays
     [height_in_blocks, width_in_blocks, 64], one per component, block-major and in natural order -- what
     Encoder.encode_coefficients_host takes -- or the MjhError in its slot.  The values are the file's own (no limit of +-1023 is
-    applied; the entropy coder refuses what it cannot code).  The quantization tables they belong to: jpeg_info(f).quantval."""
-    return _decode_grouped(files, max_batch, device, decode_opts(raw_coefs=True), progressive_sources)
+    applied; the entropy coder refuses what it cannot code).  The quantization tables they belong to: jpeg_info(f).quantval.
+    A lossless file has no coefficients: with lossless_sources=True, EUNSUPPORTED in its slot."""
+    return _decode_grouped(files, max_batch, device, decode_opts(raw_coefs=True), progressive_sources, lossless_sources)
 
 
-def _decode_grouped(files, max_batch, device, o, progressive_sources=False):
+def _decode_grouped(files, max_batch, device, o, progressive_sources=False, lossless_sources=False):
     files = [bytes(f) for f in files]
     out = [None] * len(files)
     groups = {}
     for i, f in enumerate(files):
         try:
-            info = jpeg_info(f, progressive_sources)
+            info = jpeg_info(f, progressive_sources, lossless_sources)
         except MjhError as exc:
             out[i] = exc
             continue
@@ -647,13 +672,13 @@ def _decode_grouped(files, max_batch, device, o, progressive_sources=False):
         key = (sig, device, LIB_PATH)
         enc = _decode_encoders.get(key)
         if enc is not None:
-            enc.set_sources(progressive=progressive_sources)
+            enc.set_sources(progressive=progressive_sources, lossless=lossless_sources)
         if enc is None or enc.max_batch < min(max_batch, len(idx)):
             if enc is not None:
                 enc.close()
             try:
                 enc = _decode_encoders[key] = Encoder(params_from_jpeg(info, revert=True), max_batch=min(max_batch, len(idx)), device=device)
-                enc.set_sources(progressive=progressive_sources)
+                enc.set_sources(progressive=progressive_sources, lossless=lossless_sources)
             except MjhError as exc:         # a frame no encoder exists for (fractional sampling ratios): this group's files alone
                 _decode_encoders.pop(key, None)
                 if exc.code != EUNSUPPORTED:
@@ -663,7 +688,12 @@ def _decode_grouped(files, max_batch, device, o, progressive_sources=False):
                 continue
         for a in range(0, len(idx), enc.max_batch):
             part = idx[a:a + enc.max_batch]
-            res = enc.decode_host([files[i] for i in part], errors="return", opts=o)
+            try:
+                res = enc.decode_host([files[i] for i in part], errors="return", opts=o)
+            except MjhError as exc:         # options djpeg refuses for a lossless file (a colour conversion, planes, coefficients)
+                if info.sof_type != 3 or exc.code != EUNSUPPORTED:
+                    raise
+                res = [exc] * len(part)
             bad = [k for k, r in enumerate(res) if isinstance(r, MjhError)]
             if bad and len(bad) < len(part):           # the good files of the batch once more, without the damaged ones
                 good = [k for k in range(len(part)) if k not in bad]
@@ -755,11 +785,13 @@ class Encoder:
         t = transform_spec(transform, **spec)
         _chk(lib().mjh_encoder_set_transform(self._h, C.byref(t) if t is not None else None))
 
-    def set_sources(self, progressive=True):
+    def set_sources(self, progressive=True, lossless=False):
         """The kinds of source file the following transcode / decode calls take beyond the sequential ones
-        (mjh_encoder_set_sources): progressive=True accepts Huffman-coded progressive files, False is the state of a new encoder."""
+        (mjh_encoder_set_sources): progressive=True accepts Huffman-coded progressive files, lossless=True lossless ones (decode
+        calls of an encoder made from params_from_jpeg of such a file); both False is the state of a new encoder."""
         self._progressive = bool(progressive)
-        _chk(lib().mjh_encoder_set_sources(self._h, SRC_PROGRESSIVE if progressive else 0))
+        self._lossless = bool(lossless)
+        _chk(lib().mjh_encoder_set_sources(self._h, _src_accept(progressive, lossless)))
 
     def prog_stats(self):
         """levels of scans in the last call's progressive files (first scans are level 0 and count; 0: no progressive file) and the
@@ -971,9 +1003,17 @@ class Encoder:
         return dict(width=w.value, height=h.value, pixel_size=px.value, ms=dict(idct=float(ms[0]), upcolor=float(ms[1])))
 
     def get_pixels(self, i, out=None):
-        """image i of the last decoded batch: uint8 [H, W, C], [H, W] for gray, uint16 [H, W] for RGB565 (mjh_get_pixels); out: an array of that shape with
-        contiguous rows to fill instead of a new one"""
+        """image i of the last decoded batch: uint8 [H, W, C], [H, W] for gray, uint16 [H, W] for RGB565, and for a lossless file its
+        samples, uint8 or (12 / 16 bits) uint16 (mjh_get_pixels); out: an array of that shape with contiguous rows to fill instead of a new one"""
         st = self.decode_stats()
+        if self._is_lossless():         # samples of 1 byte (8-bit files) or 2: [H, W] or [H, W, samples per pixel]
+            dt = np.uint16 if self.params.data_precision > 8 else np.uint8
+            spp = st["pixel_size"] // np.dtype(dt).itemsize
+            shape = (st["height"], st["width"]) + ((spp,) if spp > 1 else ())
+            a = np.empty(shape, dt) if out is None else out
+            assert a.shape == shape and a.dtype == dt and a.strides[1:] == np.empty(shape[1:], dt).strides, "expected %s %s" % (np.dtype(dt).name, shape)
+            _chk(lib().mjh_get_pixels(self._h, i, a.ctypes.data, a.strides[0]))
+            return a
         if st["pixel_size"] == 2:       # RGB565: one uint16 per pixel
             shape = (st["height"], st["width"])
             a = np.empty(shape, np.uint16) if out is None else out
@@ -985,6 +1025,11 @@ class Encoder:
         assert a.shape == shape and a.dtype == np.uint8 and a.strides[1:] == np.empty(shape[1:], np.uint8).strides, "expected uint8 %s" % (shape,)
         _chk(lib().mjh_get_pixels(self._h, i, a.ctypes.data, a.strides[0]))
         return a
+
+    def _is_lossless(self):
+        """the encoder was made from lossless parameters (make_params(lossless=...), params_from_jpeg of a lossless file)"""
+        p = self.params
+        return 0 < p.num_scans <= MAX_SCANS and p.scan_info[0].Ss != 0 and p.scan_info[0].Se == 0
 
     def pixels_device(self):
         """(device pointer, row pitch, image stride, decode_stats()) of the last decoded batch (mjh_get_pixels_device); wait_decode() first"""
@@ -1042,7 +1087,7 @@ class Encoder:
                 return [self.get_coefficients(i) for i in range(n)]
             if o.raw_planes:
                 k = 8 if o.scale_num == 0 and o.scale_denom == 0 else scale_idct_size(o.scale_num, o.scale_denom)
-                return [self.get_planes(i, jpeg_info(files[i], getattr(self, "_progressive", False)), k) for i in range(n)]
+                return [self.get_planes(i, jpeg_info(files[i], getattr(self, "_progressive", False), getattr(self, "_lossless", False)), k) for i in range(n)]
             return [self.get_pixels(i) for i in range(n)]
         except MjhError:
             if errors != "return":

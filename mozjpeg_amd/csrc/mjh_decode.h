@@ -1,5 +1,5 @@
 // mjh_decode.h -- descriptors shared by the host side of mjh_transcode_host (mjh_encoder.cpp) and the Huffman decoder kernels
-// (mjh_decode.hip, mjh_decode_prog.hip; their shared device code: mjh_decode_dev.h).  The host reads marker segments only (mjh_jpeg_probe); every Huffman symbol is decoded on the device.
+// (mjh_decode.hip, mjh_decode_prog.hip, mjh_decode_lossless.hip; their shared device code: mjh_decode_dev.h).  The host reads marker segments only (mjh_jpeg_probe); every Huffman symbol is decoded on the device.
 #ifndef MJH_DECODE_H
 #define MJH_DECODE_H
 #include <hip/hip_runtime.h>
@@ -74,6 +74,30 @@ struct MjhDecBatch {
 // refinement of bit Al
 struct MjhDecProg { int Ss, Se, Ah, Al; };
 
+// Lossless files (SOF3, mjh_decode_lossless.hip).  The entropy-coded data of a scan is one difference symbol per sample, so a scan
+// goes through the phases above with "block" = sample: MjhDecScan::nb is 1 for every component, mcus = W * H, mcus_per_row = W, and
+// the scan-order difference array becomes one plane of 16-bit differences per component, rows MjhLlGeom::Wp elements apart (component
+// j of a scan: diff_off + j * H * Wp).  The undifferencing kernels turn every plane into the reconstructed samples in place.
+struct MjhLlPlane {          // one (image, component), indexed image * ncomp + component
+  long long off;             // of its plane inside the image's difference array, in elements
+  int psv, pt;               // predictor 1..7 and point transform of the scan the component is in
+  int rows;                  // rows per restart interval (no interval: H)
+  int pad;
+};
+struct MjhLlGeom {
+  int W, H;
+  int Wp;                    // elements between rows of a plane: W rounded up to 8 (16-byte rows)
+  int ncomp, precision;
+  int max_intervals;         // the most restart intervals any plane of the batch has
+  long long per_image;       // elements of one image's difference array: ncomp * H * Wp
+};
+// where the samples go: `px` samples per pixel (1: gray; 3 or 4: component c at sample off[c], the fourth sample = fill), each of
+// 1 byte (precision 8) or 2 (12, 16; little-endian); rows hold whole groups of 4 pixels
+struct MjhLlOut {
+  int px, off[3], fill, bottom_up;
+  long long row_pitch, image_stride;     // bytes
+};
+
 // A lossless transform fused into the two places that store coefficients (mjh_encoder_set_transform): the kernels decode in the
 // SOURCE frame's geometry (the MjhConst they get is the source's) and store into the DESTINATION frame's planes.  Every operation
 // of transupp.c is: transpose or not; mirror the whole iMCUs in x and / or y (a partial iMCU at that edge stays in place); cut.
@@ -107,6 +131,15 @@ void mjh_launch_dec_dc(const MjhConst &C, const MjhDecBatch &B, const MjhDecProg
 // (dc_refine) or AC (ac_refine) refinement scans; sub_seg / state / carry / ord / diff are not looked at.
 void mjh_launch_pdec_dc_refine(const MjhConst &C, const MjhDecBatch &B, const MjhDecProg *PS, int16_t *coef_q, hipStream_t s);
 void mjh_launch_pdec_ac_refine(const MjhConst &C, const MjhDecBatch &B, const MjhDecProg *PS, int16_t *coef_q, hipStream_t s);
+// the first pass / a synchronisation round and the storing pass of a batch of lossless scans (k_dec_prefix between them); the stores
+// go to B.diff alone and no DC phase follows.  C: "blocks" = samples (h = v = 1, wib = W, hib = H, total_mcu_blocks = G.per_image)
+void mjh_launch_ldec_sync(const MjhConst &C, const MjhDecBatch &B, int q, int first, hipStream_t s);
+void mjh_launch_ldec_store(const MjhConst &C, const MjhDecBatch &B, hipStream_t s);
+// undifferencing (jdlossls.c) of all planes of the batch in place, then the samples << pt into the pixel layout; an image whose
+// status is set gets zeros
+// (above: n * ncomp * H words of scratch, the column-0 chain of the predictor 1 planes)
+void mjh_launch_ll_undiff(const MjhLlGeom &G, const MjhLlPlane *planes, int16_t *diff, unsigned *above, int n, hipStream_t s);
+void mjh_launch_ll_pixels(const MjhLlGeom &G, const MjhLlPlane *planes, const int16_t *diff, const MjhLlOut &O, uint8_t *pixels, const unsigned *status, int n, hipStream_t s);
 void mjh_launch_dec_scrub(const MjhConst &C, const MjhDecBatch &B, int16_t *coef_q, void *meta, hipStream_t s);
 // after the encode: image i's JFIF version / density bytes (7 bytes at file offset 11) and its status from the encoder's own checks
 void mjh_launch_dec_finish(const uint8_t *jfif7, int patch, uint8_t *out, size_t out_stride, const void *meta, unsigned *status, int n, hipStream_t s);

@@ -92,7 +92,7 @@ __device__ __forceinline__ bool dec_run(const MjhComp *lc, const MjhDecScan &sc,
 }
 
 __global__ void __launch_bounds__(MJH_DEC_WG)
-k_dec_sync(MjhConst C, MjhDecBatch B, int q, int first) { dec_sync_body<false>(C, B, nullptr, q, first); }
+k_dec_sync(MjhConst C, MjhDecBatch B, int q, int first) { dec_sync_body<MJH_DEC_SEQ>(C, B, nullptr, q, first); }
 
 // block index of every subsequence's first unfinished block: exclusive prefix sum of the counts over the segment
 __global__ void __launch_bounds__(64)
@@ -122,13 +122,13 @@ k_dec_prefix(MjhDecBatch B)
 
 // the storing pass and the DC sums, plain and with a transform (C = the SOURCE frame's geometry, *X = where things go)
 __global__ void __launch_bounds__(MJH_DEC_WG)
-k_dec_store(MjhConst C, MjhDecBatch B, int16_t *__restrict__ coef_q) { dec_store_body<false, false>(C, B, nullptr, coef_q, nullptr); }
+k_dec_store(MjhConst C, MjhDecBatch B, int16_t *__restrict__ coef_q) { dec_store_body<MJH_DEC_SEQ, false>(C, B, nullptr, coef_q, nullptr); }
 __global__ void __launch_bounds__(MJH_DEC_WG)
-k_dec_store_x(MjhConst C, MjhDecBatch B, int16_t *__restrict__ coef_q, const MjhXform *__restrict__ X) { dec_store_body<false, true>(C, B, nullptr, coef_q, X); }
+k_dec_store_x(MjhConst C, MjhDecBatch B, int16_t *__restrict__ coef_q, const MjhXform *__restrict__ X) { dec_store_body<MJH_DEC_SEQ, true>(C, B, nullptr, coef_q, X); }
 __global__ void __launch_bounds__(MJH_DEC_WG)
-k_dec_dc(MjhConst C, MjhDecBatch B, int16_t *__restrict__ coef_q) { dec_dc_body<false, false>(C, B, nullptr, coef_q, nullptr); }
+k_dec_dc(MjhConst C, MjhDecBatch B, int16_t *__restrict__ coef_q) { dec_dc_body<MJH_DEC_SEQ, false>(C, B, nullptr, coef_q, nullptr); }
 __global__ void __launch_bounds__(MJH_DEC_WG)
-k_dec_dc_x(MjhConst C, MjhDecBatch B, int16_t *__restrict__ coef_q, const MjhXform *__restrict__ X) { dec_dc_body<false, true>(C, B, nullptr, coef_q, X); }
+k_dec_dc_x(MjhConst C, MjhDecBatch B, int16_t *__restrict__ coef_q, const MjhXform *__restrict__ X) { dec_dc_body<MJH_DEC_SEQ, true>(C, B, nullptr, coef_q, X); }
 
 // a damaged image continues through the schedule as zeroed blocks; its status goes where the coefficient checks report
 __global__ void __launch_bounds__(256)

@@ -1,10 +1,12 @@
 // mjh_decode_dev.h -- device code shared by the Huffman decoder's kernel files (mjh_decode.hip: sequential files, mjh_decode_prog.hip:
-// progressive files): the bit reader, one Huffman symbol, where a block of a scan lies, the workgroup's scan into LDS, and the ONE body
+// progressive files, mjh_decode_lossless.hip: lossless files): the bit reader, one Huffman symbol, where a block of a scan lies, the workgroup's scan into LDS, and the ONE body
 // of each phase of the self-synchronising scheme (first pass and sync rounds, storing pass, DC running sums).  The __global__ kernels
 // of both files are one-line wrappers around these bodies; what differs between the source kinds is a compile-time parameter:
-//   PROG  the run function: pdec_run (first scans of a progressive file, MjhDecProg per scan) instead of dec_run (sequential)
+//   KIND  the run function: MJH_DEC_SEQ dec_run (sequential), MJH_DEC_PROG pdec_run (first scans of a progressive file, MjhDecProg
+//         per scan), MJH_DEC_LL ldec_run (a scan of a lossless file: one difference symbol per sample, no coefficient planes)
 //   XF    an MjhXform maps the stores into the destination frame
-// Only <false, false>, <false, true> and <true, false> are instantiated: a transform of a progressive file is refused on the host.
+// Only <SEQ, false>, <SEQ, true>, <PROG, false> and <LL, false> are instantiated: a transform of anything but a sequential file is
+// refused on the host.
 // The bodies are `static`: their __shared__ variables then have internal linkage like a kernel's own, and the compiler drops the ones
 // an instantiation never reads (the sync kernels' component geometry: 352 bytes of LDS).
 #ifndef MJH_DECODE_DEV_H
@@ -175,9 +177,17 @@ __device__ __forceinline__ bool pdec_run(const MjhComp *lc, const MjhDecScan &sc
                                          unsigned &p, int &k, int &b, unsigned &n, unsigned ord, unsigned total, int mcu,
                                          int16_t *coef_img, int16_t *diff_img, unsigned &flags, int lim);
 
+// ldec_run (mjh_decode_lossless.hip): b = the component inside the MCU (one sample each), mcu = the sample's index in the plane
+template <bool STORE>
+__device__ __forceinline__ bool ldec_run(const MjhDecScan &sc, const MjhDecTable *T, DecReader &R, unsigned end_bits, unsigned &p, int &b, unsigned &n,
+                                         unsigned ord, unsigned total, int mcu, int16_t *diff_img, unsigned &flags);
+#define MJH_DEC_SEQ 0
+#define MJH_DEC_PROG 1
+#define MJH_DEC_LL 2
+
 // First pass (first != 0: every lane decodes its own subsequence from the guessed state) and one synchronisation round (lanes walk on
 // into the next subsequence until the state they arrive with is the one recorded there).  PS: PROG only.
-template <bool PROG>
+template <int KIND>
 static __device__ __forceinline__ void dec_sync_body(const MjhConst &C, const MjhDecBatch &B, const MjhDecProg *__restrict__ PS, int q, int first)
 {
   __shared__ MjhDecScan sc;
@@ -189,7 +199,7 @@ static __device__ __forceinline__ void dec_sync_body(const MjhConst &C, const Mj
   const int scan = B.segs[sg0].scan;
   dec_load_scan(C, B, scan, &sc, T, lc);
   MjhDecProg ps = { 0, 63, 0, 0 };
-  if constexpr (PROG) ps = PS[scan];
+  if constexpr (KIND == MJH_DEC_PROG) ps = PS[scan];
   const unsigned sg = B.sub_seg[g];
   if (sg == 0xFFFFFFFFu) return;
   const MjhDecSeg seg = B.segs[sg];
@@ -211,7 +221,8 @@ static __device__ __forceinline__ void dec_sync_body(const MjhConst &C, const Mj
     j = (unsigned)c.next;
   }
   const unsigned end_bits = dec_sub_end_bits(R.len, j, (unsigned)seg.nsub, S), total = (unsigned)seg.nmcu * (unsigned)sc.bpm;
-  if constexpr (PROG) (void)pdec_run<false>(lc, sc, ps, T, R, end_bits, p, k, b, n, 0u, total, 0, nullptr, nullptr, flags, 0);
+  if constexpr (KIND == MJH_DEC_PROG) (void)pdec_run<false>(lc, sc, ps, T, R, end_bits, p, k, b, n, 0u, total, 0, nullptr, nullptr, flags, 0);
+  else if constexpr (KIND == MJH_DEC_LL) (void)ldec_run<false>(sc, T, R, end_bits, p, b, n, 0u, total, 0, nullptr, flags);
   else (void)dec_run<false, false>(lc, sc, T, R, end_bits, p, k, b, n, 0u, total, 0, nullptr, nullptr, flags, 0, nullptr);
   b = sc.canon[b];
   const unsigned kb = (unsigned)k | ((unsigned)b << 8);
@@ -228,7 +239,7 @@ static __device__ __forceinline__ void dec_sync_body(const MjhConst &C, const Mj
 
 // The storing pass: every subsequence again from its now known entry state and block index (k_dec_prefix).  XF: C = the SOURCE
 // frame's geometry, the stores go where *Xg says (the destination's planes).
-template <bool PROG, bool XF>
+template <int KIND, bool XF>
 static __device__ __forceinline__ void dec_store_body(const MjhConst &C, const MjhDecBatch &B, const MjhDecProg *__restrict__ PS, int16_t *__restrict__ coef_q,
                                                const MjhXform *__restrict__ Xg)
 {
@@ -242,7 +253,7 @@ static __device__ __forceinline__ void dec_store_body(const MjhConst &C, const M
   const int scan = B.segs[sg0].scan;
   dec_load_scan(C, B, scan, &sc, T, lc);
   MjhDecProg ps = { 0, 63, 0, 0 };
-  if constexpr (PROG) ps = PS[scan];
+  if constexpr (KIND == MJH_DEC_PROG) ps = PS[scan];
   const unsigned sg = B.sub_seg[g];
   if (sg == 0xFFFFFFFFu) return;
   const MjhDecSeg seg = B.segs[sg];
@@ -265,7 +276,8 @@ static __device__ __forceinline__ void dec_store_body(const MjhConst &C, const M
     if constexpr (XF) cpi = X->coefs_per_image;
     int16_t *coef_img = coef_q + (size_t)sc.image * cpi, *diff_img = B.diff + (size_t)sc.image * C.total_mcu_blocks;
     bool fin;
-    if constexpr (PROG) fin = pdec_run<true>(lc, sc, ps, T, R, end_bits, p, k, b, n, ord, total, mcu, coef_img, diff_img, flags, B.coef_limit);
+    if constexpr (KIND == MJH_DEC_PROG) fin = pdec_run<true>(lc, sc, ps, T, R, end_bits, p, k, b, n, ord, total, mcu, coef_img, diff_img, flags, B.coef_limit);
+    else if constexpr (KIND == MJH_DEC_LL) fin = ldec_run<true>(sc, T, R, end_bits, p, b, n, ord, total, mcu, diff_img, flags);
     else fin = dec_run<true, XF>(lc, sc, T, R, end_bits, p, k, b, n, ord, total, mcu, coef_img, diff_img, flags, B.coef_limit, X);
     if (fin) { if (dec_end_bad(R.d, R.len, p >> 3, p & 7u)) flags |= MJH_DEC_CORRUPT; }
     else if (last) flags |= MJH_DEC_CORRUPT;                 // the data ends in front of the segment's last block
@@ -276,7 +288,7 @@ static __device__ __forceinline__ void dec_store_body(const MjhConst &C, const M
 // DC values = per component and restart segment the running sum of the stored differences (dummy blocks take part, jdhuff.c:588-592),
 // into plane 0.  PROG: only the DC first scans of the batch, the sums shifted left by the scan's Al.  XF: C = the SOURCE frame's
 // geometry (the prediction chain is the source's, dummy blocks included); only the final store is mapped.
-template <bool PROG, bool XF>
+template <int KIND, bool XF>
 static __device__ __forceinline__ void dec_dc_body(const MjhConst &C, const MjhDecBatch &B, const MjhDecProg *__restrict__ PS, int16_t *__restrict__ coef_q,
                                             const MjhXform *__restrict__ X)
 {
@@ -286,7 +298,7 @@ static __device__ __forceinline__ void dec_dc_body(const MjhConst &C, const MjhD
   const int j = blockIdx.x, ncomp = scp->ncomp;
   if (j >= ncomp) return;
   int Al = 0;
-  if constexpr (PROG) {
+  if constexpr (KIND == MJH_DEC_PROG) {
     if (PS[blockIdx.y].Ss != 0) return;                // (uniform: an AC scan has no DC)
     Al = PS[blockIdx.y].Al;
   }
@@ -347,4 +359,7 @@ static __device__ __forceinline__ void dec_dc_body(const MjhConst &C, const MjhD
 __global__ void k_pdec_sync(MjhConst C, MjhDecBatch B, const MjhDecProg *__restrict__ PS, int q, int first);
 __global__ void k_pdec_store(MjhConst C, MjhDecBatch B, const MjhDecProg *__restrict__ PS, int16_t *__restrict__ coef_q);
 __global__ void k_pdec_dc(MjhConst C, MjhDecBatch B, const MjhDecProg *__restrict__ PS, int16_t *__restrict__ coef_q);
+// ... and those of mjh_decode_lossless.hip (a batch of lossless scans has no DC sums: the differences are the output)
+__global__ void k_ldec_sync(MjhConst C, MjhDecBatch B, int q, int first);
+__global__ void k_ldec_store(MjhConst C, MjhDecBatch B);
 #endif

@@ -103,11 +103,11 @@ __device__ __forceinline__ bool pdec_run(const MjhComp *lc, const MjhDecScan &sc
 
 // the phases of mjh_decode.hip for first scans: the shared bodies with pdec_run (launched by mjh_launch_dec_sync / _store / _dc)
 __global__ void __launch_bounds__(MJH_DEC_WG)
-k_pdec_sync(MjhConst C, MjhDecBatch B, const MjhDecProg *__restrict__ PS, int q, int first) { dec_sync_body<true>(C, B, PS, q, first); }
+k_pdec_sync(MjhConst C, MjhDecBatch B, const MjhDecProg *__restrict__ PS, int q, int first) { dec_sync_body<MJH_DEC_PROG>(C, B, PS, q, first); }
 __global__ void __launch_bounds__(MJH_DEC_WG)
-k_pdec_store(MjhConst C, MjhDecBatch B, const MjhDecProg *__restrict__ PS, int16_t *__restrict__ coef_q) { dec_store_body<true, false>(C, B, PS, coef_q, nullptr); }
+k_pdec_store(MjhConst C, MjhDecBatch B, const MjhDecProg *__restrict__ PS, int16_t *__restrict__ coef_q) { dec_store_body<MJH_DEC_PROG, false>(C, B, PS, coef_q, nullptr); }
 __global__ void __launch_bounds__(MJH_DEC_WG)
-k_pdec_dc(MjhConst C, MjhDecBatch B, const MjhDecProg *__restrict__ PS, int16_t *__restrict__ coef_q) { dec_dc_body<true, false>(C, B, PS, coef_q, nullptr); }
+k_pdec_dc(MjhConst C, MjhDecBatch B, const MjhDecProg *__restrict__ PS, int16_t *__restrict__ coef_q) { dec_dc_body<MJH_DEC_PROG, false>(C, B, PS, coef_q, nullptr); }
 
 // DC refinement: one workgroup per restart segment.  Bit i of the segment's data (stuffed zeros skipped) belongs to block i of the
 // segment in MCU order, dummy blocks included; a set bit ORs 1 << Al into the block's DC value.

@@ -435,6 +435,9 @@ struct mjh_encoder {
   unsigned src_accept = 0;
   int pg_levels = 0;                    // levels of scans in the last call's progressive files (0: none in the call)
   hipEvent_t pg_ev[2] = { nullptr, nullptr }; bool pg_timed = false;
+  // lossless files (mjh_decode_lossless.hip), decoded by a lossless encoder: one plane of differences per component and image, which
+  // the undifferencing kernels turn into samples in place, and the column-0 chains of the predictor 1 planes (made by the first call)
+  int16_t *d_lldiff = nullptr; unsigned *d_llabove = nullptr;
   // mjh_decode_host (mjh_idct.hip): the interleaved pixels of the last decoded batch (made at the first call, grown when a later
   // call asks for larger pixels), its layout, its status words on the host and the event behind everything it queued
   uint8_t *d_pixout = nullptr; size_t pixout_cap = 0;
@@ -905,7 +908,7 @@ static void free_all(mjh_encoder *e)
   if (e->d2h_stream) (void)hipStreamDestroy(e->d2h_stream);
   if (e->h_plin) (void)hipHostFree(e->h_plin);
   if (e->h_cfin) (void)hipHostFree(e->h_cfin);
-  for (void *q : { (void *)e->d_tc, (void *)e->d_tdesc, e->d_tsub, (void *)e->d_tdiff, (void *)e->d_tdiff_x, (void *)e->d_tstat, (void *)e->d_tchanged }) if (q) (void)mjh_guard_free(q);
+  for (void *q : { (void *)e->d_tc, (void *)e->d_tdesc, e->d_tsub, (void *)e->d_tdiff, (void *)e->d_tdiff_x, (void *)e->d_tstat, (void *)e->d_tchanged, (void *)e->d_lldiff, (void *)e->d_llabove }) if (q) (void)mjh_guard_free(q);
   for (void *q : { (void *)e->h_tc, (void *)e->h_tdesc, (void *)e->h_tstat[0], (void *)e->h_tstat[1], (void *)e->h_tflag }) if (q) (void)hipHostFree(q);
   for (hipEvent_t ev : e->tc_ev) if (ev) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : e->pg_ev) if (ev) (void)hipEventDestroy(ev);
@@ -2721,7 +2724,7 @@ extern "C" int mjh_encode_planes_host(mjh_encoder *e, const void *const planes[M
 // ---- re-compressing files: JPEG bytes -> device Huffman decoder (mjh_decode.hip) -> the entropy-coding passes ----------------------
 // The decoder's view of one Huffman table (ITU-T T.81 C.2 code assignment, F.2.2.3 decoding tables; what jpeg_make_d_derived_tbl
 // jdhuff.c:143-261 derives, with its checks): canonical codes length by length, the first 8 bits of every short code as a direct look-up
-static bool make_dec_table(const uint8_t bits[17], const uint8_t vals[256], bool is_dc, MjhDecTable *T)
+static bool make_dec_table(const uint8_t bits[17], const uint8_t vals[256], bool is_dc, MjhDecTable *T, int max_dc = 15)
 {
   memset(T, 0, sizeof(*T));
   unsigned code = 0;
@@ -2737,7 +2740,7 @@ static bool make_dec_table(const uint8_t bits[17], const uint8_t vals[256], bool
         const unsigned first = (code + (unsigned)c) << (8 - len);
         for (unsigned f = 0; f < (1u << (8 - len)); f++) T->look[first + f] = (uint16_t)((len << 8) | vals[idx + c]);
       }
-    if (is_dc) for (int c = 0; c < cnt; c++) if (vals[idx + c] > 15) return false;   // a DC symbol is a bit count 0..15
+    if (is_dc) for (int c = 0; c < cnt; c++) if (vals[idx + c] > max_dc) return false;   // a DC symbol is a bit count 0..15 (a lossless file's: 0..16)
     code += (unsigned)cnt;
     idx += cnt;
     T->maxcode[len] = (int)code - 1;
@@ -2787,6 +2790,144 @@ static void build_xform(const MjhXformPlan &g, const MjhConst &Cd, MjhXform *X)
   }
 }
 
+// One set of descriptor arrays of a decode call: scans that are launched together, their restart segments and subsequences
+struct DecDescSet {
+  std::vector<MjhDecScan> scans;
+  std::vector<MjhDecProg> ps;
+  std::vector<MjhDecSeg> segs;
+  std::vector<unsigned> sub_seg;
+  int max_nsub = 1;
+  size_t o_scans = 0, o_ps = 0, o_segs = 0, o_subs = 0, sub_base = 0;      // where the arrays lie in d_tdesc / d_tsub
+};
+
+// The restart segments of the scan that is about to become D.scans[D.scans.size()]: bytes [a, b) of file d, which lies at file_off
+// in the batch buffer.  RSTn markers are the only 0xFF not followed by 0x00 inside the range (mjh_jpeg_probe counted nrst of them).
+// subs: the segments get subsequences of S bytes, padded to whole workgroups behind the scan's last.  nullptr, or why the file is refused.
+static const char *dec_split_segments(const uint8_t *d, size_t a, size_t b, unsigned nrst, const MjhDecScan &sc, size_t file_off, int S, bool subs, DecDescSet &D)
+{
+  const int nseg_expected = (sc.mcus + sc.ri - 1) / sc.ri;
+  size_t seg_start = a, q = a;
+  int k_seg = 0;
+  const size_t sub_first = D.sub_seg.size();
+  auto close_seg = [&](size_t end) {
+    MjhDecSeg sg;
+    memset(&sg, 0, sizeof(sg));
+    sg.off = file_off + seg_start;
+    sg.len = (unsigned)(end - seg_start);
+    sg.scan = (int)D.scans.size();
+    sg.mcu0 = k_seg * sc.ri;
+    sg.nmcu = sc.mcus - sg.mcu0 < sc.ri ? sc.mcus - sg.mcu0 : sc.ri;
+    if (subs) {
+      sg.sub0 = (int)D.sub_seg.size();
+      sg.nsub = S > 0 ? (int)((sg.len + (unsigned)S - 1) / (unsigned)S) : 1;
+      if (sg.nsub < 1) sg.nsub = 1;
+      if (sg.nsub > D.max_nsub) D.max_nsub = sg.nsub;
+      for (int t = 0; t < sg.nsub; t++) D.sub_seg.push_back((unsigned)D.segs.size());
+    }
+    D.segs.push_back(sg);
+    k_seg++;
+  };
+  while (nrst && q < b) {      // (a scan without RSTn markers -- the probe counted them -- is one segment: no second search)
+    const uint8_t *ff = (const uint8_t *)memchr(d + q, 0xFF, b - q);
+    if (!ff) break;
+    q = (size_t)(ff - d);
+    if (q + 1 >= b) break;
+    if (d[q + 1] == 0) { q += 2; continue; }
+    size_t r = q + 1;
+    while (r < b && d[r] == 0xFF) r++;
+    if (r >= b) break;
+    // RSTn: its number is checked modulo 8 (read_restart_marker jdmarker.c:1010-1035), one marker per interval
+    if (k_seg + 1 >= nseg_expected || d[r] != 0xD0 + (k_seg & 7)) return "Corrupt JPEG data: unexpected restart marker in the entropy-coded data (JWRN_MUST_RESYNC)";
+    close_seg(q);
+    seg_start = q = r + 1;
+  }
+  close_seg(b);
+  if (k_seg != nseg_expected) return "Corrupt JPEG data: restart markers missing in the entropy-coded data (JWRN_HIT_MARKER)";
+  if (subs) while ((D.sub_seg.size() - sub_first) % MJH_DEC_WG) D.sub_seg.push_back(0xFFFFFFFFu);   // a workgroup serves one (image, scan)
+  return nullptr;
+}
+
+// b -> the smallest b' from which the same sequence of tables follows (MjhDecScan::canon); pair[b]: the tables block b decodes with
+static void dec_canon(MjhDecScan &sc, const int pair[10])
+{
+  for (int b = 0; b < sc.bpm; b++) {
+    sc.canon[b] = b;
+    for (int c = 0; c < b; c++) {
+      bool same = true;
+      for (int t = 0; t < sc.bpm && same; t++) same = pair[(c + t) % sc.bpm] == pair[(b + t) % sc.bpm];
+      if (same) { sc.canon[b] = c; break; }
+    }
+  }
+}
+
+// the staging of a decode call, grown on demand: the files (pinned + device), the descriptor block (pinned + device), the
+// per-subsequence arrays
+static int dec_grow_staging(mjh_encoder *e, size_t total_bytes, size_t desc_bytes, size_t sub_bytes)
+{
+  if (total_bytes > e->tc_cap) {
+    if (e->d_tc) { (void)mjh_guard_free(e->d_tc); e->d_tc = nullptr; }
+    if (e->h_tc) { (void)hipHostFree(e->h_tc); e->h_tc = nullptr; }
+    e->tc_cap = 0;
+    const size_t cap = total_bytes + total_bytes / 4;
+    HIPCHK(mjh_dmalloc((void **)&e->d_tc, cap));
+    HIPCHK(mjh_numa_host_alloc((void **)&e->h_tc, cap, hipHostMallocDefault, e->device));
+    e->tc_cap = cap;
+  }
+  if (desc_bytes > e->tdesc_cap) {
+    if (e->d_tdesc) { (void)mjh_guard_free(e->d_tdesc); e->d_tdesc = nullptr; }
+    if (e->h_tdesc) { (void)hipHostFree(e->h_tdesc); e->h_tdesc = nullptr; }
+    e->tdesc_cap = 0;
+    const size_t cap = desc_bytes + desc_bytes / 4;
+    HIPCHK(mjh_dmalloc((void **)&e->d_tdesc, cap));
+    HIPCHK(mjh_numa_host_alloc((void **)&e->h_tdesc, cap, hipHostMallocDefault, e->device));
+    e->tdesc_cap = cap;
+  }
+  if (sub_bytes > e->tsub_cap) {
+    if (e->d_tsub) { (void)mjh_guard_free(e->d_tsub); e->d_tsub = nullptr; }
+    e->tsub_cap = 0;
+    const size_t cap = sub_bytes + sub_bytes / 4;
+    HIPCHK(mjh_dmalloc(&e->d_tsub, cap));
+    e->tsub_cap = cap;
+  }
+  return MJH_OK;
+}
+
+// the status words, round flags and phase events of the decoder (made by the first decode call)
+static int dec_status_buffers(mjh_encoder *e)
+{
+  if (e->d_tstat) return MJH_OK;
+  HIPCHK(mjh_dmalloc((void **)&e->d_tstat, (size_t)e->max_batch * 4));
+  HIPCHK(mjh_dmalloc((void **)&e->d_tchanged, 64 * 4));
+  for (int b = 0; b < 2; b++) HIPCHK(mjh_numa_host_alloc((void **)&e->h_tstat[b], (size_t)e->max_batch * 4, hipHostMallocDefault, e->device));
+  HIPCHK(mjh_numa_host_alloc((void **)&e->h_tflag, 64, hipHostMallocDefault, e->device));
+  for (hipEvent_t &ev : e->tc_ev) HIPCHK(hipEventCreate(&ev));
+  return MJH_OK;
+}
+
+// First pass, then synchronisation rounds in groups of launches: the rounds of a group run back to back (a round that finds the
+// one before it unchanged returns at once), the host reads the group's last flag and launches the next group only when it was
+// set.  A round extends the true prefix of every segment by one subsequence at least: max_nsub - 1 rounds always suffice.
+// launch(q, first): the batch's sync kernel.
+template <class Launch>
+static int dec_sync_rounds(mjh_encoder *e, hipStream_t s, int max_nsub, Launch launch)
+{
+  launch(0, 1);
+  for (int done = 0, group = 3; done < max_nsub - 1;) {
+    const int g = group < max_nsub - 1 - done ? group : max_nsub - 1 - done;
+    HIPCHK(hipMemsetAsync(e->d_tchanged, 0, 64 * 4, s));
+    for (int q = 0; q < g; q++) launch(q, 0);
+    done += g;
+    e->tc_rounds += g;
+    if (done >= max_nsub - 1) break;
+    HIPCHK(hipMemcpyAsync(e->h_tflag, e->d_tchanged + (g - 1), 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    e->tc_syncs++;
+    if (!*(volatile unsigned *)e->h_tflag) break;
+    group = group * 2 < 64 ? group * 2 : 64;
+  }
+  return MJH_OK;
+}
+
 // The front half both mjh_transcode_host and mjh_decode_host run: marker walk, agreement with the encoder, descriptors, staging and
 // the K-D kernels.  It leaves the batch's coefficient planes in d_q and its per-image status in d_tstat, both queued on e->stream.
 // pixels: the caller is mjh_decode_host (no result arenas are made); *o_jfif_out: where the files' APP0 fields lie in d_tdesc
@@ -2818,6 +2959,9 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
       room.resize(MJH_MAX_SRC_SCANS);
       int ns = 0;
       rc = mjh_jpeg_probe_ex(jpegs[i], sizes[i], e->src_accept, &infos[i], room.data(), MJH_MAX_SRC_SCANS, &ns);
+      if (rc == MJH_OK && infos[i].sof_type == 3)
+        rc = fail(MJH_EUNSUPPORTED, "lossless source file (SOF3): it has no DCT coefficients (jpeg_copy_critical_parameters refuses it as well: JERR_NOTIMPL, jctrans.c:83); "
+                                    "mjh_decode_host decodes it on an encoder made from its own parameters (mjh_params_from_jpeg)");
       if (rc == MJH_OK && infos[i].sof_type == 2) {
         pscans[(size_t)i].assign(room.begin(), room.begin() + ns);
         if (e->xf_on) rc = fail(MJH_EUNSUPPORTED, "a lossless transform (mjh_encoder_set_transform) together with a progressive source file");
@@ -2904,15 +3048,7 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
   // its coefficient range; first scans are level 0.  Only sets 0 and 1 have subsequences.
   const int S = e->dec_subseq;
   const int frame_mcus = G.mcus_per_row * G.mcu_rows;
-  struct DescSet {
-    std::vector<MjhDecScan> scans;
-    std::vector<MjhDecProg> ps;
-    std::vector<MjhDecSeg> segs;
-    std::vector<unsigned> sub_seg;
-    int max_nsub = 1;
-    size_t o_scans = 0, o_ps = 0, o_segs = 0, o_subs = 0, sub_base = 0;      // where the arrays lie in d_tdesc / d_tsub
-  };
-  std::vector<DescSet> sets(2);
+  std::vector<DecDescSet> sets(2);
   std::vector<MjhDecTable> tables;
   std::vector<size_t> file_off((size_t)n);
   size_t total_bytes = 0;
@@ -2925,7 +3061,7 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
     const bool prog = f.sof_type == 2;
     const uint8_t *d = (const uint8_t *)jpegs[i];
     std::vector<std::array<size_t, 4>> saved;
-    for (const DescSet &t : sets) saved.push_back(std::array<size_t, 4>{ { t.scans.size(), t.segs.size(), t.sub_seg.size(), (size_t)t.max_nsub } });
+    for (const DecDescSet &t : sets) saved.push_back(std::array<size_t, 4>{ { t.scans.size(), t.segs.size(), t.sub_seg.size(), (size_t)t.max_nsub } });
     const size_t tabs0 = tables.size();
     const char *why = nullptr;
     long long diff_off = 0;
@@ -2964,7 +3100,7 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
         set_idx = lv == 0 ? 1 : 2 * lv + (x.Ss == 0 ? 0 : 1);
         if ((size_t)set_idx >= sets.size()) sets.resize((size_t)set_idx + 1);
       } else take(f.scans[k]);
-      DescSet &D = sets[(size_t)set_idx];
+      DecDescSet &D = sets[(size_t)set_idx];
       const bool need_dc = pp.Ss == 0 && pp.Ah == 0, need_ac = pp.Se != 0;      // the tables the scan decodes with (DC refinement: none)
       if (xf) {      // a scan that holds only dropped components (grayscale on a non-interleaved file) is not decoded
         bool kept = false;
@@ -3000,14 +3136,7 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
       {
         int pair[10], nbk = 0;
         for (int j = 0; j < sc.ncomp; j++) for (int t = 0; t < sc.nb[j]; t++) pair[nbk++] = (need_dc ? tbl_dc[j] : 0) * 4 + (need_ac ? tbl_ac[j] : 0);
-        for (int b = 0; b < sc.bpm; b++) {
-          sc.canon[b] = b;
-          for (int c = 0; c < b; c++) {
-            bool same = true;
-            for (int t = 0; t < sc.bpm && same; t++) same = pair[(c + t) % sc.bpm] == pair[(b + t) % sc.bpm];
-            if (same) { sc.canon[b] = c; break; }
-          }
-        }
+        dec_canon(sc, pair);
       }
       sc.mcus = sc.ncomp == 1 ? G.c[sc.comp[0]].nblk : frame_mcus;
       sc.mcus_per_row = sc.ncomp == 1 ? G.c[sc.comp[0]].wib : G.mcus_per_row;
@@ -3018,49 +3147,8 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
         if (diff_off > G.total_mcu_blocks) { why = "internal: DC difference array too small"; break; }
       }
       if (data_size >= ((size_t)1 << 28)) { why = "a scan of 256 MB or more (bit positions inside a restart segment are 32-bit)"; break; }
-      // restart segments: RSTn markers are the only 0xFF not followed by 0x00 inside the range (mjh_jpeg_probe)
-      const bool subs = set_idx < 2;
-      const int nseg_expected = (sc.mcus + sc.ri - 1) / sc.ri;
-      const size_t a = data_offset, b = a + data_size;
-      size_t seg_start = a, q = a;
-      int k_seg = 0;
-      const size_t sub_first = D.sub_seg.size();
-      auto close_seg = [&](size_t end) {
-        MjhDecSeg sg;
-        memset(&sg, 0, sizeof(sg));
-        sg.off = file_off[(size_t)i] + seg_start;
-        sg.len = (unsigned)(end - seg_start);
-        sg.scan = (int)D.scans.size();
-        sg.mcu0 = k_seg * sc.ri;
-        sg.nmcu = sc.mcus - sg.mcu0 < sc.ri ? sc.mcus - sg.mcu0 : sc.ri;
-        if (subs) {
-          sg.sub0 = (int)D.sub_seg.size();
-          sg.nsub = S > 0 ? (int)((sg.len + (unsigned)S - 1) / (unsigned)S) : 1;
-          if (sg.nsub < 1) sg.nsub = 1;
-          if (sg.nsub > D.max_nsub) D.max_nsub = sg.nsub;
-          for (int t = 0; t < sg.nsub; t++) D.sub_seg.push_back((unsigned)D.segs.size());
-        }
-        D.segs.push_back(sg);
-        k_seg++;
-      };
-      while (nrst && q < b && !why) {      // (a scan without RSTn markers -- the probe counted them -- is one segment: no second search)
-        const uint8_t *ff = (const uint8_t *)memchr(d + q, 0xFF, b - q);
-        if (!ff) break;
-        q = (size_t)(ff - d);
-        if (q + 1 >= b) break;
-        if (d[q + 1] == 0) { q += 2; continue; }
-        size_t r = q + 1;
-        while (r < b && d[r] == 0xFF) r++;
-        if (r >= b) break;
-        // RSTn: its number is checked modulo 8 (read_restart_marker jdmarker.c:1010-1035), one marker per interval
-        if (k_seg + 1 >= nseg_expected || d[r] != 0xD0 + (k_seg & 7)) { why = "Corrupt JPEG data: unexpected restart marker in the entropy-coded data (JWRN_MUST_RESYNC)"; break; }
-        close_seg(q);
-        seg_start = q = r + 1;
-      }
+      why = dec_split_segments(d, data_offset, data_offset + data_size, nrst, sc, file_off[(size_t)i], S, set_idx < 2, D);
       if (why) break;
-      close_seg(b);
-      if (k_seg != nseg_expected) { why = "Corrupt JPEG data: restart markers missing in the entropy-coded data (JWRN_HIT_MARKER)"; break; }
-      if (subs) while ((D.sub_seg.size() - sub_first) % MJH_DEC_WG) D.sub_seg.push_back(0xFFFFFFFFu);   // a workgroup serves one (image, scan)
       D.scans.push_back(sc);
       D.ps.push_back(pp);
     }
@@ -3084,7 +3172,7 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
   e->tc_syncs++;
   size_t o_end = 0, nsubp = 0;
   const size_t per_sub = sizeof(MjhDecState) + sizeof(MjhDecCarry) + sizeof(unsigned);
-  for (DescSet &D : sets) {
+  for (DecDescSet &D : sets) {
     D.o_scans = o_end;
     D.o_ps = up16(D.o_scans + D.scans.size() * sizeof(MjhDecScan));
     D.o_segs = up16(D.o_ps + D.ps.size() * sizeof(MjhDecProg));
@@ -3095,39 +3183,11 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
   }
   const size_t o_tabs = o_end, o_jfif = up16(o_tabs + tables.size() * sizeof(MjhDecTable)), o_xf = up16(o_jfif + (size_t)n * 8),
                desc_bytes = xf ? up16(o_xf + sizeof(MjhXform)) : o_xf;
-  if (total_bytes > e->tc_cap) {
-    if (e->d_tc) { (void)mjh_guard_free(e->d_tc); e->d_tc = nullptr; }
-    if (e->h_tc) { (void)hipHostFree(e->h_tc); e->h_tc = nullptr; }
-    e->tc_cap = 0;
-    const size_t cap = total_bytes + total_bytes / 4;
-    HIPCHK(mjh_dmalloc((void **)&e->d_tc, cap));
-    HIPCHK(mjh_numa_host_alloc((void **)&e->h_tc, cap, hipHostMallocDefault, e->device));
-    e->tc_cap = cap;
-  }
-  if (desc_bytes > e->tdesc_cap) {
-    if (e->d_tdesc) { (void)mjh_guard_free(e->d_tdesc); e->d_tdesc = nullptr; }
-    if (e->h_tdesc) { (void)hipHostFree(e->h_tdesc); e->h_tdesc = nullptr; }
-    e->tdesc_cap = 0;
-    const size_t cap = desc_bytes + desc_bytes / 4;
-    HIPCHK(mjh_dmalloc((void **)&e->d_tdesc, cap));
-    HIPCHK(mjh_numa_host_alloc((void **)&e->h_tdesc, cap, hipHostMallocDefault, e->device));
-    e->tdesc_cap = cap;
-  }
-  if (nsubp * per_sub > e->tsub_cap) {
-    if (e->d_tsub) { (void)mjh_guard_free(e->d_tsub); e->d_tsub = nullptr; }
-    e->tsub_cap = 0;
-    const size_t cap = nsubp * per_sub + nsubp * per_sub / 4;
-    HIPCHK(mjh_dmalloc(&e->d_tsub, cap));
-    e->tsub_cap = cap;
-  }
-  if (!e->d_tdiff) {
-    HIPCHK(mjh_dmalloc((void **)&e->d_tdiff, (size_t)e->max_batch * (size_t)C.total_mcu_blocks * 2));
-    HIPCHK(mjh_dmalloc((void **)&e->d_tstat, (size_t)e->max_batch * 4));
-    HIPCHK(mjh_dmalloc((void **)&e->d_tchanged, 64 * 4));
-    for (int b = 0; b < 2; b++) HIPCHK(mjh_numa_host_alloc((void **)&e->h_tstat[b], (size_t)e->max_batch * 4, hipHostMallocDefault, e->device));
-    HIPCHK(mjh_numa_host_alloc((void **)&e->h_tflag, 64, hipHostMallocDefault, e->device));
-    for (hipEvent_t &ev : e->tc_ev) HIPCHK(hipEventCreate(&ev));
-  }
+  rc = dec_grow_staging(e, total_bytes, desc_bytes, nsubp * per_sub);
+  if (rc) return rc;
+  if (!e->d_tdiff) HIPCHK(mjh_dmalloc((void **)&e->d_tdiff, (size_t)e->max_batch * (size_t)C.total_mcu_blocks * 2));
+  rc = dec_status_buffers(e);
+  if (rc) return rc;
   if (has_prog && !e->pg_ev[0])
     for (hipEvent_t &ev : e->pg_ev) HIPCHK(hipEventCreate(&ev));
   if (xf) {
@@ -3141,7 +3201,7 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
     memcpy(e->h_tdesc + o_xf, &X, sizeof(X));
   }
   CopyPool::get().run(n, [&](int i) { memcpy(e->h_tc + file_off[(size_t)i], jpegs[i], sizes[i]); });
-  for (const DescSet &D : sets) {
+  for (const DecDescSet &D : sets) {
     memcpy(e->h_tdesc + D.o_scans, D.scans.data(), D.scans.size() * sizeof(MjhDecScan));
     memcpy(e->h_tdesc + D.o_ps, D.ps.data(), D.ps.size() * sizeof(MjhDecProg));
     memcpy(e->h_tdesc + D.o_segs, D.segs.data(), D.segs.size() * sizeof(MjhDecSeg));
@@ -3162,7 +3222,7 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
   HIPCHK(hipMemcpyAsync(e->d_tdesc, e->h_tdesc, desc_bytes, hipMemcpyHostToDevice, s));
   // ---- 4. the decoder
   int16_t *const d_diff = xf ? e->d_tdiff_x : e->d_tdiff;
-  auto batch_of = [&](const DescSet &D) {
+  auto batch_of = [&](const DecDescSet &D) {
     MjhDecBatch B;
     memset(&B, 0, sizeof(B));
     const size_t ns = D.sub_seg.size();
@@ -3183,7 +3243,7 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
     B.coef_limit = pixels ? 32767 : 1023;     // jchuff.c:596,624 refuses what it cannot code (JERR_BAD_DCT_COEF); jdhuff.c / jidctint.c take every amplitude
     return B;
   };
-  auto ps_of = [&](const DescSet &D) { return (const MjhDecProg *)(e->d_tdesc + D.o_ps); };
+  auto ps_of = [&](const DecDescSet &D) { return (const MjhDecProg *)(e->d_tdesc + D.o_ps); };
   const MjhDecBatch B = batch_of(sets[0]), BP = batch_of(sets[1]);      // sequential scans / first scans of progressive files
   const MjhDecProg *const PS = ps_of(sets[1]);
   const bool timed = e->profiling != 0;
@@ -3192,25 +3252,8 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
   HIPCHK(hipMemsetAsync(e->d_tstat, 0, (size_t)n * 4, s));
   HIPCHK(hipMemsetAsync(e->d_meta, 0, (size_t)n * sizeof(MjhImageMeta), s));
   if (timed) HIPCHK(hipEventRecord(e->tc_ev[0], s));
-  // First pass, then synchronisation rounds in groups of launches: the rounds of a group run back to back (a round that finds the
-  // one before it unchanged returns at once), the host reads the group's last flag and launches the next group only when it was
-  // set.  A round extends the true prefix of every segment by one subsequence at least: max_nsub - 1 rounds always suffice.
   auto sync_rounds = [&](const MjhDecBatch &Bx, const MjhDecProg *ps, int max_nsub) -> int {
-    mjh_launch_dec_sync(G, Bx, ps, 0, 1, s);
-    for (int done = 0, group = 3; done < max_nsub - 1;) {
-      const int g = group < max_nsub - 1 - done ? group : max_nsub - 1 - done;
-      HIPCHK(hipMemsetAsync(e->d_tchanged, 0, 64 * 4, s));
-      for (int q = 0; q < g; q++) mjh_launch_dec_sync(G, Bx, ps, q, 0, s);
-      done += g;
-      e->tc_rounds += g;
-      if (done >= max_nsub - 1) break;
-      HIPCHK(hipMemcpyAsync(e->h_tflag, e->d_tchanged + (g - 1), 4, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipStreamSynchronize(s));
-      e->tc_syncs++;
-      if (!*(volatile unsigned *)e->h_tflag) break;
-      group = group * 2 < 64 ? group * 2 : 64;
-    }
-    return MJH_OK;
+    return dec_sync_rounds(e, s, max_nsub, [&](int q, int first) { mjh_launch_dec_sync(G, Bx, ps, q, first, s); });
   };
   if (B.nscan) { rc = sync_rounds(B, nullptr, sets[0].max_nsub); if (rc) return rc; }
   if (BP.nscan) { rc = sync_rounds(BP, PS, sets[1].max_nsub); if (rc) return rc; }
@@ -3270,7 +3313,7 @@ extern "C" int mjh_transcode_host(mjh_encoder *e, const void *const jpegs[], con
 extern "C" int mjh_encoder_set_sources(mjh_encoder *e, unsigned accept)
 {
   if (!e) return fail(MJH_EINVAL, "null encoder");
-  if (accept & ~MJH_SRC_PROGRESSIVE) return fail(MJH_EINVAL, "unknown source kinds 0x%x (MJH_SRC_PROGRESSIVE)", accept);
+  if (accept & ~(MJH_SRC_PROGRESSIVE | MJH_SRC_LOSSLESS)) return fail(MJH_EINVAL, "unknown source kinds 0x%x (MJH_SRC_PROGRESSIVE | MJH_SRC_LOSSLESS)", accept);
   e->src_accept = accept;
   return MJH_OK;
 }
@@ -3485,6 +3528,226 @@ static int decode_coefs(mjh_encoder *e, const void *const jpegs[], const size_t 
   return MJH_OK;
 }
 
+// mjh_decode_host on a lossless encoder (one made from mjh_params_from_jpeg of a lossless file): marker walk, agreement with the
+// encoder (size, components, precision), descriptors and staging as decode_front makes them, then K-DL (mjh_decode_lossless.hip):
+// the Huffman phases into planes of differences, undifferencing in place, the samples into the pixel layout.
+static int decode_lossless(mjh_encoder *e, const void *const jpegs[], const size_t sizes[], int n, const mjh_decode_opts &o)
+{
+  if (!jpegs || !sizes || n < 1 || n > e->max_batch) return fail(MJH_EINVAL, "bad arguments (n=%d, max_batch=%d)", n, e->max_batch);
+  const int W = e->L.W, H = e->L.H, NC = e->L.ncomp, P = e->L.precision;
+  // ---- 0. the options: djpeg leaves a lossless file at full size and converts nothing (jdmaster.c, jdcolor.c)
+  if (o.raw_coefs) return fail(MJH_EUNSUPPORTED, "raw_coefs on a lossless file: it has no DCT coefficients");
+  if (o.raw_planes) return fail(MJH_EUNSUPPORTED, "raw_planes on a lossless file: raw data output is not implemented in lossless mode");
+  if (o.out_color_space == MJH_CS_RGB565) return fail(MJH_EUNSUPPORTED, "Unsupported color conversion request (JERR_CONVERSION_NOTIMPL): MJH_CS_RGB565 output of a lossless file");
+  if (o.out_color_space != 0 && o.out_color_space != MJH_CS_GRAYSCALE && o.out_color_space != MJH_CS_RGB)
+    return fail(MJH_EINVAL, "out_color_space %d (0, MJH_CS_GRAYSCALE, MJH_CS_RGB or MJH_CS_RGB565)", o.out_color_space);
+  if (o.out_color_space == MJH_CS_GRAYSCALE && NC != 1) return fail(MJH_EUNSUPPORTED, "Unsupported color conversion request (JERR_CONVERSION_NOTIMPL): MJH_CS_GRAYSCALE output of an RGB lossless file");
+  if (o.out_color_space == MJH_CS_RGB && NC != 3) return fail(MJH_EUNSUPPORTED, "Unsupported color conversion request (JERR_CONVERSION_NOTIMPL): MJH_CS_RGB output of a grayscale lossless file");
+  if (NC != 1 && NC != 3) return fail(MJH_EUNSUPPORTED, "decoding lossless files of %d components", NC);
+  if ((long long)W * H * NC >= (1ll << 30)) return fail(MJH_EUNSUPPORTED, "decoding a lossless image of %d x %d x %d samples (sample indices are 32-bit)", W, H, NC);
+  MjhLlOut O;
+  memset(&O, 0, sizeof(O));
+  O.px = o.pixel_size;
+  if (NC == 1) {
+    if (O.px != 0 && O.px != 1) return fail(MJH_EINVAL, "pixel_size %d of grayscale output (0 or 1)", O.px);
+    O.px = 1;
+  } else {
+    if (O.px != 0 && O.px != 3 && O.px != 4) return fail(MJH_EINVAL, "pixel_size %d of RGB output (0, 3 or 4)", O.px);
+    if (O.px == 0) O.px = 3;
+    for (int k = 0; k < 3; k++) O.off[k] = o.rgb_offset[k];
+    if (O.off[0] == 0 && O.off[1] == 0 && O.off[2] == 0) { O.off[1] = 1; O.off[2] = 2; }
+    for (int k = 0; k < 3; k++)
+      if (O.off[k] < 0 || O.off[k] >= O.px || O.off[k] == O.off[(k + 1) % 3]) return fail(MJH_EINVAL, "rgb_offset %d,%d,%d of %d-sample pixels", O.off[0], O.off[1], O.off[2], O.px);
+  }
+  O.fill = (1 << P) - 1;
+  O.bottom_up = o.bottom_up != 0;
+  const int sample_bytes = P > 8 ? 2 : 1;
+  O.row_pitch = (long long)up16((size_t)O.px * sample_bytes * (((size_t)W + 3) & ~(size_t)3));
+  O.image_stride = O.row_pitch * H;
+  HIPCHK(hipSetDevice(e->device));
+  e->tc_code.assign((size_t)n, MJH_OK);
+  e->tc_text.assign((size_t)n, std::string());
+  e->tc_n = n; e->tc_rounds = 0; e->tc_syncs = 0; e->tc_timed = false; e->tc_queued = false;
+  e->tc_S = e->dec_subseq;
+  e->pg_levels = 0; e->pg_timed = false;
+  // ---- 1. marker segments of every file and the comparison with the encoder
+  std::vector<mjh_jpeg_info> infos((size_t)n);
+  std::vector<std::vector<mjh_jpeg_scan_ex>> xscans((size_t)n);
+  CopyPool::get().run(n, [&](int i) {
+    int rc;
+    if (!jpegs[i] || !sizes[i]) rc = fail(MJH_EINVAL, "empty file");
+    else if (!e->src_accept) rc = mjh_jpeg_probe(jpegs[i], sizes[i], &infos[i]);
+    else {
+      static thread_local std::vector<mjh_jpeg_scan_ex> room;
+      room.resize(MJH_MAX_SRC_SCANS);
+      int ns = 0;
+      rc = mjh_jpeg_probe_ex(jpegs[i], sizes[i], e->src_accept, &infos[i], room.data(), MJH_MAX_SRC_SCANS, &ns);
+      if (rc == MJH_OK && infos[i].sof_type == 3) xscans[(size_t)i].assign(room.begin(), room.begin() + ns);
+    }
+    if (rc == MJH_OK) {
+      const mjh_jpeg_info &f = infos[i];
+      static thread_local mjh_params q;
+      const char *field = nullptr;
+      if (f.sof_type != 3) field = "a DCT-based file on a lossless encoder";
+      else if ((rc = mjh_params_from_jpeg(&f, MJH_PROFILE_FASTEST, &q)) != MJH_OK) field = nullptr;
+      else if (f.image_width != W || f.image_height != H) field = "image size";
+      else if (f.num_components != NC) field = "number of components";
+      else if (f.data_precision != P) field = "data precision";
+      if (field) rc = fail(MJH_EINVAL, "does not match the encoder's parameters: %s", field);
+    }
+    if (rc != MJH_OK) { e->tc_code[(size_t)i] = rc; e->tc_text[(size_t)i] = g_err; }
+  });
+  // ---- 2. descriptors.  "Blocks" are samples: every scan has one per component and MCU, W MCUs per row, H rows.
+  MjhLlGeom G;
+  memset(&G, 0, sizeof(G));
+  G.W = W; G.H = H; G.Wp = (W + 7) & ~7; G.ncomp = NC; G.precision = P; G.max_intervals = 1;
+  const long long plane = (long long)H * G.Wp;
+  G.per_image = plane * NC;
+  MjhConst CS;
+  memset(&CS, 0, sizeof(CS));
+  CS.W = W; CS.H = H; CS.ncomp = NC; CS.precision = P; CS.maxh = CS.maxv = 1;
+  CS.mcus_per_row = W; CS.mcu_rows = H; CS.blocks_per_mcu = NC;
+  CS.total_mcu_blocks = (int)G.per_image;
+  for (int c = 0; c < NC; c++) { MjhComp &cc = CS.c[c]; cc.h = cc.v = cc.hexp = cc.vexp = 1; cc.wib = cc.wpad = W; cc.hib = cc.hpad = H; cc.nblk = W * H; }
+  const int S = e->dec_subseq;
+  DecDescSet D;
+  std::vector<MjhDecTable> tables;
+  std::vector<MjhLlPlane> planes((size_t)n * NC);
+  memset(planes.data(), 0, planes.size() * sizeof(MjhLlPlane));
+  std::vector<size_t> file_off((size_t)n);
+  size_t total_bytes = 0;
+  for (int i = 0; i < n; i++) { file_off[(size_t)i] = total_bytes; total_bytes += up16(sizes[i]); }
+  for (int i = 0; i < n; i++) {
+    if (e->tc_code[(size_t)i] != MJH_OK) continue;
+    const size_t scans0 = D.scans.size(), segs0 = D.segs.size(), subs0 = D.sub_seg.size(), tabs0 = tables.size();
+    const int nsub0 = D.max_nsub;
+    const char *why = nullptr;
+    long long diff_off = 0;
+    for (const mjh_jpeg_scan_ex &x : xscans[(size_t)i]) {
+      MjhDecScan sc;
+      memset(&sc, 0, sizeof(sc));
+      sc.image = i;
+      sc.ncomp = sc.bpm = x.comps_in_scan;
+      sc.mcus = W * H; sc.mcus_per_row = W;
+      sc.ri = (x.restart_interval && (long long)x.restart_interval < sc.mcus) ? (int)x.restart_interval : sc.mcus;
+      sc.diff_off = diff_off;
+      if (diff_off + plane * sc.ncomp > G.per_image) { why = "internal: difference array too small"; break; }
+      int pair[10];
+      for (int j = 0; j < sc.ncomp; j++) {
+        const int ci = x.component_index[j];
+        sc.comp[j] = ci;
+        sc.nb[j] = 1;
+        MjhDecTable T;
+        if (!make_dec_table(x.huff_bits[2 * x.dc_tbl_no[j]], x.huff_vals[2 * x.dc_tbl_no[j]], true, &T, 16)) { why = "Bogus Huffman table definition (JERR_BAD_HUFF_TABLE)"; break; }
+        sc.dctab[j] = sc.actab[j] = (int)tables.size();      // (a kernel that loads the scan loads two tables per component)
+        tables.push_back(T);
+        pair[j] = x.dc_tbl_no[j];
+        MjhLlPlane &pl = planes[(size_t)i * NC + ci];
+        pl.off = diff_off + plane * j; pl.psv = x.Ss; pl.pt = x.Al;
+        pl.rows = sc.ri / W;
+        const int intervals = (H + pl.rows - 1) / pl.rows;
+        if (intervals > G.max_intervals) G.max_intervals = intervals;
+      }
+      if (why) break;
+      diff_off += plane * sc.ncomp;
+      dec_canon(sc, pair);
+      if (x.data_size >= ((size_t)1 << 28)) { why = "a scan of 256 MB or more (bit positions inside a restart segment are 32-bit)"; break; }
+      why = dec_split_segments((const uint8_t *)jpegs[i], x.data_offset, x.data_offset + x.data_size, x.restart_markers, sc, file_off[(size_t)i], S, true, D);
+      if (why) break;
+      D.scans.push_back(sc);
+    }
+    if (why) {
+      D.scans.resize(scans0); D.segs.resize(segs0); D.sub_seg.resize(subs0); D.max_nsub = nsub0;
+      tables.resize(tabs0);
+      e->tc_code[(size_t)i] = MJH_EINVAL; e->tc_text[(size_t)i] = why;
+    }
+  }
+  for (int i = 0; i < n; i++)
+    if (e->tc_code[(size_t)i] != MJH_OK) return fail(e->tc_code[(size_t)i], "file %d: %s", i, e->tc_text[(size_t)i].c_str());
+  // ---- 3. staging: the files as they are + one descriptor block, two host->device copies
+  HIPCHK(hipStreamSynchronize(e->stream));   // the staging buffers may still feed the previous batch
+  e->tc_syncs++;
+  const size_t per_sub = sizeof(MjhDecState) + sizeof(MjhDecCarry) + sizeof(unsigned), ns = D.sub_seg.size();
+  D.o_scans = 0;
+  D.o_segs = up16(D.scans.size() * sizeof(MjhDecScan));
+  D.o_subs = up16(D.o_segs + D.segs.size() * sizeof(MjhDecSeg));
+  const size_t o_tabs = up16(D.o_subs + ns * 4), o_planes = up16(o_tabs + tables.size() * sizeof(MjhDecTable)),
+               desc_bytes = up16(o_planes + planes.size() * sizeof(MjhLlPlane));
+  int rc = dec_grow_staging(e, total_bytes, desc_bytes, ns * per_sub);
+  if (rc == MJH_OK) rc = dec_status_buffers(e);
+  if (rc == MJH_OK) rc = decode_host_state(e);
+  if (rc) return rc;
+  if (!e->d_lldiff) {
+    HIPCHK(mjh_dmalloc((void **)&e->d_lldiff, (size_t)e->max_batch * (size_t)G.per_image * 2));
+    HIPCHK(mjh_dmalloc((void **)&e->d_llabove, (size_t)e->max_batch * NC * (size_t)H * 4));
+  }
+  const size_t need = (size_t)e->max_batch * (size_t)O.image_stride;
+  if (need > e->pixout_cap) {
+    if (e->d_pixout) { (void)mjh_guard_free(e->d_pixout); e->d_pixout = nullptr; }
+    e->pixout_cap = 0;
+    HIPCHK(mjh_dmalloc((void **)&e->d_pixout, need));
+    e->pixout_cap = need;
+  }
+  CopyPool::get().run(n, [&](int i) { memcpy(e->h_tc + file_off[(size_t)i], jpegs[i], sizes[i]); });
+  memcpy(e->h_tdesc + D.o_scans, D.scans.data(), D.scans.size() * sizeof(MjhDecScan));
+  memcpy(e->h_tdesc + D.o_segs, D.segs.data(), D.segs.size() * sizeof(MjhDecSeg));
+  memcpy(e->h_tdesc + D.o_subs, D.sub_seg.data(), ns * 4);
+  memcpy(e->h_tdesc + o_tabs, tables.data(), tables.size() * sizeof(MjhDecTable));
+  memcpy(e->h_tdesc + o_planes, planes.data(), planes.size() * sizeof(MjhLlPlane));
+  hipStream_t s = e->stream;
+  HIPCHK(hipMemcpyAsync(e->d_tc, e->h_tc, total_bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(e->d_tdesc, e->h_tdesc, desc_bytes, hipMemcpyHostToDevice, s));
+  // ---- 4. the kernels
+  MjhDecBatch B;
+  memset(&B, 0, sizeof(B));
+  B.bytes = e->d_tc;
+  B.scans = (const MjhDecScan *)(e->d_tdesc + D.o_scans);
+  B.segs = (const MjhDecSeg *)(e->d_tdesc + D.o_segs);
+  B.sub_seg = (const unsigned *)(e->d_tdesc + D.o_subs);
+  B.tables = (const MjhDecTable *)(e->d_tdesc + o_tabs);
+  B.state = (MjhDecState *)e->d_tsub;
+  B.carry = (MjhDecCarry *)((uint8_t *)e->d_tsub + ns * sizeof(MjhDecState));
+  B.ord = (unsigned *)((uint8_t *)e->d_tsub + ns * (sizeof(MjhDecState) + sizeof(MjhDecCarry)));
+  B.changed = e->d_tchanged;
+  B.status = e->d_tstat;
+  B.diff = e->d_lldiff;
+  B.nsub_padded = (int)ns; B.nseg = (int)D.segs.size(); B.nscan = (int)D.scans.size(); B.n = n;
+  B.S = S > 0 ? S : 1;
+  B.coef_limit = 32767;
+  const MjhLlPlane *d_planes = (const MjhLlPlane *)(e->d_tdesc + o_planes);
+  const bool timed = e->profiling != 0;
+  MjhPixOut PO;
+  memset(&PO, 0, sizeof(PO));
+  PO.W = W; PO.H = H; PO.ncomp = NC; PO.px_size = O.px * sample_bytes; PO.bottom_up = O.bottom_up;
+  PO.off_r = O.off[0]; PO.off_g = O.off[1]; PO.off_b = O.off[2];
+  PO.row_pitch = O.row_pitch; PO.image_stride = O.image_stride;
+  e->dp = PO; e->dp_n = n; e->dp_raw = false; e->dp_coefs = false;
+  e->last_n = n; e->compact_last = false; e->last = nullptr;
+  HIPCHK(hipMemsetAsync(e->d_lldiff, 0, (size_t)n * (size_t)G.per_image * 2, s));
+  HIPCHK(hipMemsetAsync(e->d_tstat, 0, (size_t)n * 4, s));
+  if (timed) HIPCHK(hipEventRecord(e->tc_ev[0], s));
+  rc = dec_sync_rounds(e, s, D.max_nsub, [&](int q, int first) { mjh_launch_ldec_sync(CS, B, q, first, s); });
+  if (rc) return rc;
+  if (timed) HIPCHK(hipEventRecord(e->tc_ev[1], s));
+  mjh_launch_dec_prefix(B, s);
+  if (timed) HIPCHK(hipEventRecord(e->tc_ev[2], s));
+  mjh_launch_ldec_store(CS, B, s);
+  if (timed) { HIPCHK(hipEventRecord(e->tc_ev[3], s)); HIPCHK(hipEventRecord(e->tc_ev[4], s)); e->tc_timed = true; }
+  if (timed) HIPCHK(hipEventRecord(e->dp_ev[0], s));
+  mjh_launch_ll_undiff(G, d_planes, e->d_lldiff, e->d_llabove, n, s);
+  if (timed) HIPCHK(hipEventRecord(e->dp_ev[1], s));
+  mjh_launch_ll_pixels(G, d_planes, e->d_lldiff, O, e->d_pixout, e->d_tstat, n, s);
+  if (timed) HIPCHK(hipEventRecord(e->dp_ev[2], s));
+  e->dp_timed = timed;
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(e->h_dstat, e->d_tstat, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipEventRecord(e->dp_done, s));
+  e->last_stream = s;
+  e->dp_queued = true;
+  e->dp_waited = false;
+  return MJH_OK;
+}
+
 extern "C" int mjh_decode_host(mjh_encoder *e, const void *const jpegs[], const size_t sizes[], int n, const mjh_decode_opts *opts)
 {
   if (!e) return fail(MJH_EINVAL, "null encoder");
@@ -3492,6 +3755,7 @@ extern "C" int mjh_decode_host(mjh_encoder *e, const void *const jpegs[], const 
   if (e->xf_on) return fail(MJH_EUNSUPPORTED, "a lossless transform (mjh_encoder_set_transform) together with decoding to pixels");
   mjh_decode_opts o;
   if (opts) o = *opts; else mjh_decode_opts_defaults(&o);
+  if (e->lossless) return decode_lossless(e, jpegs, sizes, n, o);
   if (o.raw_coefs) return decode_coefs(e, jpegs, sizes, n);
   if (o.dct_method != 0 && o.dct_method != 1) return fail(MJH_EINVAL, "dct_method %d of a decode call (0 = JDCT_ISLOW, 1 = JDCT_IFAST)", o.dct_method);
   const bool ifast = o.dct_method == 1, raw = o.raw_planes != 0;
@@ -4141,6 +4405,11 @@ static int create_lossless(const mjh_params *p, int max_batch, int device, mjh_e
   for (hipEvent_t *ev : { &e->ev_done, &e->ev_tier1, &e->copy_done, &e->ev_fork, &e->ev_join })
     HIPCHK_E(hipEventCreateWithFlags(ev, hipEventDisableTiming));
   if (const char *v = getenv("MJH_INFLIGHT")) { e->inflight = atoi(v); if (e->inflight < 1 || e->inflight > 2) e->inflight = 2; }
+  // decode_lossless: bytes per subsequence.  64, not the 512 of the DCT decoder: a lossless file is nearly all entropy-coded data, 18 MB
+  // for a 4K RGB frame, and with 64 bytes a wave's lanes read 4 KB side by side instead of 32 KB (profiles/lossless_decode_bench.md:
+  // the Huffman phases of 8 such files take 12.3 ms against 34.5 ms at 512, 45.5 at 256 and 43.1 at 128)
+  e->dec_subseq = 64;
+  if (const char *v = getenv("MJH_DECODE_SUBSEQ")) { e->dec_subseq = atoi(v); if (e->dec_subseq < 0 || (e->dec_subseq > 0 && e->dec_subseq < 16)) e->dec_subseq = 16; }
   const size_t B = (size_t)max_batch;
   e->pix_image_bytes = (size_t)W * H * px * (P > 8 ? 2 : 1);
   // Budget per sample, for the scan as a whole (one sample alone can exceed it: PSV 4..7 reach category P + 1 -- 8-bit Ra = Rb = 255,

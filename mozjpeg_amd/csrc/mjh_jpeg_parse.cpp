@@ -32,14 +32,16 @@ static const int kNatural[64] = {
 // The marker walk behind mjh_jpeg_probe (accept = 0, ex = nullptr) and mjh_jpeg_probe_ex.  A progressive file (SOF2, accepted with
 // MJH_SRC_PROGRESSIVE) leaves its scans in ex[] and info->num_scans at 0; its scan script is checked as start_pass_phuff_decoder
 // checks it (jdphuff.c:91-144), except that what the reference only warns about (JWRN_BOGUS_PROGRESSION) refuses the file: the
-// device decoder then never meets a refinement of something that was not sent.
+// device decoder then never meets a refinement of something that was not sent.  A lossless file (SOF3, accepted with
+// MJH_SRC_LOSSLESS) is reported the same way: its scans in ex[] with Ss = the predictor and Al = the point transform, checked as
+// start_pass_lossless (jdlossls.c:249-258) and start_input_pass (jddiffct.c:104-110) check them.
 static_assert(offsetof(mjh_jpeg_scan_ex, Ss) == sizeof(mjh_jpeg_scan), "mjh_jpeg_scan_ex begins with the fields of mjh_jpeg_scan");
 static int probe_walk(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_info *info, mjh_jpeg_scan_ex *ex, int cap, int *num_ex)
 {
   const uint8_t *d = (const uint8_t *)jpeg;
   memset(info, 0, sizeof(*info));
   if (num_ex) *num_ex = 0;
-  bool prog = false;
+  bool prog = false, lossless = false;
   int nex = 0;
   int coef_bits[MJH_MAX_COMPS][64];
   for (int c = 0; c < MJH_MAX_COMPS; c++) for (int k = 0; k < 64; k++) coef_bits[c][k] = -1;
@@ -74,10 +76,11 @@ static int probe_walk(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_i
     case 0xC5: case 0xC6: case 0xC7: case 0xCD: case 0xCE: case 0xCF: {
       if (m == 0xC2 && !(accept & MJH_SRC_PROGRESSIVE))
         return pfail(MJH_EUNSUPPORTED, "progressive source file (SOF2): only sequential Huffman-coded files are decoded on the device");
-      if (m == 0xC3) return pfail(MJH_EUNSUPPORTED, "lossless source file (SOF3): jpeg_copy_critical_parameters refuses it as well (JERR_NOTIMPL, jctrans.c:83)");
+      if (m == 0xC3 && !(accept & MJH_SRC_LOSSLESS)) return pfail(MJH_EUNSUPPORTED, "lossless source file (SOF3): jpeg_copy_critical_parameters refuses it as well (JERR_NOTIMPL, jctrans.c:83)");
       if (m == 0xC9 || m == 0xCA || m == 0xCB) return pfail(MJH_EUNSUPPORTED, "arithmetic-coded source file (SOF%d)", m - 0xC0);
-      if (m != 0xC0 && m != 0xC1 && m != 0xC2) return pfail(MJH_EUNSUPPORTED, "Unsupported JPEG process: SOF type 0x%02x (JERR_SOF_UNSUPPORTED)", m);
+      if (m != 0xC0 && m != 0xC1 && m != 0xC2 && m != 0xC3) return pfail(MJH_EUNSUPPORTED, "Unsupported JPEG process: SOF type 0x%02x (JERR_SOF_UNSUPPORTED)", m);
       prog = m == 0xC2;
+      lossless = m == 0xC3;
       if (saw_sof) return pfail(MJH_EINVAL, "Invalid JPEG file structure: two SOF markers (JERR_SOF_DUPLICATE)");
       if (n < 6) return pfail(MJH_EINVAL, "Bogus marker length (JERR_BAD_LENGTH)");
       info->sof_type = m - 0xC0;
@@ -88,6 +91,10 @@ static int probe_walk(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_i
       if (info->image_height == 0) return pfail(MJH_EUNSUPPORTED, "image height 0 in the frame header: a DNL marker would define it, which is not supported");
       if (info->image_width <= 0 || info->num_components <= 0) return pfail(MJH_EINVAL, "Empty JPEG image (JERR_EMPTY_IMAGE)");
       if (n != 6 + 3 * (size_t)info->num_components) return pfail(MJH_EINVAL, "Bogus marker length (JERR_BAD_LENGTH)");
+      if (lossless) {                  // initial_setup (jdinput.c:60-66)
+        if (info->data_precision != 8 && info->data_precision != 12 && info->data_precision != 16)
+          return pfail(MJH_EINVAL, "Unsupported JPEG data precision %d (JERR_BAD_PRECISION)", info->data_precision);
+      } else
       if (info->data_precision != 8) return pfail(MJH_EUNSUPPORTED, "%d-bit source file: only 8-bit samples", info->data_precision);
       if (info->num_components != 1 && info->num_components != 3)
         return pfail(MJH_EUNSUPPORTED, "%d components in the source file: 1 or 3 are supported", info->num_components);
@@ -100,6 +107,10 @@ static int probe_walk(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_i
           return pfail(MJH_EINVAL, "Bogus sampling factors (JERR_BAD_SAMPLING)");
         if (info->quant_tbl_no[c] > 3) return pfail(MJH_EINVAL, "Quantization table 0x%02x was not defined (JERR_NO_QUANT_TABLE)", info->quant_tbl_no[c]);
       }
+      if (lossless)
+        for (int c = 0; c < info->num_components; c++)
+          if (info->h_samp_factor[c] != 1 || info->v_samp_factor[c] != 1)
+            return pfail(MJH_EUNSUPPORTED, "subsampled components in a lossless source file (component %d is sampled %dx%d): only 1x1 is decoded", c, info->h_samp_factor[c], info->v_samp_factor[c]);
       saw_sof = true;
       break;
     }
@@ -166,12 +177,13 @@ static int probe_walk(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_i
       if (n < 1) return pfail(MJH_EINVAL, "Bogus marker length (JERR_BAD_LENGTH)");
       const int nc = s[0];
       if (n != (size_t)(2 * nc + 4) || nc < 1 || nc > MJH_MAX_COMPS) return pfail(MJH_EINVAL, "Bogus marker length (JERR_BAD_LENGTH)");
-      if (!prog && info->num_scans >= MJH_MAX_FILE_SCANS) return pfail(MJH_EINVAL, "more than %d scans in a sequential file", MJH_MAX_FILE_SCANS);
-      // a progressive file's scan is built in a scratch record and copied into ex[] (mjh_jpeg_scan_ex begins with the fields of
-      // mjh_jpeg_scan); scans beyond the room the caller gave are walked and checked all the same, for the count in the refusal
+      if (!prog && !lossless && info->num_scans >= MJH_MAX_FILE_SCANS) return pfail(MJH_EINVAL, "more than %d scans in a sequential file", MJH_MAX_FILE_SCANS);
+      // a progressive or lossless file's scan is built in a scratch record and copied into ex[] (mjh_jpeg_scan_ex begins with the fields
+      // of mjh_jpeg_scan); scans beyond the room the caller gave are walked and checked all the same, for the count in the refusal
       static thread_local mjh_jpeg_scan scratch;
-      if (prog) memset(&scratch, 0, sizeof(scratch));
-      mjh_jpeg_scan *sc = prog ? &scratch : &info->scans[info->num_scans];
+      const bool to_ex = prog || lossless;
+      if (to_ex) memset(&scratch, 0, sizeof(scratch));
+      mjh_jpeg_scan *sc = to_ex ? &scratch : &info->scans[info->num_scans];
       const uint8_t *t = s + 1 + 2 * nc;
       const int Ss = t[0], Se = t[1], Ah = t[2] >> 4, Al = t[2] & 15;
       if (prog) {                      // start_pass_phuff_decoder (jdphuff.c:91-121)
@@ -182,6 +194,12 @@ static int probe_walk(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_i
         if (Al > 13) bad = true;
         if (bad) return pfail(MJH_EINVAL, "Invalid progressive/lossless parameters Ss=%d Se=%d Ah=%d Al=%d (JERR_BAD_PROGRESSION)", Ss, Se, Ah, Al);
       }
+      if (lossless) {                  // start_pass_lossless (jdlossls.c:249-258); start_input_pass (jddiffct.c:104-110), every MCU row W MCUs
+        if (Ss < 1 || Ss > 7 || Se != 0 || Ah != 0 || Al >= info->data_precision)
+          return pfail(MJH_EINVAL, "Invalid progressive/lossless parameters Ss=%d Se=%d Ah=%d Al=%d (JERR_BAD_PROGRESSION)", Ss, Se, Ah, Al);
+        if (ri % (unsigned)info->image_width != 0)
+          return pfail(MJH_EINVAL, "Invalid restart interval %u; must be an integer multiple of the number of MCUs in an MCU row (%d) (JERR_BAD_RESTART)", ri, info->image_width);
+      }
       sc->comps_in_scan = nc;
       for (int i = 0; i < nc; i++) {
         const int id = s[1 + 2 * i];
@@ -189,7 +207,7 @@ static int probe_walk(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_i
         for (int c = 0; c < info->num_components; c++) if (info->component_id[c] == id) { ci = c; break; }
         if (ci < 0) return pfail(MJH_EINVAL, "Invalid component ID %d in SOS (JERR_BAD_COMPONENT_ID)", id);
         if (i > 0 && ci <= sc->component_index[i - 1]) return pfail(MJH_EINVAL, "Invalid component ID %d in SOS (JERR_BAD_COMPONENT_ID)", id);
-        if (comp_scans[ci]++ && !prog) return pfail(MJH_EINVAL, "component %d is coded by two scans of a sequential file (JERR_BAD_SCAN_SCRIPT)", ci);
+        if (comp_scans[ci]++ && !prog) return pfail(MJH_EINVAL, "component %d is coded by two scans of a %s file (JERR_BAD_SCAN_SCRIPT)", ci, lossless ? "lossless" : "sequential");
         sc->component_index[i] = ci;
         sc->dc_tbl_no[i] = s[2 + 2 * i] >> 4;
         sc->ac_tbl_no[i] = s[2 + 2 * i] & 15;
@@ -208,13 +226,17 @@ static int probe_walk(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_i
           const bool need_dc = Ss == 0 && Ah == 0, need_ac = Ss != 0;
           if ((need_dc && (sc->dc_tbl_no[i] > 3 || !((hdef >> (2 * sc->dc_tbl_no[i])) & 1))) || (need_ac && (sc->ac_tbl_no[i] > 3 || !((hdef >> (2 * sc->ac_tbl_no[i] + 1)) & 1))))
             return pfail(MJH_EINVAL, "Huffman table 0x%02x was not defined (JERR_NO_HUFF_TABLE)", s[2 + 2 * i]);
+        } else if (lossless) {         // the DC table alone (jdlhuff.c start_pass_lhuff_decoder); a lossless frame has no quantization tables
+          if (sc->dc_tbl_no[i] > 3 || !((hdef >> (2 * sc->dc_tbl_no[i])) & 1))
+            return pfail(MJH_EINVAL, "Huffman table 0x%02x was not defined (JERR_NO_HUFF_TABLE)", s[2 + 2 * i]);
+          continue;
         } else
         if (sc->dc_tbl_no[i] > 3 || sc->ac_tbl_no[i] > 3 || !((hdef >> (2 * sc->dc_tbl_no[i])) & 1) || !((hdef >> (2 * sc->ac_tbl_no[i] + 1)) & 1))
           return pfail(MJH_EINVAL, "Huffman table 0x%02x was not defined (JERR_NO_HUFF_TABLE)", s[2 + 2 * i]);
         if (!((info->quant_defined >> info->quant_tbl_no[ci]) & 1))
           return pfail(MJH_EINVAL, "Quantization table 0x%02x was not defined (JERR_NO_QUANT_TABLE)", info->quant_tbl_no[ci]);
       }
-      if (!prog && (t[0] != 0 || t[1] != 63 || t[2] != 0))
+      if (!to_ex && (t[0] != 0 || t[1] != 63 || t[2] != 0))
         return pfail(MJH_EINVAL, "Invalid progressive parameters Ss=%d Se=%d Ah=%d Al=%d in a sequential file (JERR_BAD_PROGRESSION)", t[0], t[1], t[2] >> 4, t[2] & 15);
       sc->restart_interval = ri;
       sc->huff_defined = hdef;
@@ -241,7 +263,7 @@ static int probe_walk(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_i
       sc->data_size = q - pos;
       sc->restart_markers = nrst;
       pos = q;
-      if (!prog) info->num_scans++;
+      if (!to_ex) info->num_scans++;
       else {
         if (nex < cap) {
           mjh_jpeg_scan_ex *xs = &ex[nex];
@@ -260,13 +282,18 @@ static int probe_walk(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_i
   if (info->num_scans + nex == 0) return pfail(MJH_EINVAL, "JPEG datastream contains no image (JERR_NO_IMAGE)");
   for (int c = 0; c < info->num_components; c++)
     if (!comp_scans[c]) return pfail(MJH_EINVAL, "component %d of the source file is in no scan (JERR_MISSING_DATA)", c);
-  if (prog && nex > cap) return pfail(MJH_EUNSUPPORTED, "%d scans in a progressive file: at most %d are decoded (MJH_MAX_SRC_SCANS = %d)", nex, cap, MJH_MAX_SRC_SCANS);
+  if (nex > cap) return pfail(MJH_EUNSUPPORTED, "%d scans in a progressive file: at most %d are decoded (MJH_MAX_SRC_SCANS = %d)", nex, cap, MJH_MAX_SRC_SCANS);
   if (num_ex) *num_ex = nex;
   // default_decompress_parms (jdapimin.c:130-205)
   if (info->num_components == 1) info->jpeg_color_space = MJH_CS_GRAYSCALE;
   else if (info->saw_JFIF_marker) info->jpeg_color_space = MJH_CS_YCbCr;
   else if (info->saw_Adobe_marker) info->jpeg_color_space = info->Adobe_transform == 0 ? MJH_CS_RGB : MJH_CS_YCbCr;
   else info->jpeg_color_space = (info->component_id[0] == 82 && info->component_id[1] == 71 && info->component_id[2] == 66) ? MJH_CS_RGB : MJH_CS_YCbCr;
+  if (lossless) {
+    // (a three-component lossless file without a marker is RGB: jdapimin.c:157-181 guesses RGB for every lossless file)
+    if (info->num_components == 3 && !info->saw_JFIF_marker && !info->saw_Adobe_marker) info->jpeg_color_space = MJH_CS_RGB;
+    if (nex > 0 && cap > 0) { info->lossless_psv = ex[0].Ss; info->lossless_pt = ex[0].Al; }
+  }
   return MJH_OK;
 }
 
@@ -279,9 +306,9 @@ extern "C" int mjh_jpeg_probe(const void *jpeg, size_t size, mjh_jpeg_info *info
 extern "C" int mjh_jpeg_probe_ex(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_info *info, mjh_jpeg_scan_ex *scans, int cap, int *num_scans)
 {
   if (!jpeg || !info) return pfail(MJH_EINVAL, "bad arguments");
-  if (accept & ~MJH_SRC_PROGRESSIVE) return pfail(MJH_EINVAL, "unknown source kinds 0x%x (MJH_SRC_PROGRESSIVE)", accept);
-  if (!(accept & MJH_SRC_PROGRESSIVE)) { if (num_scans) *num_scans = 0; return probe_walk(jpeg, size, 0u, info, nullptr, 0, nullptr); }
-  if (!scans || !num_scans || cap < 1) return pfail(MJH_EINVAL, "bad arguments: MJH_SRC_PROGRESSIVE needs room for the scans");
+  if (accept & ~(MJH_SRC_PROGRESSIVE | MJH_SRC_LOSSLESS)) return pfail(MJH_EINVAL, "unknown source kinds 0x%x (MJH_SRC_PROGRESSIVE | MJH_SRC_LOSSLESS)", accept);
+  if (!accept) { if (num_scans) *num_scans = 0; return probe_walk(jpeg, size, 0u, info, nullptr, 0, nullptr); }
+  if (!scans || !num_scans || cap < 1) return pfail(MJH_EINVAL, "bad arguments: MJH_SRC_PROGRESSIVE and MJH_SRC_LOSSLESS need room for the scans");
   return probe_walk(jpeg, size, accept, info, scans, cap < MJH_MAX_SRC_SCANS ? cap : MJH_MAX_SRC_SCANS, num_scans);
 }
 
@@ -290,6 +317,31 @@ extern "C" int mjh_params_from_jpeg(const mjh_jpeg_info *info, int compress_prof
   if (!info || !p) return pfail(MJH_EINVAL, "bad arguments");
   const int nc = info->num_components;
   if (nc != 1 && nc != 3) return pfail(MJH_EUNSUPPORTED, "%d components", nc);
+  if (info->sof_type == 3) {
+    // A lossless file (mjh_jpeg_probe_ex with MJH_SRC_LOSSLESS): the parameters of an encoder that writes such files and owns the
+    // geometry its decode calls need -- jpeg_enable_lossless(predictor, point transform) of the file's first scan as a script of one
+    // scan, the file's precision and components, no colour conversion (gray as gray, RGB as RGB)
+    if (nc == 3 && info->jpeg_color_space != MJH_CS_RGB)
+      return pfail(MJH_EUNSUPPORTED, "a three-component lossless file that is not RGB: its colour conversion is not built");
+    int rc = mjh_params_defaults(p, info->image_width, info->image_height, nc == 1 ? 1 : 3, nc == 1, compress_profile, 2, 2);
+    if (rc) return rc;
+    p->trellis_quant = 0;
+    p->data_precision = info->data_precision;
+    p->num_components = nc;
+    p->num_scans = 1;
+    p->optimize_scans = 0;
+    memset(&p->scan_info[0], 0, sizeof(p->scan_info[0]));
+    p->scan_info[0].comps_in_scan = nc;
+    for (int c = 0; c < nc; c++) p->scan_info[0].component_index[c] = c;
+    p->scan_info[0].Ss = info->lossless_psv; p->scan_info[0].Al = info->lossless_pt;
+    if (nc == 3) { p->color_transform = MJH_COLOR_NONE; p->write_JFIF_header = 0; }
+    for (int c = 0; c < nc; c++) {
+      p->component_id[c] = info->component_id[c];
+      p->h_samp_factor[c] = p->v_samp_factor[c] = 1;
+      p->quant_tbl_no[c] = p->dc_tbl_no[c] = p->ac_tbl_no[c] = 0;
+    }
+    return MJH_OK;
+  }
   // jpeg_set_defaults + jpeg_set_colorspace(srcinfo->jpeg_color_space)
   int rc = mjh_params_defaults(p, info->image_width, info->image_height, nc == 1 ? 1 : 3, nc == 1, compress_profile, 2, 2);
   if (rc) return rc;
