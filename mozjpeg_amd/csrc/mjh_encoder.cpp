@@ -300,11 +300,8 @@ struct mjh_encoder {
   unsigned long long *d_nzmask = nullptr; bool use_compact = false, compact_last = false;
   size_t small_batch = 400000;       // batches of fewer blocks run the AC trellis' first tier with one pass per tile
   uint8_t *d_nq8 = nullptr;          // per block: non-zero conventionally quantized AC coefficients (FDCT kernel) = tile-sort key of the AC trellis
-  int copy_prio = 0;
   int fastdiv_all = 0;               // every table in use has q <= 255: the kernels divide by 8q with one multiply-high (MjhQuant.mdiv)
-  int dc_mode = 0;
   int dc_late = 1;                   // large sequential batches: the DC chains of components >= dc_late (1: both chroma components, 2: Cr only) run behind the AC kernel, under the tail of small kernels (MJH_DC_LATE=0: all next to it)
-  int dc_stats_side = 1;             // the final DC statistics run on the side stream behind the DC trellis (MJH_DC_STATS_SIDE=0: main stream)
   int dc_lanes = 12000;              // MJH_DC_LANES: the DC trellis runs one lane per chain (k_trellis_dc_lane) in a call with at least this many chains per component (frames x iMCU rows) that meets dc_window_ok's conditions (0: never, 1: whenever they hold; the default: profiles/dc_lanes_ab.md)
   int dc_lanes_set = 0;              // MJH_DC_LANES was given: only then may the lane kernel take a call of one or two frames from the speculative pair
   int dc_path = 0;                   // the DC kernel family of the latest call (MJH_DC_PATH_*; mjh_get_dc_path)
@@ -1092,12 +1089,9 @@ extern "C" int mjh_encoder_create(const mjh_params *p, int max_batch, int device
   HIPCHK_E(hipEventCreateWithFlags(&e->ev_tier1, hipEventDisableTiming));
   if (const char *v = getenv("MJH_INFLIGHT")) { e->inflight = atoi(v); if (e->inflight < 1 || e->inflight > 2) e->inflight = 2; }
   if (const char *v = getenv("MJH_INFLIGHT_MODE")) { e->inflight_mode = atoi(v); if (e->inflight_mode < 0 || e->inflight_mode > 2) e->inflight_mode = 1; }
-  {
-    // (copy and hand-over streams at the greatest priority, i.e. in a hardware-queue pool of their own, were measured in round 3
-    // with 16 libjpeg client threads: no gain with the coalescing shim, a loss without it -- default priority)
-    e->copy_prio = 0;
-    HIPCHK_E(hipStreamCreateWithPriority(&e->copy_stream, hipStreamNonBlocking, e->copy_prio));
-  }
+  // (copy and hand-over streams at the greatest priority, i.e. in a hardware-queue pool of their own, were measured in round 3
+  // with 16 libjpeg client threads: no gain with the coalescing shim, a loss without it -- default priority)
+  HIPCHK_E(hipStreamCreateWithPriority(&e->copy_stream, hipStreamNonBlocking, 0));
   HIPCHK_E(hipEventCreateWithFlags(&e->copy_done, hipEventDisableTiming));
   HIPCHK_E(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
   HIPCHK_E(hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
@@ -1863,11 +1857,7 @@ static int run_pipeline(mjh_encoder *e, const void *d_pixels, size_t row_pitch, 
     // DC kernel runs on a side stream underneath the AC kernel.
     e->side_timed = false;
     bool dc_late = false;
-    const int dc_mode = e->dc_mode;   // experiments (MJH_DC_MODE): 1 = DC trellis on the main stream, before the AC kernel
-    if (p.trellis_quant_dc && dc_mode == 1) {
-      pr.mark("trellis_dc(serial)");
-      e->dc_path = mjh_launch_trellis_dc(dc_chain_view(e, CV), e->d_quant, e->d_uq, e->d_q, e->d_tabs, spi, sl_dc, e->d_lambda, e->d_back, n, s, e->dc_window_ok, 0, -1, e->dc_lanes);
-    } else if (p.trellis_quant_dc) {
+    if (p.trellis_quant_dc) {
       HIPCHK(hipEventRecord(e->ev_fork, s));
       HIPCHK(hipStreamWaitEvent(e->side_stream, e->ev_fork, 0));
       if (pr.enabled && e->profiling == 1) {
@@ -1892,7 +1882,7 @@ static int run_pipeline(mjh_encoder *e, const void *d_pixels, size_t row_pitch, 
       // mostly idle.  So, for a large sequential batch, only the LUMA chains (two thirds of the DC work) start next to the AC
       // kernel; the chroma chains and the final DC statistics start when it has finished and run under that tail, and the
       // main stream joins the side stream in front of the final tables instead of behind the trellis.
-      const bool final_dc_here = !e->progressive && p.optimize_coding && last_loop && nbands == 1 && qstride == 0 && !ext_eob && e->dc_stats_side && e->seq_scans.empty();
+      const bool final_dc_here = !e->progressive && p.optimize_coding && last_loop && nbands == 1 && qstride == 0 && !ext_eob && e->seq_scans.empty();
       // (the late chains hang on the tile-sorted AC kernel's event: without that kernel -- MJH_TRELLIS_V3=0, a capacity beyond its tiers --
       // every chain starts here, the older schedule)
       const bool sorted_tier = nzm && e->d_nq8 && e->trellis_v3 > 0 && e->trellis_variant <= 4;
@@ -1957,7 +1947,7 @@ static int run_pipeline(mjh_encoder *e, const void *d_pixels, size_t row_pitch, 
       pr.mark("trellis_q_opt(sums)");
       mjh_launch_qopt_accumulate(CV, e->d_uq, e->d_q, e->d_qsums, n, s);
     }
-    if (p.trellis_quant_dc && dc_mode != 1 && !dc_late) {
+    if (p.trellis_quant_dc && !dc_late) {
       pr.mark("join(trellis_dc)");
       HIPCHK(hipStreamWaitEvent(s, e->ev_join, 0));
     }
@@ -2350,7 +2340,7 @@ static int host_buffers(mjh_encoder *e)
   // the device buffer one by one (slow path, flagged in the table)
   // (a lossless file is about as large as its input, and larger for noise)
   e->res_cap = (size_t)e->max_batch * ((e->lossless ? e->pix_image_bytes * 3 / 2 : e->pix_image_bytes / 2) + 65536);
-  HIPCHK(hipStreamCreateWithPriority(&e->d2h_stream, hipStreamNonBlocking, e->copy_prio));
+  HIPCHK(hipStreamCreateWithPriority(&e->d2h_stream, hipStreamNonBlocking, 0));
   for (int b = 0; b < 2; b++) {
     HIPCHK(mjh_dmalloc((void **)&e->d_pixb[b], in_bytes));
     HIPCHK(mjh_guard_host_alloc((void **)&e->h_res[b], e->res_cap, hipHostMallocMapped, "h_res"));

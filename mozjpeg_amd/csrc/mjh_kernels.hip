@@ -1264,6 +1264,87 @@ __device__ __forceinline__ float grp_shfl_f(float v, int srclane_in_group, int l
 template <int L> __device__ __forceinline__ int row_bcast(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x150 + L, 0xF, 0xF, true); }   // row_newbcast:L
 template <int L> __device__ __forceinline__ float row_bcast_f(float v) { return __int_as_float(row_bcast<L>(__float_as_int(v))); }
 
+// What a chain of component `comp` of image `img` needs, whichever kernel walks it (k_trellis_dc2, k_trellis_dc3, k_trellis_dc3_fwd).
+struct DcChain {
+  MjhComp cc;
+  unsigned long long rsi;   // 12 x 5 bits: category + its code length = the rate of a DC difference of that category
+  int dq;                   // the DC quantizer step 8 q0
+  float rcp, lt0;
+  int ncand;                // get_num_dc_trellis_candidates :930-933
+  const int16_t *uq0;       // plane k = 0 of the image's raw coefficients,
+  int16_t *qo0;             // of its quantized ones (nullptr: the kernel writes none),
+  const float *lam;         // and its per-block lambda
+};
+__device__ __forceinline__ DcChain dc_chain_setup(const MjhConst &C, const MjhQuant *__restrict__ Q, const int16_t *__restrict__ coef_uq, int16_t *__restrict__ coef_q,
+                                                  const MjhHuffTable *__restrict__ tabs, int slots_per_image, int4 dc_slot_of_comp, const float *__restrict__ lambda_in, int img, int comp)
+{
+  DcChain ch;
+  ch.cc = C.c[comp];      // (in front of the slot's choice: behind it these loads start later, and one 4K frame's speculative walk measured 1.4 % longer; profiles/dc_trellis_refactor_ab.md)
+  const int slot = comp == 0 ? dc_slot_of_comp.x : comp == 1 ? dc_slot_of_comp.y : comp == 2 ? dc_slot_of_comp.z : dc_slot_of_comp.w;
+  const MjhHuffTable *T = tabs + (size_t)img * slots_per_image + slot;
+  ch.rsi = 0;
+  for (int s = 0; s < 12; s++) ch.rsi |= (unsigned long long)((T->ehufsi[s] + s) & 31) << (5 * s);
+  const int q0 = Q->q[ch.cc.qtbl][0];
+  ch.dq = 8 * q0;
+  ch.rcp = Q->rcp8q[ch.cc.qtbl][0];
+  ch.lt0 = Q->lambda_tbl[ch.cc.qtbl][0];
+  ch.ncand = (2 + 60 / q0) | 1;
+  if (ch.ncand > 9) ch.ncand = 9;
+  ch.uq0 = coef_uq + (size_t)img * C.coefs_per_image + ch.cc.coef_off;
+  ch.qo0 = coef_q ? coef_q + (size_t)img * C.coefs_per_image + ch.cc.coef_off : nullptr;
+  ch.lam = lambda_in + (size_t)img * C.total_real_blocks + ch.cc.blk_off;
+  return ch;
+}
+
+// The back-track of one block row, 16 blocks per step, from candidate j of its last block: lane k owns block top-k, and the next
+// 16 blocks' loads are issued before these are walked.  word_at(b): the 16 back-pointer bytes of block b, out_at(b): where its
+// value goes.  Returns the value of block wib-1, the next block row's lastDC, in every lane of the group.
+template <class WordAt, class OutAt>
+__device__ __forceinline__ int dc_backtrack_row(const DcChain &ch, int k, int row0, int j, WordAt word_at, OutAt out_at)
+{
+  const int wib = ch.cc.wib, dq = ch.dq;
+  auto fetch_back = [&](int top, int &xs_o, uint4 &w_o) {
+    const int b = top - k;
+    xs_o = 0; w_o = make_uint4(0, 0, 0, 0);
+    if (top >= 0 && b >= 0) {
+      xs_o = ch.uq0[row0 + b];
+      w_o = *word_at(b);
+    }
+  };
+  int bx, last_dc = 0;
+  uint4 w;
+  fetch_back(wib - 1, bx, w);
+  for (int top = wib - 1; top >= 0; top -= 16) {
+    int bx_n;
+    uint4 w_n;
+    fetch_back(top - 16, bx_n, w_n);
+    const int b = top - k;
+    const int x = bx < 0 ? -bx : bx;
+    const int qv = udiv_exact(x + (dq >> 1), dq, ch.rcp);
+    int myj = 0;
+    const int steps = min(16, top + 1);
+#define DC_BACK(S)                                                                         \
+    if (S < steps) {                                                                       \
+      if (k == S) myj = j;                                                                 \
+      const unsigned word = j < 4 ? w.x : (j < 8 ? w.y : w.z);                             \
+      const int nj = (int)((word >> (8 * (j & 3))) & 0xFF);                                \
+      j = row_bcast<S>(nj);                                                                \
+    }
+    DC_BACK(0) DC_BACK(1) DC_BACK(2) DC_BACK(3) DC_BACK(4) DC_BACK(5) DC_BACK(6) DC_BACK(7)
+    DC_BACK(8) DC_BACK(9) DC_BACK(10) DC_BACK(11) DC_BACK(12) DC_BACK(13) DC_BACK(14) DC_BACK(15)
+#undef DC_BACK
+    if (b >= 0) {
+      int cnd = qv - ch.ncand / 2 + myj;
+      cnd = min(1023, max(-1023, cnd));
+      if (bx < 0) cnd = -cnd;
+      *out_at(b) = (int16_t)cnd;
+      if (b == wib - 1) last_dc = cnd;
+    }
+    bx = bx_n; w = w_n;
+  }
+  return row_bcast<0>(last_dc);        // owner of block wib-1 is lane 0 of the first step
+}
+
 __global__ void __launch_bounds__(64)
 k_trellis_dc2(MjhConst C, const MjhQuant *__restrict__ Q, const int16_t *__restrict__ coef_uq,
               int16_t *__restrict__ coef_q, const MjhHuffTable *__restrict__ tabs, int slots_per_image,
@@ -1276,20 +1357,14 @@ k_trellis_dc2(MjhConst C, const MjhQuant *__restrict__ Q, const int16_t *__restr
   const int chain = chain0 + blockIdx.x * 4 + (lane >> 4);     // chains [chain0, chain1) of the image: component-major, one per iMCU row
   if (chain >= chain1) return;   // whole 16-lane groups (= DPP rows) leave together
   const int comp = chain / C.mcu_rows, imcu = chain - comp * C.mcu_rows;
-  const MjhComp cc = C.c[comp];
-  const int slot = comp == 0 ? dc_slot_of_comp.x : comp == 1 ? dc_slot_of_comp.y : comp == 2 ? dc_slot_of_comp.z : dc_slot_of_comp.w;
-  const MjhHuffTable *T = tabs + (size_t)img * slots_per_image + slot;
-  unsigned long long rsi = 0;   // 12 x 5 bits: category + its code length = the rate of a DC difference of that category
-  for (int s = 0; s < 12; s++) rsi |= (unsigned long long)((T->ehufsi[s] + s) & 31) << (5 * s);
-  const int q0 = Q->q[cc.qtbl][0];
-  const int dq = 8 * q0;
-  const float rcp = Q->rcp8q[cc.qtbl][0];
-  const float lt0 = Q->lambda_tbl[cc.qtbl][0];
-  int ncand = (2 + 60 / q0) | 1;                 // get_num_dc_trellis_candidates :930-933
-  if (ncand > 9) ncand = 9;
-  const int16_t *uq0 = coef_uq + (size_t)img * C.coefs_per_image + cc.coef_off;  // plane k = 0
-  int16_t *qo0 = coef_q + (size_t)img * C.coefs_per_image + cc.coef_off;
-  const float *lam = lambda_in + (size_t)img * C.total_real_blocks + cc.blk_off;
+  const DcChain ch = dc_chain_setup(C, Q, coef_uq, coef_q, tabs, slots_per_image, dc_slot_of_comp, lambda_in, img, comp);
+  const MjhComp &cc = ch.cc;
+  const unsigned long long rsi = ch.rsi;
+  const int dq = ch.dq, ncand = ch.ncand;
+  const float rcp = ch.rcp, lt0 = ch.lt0;
+  const int16_t *uq0 = ch.uq0;
+  int16_t *qo0 = ch.qo0;
+  const float *lam = ch.lam;
   uint8_t *bk = back + ((size_t)img * C.total_real_blocks + cc.blk_off) * 16;
   int last_dc = 0;
   for (int sub = 0; sub < cc.v; sub++) {
@@ -1379,47 +1454,9 @@ k_trellis_dc2(MjhConst C, const MjhQuant *__restrict__ Q, const int16_t *__restr
 #undef DC2_LAST
     }
     __threadfence_block();
-    // back-track, 16 blocks per step: lane k owns block top-k; the next 16 blocks' loads are issued before these are walked
-    auto fetch_back = [&](int top, int &xs_o, uint4 &w_o) {
-      const int b = top - k;
-      xs_o = 0; w_o = make_uint4(0, 0, 0, 0);
-      if (top >= 0 && b >= 0) {
-        xs_o = uq0[row0 + b];
-        w_o = *reinterpret_cast<const uint4 *>(bk + (size_t)(row0 + b) * 16);
-      }
-    };
-    int bx;
-    uint4 w;
-    fetch_back(cc.wib - 1, bx, w);
-    for (int top = cc.wib - 1; top >= 0; top -= 16) {
-      int bx_n;
-      uint4 w_n;
-      fetch_back(top - 16, bx_n, w_n);
-      const int b = top - k;
-      const int x = bx < 0 ? -bx : bx;
-      const int qv = udiv_exact(x + (dq >> 1), dq, rcp);
-      int myj = 0;
-      const int steps = min(16, top + 1);
-#define DC2_BACK(S)                                                                        \
-      if (S < steps) {                                                                     \
-        if (k == S) myj = j;                                                               \
-        const unsigned word = j < 4 ? w.x : (j < 8 ? w.y : w.z);                           \
-        const int nj = (int)((word >> (8 * (j & 3))) & 0xFF);                              \
-        j = row_bcast<S>(nj);                                                              \
-      }
-      DC2_BACK(0) DC2_BACK(1) DC2_BACK(2) DC2_BACK(3) DC2_BACK(4) DC2_BACK(5) DC2_BACK(6) DC2_BACK(7)
-      DC2_BACK(8) DC2_BACK(9) DC2_BACK(10) DC2_BACK(11) DC2_BACK(12) DC2_BACK(13) DC2_BACK(14) DC2_BACK(15)
-#undef DC2_BACK
-      if (b >= 0) {
-        int cnd = qv - ncand / 2 + myj;
-        cnd = min(1023, max(-1023, cnd));
-        if (bx < 0) cnd = -cnd;
-        qo0[row0 + b] = (int16_t)cnd;
-        if (b == cc.wib - 1) last_dc = cnd;
-      }
-      bx = bx_n; w = w_n;
-    }
-    last_dc = row_bcast<0>(last_dc);        // owner of block wib-1 is lane 0 of the first step
+    last_dc = dc_backtrack_row(ch, k, row0, j,
+                               [&](int b) { return reinterpret_cast<const uint4 *>(bk + (size_t)(row0 + b) * 16); },
+                               [&](int b) { return qo0 + row0 + b; });
     if (C.delta_dc_weight > 0.0f) __threadfence();   // the next sub-row reads this row's final DC values back (other lanes of the group)
     else __threadfence_block();
   }
@@ -1498,6 +1535,91 @@ __device__ __forceinline__ float min9_f(float a0, float a1, float a2, float a3, 
   return min3_f(min3_f(a0, a1, a2), min3_f(a3, a4, a5), min3_f(a6, a7, a8));
 }
 
+// The window form's walk of one block row, first block to last.  last_dc: the value the first block is rated against; back_at(bi):
+// the 16 back-pointer bytes of block bi.  Returns the first minimum over the candidates of the last block, as a candidate index.
+template <class BackAt>
+__device__ __forceinline__ int dc3_row_forward(const DcChain &ch, int lane, int row0, int last_dc, BackAt back_at)
+{
+  const int k = lane & 15;                      // lane in the group = rank of its candidate VALUE
+  const int wib = ch.cc.wib, dq = ch.dq, ncand = ch.ncand, h = ncand / 2;
+  const unsigned long long rsi = ch.rsi;
+  const bool vlane = k < ncand;
+  int prev_c0 = 0, prev_neg = 0;
+  float prev_cost = 0.0f;
+  // per block, computed 16 blocks at a time (lane j: block g+j): |raw DC| | conventional quantized value << 16 | negative << 26,
+  // and lambda * (1 / q0^2)
+  auto fetch = [&](int b, unsigned &pk_o, float &lam_o) {
+    const int xs = b < wib ? (int)ch.uq0[row0 + b] : 0;
+    const float l = b < wib ? ch.lam[row0 + b] : 0.0f;
+    const int x = xs < 0 ? -xs : xs;
+    const int qv = udiv_exact(x + (dq >> 1), dq, ch.rcp);
+    pk_o = (unsigned)x | ((unsigned)qv << 16) | (xs < 0 ? 1u << 26 : 0u);
+    lam_o = l * ch.lt0;
+  };
+  unsigned pk_l;
+  float lam_l;
+  fetch(k, pk_l, lam_l);
+  for (int g = 0; g < wib; g += 16) {
+    unsigned pk_n;
+    float lam_n;
+    fetch(g + 16 + k, pk_n, lam_n);          // the next 16 blocks: in flight while these 16 are walked
+    const int steps = min(16, wib - g);
+    unsigned pk_s = (unsigned)grp_shfl((int)pk_l, 0, lane);
+    float lam_s = grp_shfl_f(lam_l, 0, lane);
+    for (int s = 0; s < steps; s++) {
+      const int bi = g + s;
+      const unsigned pk = pk_s;
+      const float lambda_dc = lam_s;
+      pk_s = (unsigned)grp_shfl((int)pk_l, (s + 1) & 15, lane);     // the next step's inputs (their LDS round trip hides behind this step)
+      lam_s = grp_shfl_f(lam_l, (s + 1) & 15, lane);
+      const int x = (int)(pk & 0xFFFFu), qv = (int)((pk >> 16) & 1023u), neg = (int)(pk >> 26);
+      const int kk = neg ? ncand - 1 - k : k;            // candidate index held by this lane
+      const int c0 = neg ? -(qv + h) : qv - h;           // value of lane 0's candidate; this lane's is c0 + k
+      const int delta = mul24(qv - h + kk, dq) - x;
+      const float dist = (float)mul24(delta, delta) * lambda_dc;
+      float best;
+      int bb = 0;
+      if (bi == 0) {
+        best = dc_rate(rsi, c0 + k - last_dc) + dist;
+      } else {
+        const int D = c0 - prev_c0;
+        const float Rj = dc_rate(rsi, D + k - 7), R0 = dc_rate(rsi, D - 8);
+        // predecessor in lane M: rate of difference number k - M + 8 = the value of lane k + 7 - M (number 0: R0)
+        const float c_0 = add_bcast<0>(prev_cost, add_shl<7>(Rj, dist, true), true);
+        const float c_1 = add_bcast<1>(prev_cost, add_shl<6>(Rj, dist));
+        const float c_2 = add_bcast<2>(prev_cost, add_shl<5>(Rj, dist));
+        const float c_3 = add_bcast<3>(prev_cost, add_shl<4>(Rj, dist));
+        const float c_4 = add_bcast<4>(prev_cost, add_shl<3>(Rj, dist));
+        const float c_5 = add_bcast<5>(prev_cost, add_shl<2>(Rj, dist));
+        const float c_6 = add_bcast<6>(prev_cost, add_shl<1>(Rj, dist));
+        const float c_7 = add_bcast<7>(prev_cost, Rj + dist);
+        const float c_8 = add_bcast<8>(prev_cost, dpp_f<0x111>(R0, Rj) + dist);     // row_shr:1; lane 0 keeps R0
+        const float m = min9_f(c_0, c_1, c_2, c_3, c_4, c_5, c_6, c_7, c_8);
+        // first minimum in CANDIDATE order of the predecessor (:1100-1106): lanes of invalid candidates hold 3e38
+        // (tried in round 6: the mask shifted in by an add-with-carry behind each compare, 18 instead of ~26 instructions -- a
+        // chain of nine dependent adds through vcc, 0.3 % slower than the select / or tree)
+        unsigned e = (c_0 == m ? 1u : 0u) | (c_1 == m ? 2u : 0u) | (c_2 == m ? 4u : 0u) | (c_3 == m ? 8u : 0u) | (c_4 == m ? 16u : 0u) |
+                     (c_5 == m ? 32u : 0u) | (c_6 == m ? 64u : 0u) | (c_7 == m ? 128u : 0u) | (c_8 == m ? 256u : 0u);
+        bb = prev_neg ? ncand - 1 - (31 - __clz((int)e)) : __ffs((int)e) - 1;
+        best = m;
+      }
+      prev_cost = vlane ? best : 3e38f;
+      prev_c0 = c0;
+      prev_neg = neg;
+      if (vlane) back_at(bi)[kk] = (uint8_t)bb;
+    }
+    pk_l = pk_n; lam_l = lam_n;
+  }
+  // first minimum over the candidates of the last block, in candidate order (:1309-1313)
+  const float p0 = row_bcast_f<0>(prev_cost), p1 = row_bcast_f<1>(prev_cost), p2 = row_bcast_f<2>(prev_cost), p3 = row_bcast_f<3>(prev_cost),
+              p4 = row_bcast_f<4>(prev_cost), p5 = row_bcast_f<5>(prev_cost), p6 = row_bcast_f<6>(prev_cost), p7 = row_bcast_f<7>(prev_cost),
+              p8 = row_bcast_f<8>(prev_cost);
+  const float m = min9_f(p0, p1, p2, p3, p4, p5, p6, p7, p8);
+  const unsigned e = (p0 == m ? 1u : 0u) | (p1 == m ? 2u : 0u) | (p2 == m ? 4u : 0u) | (p3 == m ? 8u : 0u) | (p4 == m ? 16u : 0u) |
+                     (p5 == m ? 32u : 0u) | (p6 == m ? 64u : 0u) | (p7 == m ? 128u : 0u) | (p8 == m ? 256u : 0u);
+  return prev_neg ? ncand - 1 - (31 - __clz((int)e)) : __ffs((int)e) - 1;
+}
+
 __global__ void __launch_bounds__(64)
 k_trellis_dc3(MjhConst C, const MjhQuant *__restrict__ Q, const int16_t *__restrict__ coef_uq,
               int16_t *__restrict__ coef_q, const MjhHuffTable *__restrict__ tabs, int slots_per_image,
@@ -1506,151 +1628,22 @@ k_trellis_dc3(MjhConst C, const MjhQuant *__restrict__ Q, const int16_t *__restr
   const int img = blockIdx.y;
   const int lane = threadIdx.x;
   MJH_WAVE_GROUPS(16);
-  const int k = lane & 15;                      // lane in the group = rank of its candidate VALUE
   const int chain = chain0 + blockIdx.x * 4 + (lane >> 4);     // chains [chain0, chain1) of the image: component-major, one per iMCU row
   if (chain >= chain1) return;   // whole 16-lane groups (= DPP rows) leave together
   const int comp = chain / C.mcu_rows, imcu = chain - comp * C.mcu_rows;
-  const MjhComp cc = C.c[comp];
-  const int slot = comp == 0 ? dc_slot_of_comp.x : comp == 1 ? dc_slot_of_comp.y : comp == 2 ? dc_slot_of_comp.z : dc_slot_of_comp.w;
-  const MjhHuffTable *T = tabs + (size_t)img * slots_per_image + slot;
-  unsigned long long rsi = 0;   // 12 x 5 bits: category + its code length
-  for (int s = 0; s < 12; s++) rsi |= (unsigned long long)((T->ehufsi[s] + s) & 31) << (5 * s);
-  const int q0 = Q->q[cc.qtbl][0];
-  const int dq = 8 * q0;
-  const float rcp = Q->rcp8q[cc.qtbl][0];
-  const float lt0 = Q->lambda_tbl[cc.qtbl][0];
-  int ncand = (2 + 60 / q0) | 1;                 // get_num_dc_trellis_candidates :930-933
-  if (ncand > 9) ncand = 9;
-  const int h = ncand / 2;
-  const bool vlane = k < ncand;
-  const int16_t *uq0 = coef_uq + (size_t)img * C.coefs_per_image + cc.coef_off;  // plane k = 0
-  int16_t *qo0 = coef_q + (size_t)img * C.coefs_per_image + cc.coef_off;
-  const float *lam = lambda_in + (size_t)img * C.total_real_blocks + cc.blk_off;
+  const DcChain ch = dc_chain_setup(C, Q, coef_uq, coef_q, tabs, slots_per_image, dc_slot_of_comp, lambda_in, img, comp);
+  const MjhComp &cc = ch.cc;
   uint8_t *bk = back + ((size_t)img * C.total_real_blocks + cc.blk_off) * 16;
   int last_dc = 0;
   for (int sub = 0; sub < cc.v; sub++) {
     const int br = imcu * cc.v + sub;
     if (br >= cc.hib) break;
     const int row0 = br * cc.wib;
-    int prev_c0 = 0, prev_neg = 0;
-    float prev_cost = 0.0f;
-    // per block, computed 16 blocks at a time (lane j: block g+j): |raw DC| | conventional quantized value << 16 | negative << 26,
-    // and lambda * (1 / q0^2)
-    auto fetch = [&](int b, unsigned &pk_o, float &lam_o) {
-      const int xs = b < cc.wib ? (int)uq0[row0 + b] : 0;
-      const float l = b < cc.wib ? lam[row0 + b] : 0.0f;
-      const int x = xs < 0 ? -xs : xs;
-      const int qv = udiv_exact(x + (dq >> 1), dq, rcp);
-      pk_o = (unsigned)x | ((unsigned)qv << 16) | (xs < 0 ? 1u << 26 : 0u);
-      lam_o = l * lt0;
-    };
-    unsigned pk_l;
-    float lam_l;
-    fetch(k, pk_l, lam_l);
-    for (int g = 0; g < cc.wib; g += 16) {
-      unsigned pk_n;
-      float lam_n;
-      fetch(g + 16 + k, pk_n, lam_n);          // the next 16 blocks: in flight while these 16 are walked
-      const int steps = min(16, cc.wib - g);
-      unsigned pk_s = (unsigned)grp_shfl((int)pk_l, 0, lane);
-      float lam_s = grp_shfl_f(lam_l, 0, lane);
-      for (int s = 0; s < steps; s++) {
-        const int bi = g + s;
-        const unsigned pk = pk_s;
-        const float lambda_dc = lam_s;
-        pk_s = (unsigned)grp_shfl((int)pk_l, (s + 1) & 15, lane);     // the next step's inputs (their LDS round trip hides behind this step)
-        lam_s = grp_shfl_f(lam_l, (s + 1) & 15, lane);
-        const int x = (int)(pk & 0xFFFFu), qv = (int)((pk >> 16) & 1023u), neg = (int)(pk >> 26);
-        const int kk = neg ? ncand - 1 - k : k;            // candidate index held by this lane
-        const int c0 = neg ? -(qv + h) : qv - h;           // value of lane 0's candidate; this lane's is c0 + k
-        const int delta = mul24(qv - h + kk, dq) - x;
-        const float dist = (float)mul24(delta, delta) * lambda_dc;
-        float best;
-        int bb = 0;
-        if (bi == 0) {
-          best = dc_rate(rsi, c0 + k - last_dc) + dist;
-        } else {
-          const int D = c0 - prev_c0;
-          const float Rj = dc_rate(rsi, D + k - 7), R0 = dc_rate(rsi, D - 8);
-          // predecessor in lane M: rate of difference number k - M + 8 = the value of lane k + 7 - M (number 0: R0)
-          const float c_0 = add_bcast<0>(prev_cost, add_shl<7>(Rj, dist, true), true);
-          const float c_1 = add_bcast<1>(prev_cost, add_shl<6>(Rj, dist));
-          const float c_2 = add_bcast<2>(prev_cost, add_shl<5>(Rj, dist));
-          const float c_3 = add_bcast<3>(prev_cost, add_shl<4>(Rj, dist));
-          const float c_4 = add_bcast<4>(prev_cost, add_shl<3>(Rj, dist));
-          const float c_5 = add_bcast<5>(prev_cost, add_shl<2>(Rj, dist));
-          const float c_6 = add_bcast<6>(prev_cost, add_shl<1>(Rj, dist));
-          const float c_7 = add_bcast<7>(prev_cost, Rj + dist);
-          const float c_8 = add_bcast<8>(prev_cost, dpp_f<0x111>(R0, Rj) + dist);     // row_shr:1; lane 0 keeps R0
-          const float m = min9_f(c_0, c_1, c_2, c_3, c_4, c_5, c_6, c_7, c_8);
-          // first minimum in CANDIDATE order of the predecessor (:1100-1106): lanes of invalid candidates hold 3e38
-          // (tried in round 6: the mask shifted in by an add-with-carry behind each compare, 18 instead of ~26 instructions -- a
-          // chain of nine dependent adds through vcc, 0.3 % slower than the select / or tree)
-          unsigned e = (c_0 == m ? 1u : 0u) | (c_1 == m ? 2u : 0u) | (c_2 == m ? 4u : 0u) | (c_3 == m ? 8u : 0u) | (c_4 == m ? 16u : 0u) |
-                       (c_5 == m ? 32u : 0u) | (c_6 == m ? 64u : 0u) | (c_7 == m ? 128u : 0u) | (c_8 == m ? 256u : 0u);
-          bb = prev_neg ? ncand - 1 - (31 - __clz((int)e)) : __ffs((int)e) - 1;
-          best = m;
-        }
-        prev_cost = vlane ? best : 3e38f;
-        prev_c0 = c0;
-        prev_neg = neg;
-        if (vlane) bk[(size_t)(row0 + bi) * 16 + kk] = (uint8_t)bb;
-      }
-      pk_l = pk_n; lam_l = lam_n;
-    }
-    // first minimum over the candidates of the last block, in candidate order (:1309-1313)
-    int j;
-    {
-      const float p0 = row_bcast_f<0>(prev_cost), p1 = row_bcast_f<1>(prev_cost), p2 = row_bcast_f<2>(prev_cost), p3 = row_bcast_f<3>(prev_cost),
-                  p4 = row_bcast_f<4>(prev_cost), p5 = row_bcast_f<5>(prev_cost), p6 = row_bcast_f<6>(prev_cost), p7 = row_bcast_f<7>(prev_cost),
-                  p8 = row_bcast_f<8>(prev_cost);
-      const float m = min9_f(p0, p1, p2, p3, p4, p5, p6, p7, p8);
-      const unsigned e = (p0 == m ? 1u : 0u) | (p1 == m ? 2u : 0u) | (p2 == m ? 4u : 0u) | (p3 == m ? 8u : 0u) | (p4 == m ? 16u : 0u) |
-                         (p5 == m ? 32u : 0u) | (p6 == m ? 64u : 0u) | (p7 == m ? 128u : 0u) | (p8 == m ? 256u : 0u);
-      j = prev_neg ? ncand - 1 - (31 - __clz((int)e)) : __ffs((int)e) - 1;
-    }
+    const int j = dc3_row_forward(ch, lane, row0, last_dc, [&](int bi) { return bk + (size_t)(row0 + bi) * 16; });
     __threadfence_block();
-    // back-track, 16 blocks per step: lane k owns block top-k; the next 16 blocks' loads are issued before these are walked
-    auto fetch_back = [&](int top, int &xs_o, uint4 &w_o) {
-      const int b = top - k;
-      xs_o = 0; w_o = make_uint4(0, 0, 0, 0);
-      if (top >= 0 && b >= 0) {
-        xs_o = uq0[row0 + b];
-        w_o = *reinterpret_cast<const uint4 *>(bk + (size_t)(row0 + b) * 16);
-      }
-    };
-    int bx;
-    uint4 w;
-    fetch_back(cc.wib - 1, bx, w);
-    for (int top = cc.wib - 1; top >= 0; top -= 16) {
-      int bx_n;
-      uint4 w_n;
-      fetch_back(top - 16, bx_n, w_n);
-      const int b = top - k;
-      const int x = bx < 0 ? -bx : bx;
-      const int qv = udiv_exact(x + (dq >> 1), dq, rcp);
-      int myj = 0;
-      const int steps = min(16, top + 1);
-#define DC3_BACK(S)                                                                        \
-      if (S < steps) {                                                                     \
-        if (k == S) myj = j;                                                               \
-        const unsigned word = j < 4 ? w.x : (j < 8 ? w.y : w.z);                           \
-        const int nj = (int)((word >> (8 * (j & 3))) & 0xFF);                              \
-        j = row_bcast<S>(nj);                                                              \
-      }
-      DC3_BACK(0) DC3_BACK(1) DC3_BACK(2) DC3_BACK(3) DC3_BACK(4) DC3_BACK(5) DC3_BACK(6) DC3_BACK(7)
-      DC3_BACK(8) DC3_BACK(9) DC3_BACK(10) DC3_BACK(11) DC3_BACK(12) DC3_BACK(13) DC3_BACK(14) DC3_BACK(15)
-#undef DC3_BACK
-      if (b >= 0) {
-        int cnd = qv - h + myj;
-        cnd = min(1023, max(-1023, cnd));
-        if (bx < 0) cnd = -cnd;
-        qo0[row0 + b] = (int16_t)cnd;
-        if (b == cc.wib - 1) last_dc = cnd;
-      }
-      bx = bx_n; w = w_n;
-    }
-    last_dc = row_bcast<0>(last_dc);        // owner of block wib-1 is lane 0 of the first step
+    last_dc = dc_backtrack_row(ch, lane & 15, row0, j,
+                               [&](int b) { return reinterpret_cast<const uint4 *>(bk + (size_t)(row0 + b) * 16); },
+                               [&](int b) { return ch.qo0 + row0 + b; });
     __threadfence_block();
   }
 }
@@ -1879,145 +1872,28 @@ k_trellis_dc3_fwd(MjhConst C, const MjhQuant *__restrict__ Q, const int16_t *__r
   const int grow = chain / DC3_HYP, hyp = chain - grow * DC3_HYP;
   int comp = 0, br = grow;
   while (comp + 1 < C.ncomp && br >= C.c[comp].hib) { br -= C.c[comp].hib; comp++; }
-  const MjhComp cc = C.c[comp];
+  const DcChain ch = dc_chain_setup(C, Q, coef_uq, nullptr, tabs, slots_per_image, dc_slot_of_comp, lambda_in, img, comp);
+  const MjhComp &cc = ch.cc;
   const int sub = br % cc.v;
-  const int slot = comp == 0 ? dc_slot_of_comp.x : comp == 1 ? dc_slot_of_comp.y : comp == 2 ? dc_slot_of_comp.z : dc_slot_of_comp.w;
-  const MjhHuffTable *T = tabs + (size_t)img * slots_per_image + slot;
-  const int q0 = Q->q[cc.qtbl][0];
-  const int dq = 8 * q0;
-  const float rcp = Q->rcp8q[cc.qtbl][0];
-  const float lt0 = Q->lambda_tbl[cc.qtbl][0];
-  int ncand = (2 + 60 / q0) | 1;
-  if (ncand > 9) ncand = 9;
-  const int h = ncand / 2;
-  if (hyp >= ncand || (sub == 0 && hyp > 0)) return;        // whole 16-lane groups leave together
-  unsigned long long rsi = 0;
-  for (int s = 0; s < 12; s++) rsi |= (unsigned long long)((T->ehufsi[s] + s) & 31) << (5 * s);
-  const bool vlane = k < ncand;
-  const int16_t *uq0 = coef_uq + (size_t)img * C.coefs_per_image + cc.coef_off;
-  const float *lam = lambda_in + (size_t)img * C.total_real_blocks + cc.blk_off;
+  if (hyp >= ch.ncand || (sub == 0 && hyp > 0)) return;        // whole 16-lane groups leave together
   const int row0 = br * cc.wib;
   uint8_t *bk = back9 + (((size_t)img * C.total_real_blocks + cc.blk_off + row0) * DC3_HYP) * 16;   // + (bi * 9 + hyp) * 16 + kk
   int last_dc = 0;
   if (sub > 0) {     // the hypothesis: the row above ended on candidate `hyp` of its last block
-    const int xs = uq0[row0 - 1];
+    const int xs = ch.uq0[row0 - 1];
     const int x = xs < 0 ? -xs : xs;
-    int cnd = udiv_exact(x + (dq >> 1), dq, rcp) - h + hyp;
+    int cnd = udiv_exact(x + (ch.dq >> 1), ch.dq, ch.rcp) - ch.ncand / 2 + hyp;
     cnd = min(1023, max(-1023, cnd));
     last_dc = xs < 0 ? -cnd : cnd;
   }
-  int prev_c0 = 0, prev_neg = 0;
-  float prev_cost = 0.0f;
-  auto fetch = [&](int b, unsigned &pk_o, float &lam_o) {
-    const int xs = b < cc.wib ? (int)uq0[row0 + b] : 0;
-    const float l = b < cc.wib ? lam[row0 + b] : 0.0f;
-    const int x = xs < 0 ? -xs : xs;
-    const int qv = udiv_exact(x + (dq >> 1), dq, rcp);
-    pk_o = (unsigned)x | ((unsigned)qv << 16) | (xs < 0 ? 1u << 26 : 0u);
-    lam_o = l * lt0;
-  };
-  unsigned pk_l;
-  float lam_l;
-  fetch(k, pk_l, lam_l);
-  for (int g = 0; g < cc.wib; g += 16) {
-    unsigned pk_n;
-    float lam_n;
-    fetch(g + 16 + k, pk_n, lam_n);
-    const int steps = min(16, cc.wib - g);
-    unsigned pk_s = (unsigned)grp_shfl((int)pk_l, 0, lane);
-    float lam_s = grp_shfl_f(lam_l, 0, lane);
-    for (int s = 0; s < steps; s++) {
-      const int bi = g + s;
-      const unsigned pk = pk_s;
-      const float lambda_dc = lam_s;
-      pk_s = (unsigned)grp_shfl((int)pk_l, (s + 1) & 15, lane);
-      lam_s = grp_shfl_f(lam_l, (s + 1) & 15, lane);
-      const int x = (int)(pk & 0xFFFFu), qv = (int)((pk >> 16) & 1023u), neg = (int)(pk >> 26);
-      const int kk = neg ? ncand - 1 - k : k;
-      const int c0 = neg ? -(qv + h) : qv - h;
-      const int delta = mul24(qv - h + kk, dq) - x;
-      const float dist = (float)mul24(delta, delta) * lambda_dc;
-      float best;
-      int bb = 0;
-      if (bi == 0) {
-        best = dc_rate(rsi, c0 + k - last_dc) + dist;
-      } else {
-        const int D = c0 - prev_c0;
-        const float Rj = dc_rate(rsi, D + k - 7), R0 = dc_rate(rsi, D - 8);
-        const float c_0 = add_bcast<0>(prev_cost, add_shl<7>(Rj, dist, true), true);
-        const float c_1 = add_bcast<1>(prev_cost, add_shl<6>(Rj, dist));
-        const float c_2 = add_bcast<2>(prev_cost, add_shl<5>(Rj, dist));
-        const float c_3 = add_bcast<3>(prev_cost, add_shl<4>(Rj, dist));
-        const float c_4 = add_bcast<4>(prev_cost, add_shl<3>(Rj, dist));
-        const float c_5 = add_bcast<5>(prev_cost, add_shl<2>(Rj, dist));
-        const float c_6 = add_bcast<6>(prev_cost, add_shl<1>(Rj, dist));
-        const float c_7 = add_bcast<7>(prev_cost, Rj + dist);
-        const float c_8 = add_bcast<8>(prev_cost, dpp_f<0x111>(R0, Rj) + dist);
-        const float m = min9_f(c_0, c_1, c_2, c_3, c_4, c_5, c_6, c_7, c_8);
-        unsigned e = (c_0 == m ? 1u : 0u) | (c_1 == m ? 2u : 0u) | (c_2 == m ? 4u : 0u) | (c_3 == m ? 8u : 0u) | (c_4 == m ? 16u : 0u) |
-                     (c_5 == m ? 32u : 0u) | (c_6 == m ? 64u : 0u) | (c_7 == m ? 128u : 0u) | (c_8 == m ? 256u : 0u);
-        bb = prev_neg ? ncand - 1 - (31 - __clz((int)e)) : __ffs((int)e) - 1;
-        best = m;
-      }
-      prev_cost = vlane ? best : 3e38f;
-      prev_c0 = c0;
-      prev_neg = neg;
-      if (vlane) bk[((size_t)bi * DC3_HYP + hyp) * 16 + kk] = (uint8_t)bb;
-    }
-    pk_l = pk_n; lam_l = lam_n;
-  }
-  {   // first minimum over the candidates of the last block, in candidate order (jcdctmgr.c:1309-1313)
-    const float p0 = row_bcast_f<0>(prev_cost), p1 = row_bcast_f<1>(prev_cost), p2 = row_bcast_f<2>(prev_cost), p3 = row_bcast_f<3>(prev_cost),
-                p4 = row_bcast_f<4>(prev_cost), p5 = row_bcast_f<5>(prev_cost), p6 = row_bcast_f<6>(prev_cost), p7 = row_bcast_f<7>(prev_cost),
-                p8 = row_bcast_f<8>(prev_cost);
-    const float m = min9_f(p0, p1, p2, p3, p4, p5, p6, p7, p8);
-    const unsigned e = (p0 == m ? 1u : 0u) | (p1 == m ? 2u : 0u) | (p2 == m ? 4u : 0u) | (p3 == m ? 8u : 0u) | (p4 == m ? 16u : 0u) |
-                       (p5 == m ? 32u : 0u) | (p6 == m ? 64u : 0u) | (p7 == m ? 128u : 0u) | (p8 == m ? 256u : 0u);
-    int j = prev_neg ? ncand - 1 - (31 - __clz((int)e)) : __ffs((int)e) - 1;
-    if (k == 0) jfin[((size_t)img * rows_total + grow) * DC3_HYP + hyp] = j;
-    // ... and this walk's own back-track, 16 blocks per step, into the hypothesis' copy of the row (k_trellis_dc3_resolve keeps
-    // the copy whose hypothesis held)
-    __threadfence_block();
-    int16_t *qs = qspec + ((size_t)img * C.total_real_blocks + cc.blk_off + row0) * DC3_HYP;
-    auto fetch_back = [&](int top, int &xs_o, uint4 &w_o) {
-      const int b = top - k;
-      xs_o = 0; w_o = make_uint4(0, 0, 0, 0);
-      if (top >= 0 && b >= 0) {
-        xs_o = uq0[row0 + b];
-        w_o = *reinterpret_cast<const uint4 *>(bk + ((size_t)b * DC3_HYP + hyp) * 16);
-      }
-    };
-    int bx;
-    uint4 w;
-    fetch_back(cc.wib - 1, bx, w);
-    for (int top = cc.wib - 1; top >= 0; top -= 16) {
-      int bx_n;
-      uint4 w_n;
-      fetch_back(top - 16, bx_n, w_n);
-      const int b = top - k;
-      const int x = bx < 0 ? -bx : bx;
-      const int qv = udiv_exact(x + (dq >> 1), dq, rcp);
-      int myj = 0;
-      const int steps = min(16, top + 1);
-#define DC3_BACK(S)                                                                        \
-      if (S < steps) {                                                                     \
-        if (k == S) myj = j;                                                               \
-        const unsigned word = j < 4 ? w.x : (j < 8 ? w.y : w.z);                           \
-        const int nj = (int)((word >> (8 * (j & 3))) & 0xFF);                              \
-        j = row_bcast<S>(nj);                                                              \
-      }
-      DC3_BACK(0) DC3_BACK(1) DC3_BACK(2) DC3_BACK(3) DC3_BACK(4) DC3_BACK(5) DC3_BACK(6) DC3_BACK(7)
-      DC3_BACK(8) DC3_BACK(9) DC3_BACK(10) DC3_BACK(11) DC3_BACK(12) DC3_BACK(13) DC3_BACK(14) DC3_BACK(15)
-#undef DC3_BACK
-      if (b >= 0) {
-        int cnd = qv - h + myj;
-        cnd = min(1023, max(-1023, cnd));
-        if (bx < 0) cnd = -cnd;
-        qs[(size_t)b * DC3_HYP + hyp] = (int16_t)cnd;
-      }
-      bx = bx_n; w = w_n;
-    }
-  }
+  const int j = dc3_row_forward(ch, lane, row0, last_dc, [&](int bi) { return bk + ((size_t)bi * DC3_HYP + hyp) * 16; });
+  if (k == 0) jfin[((size_t)img * rows_total + grow) * DC3_HYP + hyp] = j;
+  // ... and this walk's own back-track into the hypothesis' copy of the row (k_trellis_dc3_resolve keeps the copy whose hypothesis held)
+  __threadfence_block();
+  int16_t *qs = qspec + ((size_t)img * C.total_real_blocks + cc.blk_off + row0) * DC3_HYP;
+  dc_backtrack_row(ch, k, row0, j,
+                   [&](int b) { return reinterpret_cast<const uint4 *>(bk + ((size_t)b * DC3_HYP + hyp) * 16); },
+                   [&](int b) { return qs + (size_t)b * DC3_HYP + hyp; });
 }
 
 // row after row of an iMCU row: keep the copy of the walk whose hypothesis = the candidate the row above ended on (its last
