@@ -30,7 +30,8 @@
 // scans of a search phase run concurrently; the host never sees a symbol.
 // AC-FIRST scans without restart intervals need none of this: a block's bits depend on the blocks before it
 // only through the LENGTH of the EOB run in front of it, so their statistics and their encoding run in
-// parallel over the whole component (k_prog_stats_acfirst/_resolve, k_pe_len/_resolve/_write/_finish below).
+// parallel over the whole component -- and so do the other kinds of scan once the forced flushes are found up front: the
+// parallel chain (k_pp_stats/_carry/_cuts/_runs/_resolve, k_pp_len/_write/_finish and k_pp_chunk_bits/_emit below).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "mjh_internal.h"
@@ -64,21 +65,37 @@ __device__ __forceinline__ int eobrun_symbol(unsigned eobrun, int *nextra)
   return nb << 4;
 }
 
-// waves per (scan, image) workgroup: the walk is latency-bound (one workgroup per CU, dependent LDS look-ups
-// and 63 plane loads per step), so as many waves as a workgroup can have: 16 = 4 per SIMD = 128 VGPRs each
-// (statistics 96; encode exactly 128 with 3 spilled registers -- still 10 % faster than 12 waves of 154)
 // scan search: a candidate of luma level k+1 is coded only for the images whose search still improved at level k
 __device__ __forceinline__ bool prog_skip(const MjhProgScan &sc, const MjhProgCtl *ct) { return sc.cond > 0 && ct->al_continue < sc.cond; }
 
-#define PROG_WAVES(ENCODE) 16
+// Al of a scan: as given, or what the scan search chose for the image (jcmaster.c:487-497)
+__device__ __forceinline__ int prog_scan_al(const MjhProgScan &sc, const MjhProgCtl *ct)
+{
+  return sc.al_sel == 1 ? ct->best_Al_luma : (sc.al_sel == 2 ? ct->best_Al_chroma : sc.Al);
+}
+
+// bits of the EOBRUN symbol of a run of cnt > 0 blocks and its extra bits (emit_eobrun jcphuff.c:409-431); s_size: code lengths
+__device__ __forceinline__ unsigned pp_eobrun_bits(unsigned cnt, const unsigned char *s_size)
+{
+  int nextra;
+  const int sym = eobrun_symbol(cnt, &nextra);
+  return s_size[sym] + (unsigned)nextra;
+}
+
+// waves per (scan, image) workgroup: the walk is latency-bound (one workgroup per CU, dependent LDS look-ups
+// and 63 plane loads per step), so as many waves as a workgroup can have: 16 = 4 per SIMD = 128 VGPRs each
+// (statistics 96; encode exactly 128 with 3 spilled registers -- still 10 % faster than 12 waves of 154)
+#define PROG_WAVES 16
 template <int ENCODE>
-__global__ void __launch_bounds__(64 * PROG_WAVES(ENCODE))
+__global__ void __launch_bounds__(64 * PROG_WAVES)
 k_prog_scan(MjhConst C, const MjhProgScan *__restrict__ scans, const int *__restrict__ scan_list,
             MjhProgCtl *__restrict__ ctl, const int16_t *__restrict__ coef_q, MjhHuffTable *__restrict__ tabs,
             int slots_per_image, unsigned *__restrict__ pool, size_t pool_words_per_image,
             unsigned *__restrict__ mpos_pool, int mpos_per_image, const MjhProgPair *__restrict__ run_if)
 {
-  // fallback of the parallel encode: only the pairs it flagged are walked sequentially
+  // (run_if is null at both launches and MjhProgPair::fallback always 0: the fallback of the parallel encode they served is gone.
+  // They stay because this kernel, at exactly 128 VGPRs with spills, measured slower without the parameter: 6-9 % in statistics
+  // mode on 4K frames with restart intervals)
   if (run_if && !run_if[(size_t)blockIdx.x * gridDim.y + blockIdx.y].fallback) return;
   __shared__ unsigned hist[2][256];
   __shared__ unsigned s_tab[2][256];   // size << 16 | code
@@ -92,7 +109,7 @@ k_prog_scan(MjhConst C, const MjhProgScan *__restrict__ scans, const int *__rest
   MjhProgCtl *ct = ctl + img;
   if (prog_skip(sc, ct)) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int Al = sc.al_sel == 1 ? ct->best_Al_luma : (sc.al_sel == 2 ? ct->best_Al_chroma : sc.Al);
+  const int Al = prog_scan_al(sc, ct);
   const int16_t *qimg = coef_q + (size_t)img * C.coefs_per_image;
   const bool has0 = sc.slot[0] >= 0, has1 = sc.slot[1] >= 0;   // DC scans: table number 0 / 1; AC scans: slot[0]
   MjhHuffTable *T0 = tabs + (size_t)img * slots_per_image + (has0 ? sc.slot[0] : 0);
@@ -103,7 +120,7 @@ k_prog_scan(MjhConst C, const MjhProgScan *__restrict__ scans, const int *__rest
   if (ENCODE && ct->error) return;
   const unsigned long long t_start = wall_clock64();   // 100 MHz constant clock
 
-  for (int i = threadIdx.x; i < 256; i += 64 * PROG_WAVES(ENCODE)) {
+  for (int i = threadIdx.x; i < 256; i += 64 * PROG_WAVES) {
     hist[0][i] = 0; hist[1][i] = 0;
     if (ENCODE) {
       s_tab[0][i] = has0 ? ((unsigned)T0->ehufsi[i] << 16) | T0->ehufco[i] : 0u;
@@ -126,7 +143,7 @@ k_prog_scan(MjhConst C, const MjhProgScan *__restrict__ scans, const int *__rest
     const MjhComp c0 = C.c[sc.comp[0]];
     const int nunits = inter ? C.mcus_per_row * C.mcu_rows : c0.nblk;
     const int nsteps = (nunits + 63) >> 6;
-    for (int step = wave; step < nsteps; step += PROG_WAVES(ENCODE)) {
+    for (int step = wave; step < nsteps; step += PROG_WAVES) {
       const int u = step * 64 + lane;
       const bool valid = u < nunits;
       unsigned mybits = 0;
@@ -278,7 +295,7 @@ k_prog_scan(MjhConst C, const MjhProgScan *__restrict__ scans, const int *__rest
     };
 
     const int nsteps = (cc.nblk + 63) >> 6;
-    for (int step = wave; step < nsteps; step += PROG_WAVES(ENCODE)) {
+    for (int step = wave; step < nsteps; step += PROG_WAVES) {
       const int base = step * 64;
       const int b = base + lane;
       const bool valid = b < cc.nblk;
@@ -591,7 +608,7 @@ k_prog_scan(MjhConst C, const MjhProgScan *__restrict__ scans, const int *__rest
   __syncthreads();
   if (!ENCODE) {
     // statistics -> table slots (+ the trellis-pass seeding of jcphuff.c:257-264)
-    for (int i = threadIdx.x; i < 256; i += 64 * PROG_WAVES(ENCODE)) {
+    for (int i = threadIdx.x; i < 256; i += 64 * PROG_WAVES) {
       unsigned s0 = hist[0][i];
       if (sc.seed && (i & 15) < 12) s0 += 1;
       if (has0) T0->counts[i] = s0;
@@ -834,15 +851,26 @@ k_pp_init(MjhProgPE pe, int npairs)
   if (i < npairs) { pe.info[i].final_run = 0; pe.info[i].final_be = 0; pe.info[i].fallback = 0; pe.info[i].corr_total = 0; }
 }
 
+// the two DC code tables of a scan as size << 16 | code by category (a refinement scan has no symbols: zeros)
+__device__ __forceinline__ void pp_stage_dc_tables(unsigned (*s_dc)[16], const MjhHuffTable *__restrict__ tabs, size_t slot0, const MjhProgScan &sc, int kind)
+{
+  const int tid = threadIdx.x;
+  if (tid < 32) {
+    const int t = tid >> 4, sym = tid & 15;
+    const MjhHuffTable *T = tabs + slot0 + (sc.slot[t] >= 0 ? sc.slot[t] : 0);
+    s_dc[t][sym] = sc.slot[t] >= 0 && kind == PP_DC_FIRST ? ((unsigned)T->ehufsi[sym] << 16) | T->ehufco[sym] : 0u;
+  }
+  __syncthreads();
+}
 
-template <bool COMPACT, int SELX>   // SELX: SEL as in k_pp_len
+template <bool COMPACT, int SEL>
 __global__ void __launch_bounds__(256)
 k_pp_stats(MjhConst C, const MjhProgScan *__restrict__ scans, const int *__restrict__ scan_list,
            const MjhProgCtl *__restrict__ ctl, const int16_t *__restrict__ coef_q, const unsigned long long *__restrict__ nzmask,
            MjhHuffTable *__restrict__ tabs, int slots_per_image, MjhProgPE pe, int li0)
 {
-  constexpr int SEL = SELX;
-  constexpr bool SKIPLOW = SELX == 1;     // first-pass AC scans: the non-zeros below the band leave the mask up front (pp_band_nonzeros)
+  static_assert(COMPACT == (SEL != 0), "compact records come with one kernel per kind of scan, planes with one for all");
+  constexpr bool SKIPLOW = SEL == 1;     // first-pass AC scans: the non-zeros below the band leave the mask up front (pp_band_nonzeros)
   constexpr int NH = SEL == 1 ? 16 : 4;   // (first-pass AC scans: a handful of symbols takes most of the counts)
   __shared__ unsigned hist[NH][256];   // DC scans: [table 0 / 1]; AC scans: NH interleaved copies (the hot symbols serialise the LDS atomics)
   __shared__ unsigned long long ne_bits[MJH_PSTAT_BLOCKS / 64], e_bits[MJH_PSTAT_BLOCKS / 64];
@@ -860,7 +888,7 @@ k_pp_stats(MjhConst C, const MjhProgScan *__restrict__ scans, const int *__restr
   const int nb = min(MJH_PSTAT_BLOCKS, nunits - cb);
   const MjhProgCtl *ct = ctl + img;
   if (prog_skip(sc, ct)) return;
-  const int Al = sc.al_sel == 1 ? ct->best_Al_luma : (sc.al_sel == 2 ? ct->best_Al_chroma : sc.Al);
+  const int Al = prog_scan_al(sc, ct);
   const int16_t *qimg = coef_q + (size_t)img * C.coefs_per_image;
 #pragma unroll
   for (int c = 0; c < NH; c++) hist[c][tid] = 0;
@@ -1254,13 +1282,15 @@ __device__ __forceinline__ unsigned pp_dc_unit(const MjhConst &C, const MjhProgS
   return bits;
 }
 
-// SEL: 0 = every kind of scan; 1 = only the first-pass AC scans (most scans of a search; its own kernel needs half the
-// registers and no scratch, so twice the waves hide the dependent loads); 2 = the other kinds
+// SEL: 0 = every kind of scan (planes); 1 = only the first-pass AC scans (most scans of a search; its own kernel needs half the
+// registers and no scratch, so twice the waves hide the dependent loads); 2 = the other kinds.  Compact records come with one
+// kernel per kind of scan (SEL != 0); their first-pass AC scans are sized and written by k_pp_emit, so here COMPACT means SEL == 2
 template <bool COMPACT, int SEL>
 __global__ void __launch_bounds__(256)
 k_pp_len(MjhConst C, const MjhProgScan *__restrict__ scans, const int *__restrict__ scan_list, const MjhProgCtl *__restrict__ ctl,
          const int16_t *__restrict__ coef_q, const unsigned long long *__restrict__ nzmask, const MjhHuffTable *__restrict__ tabs, int slots_per_image, MjhProgPE pe, int li0)
 {
+  static_assert(COMPACT == (SEL != 0) && SEL != 1, "compact records: one kernel for the scans that are not first-pass AC scans (those: k_pp_emit); planes: one for all");
   __shared__ unsigned char s_size[256];
   __shared__ unsigned s_dc[2][16];
   const int img = blockIdx.z, li = li0 + blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;   // scans li0.. of the list
@@ -1280,15 +1310,10 @@ k_pp_len(MjhConst C, const MjhProgScan *__restrict__ scans, const int *__restric
   const int nb = min(MJH_PSTAT_BLOCKS, nunits - cb);
   const MjhProgCtl *ct = ctl + img;
   if (prog_skip(sc, ct)) return;
-  const int Al = sc.al_sel == 1 ? ct->best_Al_luma : (sc.al_sel == 2 ? ct->best_Al_chroma : sc.Al);
+  const int Al = prog_scan_al(sc, ct);
   const int16_t *qimg = coef_q + (size_t)img * C.coefs_per_image;
   if (SEL != 1 && (kind == PP_DC_FIRST || kind == PP_DC_REFINE)) {
-    if (tid < 32) {
-      const int t = tid >> 4, sym = tid & 15;
-      const MjhHuffTable *T = tabs + (size_t)img * slots_per_image + (sc.slot[t] >= 0 ? sc.slot[t] : 0);
-      s_dc[t][sym] = sc.slot[t] >= 0 && kind == PP_DC_FIRST ? ((unsigned)T->ehufsi[sym] << 16) | T->ehufco[sym] : 0u;
-    }
-    __syncthreads();
+    pp_stage_dc_tables(s_dc, tabs, (size_t)img * slots_per_image, sc, kind);
     for (int i = 0; i < MJH_PSTAT_BLOCKS / 256; i++) {
       const int j = i * 256 + tid;
       len[j] = j < nb ? (uint16_t)pp_dc_unit<false>(C, sc, qimg, cb + j, Al, s_dc, nullptr) : (uint16_t)0;
@@ -1323,28 +1348,14 @@ k_pp_len(MjhConst C, const MjhProgScan *__restrict__ scans, const int *__restric
         const int jb = cb + (j < nb ? j : nb - 1);
         const bool cached = SEL == 2 && pe.rmask != nullptr;
         const unsigned long long m = cached ? 0ull : nzmask[(size_t)img * C.total_real_blocks + cc.blk_off + jb];
-        if (!refine) {
-          int prev = Ss - 1;
-          const unsigned zrl = s_size[0xF0];
-          pp_band_nonzeros(qc + jb, (size_t)cc.kstride, m, Ss, Se, has_own, [&](int k, int v) {
-            const int a = (v < 0 ? -v : v) >> Al;
-            if (a == 0) return;
-            const int r = k - prev - 1;
-            prev = k;
-            const int nbits = bitlen((unsigned)a);
-            own += (unsigned)(r >> 4) * zrl + s_size[((r & 15) << 4) + nbits] + (unsigned)nbits;
-          });
-          ne = prev != Ss - 1;
-        } else {
-          const PPRefine R = cached ? pp_refine_block_cached<false>(pe.rmask + (pair - (size_t)li0 * gridDim.z) * 3 * pe.nblk_pad + jb, (size_t)pe.nblk_pad, has_own, Ss, Se, s_size, nullptr)
-                                    : pp_refine_block_compact<false>(qc + jb, (size_t)cc.kstride, m, has_own, Ss, Se, Al, s_size, nullptr);
-          ne = R.ne; own = R.own;
-        }
+        const PPRefine R = cached ? pp_refine_block_cached<false>(pe.rmask + (pair - (size_t)li0 * gridDim.z) * 3 * pe.nblk_pad + jb, (size_t)pe.nblk_pad, has_own, Ss, Se, s_size, nullptr)
+                                  : pp_refine_block_compact<false>(qc + jb, (size_t)cc.kstride, m, has_own, Ss, Se, Al, s_size, nullptr);
+        ne = R.ne; own = R.own;
         if (!ne || !has_own) own = 0;
       }
       if (j < nb && ((fp_bits[j >> 6] >> (j & 63)) & 1ull)) {
         const unsigned cnt = run[j];
-        if (cnt) { int nextra; const int sym = eobrun_symbol(cnt, &nextra); own += s_size[sym] + (unsigned)nextra + (refine ? be16[j] : 0u); }
+        if (cnt) own += pp_eobrun_bits(cnt, s_size) + (refine ? be16[j] : 0u);
       }
       len[j] = (uint16_t)own;
       continue;
@@ -1387,7 +1398,7 @@ k_pp_len(MjhConst C, const MjhProgScan *__restrict__ scans, const int *__restric
     }
     if (j < nb && ((fp_bits[j >> 6] >> (j & 63)) & 1ull)) {     // the pending run (+ its buffered correction bits) goes out in front of this block
       const unsigned cnt = run[j];
-      if (cnt) { int nextra; const int sym = eobrun_symbol(cnt, &nextra); own += s_size[sym] + (unsigned)nextra + (refine ? be16[j] : 0u); }
+      if (cnt) own += pp_eobrun_bits(cnt, s_size) + (refine ? be16[j] : 0u);
     }
     len[j] = (uint16_t)own;
   }
@@ -1399,6 +1410,7 @@ k_pp_write(MjhConst C, const MjhProgScan *__restrict__ scans, const int *__restr
            const int16_t *__restrict__ coef_q, const unsigned long long *__restrict__ nzmask, const MjhHuffTable *__restrict__ tabs, int slots_per_image,
            unsigned *__restrict__ pool, size_t pool_words_per_image, MjhProgPE pe, int li0)
 {
+  static_assert(COMPACT == (SEL != 0) && SEL != 1, "compact records: one kernel for the scans that are not first-pass AC scans (those: k_pp_emit); planes: one for all");
   __shared__ unsigned s_tab[256];   // size << 16 | code
   __shared__ unsigned s_dc[2][16];
   __shared__ unsigned long long ne_bits[MJH_PSTAT_BLOCKS / 64];
@@ -1415,19 +1427,14 @@ k_pp_write(MjhConst C, const MjhProgScan *__restrict__ scans, const int *__restr
   if (prog_skip(sc, ct)) return;
   if (cb >= nunits || ct->error) return;
   const int nb = min(MJH_PSTAT_BLOCKS, nunits - cb);
-  const int Al = sc.al_sel == 1 ? ct->best_Al_luma : (sc.al_sel == 2 ? ct->best_Al_chroma : sc.Al);
+  const int Al = prog_scan_al(sc, ct);
   const int16_t *qimg = coef_q + (size_t)img * C.coefs_per_image;
   unsigned *stream = pool + (size_t)img * pool_words_per_image;
   const unsigned base = ct->scan_words_off[sidx] * 32u;
   const uint16_t *len = pe.len16 + pair * pe.nblk_pad + cb;
   const unsigned *off = pe.off32 + pair * pe.nblk_pad + cb;
   if (SEL != 1 && (kind == PP_DC_FIRST || kind == PP_DC_REFINE)) {
-    if (tid < 32) {
-      const int t = tid >> 4, sym = tid & 15;
-      const MjhHuffTable *T = tabs + (size_t)img * slots_per_image + (sc.slot[t] >= 0 ? sc.slot[t] : 0);
-      s_dc[t][sym] = sc.slot[t] >= 0 && kind == PP_DC_FIRST ? ((unsigned)T->ehufsi[sym] << 16) | T->ehufco[sym] : 0u;
-    }
-    __syncthreads();
+    pp_stage_dc_tables(s_dc, tabs, (size_t)img * slots_per_image, sc, kind);
     for (int i = 0; i < MJH_PSTAT_BLOCKS / 256; i++) {
       const int j = i * 256 + tid;
       if (j >= nb) break;
@@ -1476,34 +1483,6 @@ k_pp_write(MjhConst C, const MjhProgScan *__restrict__ scans, const int *__restr
     if (!COMPACT) {
       const int16_t *qs = qc + jb;
       PP_LOAD_BAND(x, qs, cc.kstride, Ss, Se)
-    }
-    if (COMPACT && !refine) {
-      // AC-first scan from compact records: every lane of the wave takes part in the (wave-uniform) plane loads
-      const bool wr = has_data && len_j != 0;
-      BitWriter bw;
-      bw.init(stream, base + (wr ? off[j] : 0u));
-      if (wr) {
-        const unsigned cnt = run[j];
-        if (cnt) {
-          int nextra;
-          const unsigned e = s_tab[eobrun_symbol(cnt, &nextra)];
-          bw.put(e & 0xFFFF, (int)(e >> 16));
-          if (nextra) bw.put(cnt & ((1u << nextra) - 1u), nextra);
-        }
-      }
-      int prev = Ss - 1;
-      pp_band_nonzeros(qc + jb, (size_t)cc.kstride, cmask, Ss, Se, wr, [&](int k, int v) {
-        const int a = (v < 0 ? -v : v) >> Al;
-        if (a == 0) return;
-        int r = k - prev - 1;
-        prev = k;
-        while (r > 15) { const unsigned e = s_tab[0xF0]; bw.put(e & 0xFFFF, (int)(e >> 16)); r -= 16; }
-        const int nbits = bitlen((unsigned)a);
-        const unsigned e = s_tab[(r << 4) + nbits];
-        bw.put_sym(e, (unsigned)(v < 0 ? ~a : a), nbits);
-      });
-      if (wr) bw.flush();
-      continue;
     }
     PPRefine Rc;
     if (COMPACT) {
@@ -1758,7 +1737,7 @@ k_pp_emit(MjhConst C, const MjhProgScan *__restrict__ scans, const int *__restri
   const unsigned cbase = base + pe.sums[pair * pe.chunks_per_scan + chunk];
   const unsigned cend = base + (last_chunk ? pe.totals[pair] : pe.sums[pair * pe.chunks_per_scan + chunk + 1]);
   if (cend == cbase) return;        // uniform: the chunk has no bits
-  const int Al = sc.al_sel == 1 ? ct->best_Al_luma : (sc.al_sel == 2 ? ct->best_Al_chroma : sc.Al);
+  const int Al = prog_scan_al(sc, ct);
   const MjhHuffTable *T0 = tabs + (size_t)img * slots_per_image + sc.slot[0];
   const int16_t *qc = coef_q + (size_t)img * C.coefs_per_image + cc.coef_off + cb;
   const unsigned long long *nzc = nzmask + (size_t)img * C.total_real_blocks + cc.blk_off + cb;
@@ -1947,7 +1926,7 @@ k_prog_header(const MjhProgScan *__restrict__ scans, const int *__restrict__ sca
     pos += 17 + n;
   }
   if (lane == 0) {     // emit_dri jcmarker.c:404-414 (only when the interval changes, :778-781), emit_sos :494-531
-    const int Al = sc.al_sel == 1 ? ct->best_Al_luma : (sc.al_sel == 2 ? ct->best_Al_chroma : sc.Al);
+    const int Al = prog_scan_al(sc, ct);
     uint8_t *s = o + pos;
     int k = 0;
     if (sc.emit_dri) { s[k++] = 0xFF; s[k++] = 0xDD; s[k++] = 0; s[k++] = 4; s[k++] = (uint8_t)(sc.ri >> 8); s[k++] = (uint8_t)sc.ri; }
@@ -2216,7 +2195,7 @@ void mjh_launch_prog_reset(void *ctl, int nscans, int n, hipStream_t s)
 void mjh_launch_prog_stats(const MjhConst &C, const void *scans, const int *list, int nlist, void *ctl, const void *q,
                            MjhHuffTable *tabs, int spi, unsigned *mpos, int mpos_per_image, int n, hipStream_t s)
 {
-  hipLaunchKernelGGL((k_prog_scan<0>), dim3(n, nlist), dim3(64 * PROG_WAVES(0)), 0, s, C, (const MjhProgScan *)scans, list, (MjhProgCtl *)ctl,
+  hipLaunchKernelGGL((k_prog_scan<0>), dim3(n, nlist), dim3(64 * PROG_WAVES), 0, s, C, (const MjhProgScan *)scans, list, (MjhProgCtl *)ctl,
                      (const int16_t *)q, tabs, spi, (unsigned *)nullptr, (size_t)0, mpos, mpos_per_image, (const MjhProgPair *)nullptr);
 }
 
@@ -2233,9 +2212,7 @@ void mjh_launch_prog_stats_par(const MjhConst &C, const void *scans, const int *
                                      nzmask, tabs, spi, pe, 0);
     if (nlist > nacf) hipLaunchKernelGGL((k_pp_stats<true, 2>), dim3(pe.chunks_per_scan, nlist - nacf, n), dim3(256), 0, s, C, (const MjhProgScan *)sv, list, (const MjhProgCtl *)ctl, qv,
                                          nzmask, tabs, spi, pe, nacf);
-  } else if (nzmask) hipLaunchKernelGGL((k_pp_stats<true, 0>), gchunks, dim3(256), 0, s, C, (const MjhProgScan *)sv, list, (const MjhProgCtl *)ctl, qv,
-                                 nzmask, tabs, spi, pe, 0);
-  else hipLaunchKernelGGL((k_pp_stats<false, 0>), gchunks, dim3(256), 0, s, C, (const MjhProgScan *)sv, list, (const MjhProgCtl *)ctl, qv,
+  } else hipLaunchKernelGGL((k_pp_stats<false, 0>), gchunks, dim3(256), 0, s, C, (const MjhProgScan *)sv, list, (const MjhProgCtl *)ctl, qv,
                           nzmask, tabs, spi, pe, 0);
   if (any_refine) {   // prefix sums of the trailing correction bits: only refinement scans have any, and they sit behind the first-pass AC scans
     const size_t po = nzmask ? (size_t)nacf * n : 0;
@@ -2271,13 +2248,13 @@ void mjh_launch_prog_encode(const MjhConst &C, const void *scans, const int *lis
   }
   if (npar > 0) {
     const dim3 gchunks(pe.chunks_per_scan, npar, n), gpairs(npar, n);
-    const bool splitk = nzmask != nullptr;       // compact records: one kernel per kind of scan
     const MjhProgScan *sv = (const MjhProgScan *)scans; const MjhProgCtl *cv = (const MjhProgCtl *)ctl; const int16_t *qv = (const int16_t *)q;
     const MjhHuffTable *tv = (const MjhHuffTable *)tabs;
-    const dim3 gacf(pe.chunks_per_scan, nacf, n), goth(pe.chunks_per_scan, npar - nacf, n);   // the list starts with its nacf first-pass AC scans
-    if (splitk) {
-      // first-pass AC scans (the list starts with them): k_pp_chunk_bits + k_pp_emit; the other scans: sizes, prefix sums, bits
-      const size_t po = (size_t)nacf * n;      // their pairs come first
+    if (nzmask) {
+      // compact records: one kernel per kind of scan.  First-pass AC scans (the list starts with its nacf of them, their pairs come
+      // first): k_pp_chunk_bits + k_pp_emit; the other scans: sizes, prefix sums, bits
+      const dim3 gacf(pe.chunks_per_scan, nacf, n), goth(pe.chunks_per_scan, npar - nacf, n);
+      const size_t po = (size_t)nacf * n;
       if (nacf > 0) {
         hipLaunchKernelGGL(k_pp_chunk_bits, dim3(nacf, n), dim3(256), 0, ps, C, sv, par_list, cv, tv, spi, pe);
         hipLaunchKernelGGL(k_pp_emit, gacf, dim3(256), 0, ps, C, sv, par_list, cv, qv, nzmask, tv, spi, pool, pool_words, pe);
@@ -2289,18 +2266,16 @@ void mjh_launch_prog_encode(const MjhConst &C, const void *scans, const int *lis
         hipLaunchKernelGGL((k_pp_write<true, 2>), goth, dim3(256), 0, ps, C, sv, par_list, cv, qv, nzmask, tv, spi, pool, pool_words, pe, nacf);
       }
     } else {
-      if (nzmask) hipLaunchKernelGGL((k_pp_len<true, 0>), gchunks, dim3(256), 0, ps, C, sv, par_list, cv, qv, nzmask, tv, spi, pe, 0);
-      else hipLaunchKernelGGL((k_pp_len<false, 0>), gchunks, dim3(256), 0, ps, C, sv, par_list, cv, qv, nzmask, tv, spi, pe, 0);
+      hipLaunchKernelGGL((k_pp_len<false, 0>), gchunks, dim3(256), 0, ps, C, sv, par_list, cv, qv, nzmask, tv, spi, pe, 0);
       mjh_launch_scan16(pe.len16, pe.nblk_pad, pe.sums, pe.chunks_per_scan, pe.totals, pe.off32, npar * n, ps);
-      if (nzmask) hipLaunchKernelGGL((k_pp_write<true, 0>), gchunks, dim3(256), 0, ps, C, sv, par_list, cv, qv, nzmask, tv, spi, pool, pool_words, pe, 0);
-      else hipLaunchKernelGGL((k_pp_write<false, 0>), gchunks, dim3(256), 0, ps, C, sv, par_list, cv, qv, nzmask, tv, spi, pool, pool_words, pe, 0);
+      hipLaunchKernelGGL((k_pp_write<false, 0>), gchunks, dim3(256), 0, ps, C, sv, par_list, cv, qv, nzmask, tv, spi, pool, pool_words, pe, 0);
     }
     hipLaunchKernelGGL(k_pp_finish, gpairs, dim3(64), 0, ps, (const MjhProgScan *)scans, par_list, (MjhProgCtl *)ctl, (const MjhHuffTable *)tabs, spi,
                        pool, pool_words, pe);
   }
   if (both) (void)hipEventRecord(ev_join, side);
   if (nseq > 0)     // scans with restart intervals: the sequential walk
-    hipLaunchKernelGGL((k_prog_scan<1>), dim3(n, nseq), dim3(64 * PROG_WAVES(1)), 0, s, C, (const MjhProgScan *)scans, seq_list, (MjhProgCtl *)ctl,
+    hipLaunchKernelGGL((k_prog_scan<1>), dim3(n, nseq), dim3(64 * PROG_WAVES), 0, s, C, (const MjhProgScan *)scans, seq_list, (MjhProgCtl *)ctl,
                        (const int16_t *)q, tabs, spi, pool, pool_words, mpos, mpos_per_image, (const MjhProgPair *)nullptr);
   if (both) (void)hipStreamWaitEvent(s, ev_join, 0);
   hipLaunchKernelGGL((k_prog_stuff<false>), dim3(PROG_STUFF_SPLIT, nlist, n), dim3(256), 0, s, (const MjhProgScan *)scans, list, (MjhProgCtl *)ctl, (const unsigned *)pool,
