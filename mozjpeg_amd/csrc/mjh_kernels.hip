@@ -512,7 +512,7 @@ __device__ __forceinline__ void dct_quant_body(const MjhConst &C, const MjhQuant
   if (set * 64 >= cc.nblk) break;                        // uniform
   load_rows(set, rows_cur);
   const int blk_raw = set * 64 + lane;
-  const bool valid = blk_raw < cc.nblk;                  // tail lanes redo the last block (identical stores), they only stay out of the statistics
+  const bool valid = blk_raw < cc.nblk;                  // tail lanes redo the last block: identical stores without STATS, none with it (below)
   const int blk = valid ? blk_raw : cc.nblk - 1;
   int d[64];
   unsigned ff = 0;     // 8-bit samples: some byte of the block is 255 (the only value that reaches maxsample after the level shift)
@@ -613,7 +613,10 @@ __device__ __forceinline__ void dct_quant_body(const MjhConst &C, const MjhQuant
   int du[IFAST ? 64 : 1];
   if (IFAST && !W12) aan_unscale_all(d, du);      // (12-bit samples have no trellis: nothing reads the copy)
 
-  float lambda_blk = 0.0f;
+  // STATS: the lanes beyond cc.nblk leave here, once per set (they redid the last block up to this point and own nothing below:
+  // no store, no statistics); tested at every one of the 63 positions instead, the predicate cost each an exec save and a branch.
+  // The others keep their tail lanes' identical stores of the last block: one set per wave, nothing to save.
+  if (!STATS || valid) {
   if (!W12 && C.trellis) {
     // per-block trellis lambda (jcdctmgr.c:1027-1037): norm of the 63 AC coefficients summed in
     // NATURAL index order in float, /63 in double, then lambda in double -> float.  pow(2, .) comes
@@ -626,12 +629,17 @@ __device__ __forceinline__ void dct_quant_body(const MjhConst &C, const MjhQuant
     if (C.lambda_log_scale2 > 0.0f) lambda = (float)(C.pow_scale1 * 1.0 / (C.pow_scale2 + (double)norm));
     else lambda = (float)(C.pow_scale1 * 1.0);
     lambda_out[(size_t)img * C.total_real_blocks + cc.blk_off + blk] = lambda;
-    lambda_blk = lambda;
   }
   int16_t *uq = coef_uq + (size_t)img * C.coefs_per_image + cc.coef_off + blk;
   int16_t *qo = coef_q + (size_t)img * C.coefs_per_image + cc.coef_off + blk;
   const bool clampq = C.deringing != 0;
-  int run = 0, nzc = 0;   // nzc: non-zero quantized AC coefficients = the AC trellis' queue length (its tile-sort key)
+  // nzc: non-zero quantized AC coefficients = the AC trellis' queue length (its tile-sort key).  prevnz: zig-zag position of the
+  // last of them (0: none yet).  The zero run in front of a non-zero at k is k - 1 - prevnz, computed where one is counted: a
+  // position that quantizes to zero issues nothing for the run (a counter kept in the else arm cost every position 3 VALU and 5
+  // scalar instructions of exec bookkeeping), and "the block ends in zeros" is prevnz < 63.
+  int prevnz = 0, nzc = 0;
+  // the post-clamp to +-1023 (jcdctmgr.c:761-770) is applied to the category: bitlen(min(qa, 1023)) == min(bitlen(qa), 10)
+  const int nbmax = clampq ? 10 : 15;     // (wave-uniform; unclamped, no block of 8-bit samples quantizes beyond 13 bits)
   // The quantizer's constants are wave-uniform (scalar loads).  Fetched where they are used -- inside the per-position branches --
   // every position paid two scalar-memory round trips (s_waitcnt lgkmcnt(0) on 8q, then on the divider pair) that two waves per
   // SIMD cannot hide; they are fetched for QCH positions at a time, unconditionally: one round trip per QCH positions.
@@ -657,17 +665,15 @@ __device__ __forceinline__ void dct_quant_body(const MjhConst &C, const MjhQuant
       // "Quantizes to non-zero" (|x| + 4q >= 8q) is one conversion + one compare of |(float)x| with MjhQuant.thr8 (exact: both
       // are integers below 2^24); |x| as an integer only where the division happens
       uq[(size_t)k * cc.kstride] = (int16_t)x;
-      if (valid) {
-        const float xf = (float)x;
-        if (__builtin_fabsf(xf) >= thr_c[k % QCH]) {
-          const int ax = (int)__builtin_fabsf(xf);
-          int qa = udiv_mh(ax + (dq >> 1), sdiv_c[k % QCH], mdiv_c[k % QCH]);
-          if (clampq) qa = min(qa, 1023);
-          nzc++;
-          if (run > 15) { atomicAdd(&hh[0xF0 * NCOPY], (unsigned)(run >> 4)); run &= 15; }
-          atomicAdd(&hh[((run << 4) + bitlen((unsigned)qa)) * NCOPY], 1u);
-          run = 0;
-        } else run++;
+      const float xf = (float)x;
+      if (__builtin_fabsf(xf) >= thr_c[k % QCH]) {
+        const int ax = (int)__builtin_fabsf(xf);
+        const int qa = udiv_mh(ax + (dq >> 1), sdiv_c[k % QCH], mdiv_c[k % QCH]);
+        int run = k - 1 - prevnz;
+        prevnz = k;
+        nzc++;
+        if (k > 16 && run > 15) { atomicAdd(&hh[0xF0 * NCOPY], (unsigned)(run >> 4)); run &= 15; }   // (k <= 16: no room for 16 zeros)
+        atomicAdd(&hh[((run << 4) + min(bitlen((unsigned)qa), nbmax)) * NCOPY], 1u);
       }
       continue;
     }
@@ -678,19 +684,18 @@ __device__ __forceinline__ void dct_quant_body(const MjhConst &C, const MjhQuant
     if (!W12) uq[(size_t)k * cc.kstride] = (int16_t)(IFAST ? du[IFAST ? kZZ.v[k] : 0] : x);   // raw x8 coefficients only feed the (8-bit only) trellis
     if (k == 0 || !STATS) qo[(size_t)k * cc.kstride] = (int16_t)v;   // STATS: the AC planes would never be read
     if (!stats && !W12 && k > 0) nzc += (v != 0);
-    if (stats && k > 0 && valid) {
-      if (v == 0) run++;
-      else {
-        nzc++;
-        if (run > 15) { atomicAdd(&hh[0xF0 * NCOPY], (unsigned)(run >> 4)); run &= 15; }
-        const int nb = bitlen((unsigned)(v < 0 ? -v : v));
-        atomicAdd(&hh[((run << 4) + nb) * NCOPY], 1u);
-        run = 0;
-      }
+    if (stats && k > 0 && v != 0) {
+      int run = k - 1 - prevnz;
+      prevnz = k;
+      nzc++;
+      if (k > 16 && run > 15) { atomicAdd(&hh[0xF0 * NCOPY], (unsigned)(run >> 4)); run &= 15; }
+      const int nb = bitlen((unsigned)(v < 0 ? -v : v));
+      atomicAdd(&hh[((run << 4) + nb) * NCOPY], 1u);
     }
   }
   if (!W12 && nq8_out && valid) nq8_out[(size_t)img * C.total_real_blocks + cc.blk_off + blk] = (uint8_t)nzc;
-  if (stats && valid && run > 0) atomicAdd(&hh[0], 1u);
+  if (stats && prevnz < 63) atomicAdd(&hh[0], 1u);      // end of block
+  }   // (valid)
   }   // (sets of this wave)
   if (stats) {
     __syncthreads();
