@@ -173,6 +173,11 @@ typedef struct {
                               * jccolor.c:479 via jinit_color_converter :687-692): unconverted like MJH_COLOR_NONE, but the file is an
                               * ordinary YCbCr one -- JFIF APP0, no Adobe marker, YCbCr's progressive scripts; with num_components = 1 the Y
                               * samples become a grayscale file (grayscale_convert :448-466) */
+/* Four-component files are decoded, not written: these two values come from mjh_params_from_jpeg on a CMYK / YCCK file alone and
+ * name the colour kind an encoder made from such parameters owns for its mjh_decode_host calls (num_components 4,
+ * input_components 4).  Every call that would write a file on such an encoder is MJH_EUNSUPPORTED. */
+#define MJH_COLOR_CMYK 3     /* JCS_CMYK: the four components as they are (null_convert jdcolor.c) */
+#define MJH_COLOR_YCCK 4     /* JCS_YCCK: Y, Cb, Cr to inverted R, G, B = C, M, Y; K as it is (ycck_cmyk_convert jdcolor.c:543-587) */
 
 typedef struct mjh_encoder mjh_encoder;
 
@@ -321,11 +326,20 @@ int mjh_encoder_sync(mjh_encoder *e);
  * Accepted: Huffman-coded sequential DCT files (SOF0, SOF1), 8-bit, 1 or 3 components, one interleaved scan or several
  * scans (every component in exactly one), any restart intervals.  MJH_EUNSUPPORTED: progressive (unless asked for, see
  * mjh_encoder_set_sources below), arithmetic, lossless (decoded to samples when asked for, MJH_SRC_LOSSLESS below; never re-compressed),
- * 12-bit, 2 or 4 components, DNL.  COM / APPn markers are not copied (-copy none). */
+ * 12-bit, 2 components, DNL.  COM / APPn markers are not copied (-copy none).
+ * Four components (Adobe-style CMYK and YCCK files) are read by the marker walk and DECODED (mjh_decode_host: pixels, planes,
+ * coefficients), never written: mjh_params_from_jpeg gives parameters an encoder can be created from (color_transform
+ * MJH_COLOR_CMYK / MJH_COLOR_YCCK), and mjh_transcode_host, mjh_encoder_set_transform and every mjh_encode_* call on such an
+ * encoder is MJH_EUNSUPPORTED.  The colour space is guessed as default_decompress_parms does (jdapimin.c:130-205): an Adobe
+ * APP14 marker with transform 0 or no Adobe marker is CMYK, transform 2 is YCCK; any other transform, which the reference only
+ * warns about (JWRN_ADOBE_XFORM), is MJH_EUNSUPPORTED naming the code.  Still refused for four components: lossless files,
+ * and an interleaved scan whose MCU exceeds 10 blocks (MJH_EINVAL, JERR_BAD_MCU_SIZE). */
 #define MJH_MAX_FILE_SCANS 4
 #define MJH_CS_GRAYSCALE 1   /* J_COLOR_SPACE values (jpeglib.h:232-234) */
 #define MJH_CS_RGB       2
 #define MJH_CS_YCbCr     3
+#define MJH_CS_CMYK      4   /* a four-component file; as out_color_space, the one output of four-component files */
+#define MJH_CS_YCCK      5   /* a four-component file with Adobe transform 2 (never an output) */
 #define MJH_CS_RGB565    16  /* JCS_RGB565: an output of mjh_decode_host only */
 typedef struct {
   int comps_in_scan;
@@ -361,8 +375,8 @@ int mjh_jpeg_probe(const void *jpeg, size_t size, mjh_jpeg_info *info);
 /* ---- progressive source files (SOF2, Huffman-coded), opt-in ----
  * With nothing set every entry point refuses a progressive file as the list above says.  mjh_jpeg_probe_ex with
  * MJH_SRC_PROGRESSIVE in `accept`, and the calls of an encoder that mjh_encoder_set_sources(e, MJH_SRC_PROGRESSIVE) was called on
- * (mjh_transcode_host, mjh_decode_host with and without raw_coefs), accept 8-bit SOF2 files of 1 or 3 components; SOF9 / SOF10,
- * 12-bit, lossless, four components and DNL stay refused in the same words.
+ * (mjh_transcode_host, mjh_decode_host with and without raw_coefs), accept 8-bit SOF2 files of 1, 3 or (mjh_decode_host only) 4
+ * components; SOF9 / SOF10, 12-bit, lossless, two components and DNL stay refused in the same words.
  * A progressive file has more scans than mjh_jpeg_info holds: info->sof_type is 2, info->num_scans is 0 and the scans go to
  * scans[0 .. *num_scans), each with its spectral selection (Ss, Se), its successive approximation (Ah, Al) and the Huffman tables
  * and restart interval in force at its SOS (DHT and DRI between scans are normal in these files).  More than
@@ -427,7 +441,11 @@ int mjh_decode_prog_stats(mjh_encoder *e, int *levels, float *ms);
  * (the max-compression profile: optimal tables, progressive with scan search), trellis_quant = 0, and the source's size,
  * colour space, precision, component ids, sampling factors, quantization-table numbers and tables -- not its Huffman tables,
  * scan script or restart interval.  Apply jpegtran's switches to *p afterwards (optimize_coding,
- * mjh_params_simple_progression, restart_interval, num_scans = 0 for a sequential file, ...). */
+ * mjh_params_simple_progression, restart_interval, num_scans = 0 for a sequential file, ...).
+ * A four-component file (jpeg_color_space MJH_CS_CMYK / MJH_CS_YCCK) gives parameters for DECODING alone: num_components and
+ * input_components 4, color_transform MJH_COLOR_CMYK / MJH_COLOR_YCCK, the file's ids, factors and quantization tables, a
+ * sequential script in either profile.  mjh_encoder_create accepts them as they are (and four components made any other way
+ * are MJH_EUNSUPPORTED); the encoder serves mjh_decode_host, and every call that would write a file is MJH_EUNSUPPORTED. */
 int mjh_params_from_jpeg(const mjh_jpeg_info *info, int compress_profile, mjh_params *p);
 /* Re-codes n files with the encoder's parameters, which mjh_params_from_jpeg made (trellis_quant must be 0).  Every file has
  * to agree with the encoder in everything mjh_params_from_jpeg copies (else MJH_EINVAL naming the file and the field) and
@@ -508,7 +526,13 @@ int mjh_encoder_set_transform(mjh_encoder *e, const mjh_transform *t);
  * (0 = 3), the byte of R, G and B inside it (all 0 = 0, 1, 2); the fourth byte of a 4-byte pixel is 0xFF.  Gray pixels are
  * one byte.  fancy_upsampling: 1 = djpeg's default, 0 = -nosmooth.
  * MJH_CS_RGB565 (djpeg -rgb565, jdcol565.c): 16-bit pixels ((r << 8) & 0xF800) | ((g << 3) & 0x7E0) | (b >> 3), little-endian, of
- * any file RGB output is made of.  pixel_size is 0 or 2, rgb_offset all 0 (mjh_decode_opts_defaults sets 0, 1, 2).  no_dither 0: the reference's ordered dither
+ * any file RGB output is made of.
+ * Four-component files (CMYK, YCCK): out_color_space 0 resolves to MJH_CS_CMYK, which may also be named; pixel_size is 0 or 4
+ * and rgb_offset is ignored.  The pixels are four bytes C, M, Y, K: a CMYK file's samples as they are (Adobe's inverted samples
+ * stay inverted, null_convert), a YCCK file's through ycck_cmyk_convert.  Gray, RGB and RGB565 output of such a file, and
+ * MJH_CS_CMYK of a file of one or three components, are MJH_EUNSUPPORTED ("Unsupported color conversion request",
+ * JERR_CONVERSION_NOTIMPL).  raw_planes gives four planes, raw_coefs four arrays.  CMYK and YCCK files do not share a call.
+ * RGB565: pixel_size is 0 or 2, rgb_offset all 0 (mjh_decode_opts_defaults sets 0, 1, 2).  no_dither 0: the reference's ordered dither
  * (dither_mode other than JDITHER_NONE, djpeg's default), added in front of the range limit -- byte x & 3 of
  * dither_matrix[y & 3] (jdcolor.c:619) to red and blue, half of it to green, (x, y) the pixel's place in the (scaled) image:
  * what the reference gives a client that reads one row per jpeg_read_scanlines call into 4-byte aligned rows, as djpeg does

@@ -18,6 +18,7 @@ PROFILE_MAX_COMPRESSION = 0x5D083AAD
 PROFILE_FASTEST = 0x2AEA5CB4
 COLOR_YCC, COLOR_NONE, COLOR_YCC_IN = 0, 1, 2
 CS_GRAYSCALE, CS_RGB, CS_YCBCR = 1, 2, 3      # JpegInfo.jpeg_color_space
+CS_CMYK, CS_YCCK = 4, 5                       # four-component files (Adobe-style); CS_CMYK is also their one out_color_space
 CS_RGB565 = 16                                # JCS_RGB565: DecodeOpts.out_color_space only
 OK, EINVAL, EUNSUPPORTED, EHIP, ENOMEM, ETOOSMALL = 0, -1, -2, -3, -4, -5
 TAP_PLANE, TAP_COEF_UQ, TAP_COEF_Q, TAP_COEF_Q0, TAP_HUFF_BITS, TAP_HUFF_VALS, TAP_PROG_SCAN_US, TAP_LL_COUNTS = 1, 2, 3, 4, 5, 6, 7, 8
@@ -348,7 +349,9 @@ def _src_accept(progressive_sources, lossless_sources):
 def jpeg_info(data, progressive_sources=False, lossless_sources=False):
     """The marker segments of a JPEG file (mjh_jpeg_probe): frame, tables, colour space, JFIF / Adobe fields, and per scan its
     components, Huffman tables, restart interval and the byte range of its entropy-coded data.  Raises MjhError (EUNSUPPORTED:
-    progressive, arithmetic, lossless, 12-bit, 4 components; EINVAL: malformed).
+    progressive, arithmetic, lossless, 12-bit, 2 components, a four-component file with an Adobe transform other than 0 or 2;
+    EINVAL: malformed).  jpeg_color_space is one of CS_GRAYSCALE, CS_RGB, CS_YCBCR and, for the four-component files that
+    decode() reads and nothing writes, CS_CMYK (Adobe transform 0, or no Adobe marker) and CS_YCCK (Adobe transform 2).
     progressive_sources=True (mjh_jpeg_probe_ex with MJH_SRC_PROGRESSIVE): a Huffman-coded progressive file is accepted; its
     JpegInfo has sof_type 2 and num_scans 0, and its scans are the list `prog_scans` of JpegScanEx (empty for a sequential file).
     lossless_sources=True (MJH_SRC_LOSSLESS): a Huffman-coded lossless file of 8, 12 or 16 bits is accepted; its JpegInfo has
@@ -426,7 +429,8 @@ def params_from_jpeg(data, *, revert=False, optimize=False, progressive=None, fa
 
 
 def _signature(info):
-    """what the files of one mjh_transcode_host batch have in common (everything mjh_params_from_jpeg copies)"""
+    """what the files of one mjh_transcode_host batch have in common (everything mjh_params_from_jpeg copies; the colour space
+    tells a CMYK file from a YCCK one of the same frame)"""
     nc = info.num_components
     used = sorted(set(info.quant_tbl_no[c] for c in range(nc)))
     return (info.image_width, info.image_height, nc, info.jpeg_color_space, info.sof_type == 3, info.data_precision,
@@ -491,7 +495,12 @@ def recompress(files, *, max_batch=64, device=0, progressive_sources=False, loss
                 continue
         for o in range(0, len(idx), enc.max_batch):
             part = idx[o:o + enc.max_batch]
-            res = enc.transcode_host([files[i] for i in part], errors="return")
+            try:
+                res = enc.transcode_host([files[i] for i in part], errors="return")
+            except MjhError as exc:         # four components: decoded, not written (the encoder refuses the call as a whole)
+                if info.num_components != 4 or exc.code != EUNSUPPORTED:
+                    raise
+                res = [exc] * len(part)
             bad = [k for k, r in enumerate(res) if isinstance(r, MjhError)]
             if bad and len(bad) < len(part):           # the good files of the batch once more, without the damaged ones
                 good = [k for k in range(len(part)) if k not in bad]
@@ -549,8 +558,10 @@ DCT_METHODS = {None: 0, "int": 0, "islow": 0, "fast": 1, "ifast": 1}     # djpeg
 
 def decode_opts(color=None, layout=None, pixel_size=0, rgb_offset=None, fancy_upsampling=True, scale=None, dct=None, bottom_up=False,
                 raw_planes=False, dither=True, raw_coefs=False):
-    """DecodeOpts from djpeg's vocabulary.  color: None (the file's default: gray stays gray, everything else RGB), "gray" /
-    "grayscale" (-grayscale), "rgb" (-rgb), "rgb565" (-rgb565: 16-bit pixels, with dither=False -dither none) or a CS_* number; layout: a name out of PIXEL_LAYOUTS, or pixel_size and rgb_offset;
+    """DecodeOpts from djpeg's vocabulary.  color: None (the file's default: gray stays gray, a CMYK or YCCK file gives CMYK,
+    everything else RGB), "gray" / "grayscale" (-grayscale), "rgb" (-rgb), "rgb565" (-rgb565: 16-bit pixels, with dither=False
+    -dither none), "cmyk" (the one output of four-component files: [H, W, 4], C, M, Y, K; pixel_size 0 or 4, rgb_offset is
+    ignored) or a CS_* number; layout: a name out of PIXEL_LAYOUTS, or pixel_size and rgb_offset;
     fancy_upsampling=False: -nosmooth; scale: -scale, a pair (num, denom) or a string "M/N" that resolves to 1/8, 2/8, 4/8 or
     8/8 as djpeg resolves it (scale_idct_size); dct: "int" (the default) or "fast" (-dct fast, TurboJPEG's FASTDCT);
     bottom_up=True: the rows last to first (TurboJPEG's BOTTOMUP); raw_planes=True: no pixels, the sample planes (decode_planes);
@@ -558,9 +569,9 @@ def decode_opts(color=None, layout=None, pixel_size=0, rgb_offset=None, fancy_up
     o = DecodeOpts()
     lib().mjh_decode_opts_defaults(C.byref(o))
     if isinstance(color, str):
-        names = {"gray": CS_GRAYSCALE, "grayscale": CS_GRAYSCALE, "rgb": CS_RGB, "rgb565": CS_RGB565}
+        names = {"gray": CS_GRAYSCALE, "grayscale": CS_GRAYSCALE, "rgb": CS_RGB, "rgb565": CS_RGB565, "cmyk": CS_CMYK}
         if color not in names:
-            raise MjhError(EINVAL, "color %r (None, 'gray', 'rgb' or 'rgb565')" % (color,))
+            raise MjhError(EINVAL, "color %r (None, 'gray', 'rgb', 'rgb565' or 'cmyk')" % (color,))
         o.out_color_space = names[color]
     elif color is not None:
         o.out_color_space = int(color)
@@ -588,8 +599,12 @@ def decode_opts(color=None, layout=None, pixel_size=0, rgb_offset=None, fancy_up
     # the library's own checks (plan_pixels), made here as well so that decode() can refuse its options before it groups files
     if o.dct_method not in (0, 1):
         raise MjhError(EINVAL, "dct_method %d of a decode call (0 = JDCT_ISLOW, 1 = JDCT_IFAST)" % o.dct_method)
-    if o.out_color_space not in (0, CS_GRAYSCALE, CS_RGB, CS_RGB565):
-        raise MjhError(EINVAL, "out_color_space %d (0, CS_GRAYSCALE, CS_RGB or CS_RGB565)" % o.out_color_space)
+    if o.out_color_space not in (0, CS_GRAYSCALE, CS_RGB, CS_RGB565, CS_CMYK):
+        raise MjhError(EINVAL, "out_color_space %d (0, CS_GRAYSCALE, CS_RGB, CS_RGB565 or CS_CMYK)" % o.out_color_space)
+    if o.out_color_space == CS_CMYK:
+        if o.pixel_size not in (0, 4):
+            raise MjhError(EINVAL, "pixel_size %d of CMYK output (0 or 4)" % o.pixel_size)
+        return o
     if o.out_color_space == CS_RGB565:
         if o.pixel_size not in (0, 2):
             raise MjhError(EINVAL, "pixel_size %d of RGB565 output (0 or 2)" % o.pixel_size)
@@ -614,7 +629,10 @@ _decode_encoders = {}
 
 def decode(files, *, max_batch=64, device=0, progressive_sources=False, lossless_sources=False, **opts):
     """Decode JPEG files to pixels on the GPU: the bytes `djpeg` (+ -grayscale / -rgb / -nosmooth / -scale / -dct fast, see
-    decode_opts) writes for each of them, as numpy arrays [H, W, C] ([H, W] for gray) in input order; with scale=,
+    decode_opts) writes for each of them, as numpy arrays [H, W, C] ([H, W] for gray) in input order.  A four-component file
+    (Adobe-style CMYK or YCCK) gives [H, W, 4], C, M, Y, K -- what tj3Decompress8 gives for TJPF_CMYK, a CMYK file's samples as
+    they are, a YCCK file's converted; any other color= for it, and color="cmyk" for any other file, is EUNSUPPORTED
+    ("Unsupported color conversion request") in that file's slot.  With scale=,
     [ceil(H k / 8), ceil(W k / 8), C]; with bottom_up=True, the rows last to first.
     The files are grouped by what a batch must have in common, which the scale is not part of; one encoder per group is kept for
     later calls.  A file that cannot be decoded (unsupported type, malformed headers,
@@ -690,8 +708,12 @@ def _decode_grouped(files, max_batch, device, o, progressive_sources=False, loss
             part = idx[a:a + enc.max_batch]
             try:
                 res = enc.decode_host([files[i] for i in part], errors="return", opts=o)
-            except MjhError as exc:         # options djpeg refuses for a lossless file (a colour conversion, planes, coefficients)
-                if info.sof_type != 3 or exc.code != EUNSUPPORTED:
+            except MjhError as exc:         # options djpeg refuses for a lossless file (a colour conversion, planes, coefficients),
+                # and a colour conversion the reference has none of (CMYK from or to anything else): this group's files alone
+                pixels = not (o.raw_planes or o.raw_coefs)
+                four = info.num_components == 4
+                no_conversion = pixels and (o.out_color_space not in (0, CS_CMYK) if four else o.out_color_space == CS_CMYK)
+                if exc.code != EUNSUPPORTED or not (info.sof_type == 3 or no_conversion):
                     raise
                 res = [exc] * len(part)
             bad = [k for k, r in enumerate(res) if isinstance(r, MjhError)]

@@ -13,6 +13,10 @@
  * reference's padded dimensions and hold the reference's real blocks; their PADDING blocks are zero, where the reference keeps
  * whatever an interleaved scan coded for its dummy blocks (jpeg_write_coefficients and transupp.c read real blocks only).
  *
+ * Four-component files (Adobe-style CMYK and YCCK) are served like any other: out_color_space JCS_CMYK, which jpeg_read_header leaves
+ * for them, gives four output components (null_convert / ycck_cmyk_convert on the device); every other output of them, and JCS_CMYK
+ * of any other file, is JERR_CONVERSION_NOTIMPL as in the reference.
+ *
  * Not built (JERR_NOT_COMPILED with one line on stderr): suspension (a source that returns FALSE: JERR_CANT_SUSPEND), buffered-image
  * mode, colour quantization, the float IDCT, IDCT sizes other than 1, 2, 4, 8, cropping / skipping scanlines,
  * and every source mjh_jpeg_probe refuses.  Damaged entropy-coded data is FATAL at jpeg_start_decompress (the reference warns and
@@ -868,7 +872,7 @@ int jpeg_read_header(j_decompress_ptr cinfo, boolean require_image)
   if (cinfo->arith_code) refuse(cinfo, "arithmetic-coded JPEG files are not decoded on the GPU path (no CPU fallback)");
   if (cinfo->master->lossless) refuse(cinfo, "lossless JPEG files are not decoded on the GPU path (no CPU fallback)");
   if (cinfo->data_precision != 8) refuse(cinfo, "12-bit JPEG files are not decoded on the GPU path (no CPU fallback)");
-  if (cinfo->num_components != 1 && cinfo->num_components != 3) refuse(cinfo, "JPEG files of 2 or 4 components are not decoded on the GPU path (no CPU fallback)");
+  if (cinfo->num_components != 1 && cinfo->num_components != 3 && cinfo->num_components != 4) refuse(cinfo, "JPEG files of 2 components are not decoded on the GPU path (no CPU fallback)");
   return JPEG_HEADER_OK;
 }
 
@@ -1138,6 +1142,11 @@ boolean jpeg_start_decompress(j_decompress_ptr cinfo)
     for (ci = 0; ci < cinfo->num_components; ci++)
       if (cinfo->comp_info[ci].DCT_scaled_size != k) refuse(cinfo, "raw_data_out with a scale at which the components are transformed at different sizes is not built on the GPU path");
     o.raw_planes = 1;
+  } else if (cinfo->num_components == 4 || cinfo->out_color_space == JCS_CMYK) {
+    /* jinit_color_deconverter jdcolor.c:901-918: CMYK from a CMYK file (null_convert) or a YCCK file (ycck_cmyk_convert), and
+     * nothing else from either; JCS_CMYK from no other file (djpeg's writers turn the four samples into RGB, wrppm.c cmyk_to_rgb) */
+    if (cinfo->out_color_space != JCS_CMYK || (cinfo->jpeg_color_space != JCS_CMYK && cinfo->jpeg_color_space != JCS_YCCK)) ERREXIT(cinfo, JERR_CONVERSION_NOTIMPL);
+    o.out_color_space = MJH_CS_CMYK; px = 4; o.pixel_size = 4;
   } else if (cinfo->out_color_space == JCS_GRAYSCALE) {
     if (cinfo->jpeg_color_space != JCS_GRAYSCALE && cinfo->jpeg_color_space != JCS_YCbCr && cinfo->jpeg_color_space != JCS_RGB) ERREXIT(cinfo, JERR_CONVERSION_NOTIMPL);
     o.out_color_space = MJH_CS_GRAYSCALE; px = 1;
@@ -1149,7 +1158,7 @@ boolean jpeg_start_decompress(j_decompress_ptr cinfo)
     o.out_color_space = MJH_CS_RGB; o.pixel_size = px;
     o.rgb_offset[0] = off[0]; o.rgb_offset[1] = off[1]; o.rgb_offset[2] = off[2];
   } else
-    ERREXIT(cinfo, JERR_CONVERSION_NOTIMPL);              /* JCS_YCbCr, JCS_CMYK, JCS_YCCK */
+    ERREXIT(cinfo, JERR_CONVERSION_NOTIMPL);              /* JCS_YCbCr, JCS_YCCK */
   decode_file(cinfo, &o);
   if (d_timing) t0 = d_now();
   if (cinfo->raw_data_out) {

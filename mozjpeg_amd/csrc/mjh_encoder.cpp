@@ -257,6 +257,14 @@ extern "C" int mjh_params_search_progression(mjh_params *p)
 enum { SLOTS_BASE = 16, SLOT_FINAL = 8, SLOT_PROG = 16 };   // 0..7: per-component trellis-pass tables (DC,AC); 8..15: final DC t / AC t
 
 
+// the output buffer of a decode call, whatever kernel filled it: what mjh_get_pixels, mjh_get_pixels_device and mjh_decode_stats
+// read.  The plans of the colour kernels (MjhPixOut, MjhPixOut4) repeat these numbers for the device.
+struct DecOut {
+  int W = 0, H = 0;                       // of the (scaled) image
+  int px_size = 0;                        // bytes per pixel
+  long long row_pitch = 0, image_stride = 0;
+};
+
 struct mjh_encoder {
   mjh_params p;
   MjhConst C;
@@ -406,6 +414,7 @@ struct mjh_encoder {
   void *g_in[MJH_MAX_COMPS] = { nullptr, nullptr, nullptr, nullptr }; size_t g_in_bytes[MJH_MAX_COMPS] = { 0, 0, 0, 0 }; std::vector<void *> g_in_old;   // MJH_GUARD=2/3: fenced copies of the caller's device input
   // lossless mode (mjh_lossless.hip): histogram, bits and final bit offset of every work unit, bits in front of every restart segment
   bool lossless = false;
+  bool four = false;                    // made from the parameters of a CMYK / YCCK file: decode calls only (four_refusal)
   LlConst L{};
   unsigned *d_ll_hist = nullptr, *d_ll_len = nullptr, *d_ll_off = nullptr, *d_ll_segE = nullptr;
   int ll_sos_off[4] = { 0, 0, 0, 0 };   // scan k's SOS (the first with the DRI in front) is d_sos[ll_sos_off[k], ll_sos_off[k + 1])
@@ -438,7 +447,7 @@ struct mjh_encoder {
   // mjh_decode_host (mjh_idct.hip): the interleaved pixels of the last decoded batch (made at the first call, grown when a later
   // call asks for larger pixels), its layout, its status words on the host and the event behind everything it queued
   uint8_t *d_pixout = nullptr; size_t pixout_cap = 0;
-  MjhPixOut dp{};
+  DecOut dp{};
   unsigned *h_dstat = nullptr;
   hipEvent_t dp_ev[3] = { nullptr, nullptr, nullptr }, dp_done = nullptr; bool dp_timed = false;
   bool dp_waited = false;               // ... and has been waited for (the guard check runs once per batch)
@@ -458,6 +467,9 @@ struct mjh_encoder {
 };
 
 static long div_round_up(long a, long b) { return (a + b - 1) / b; }
+
+// what every call that would write a file answers on an encoder of four components
+static int four_refusal() { return fail(MJH_EUNSUPPORTED, "four-component files (CMYK, YCCK) are decoded, not written: this encoder serves mjh_decode_host only"); }
 
 // the AA&N scale factors of every position (natural order) scaled up by 14 bits: aanscales of jcdctmgr.c:291-345 and jddctmgr.c:284-316
 static const int kAanScales[64] = { 16384, 22725, 21407, 19266, 16384, 12873, 8867, 4520, 22725, 31521, 29692, 26722, 22725, 17855, 12299, 6270,
@@ -528,10 +540,26 @@ static int check_supported(const mjh_params *p)
   if (!(p->trellis_delta_dc_weight == p->trellis_delta_dc_weight)) return fail(MJH_EINVAL, "trellis_delta_dc_weight is not a number");
   if (p->data_precision == 12 && p->trellis_quant)
     return fail(MJH_EUNSUPPORTED, "trellis quantization is 8-bit only in the reference (jccoefct.c:132-138: 12-bit + trellis aborts)");
-  if (p->input_components != 1 && p->input_components != 3) return fail(MJH_EUNSUPPORTED, "input_components %d (RGB or gray only)", p->input_components);
-  if (p->num_components != 1 && p->num_components != 3) return fail(MJH_EUNSUPPORTED, "num_components %d", p->num_components);
+  // Four components: the parameters mjh_params_from_jpeg gives for a CMYK / YCCK file and nothing else -- an encoder that owns the
+  // geometry and the tables of decode calls and writes no file (every call that would is refused: four_refusal)
+  const bool four = p->num_components == 4 && p->input_components == 4 && (p->color_transform == MJH_COLOR_CMYK || p->color_transform == MJH_COLOR_YCCK);
+  if (four) {
+    if (p->num_scans != 0 || p->arith_code || p->trellis_quant || (p->data_precision != 0 && p->data_precision != 8) || p->input_pixel_size != 4 || p->write_JFIF_header)
+      return fail(MJH_EUNSUPPORTED, "num_components 4: four-component files (CMYK, YCCK) are decoded, not written -- only the parameters mjh_params_from_jpeg makes of such a file create an encoder");
+    int maxh = 1, maxv = 1;
+    for (int i = 0; i < 4; i++) {
+      const int h = p->h_samp_factor[i], v = p->v_samp_factor[i];
+      if (h < 1 || h > 4 || v < 1 || v > 4) return fail(MJH_EINVAL, "sampling factors %dx%d of component %d (1..4, JERR_BAD_SAMPLING)", h, v, i);
+      maxh = h > maxh ? h : maxh; maxv = v > maxv ? v : maxv;
+    }
+    // (more than 10 blocks per MCU is legal for a file whose components have scans of their own; an interleaved scan is checked per file)
+    for (int i = 0; i < 4; i++)
+      if (maxh % p->h_samp_factor[i] || maxv % p->v_samp_factor[i]) return fail(MJH_EUNSUPPORTED, "fractional sampling ratio (JERR_FRACT_SAMPLE_NOTIMPL, jdsample.c:529)");
+  }
+  if (!four && p->input_components != 1 && p->input_components != 3) return fail(MJH_EUNSUPPORTED, "input_components %d (RGB or gray only)", p->input_components);
+  if (!four && p->num_components != 1 && p->num_components != 3) return fail(MJH_EUNSUPPORTED, "num_components %d", p->num_components);
   if (p->num_components == 3 && p->input_components != 3) return fail(MJH_EUNSUPPORTED, "gray input cannot produce 3 components");
-  if (p->color_transform != MJH_COLOR_YCC && p->color_transform != MJH_COLOR_NONE && p->color_transform != MJH_COLOR_YCC_IN) return fail(MJH_EINVAL, "color_transform %d", p->color_transform);
+  if (!four && p->color_transform != MJH_COLOR_YCC && p->color_transform != MJH_COLOR_NONE && p->color_transform != MJH_COLOR_YCC_IN) return fail(MJH_EINVAL, "color_transform %d", p->color_transform);
   if (p->color_transform == MJH_COLOR_NONE && p->num_components != 3) return fail(MJH_EUNSUPPORTED, "MJH_COLOR_NONE needs three components");
   if (p->color_transform == MJH_COLOR_YCC_IN && p->input_components != 3) return fail(MJH_EINVAL, "MJH_COLOR_YCC_IN needs three input samples per pixel");   // (one component out: grayscale_convert takes the Y samples, jccolor.c:448-466)
   if (p->num_components == 1) {
@@ -559,7 +587,9 @@ static int check_supported(const mjh_params *p)
       if (maxh % p->h_samp_factor[i] || maxv % p->v_samp_factor[i]) return fail(MJH_EUNSUPPORTED, "fractional sampling ratio (the reference: JERR_FRACT_SAMPLE_NOTIMPL, jcsample.c:531)");
     if (blocks > 10) return fail(MJH_EINVAL, "%d blocks per MCU (at most 10, jcmaster.c:540-544)", blocks);
   }
-  if (p->input_components == 3) {
+  if (four) {
+    // (four samples per pixel in, nothing to lay out: no pixels are ever read)
+  } else if (p->input_components == 3) {
     const int ps = p->input_pixel_size ? p->input_pixel_size : 3;
     if (ps != 3 && ps != 4) return fail(MJH_EINVAL, "input_pixel_size %d", ps);
     for (int i = 0; i < 3; i++) if (p->rgb_offset[i] < 0 || p->rgb_offset[i] >= ps) return fail(MJH_EINVAL, "rgb_offset out of range");
@@ -1065,6 +1095,7 @@ extern "C" int mjh_encoder_create(const mjh_params *p, int max_batch, int device
   mjh_encoder *e = new mjh_encoder();
   e->p = *p;
   e->p_created = *p;
+  e->four = p->num_components == 4;
   e->high_priority_streams = g_create_twin;
   if (p->num_components == 1 && (p->h_samp_factor[0] != 1 || p->v_samp_factor[0] != 1)) {   // (check_supported: only the SOF byte differs)
     e->sof_hv0 = (p->h_samp_factor[0] << 4) + p->v_samp_factor[0];
@@ -2187,6 +2218,7 @@ static int guard_input(mjh_encoder *e, int slot, const void **p, size_t bytes)
 
 extern "C" int mjh_encode_device(mjh_encoder *e, const void *d_pixels, size_t row_pitch, size_t image_stride, int n, void *stream)
 {
+  if (e && e->four) return four_refusal();
   if (!e || !d_pixels || n < 1 || n > e->max_batch) return fail(MJH_EINVAL, "bad arguments (n=%d, max_batch=%d)", n, e ? e->max_batch : 0);
   {
     const size_t row_bytes = (size_t)e->C.W * e->C.px_size * (e->C.precision > 8 ? 2 : 1);
@@ -2379,6 +2411,7 @@ static int queue_pack(mjh_encoder *e, int b, int n)
 
 extern "C" int mjh_encode_host(mjh_encoder *e, const void *pixels, size_t row_pitch, size_t image_stride, int n)
 {
+  if (e && e->four) return four_refusal();
   if (!e || !pixels || n < 1 || n > e->max_batch) return fail(MJH_EINVAL, "bad arguments");
   HIPCHK(hipSetDevice(e->device));
   const size_t row_bytes = (size_t)e->C.W * e->C.px_size * (e->C.precision > 8 ? 2 : 1);
@@ -2449,6 +2482,7 @@ extern "C" int mjh_encode_host(mjh_encoder *e, const void *pixels, size_t row_pi
 // encoders during the call (the libjpeg shim: their client threads are blocked in jpeg_finish_compress, waiting for this batch).
 extern "C" int mjh_encode_gather(mjh_encoder *e, mjh_encoder *const *members, int n)
 {
+  if (e && e->four) return four_refusal();
   if (!e || !members || n < 1 || n > e->max_batch) return fail(MJH_EINVAL, "bad arguments");
   HIPCHK(hipSetDevice(e->device));
   int rc = host_buffers(e);
@@ -2487,6 +2521,7 @@ extern "C" int mjh_encode_gather(mjh_encoder *e, mjh_encoder *const *members, in
 
 extern "C" int mjh_host_staging(mjh_encoder *e, void **buffer, size_t *bytes)
 {
+  if (e && e->four) return four_refusal();
   if (!e || !buffer) return fail(MJH_EINVAL, "bad arguments");
   HIPCHK(hipSetDevice(e->device));
   int rc = host_buffers(e);
@@ -2587,6 +2622,7 @@ static int check_coef_args(mjh_encoder *e, const void *const coefs[], const size
 extern "C" int mjh_encode_coefficients_device(mjh_encoder *e, const void *const d_coefs[MJH_MAX_COMPS], const size_t blocks_per_row[MJH_MAX_COMPS],
                                               const size_t image_stride[MJH_MAX_COMPS], int n, void *stream)
 {
+  if (e && e->four) return four_refusal();
   int rc = check_coef_args(e, d_coefs, blocks_per_row, n);
   if (rc) return rc;
   if (n > 1 && !image_stride) return fail(MJH_EINVAL, "image_stride is required for n > 1");
@@ -2606,6 +2642,7 @@ extern "C" int mjh_encode_coefficients_device(mjh_encoder *e, const void *const 
 extern "C" int mjh_encode_coefficients_host(mjh_encoder *e, const void *const coefs[MJH_MAX_COMPS], const size_t blocks_per_row[MJH_MAX_COMPS],
                                             const size_t image_stride[MJH_MAX_COMPS], int n)
 {
+  if (e && e->four) return four_refusal();
   int rc = check_coef_args(e, coefs, blocks_per_row, n);
   if (rc) return rc;
   if (n > 1 && !image_stride) return fail(MJH_EINVAL, "image_stride is required for n > 1");
@@ -2653,6 +2690,7 @@ extern "C" int mjh_encode_planes_device(mjh_encoder *e, const void *const d_plan
                                         const size_t image_stride[MJH_MAX_COMPS], const int plane_width[MJH_MAX_COMPS],
                                         const int plane_height[MJH_MAX_COMPS], int n, void *stream)
 {
+  if (e && e->four) return four_refusal();
   int rc = check_plane_args(e, d_planes, row_pitch, plane_width, plane_height, n);
   if (rc) return rc;
   if (n > 1 && !image_stride) return fail(MJH_EINVAL, "image_stride is required for n > 1");
@@ -2673,6 +2711,7 @@ extern "C" int mjh_encode_planes_host(mjh_encoder *e, const void *const planes[M
                                       const size_t image_stride[MJH_MAX_COMPS], const int plane_width[MJH_MAX_COMPS],
                                       const int plane_height[MJH_MAX_COMPS], int n)
 {
+  if (e && e->four) return four_refusal();
   int rc = check_plane_args(e, planes, row_pitch, plane_width, plane_height, n);
   if (rc) return rc;
   if (n > 1 && !image_stride) return fail(MJH_EINVAL, "image_stride is required for n > 1");
@@ -2749,6 +2788,7 @@ extern "C" int mjh_encoder_set_transform(mjh_encoder *e, const mjh_transform *t)
   if (!e) return fail(MJH_EINVAL, "null encoder");
   e->xf_on = false;
   if (!t) return MJH_OK;
+  if (e->four) return four_refusal();
   if (t->transform < MJH_XFORM_NONE || t->transform > MJH_XFORM_ROT_270) return fail(MJH_EINVAL, "transform %d (MJH_XFORM_NONE .. MJH_XFORM_ROT_270)", t->transform);
   e->xf_t = *t;
   e->xf_on = t->transform != MJH_XFORM_NONE || t->crop || t->grayscale;     // (anything else asks for nothing: today's path)
@@ -3278,6 +3318,10 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
 
 extern "C" int mjh_transcode_host(mjh_encoder *e, const void *const jpegs[], const size_t sizes[], int n)
 {
+  if (e && e->four) {
+    e->tc_n = 0; e->tc_code.clear(); e->tc_text.clear(); e->tc_queued = false; e->dp_queued = false;     // (as decode_front: the call's refusal, not a file's)
+    return four_refusal();
+  }
   size_t o_jfif = 0;
   int rc = decode_front(e, jpegs, sizes, n, false, &o_jfif);
   if (rc) return rc;
@@ -3403,18 +3447,29 @@ static int resolve_scale(const mjh_decode_opts *o, int *k)
 // k: the IDCT size of the call (resolve_scale).  ssize[c]: DCT_scaled_size of component c -- k, doubled while the sampling
 // ratios allow it (jpeg_calc_output_dimensions jdmaster.c:287-320), so that the transform does the upsampling where it can.
 // At k = 8 every component is at size 8 and this is the full-size plan.
-static int plan_pixels(const mjh_encoder *e, const mjh_decode_opts *o, int k, MjhPixOut *P, int ssize[3])
+// *out: the output buffer's geometry.  Exactly one plan is made: *P4 for a four-component file (e->four, k_upcolor4), else *P
+// (k_upcolor, k_upcolor_565); the other stays zeroed.  up[c]: the upsampling of every component the plan reads, *ncomp of them.
+static int plan_pixels(const mjh_encoder *e, const mjh_decode_opts *o, int k, DecOut *out, MjhPixOut *P, MjhPixOut4 *P4, MjhUpComp up[MJH_MAXC], int *ncomp, int ssize[MJH_MAXC])
 {
   const MjhConst &C = e->C;
   memset(P, 0, sizeof(*P));
-  if (C.ncomp != 1 && C.ncomp != 3) return fail(MJH_EUNSUPPORTED, "decoding files of %d components", C.ncomp);
+  memset(P4, 0, sizeof(*P4));
+  if (C.ncomp != 1 && C.ncomp != 3 && C.ncomp != 4) return fail(MJH_EUNSUPPORTED, "decoding files of %d components", C.ncomp);
   if (C.precision != 8) return fail(MJH_EUNSUPPORTED, "decoding %d-bit files", C.precision);
-  const bool src_gray = C.ncomp == 1, src_rgb = C.ncomp == 3 && e->p_created.color_transform == MJH_COLOR_NONE;
+  const bool src_gray = C.ncomp == 1, src_rgb = C.ncomp == 3 && e->p_created.color_transform == MJH_COLOR_NONE, src_four = C.ncomp == 4;
   int cs = o->out_color_space;
-  if (cs == 0) cs = src_gray ? MJH_CS_GRAYSCALE : MJH_CS_RGB;
-  if (cs != MJH_CS_GRAYSCALE && cs != MJH_CS_RGB && cs != MJH_CS_RGB565)
-    return fail(MJH_EINVAL, "out_color_space %d (0, MJH_CS_GRAYSCALE, MJH_CS_RGB or MJH_CS_RGB565)", o->out_color_space);
+  if (cs == 0) cs = src_gray ? MJH_CS_GRAYSCALE : (src_four ? MJH_CS_CMYK : MJH_CS_RGB);
+  if (cs != MJH_CS_GRAYSCALE && cs != MJH_CS_RGB && cs != MJH_CS_RGB565 && cs != MJH_CS_CMYK)
+    return fail(MJH_EINVAL, "out_color_space %d (0, MJH_CS_GRAYSCALE, MJH_CS_RGB, MJH_CS_RGB565 or MJH_CS_CMYK)", o->out_color_space);
+  // jinit_color_deconverter (jdcolor.c:784-931): CMYK output of CMYK and YCCK files alone, and nothing else of them
+  if (src_four != (cs == MJH_CS_CMYK))
+    return fail(MJH_EUNSUPPORTED, "Unsupported color conversion request (JERR_CONVERSION_NOTIMPL): %s", src_four ? "a CMYK or YCCK file decodes to CMYK pixels only" : "CMYK pixels come from CMYK and YCCK files only");
   int px = o->pixel_size;
+  if (src_four) {
+    if (px != 0 && px != 4) return fail(MJH_EINVAL, "pixel_size %d of CMYK output (0 or 4)", px);
+    px = 4;
+    P4->conv = e->p_created.color_transform == MJH_COLOR_YCCK ? MJH_CC4_YCCK : MJH_CC4_NULL;
+  } else
   if (cs == MJH_CS_RGB565) {
     // jdcol565.c: 16-bit pixels, one layout; k_upcolor_565 reads no offsets
     if (px != 0 && px != 2) return fail(MJH_EINVAL, "pixel_size %d of RGB565 output (0 or 2)", px);
@@ -3435,16 +3490,17 @@ static int plan_pixels(const mjh_encoder *e, const mjh_decode_opts *o, int k, Mj
     for (int k = 0; k < 3; k++)
       if (off[k] < 0 || off[k] >= px || off[k] == off[(k + 1) % 3]) return fail(MJH_EINVAL, "rgb_offset %d,%d,%d of %d-byte pixels", off[0], off[1], off[2], px);
   }
-  P->W = (int)div_round_up((long)C.W * k, 8); P->H = (int)div_round_up((long)C.H * k, 8);
-  P->px_size = px;
-  P->ncomp = (P->conv == MJH_CC_GRAY || P->conv == MJH_CC_GRAY_RGB) ? 1 : 3;     // component_needed: a YCbCr file's gray output reads Y alone
-  P->row_pitch = (long long)up16((size_t)px * (((size_t)P->W + 3) & ~(size_t)3));
-  P->image_stride = P->row_pitch * P->H;
-  P->planes_per_image = C.planes_per_image;
+  *out = DecOut();
+  out->W = (int)div_round_up((long)C.W * k, 8); out->H = (int)div_round_up((long)C.H * k, 8);
+  out->px_size = px;
+  out->row_pitch = (long long)up16((size_t)px * (((size_t)out->W + 3) & ~(size_t)3));
+  out->image_stride = out->row_pitch * out->H;
+  *ncomp = src_four ? 4 : (P->conv == MJH_CC_GRAY || P->conv == MJH_CC_GRAY_RGB) ? 1 : 3;     // component_needed: a YCbCr file's gray output reads Y alone
   const bool fancy = o->fancy_upsampling != 0 && k > 1;       // do_fancy: && min_DCT_scaled_size > 1 (jdsample.c:444)
-  for (int c = 0; c < P->ncomp; c++) {
+  for (int c = 0; c < *ncomp; c++) {
     const MjhComp &cc = C.c[c];
-    MjhUpComp &u = P->c[c];
+    MjhUpComp &u = up[c];
+    memset(&u, 0, sizeof(u));
     if (C.maxh % cc.h || C.maxv % cc.v) return fail(MJH_EUNSUPPORTED, "fractional sampling ratios (JERR_FRACT_SAMPLE_NOTIMPL, jdsample.c:529)");
     int ss = k;
     while (ss < 8 && (C.maxh * k) % (cc.h * ss * 2) == 0 && (C.maxv * k) % (cc.v * ss * 2) == 0) ss *= 2;
@@ -3459,6 +3515,15 @@ static int plan_pixels(const mjh_encoder *e, const mjh_decode_opts *o, int k, Mj
     if (u.hexp == 2 && u.vexp == 1) { if (fancy && u.dw > 2) u.mode = MJH_UP_H2V1_FANCY; }
     else if (u.hexp == 1 && u.vexp == 2) { if (fancy) u.mode = MJH_UP_H1V2_FANCY; }
     else if (u.hexp == 2 && u.vexp == 2) { if (fancy && u.dw > 2) u.mode = MJH_UP_H2V2_FANCY; }
+  }
+  if (src_four) {
+    P4->W = out->W; P4->H = out->H;
+    P4->row_pitch = out->row_pitch; P4->image_stride = out->image_stride; P4->planes_per_image = C.planes_per_image;
+    for (int c = 0; c < 4; c++) P4->c[c] = up[c];
+  } else {
+    P->W = out->W; P->H = out->H; P->px_size = px; P->ncomp = *ncomp;
+    P->row_pitch = out->row_pitch; P->image_stride = out->image_stride; P->planes_per_image = C.planes_per_image;
+    for (int c = 0; c < P->ncomp; c++) P->c[c] = up[c];
   }
   return MJH_OK;
 }
@@ -3501,7 +3566,7 @@ static int decode_coefs(mjh_encoder *e, const void *const jpegs[], const size_t 
   if (rc) return rc;
   hipStream_t s = e->stream;
   const bool timed = e->profiling != 0;
-  memset(&e->dp, 0, sizeof(e->dp));
+  e->dp = DecOut();
   e->dp.W = C.W; e->dp.H = C.H;
   e->dp_n = n; e->dp_raw = false; e->dp_coefs = true; e->dp_timed = false;
   e->last_n = n; e->compact_last = false; e->last = nullptr;
@@ -3711,7 +3776,9 @@ static int decode_lossless(mjh_encoder *e, const void *const jpegs[], const size
   PO.W = W; PO.H = H; PO.ncomp = NC; PO.px_size = O.px * sample_bytes; PO.bottom_up = O.bottom_up;
   PO.off_r = O.off[0]; PO.off_g = O.off[1]; PO.off_b = O.off[2];
   PO.row_pitch = O.row_pitch; PO.image_stride = O.image_stride;
-  e->dp = PO; e->dp_n = n; e->dp_raw = false; e->dp_coefs = false;
+  e->dp = DecOut();
+  e->dp.W = W; e->dp.H = H; e->dp.px_size = PO.px_size; e->dp.row_pitch = PO.row_pitch; e->dp.image_stride = PO.image_stride;
+  e->dp_n = n; e->dp_raw = false; e->dp_coefs = false;
   e->last_n = n; e->compact_last = false; e->last = nullptr;
   HIPCHK(hipMemsetAsync(e->d_lldiff, 0, (size_t)n * (size_t)G.per_image * 2, s));
   HIPCHK(hipMemsetAsync(e->d_tstat, 0, (size_t)n * 4, s));
@@ -3749,31 +3816,35 @@ extern "C" int mjh_decode_host(mjh_encoder *e, const void *const jpegs[], const 
   if (o.raw_coefs) return decode_coefs(e, jpegs, sizes, n);
   if (o.dct_method != 0 && o.dct_method != 1) return fail(MJH_EINVAL, "dct_method %d of a decode call (0 = JDCT_ISLOW, 1 = JDCT_IFAST)", o.dct_method);
   const bool ifast = o.dct_method == 1, raw = o.raw_planes != 0;
-  int k = 8, ssize[3] = { 8, 8, 8 };
+  int k = 8, ssize[MJH_MAXC] = { 8, 8, 8, 8 }, ncomp = 0;
   int rc = resolve_scale(&o, &k);
   if (rc) return rc;
+  DecOut out;
   MjhPixOut P;
+  MjhPixOut4 P4;
+  MjhUpComp up[MJH_MAXC];
+  memset(&P, 0, sizeof(P));
+  memset(&P4, 0, sizeof(P4));
+  memset(up, 0, sizeof(up));
   if (raw) {
     // the planes alone: every component at the scale's own size (what TurboJPEG forces for planar output, turbojpeg.c:2151-2167),
     // so that they keep the file's subsampling at every scale; nothing of the pixel options is looked at
     const MjhConst &C0 = e->C;
-    if (C0.ncomp != 1 && C0.ncomp != 3) return fail(MJH_EUNSUPPORTED, "decoding files of %d components", C0.ncomp);
+    if (C0.ncomp != 1 && C0.ncomp != 3 && C0.ncomp != 4) return fail(MJH_EUNSUPPORTED, "decoding files of %d components", C0.ncomp);
     if (C0.precision != 8) return fail(MJH_EUNSUPPORTED, "decoding %d-bit files", C0.precision);
-    memset(&P, 0, sizeof(P));
-    P.W = (int)div_round_up((long)C0.W * k, 8); P.H = (int)div_round_up((long)C0.H * k, 8);
-    P.ncomp = C0.ncomp;
-    P.planes_per_image = C0.planes_per_image;
-    for (int c = 0; c < P.ncomp; c++) { ssize[c] = k; P.c[c].pw = k == 8 ? C0.c[c].pw : (C0.c[c].wib * k + 3) & ~3; }
+    out.W = (int)div_round_up((long)C0.W * k, 8); out.H = (int)div_round_up((long)C0.H * k, 8);
+    ncomp = C0.ncomp;
+    for (int c = 0; c < ncomp; c++) { ssize[c] = k; up[c].pw = k == 8 ? C0.c[c].pw : (C0.c[c].wib * k + 3) & ~3; }
   } else {
-    rc = plan_pixels(e, &o, k, &P, ssize);
+    rc = plan_pixels(e, &o, k, &out, &P, &P4, up, &ncomp, ssize);
     if (rc) return rc;
-    P.bottom_up = o.bottom_up != 0;
+    P.bottom_up = P4.bottom_up = o.bottom_up != 0;
   }
   size_t o_jfif = 0;
   rc = decode_front(e, jpegs, sizes, n, true, &o_jfif, true);
   if (rc) return rc;
   const MjhConst &C = e->C;
-  const size_t need = raw ? 0 : (size_t)e->max_batch * (size_t)P.image_stride;
+  const size_t need = raw ? 0 : (size_t)e->max_batch * (size_t)out.image_stride;
   if (need > e->pixout_cap) {
     HIPCHK(hipStreamSynchronize(e->stream));
     if (e->d_pixout) { (void)mjh_guard_free(e->d_pixout); e->d_pixout = nullptr; }
@@ -3796,10 +3867,10 @@ extern "C" int mjh_decode_host(mjh_encoder *e, const void *const jpegs[], const 
     }
   hipStream_t s = e->stream;
   const bool timed = e->profiling != 0;
-  e->dp = P; e->dp_n = n; e->dp_raw = raw; e->dp_coefs = false;
+  e->dp = out; e->dp_n = n; e->dp_raw = raw; e->dp_coefs = false;
   e->last_n = n; e->compact_last = false; e->last = nullptr;      // (mjh_read_tap: d_q holds this batch's plain planes, d_planes its samples)
   if (timed) HIPCHK(hipEventRecord(e->dp_ev[0], s));
-  if (k == 8) (ifast ? mjh_launch_idct_ifast : mjh_launch_idct)(C, ifast ? QF : Q, P.ncomp, e->d_q, e->d_planes, e->d_tstat, n, s);
+  if (k == 8) (ifast ? mjh_launch_idct_ifast : mjh_launch_idct)(C, ifast ? QF : Q, ncomp, e->d_q, e->d_planes, e->d_tstat, n, s);
   else {
     // a scaled call: the reduced transforms component by component; the components the ratios leave at size 8 (chroma of a
     // 4:2:0 file at 1/2) go through k_idct or k_idct_ifast -- only they have a method to choose (jddctmgr.c start_pass) --
@@ -3814,13 +3885,13 @@ extern "C" int mjh_decode_host(mjh_encoder *e, const void *const jpegs[], const 
     // are the contract: the same table goes to k_idct_scaled here.
     MjhIdctQ QS = Q;
     if (raw && ifast)
-      for (int c = 0; c < P.ncomp; c++) {
+      for (int c = 0; c < ncomp; c++) {
         int ss = k;
         while (ss < 8 && (C.maxh * k) % (C.c[c].h * ss * 2) == 0 && (C.maxv * k) % (C.c[c].v * ss * 2) == 0) ss *= 2;
         if (ss == 8) memcpy(QS.q[c], QF.q[c], sizeof(QS.q[c]));
       }
-    for (int c = 0; c < P.ncomp; c++) {
-      if (ssize[c] != 8) { mjh_launch_idct_scaled(C, QS, c, ssize[c], P.c[c].pw, e->d_q, e->d_planes, e->d_tstat, n, s); continue; }
+    for (int c = 0; c < ncomp; c++) {
+      if (ssize[c] != 8) { mjh_launch_idct_scaled(C, QS, c, ssize[c], up[c].pw, e->d_q, e->d_planes, e->d_tstat, n, s); continue; }
       C8.c[n8] = C.c[c];
       memcpy(Q8.q[n8], (ifast ? QF : Q).q[c], sizeof(Q8.q[n8]));
       n8++;
@@ -3829,9 +3900,10 @@ extern "C" int mjh_decode_host(mjh_encoder *e, const void *const jpegs[], const 
   }
   if (timed) HIPCHK(hipEventRecord(e->dp_ev[1], s));
   if (raw) {
-    e->rp_ncomp = P.ncomp;
-    for (int c = 0; c < P.ncomp; c++) { e->rp_w[c] = C.c[c].wib * k; e->rp_h[c] = C.c[c].hib * k; e->rp_pitch[c] = P.c[c].pw; }
-  } else if (P.px_size == 2) mjh_launch_upcolor_565(P, o.no_dither == 0, e->d_planes, e->d_pixout, e->d_tstat, n, s);
+    e->rp_ncomp = ncomp;
+    for (int c = 0; c < ncomp; c++) { e->rp_w[c] = C.c[c].wib * k; e->rp_h[c] = C.c[c].hib * k; e->rp_pitch[c] = up[c].pw; }
+  } else if (e->four) mjh_launch_upcolor4(P4, e->d_planes, e->d_pixout, e->d_tstat, n, s);
+  else if (out.px_size == 2) mjh_launch_upcolor_565(P, o.no_dither == 0, e->d_planes, e->d_pixout, e->d_tstat, n, s);
   else mjh_launch_upcolor(P, e->d_planes, e->d_pixout, e->d_tstat, n, s);
   if (timed) HIPCHK(hipEventRecord(e->dp_ev[2], s));
   e->dp_timed = timed;

@@ -40,6 +40,19 @@ struct MjhPixOut {
   MjhUpComp c[3];
 };
 
+// the plan of a four-component file (CMYK, YCCK), whose one output is four bytes C, M, Y, K per pixel (jdcolor.c:901-918).  A
+// descriptor of its own: MjhPixOut and the kernels that read it stay as they are.
+#define MJH_CC4_NULL 0           // a JCS_CMYK file: null_convert, the four samples as they are (Adobe's inverted ones stay inverted)
+#define MJH_CC4_YCCK 1           // a JCS_YCCK file: ycck_cmyk_convert (jdcolor.c:543-587)
+struct MjhPixOut4 {
+  int W, H;
+  int conv;                  // MJH_CC4_*
+  int bottom_up;
+  long long row_pitch, image_stride;      // of the output, bytes; rows hold whole groups of 4 pixels (16 bytes each)
+  long long planes_per_image;
+  MjhUpComp c[4];
+};
+
 // K-I1: coefficient planes (what k_dec_store / k_dec_dc leave) -> 8-bit sample planes, real blocks only; comps: the first
 // `comps` components.  status != 0: that image is skipped.
 void mjh_launch_idct(const MjhConst &C, const MjhIdctQ &Q, int comps, const int16_t *coef_q, uint8_t *planes, const unsigned *status, int n, hipStream_t s);
@@ -56,4 +69,6 @@ void mjh_launch_upcolor(const MjhPixOut &P, const uint8_t *planes, uint8_t *pixe
 // K-I2 for JCS_RGB565: P.px_size 2, P.conv one of MJH_CC_GRAY_RGB / MJH_CC_YCC_RGB / MJH_CC_RGB_RGB; 16-bit little-endian pixels,
 // dither != 0: the ordered dither of jdcol565.c by image row and column, 0: plain (JDITHER_NONE)
 void mjh_launch_upcolor_565(const MjhPixOut &P, int dither, const uint8_t *planes, uint8_t *pixels, const unsigned *status, int n, hipStream_t s);
+// K-I2 for four components: the grid of mjh_launch_upcolor, 4 pixels = 16 bytes = one store per lane
+void mjh_launch_upcolor4(const MjhPixOut4 &P, const uint8_t *planes, uint8_t *pixels, const unsigned *status, int n, hipStream_t s);
 #endif

@@ -26,6 +26,7 @@
 //   controller (jdmainct.c make_funny_pointers / set_bottom_pointers) amount to; samples beyond are never read.
 // K-I2' k_upcolor_565: the same lanes for JCS_RGB565 (djpeg -rgb565): 4 packed 16-bit pixels, one 8-byte store, with or without
 //   the reference's ordered dither; see the kernel.
+// K-I2'' k_upcolor4: the same lanes for the four-component files (CMYK, YCCK): 4 pixels of C, M, Y, K, one 16-byte store; see the kernel.
 #include <hip/hip_runtime.h>
 #include "mjh_device.h"
 #include "mjh_idct.h"
@@ -414,6 +415,41 @@ k_upcolor_565(MjhPixOut P, int dither, const uint8_t *__restrict__ planes, uint8
   *reinterpret_cast<uint2 *>(pixels + (size_t)img * P.image_stride + (size_t)yo * P.row_pitch + (size_t)x0 * 2) = v;
 }
 
+// ---- K-I2 for four components (Adobe-style CMYK and YCCK files): pixels of four bytes C, M, Y, K ---------------------------------
+// The grid and the lanes of k_upcolor: one lane per 4 output pixels of a row, every sample through up_sample with its component's
+// own mode (K may be sampled like Y or lower: jinit_upsampler treats it as any component, and there is no merged upsampling for
+// four components), then one 16-byte store.  MJH_CC4_NULL: null_convert, the samples interleaved as they are.  MJH_CC4_YCCK:
+// ycck_cmyk_convert (jdcolor.c:543-587): range_limit[255 - (y + table terms)] with the tables of build_ycc_rgb_table as k_upcolor
+// has them; the index stays inside the part of the table that is a plain clamp, where range_limit[255 - v] = 255 - clamp(v).
+__global__ void __launch_bounds__(256)
+k_upcolor4(MjhPixOut4 P, const uint8_t *__restrict__ planes, uint8_t *__restrict__ pixels, const unsigned *__restrict__ status)
+{
+  const int img = blockIdx.z, y = blockIdx.y;
+  const int x0 = (int)(blockIdx.x * 256u + threadIdx.x) * 4;
+  if (x0 >= P.W) return;
+  if (status[img] != 0u) return;
+  const uint8_t *pl = planes + (size_t)img * P.planes_per_image;
+  const int yo = P.bottom_up ? P.H - 1 - y : y;
+  unsigned w[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const int x = x0 + i < P.W ? x0 + i : P.W - 1;      // (the pad of the last group, as in k_upcolor)
+    int c0 = up_sample(P.c[0], pl + P.c[0].plane_off, x, y), c1 = up_sample(P.c[1], pl + P.c[1].plane_off, x, y);
+    int c2 = up_sample(P.c[2], pl + P.c[2].plane_off, x, y);
+    const int c3 = up_sample(P.c[3], pl + P.c[3].plane_off, x, y);
+    if (P.conv == MJH_CC4_YCCK) {
+      const int a = c0, cb = c1 - 128, cr = c2 - 128;
+      c0 = 255 - clamp255(a + ((91881 * cr + 32768) >> 16));
+      c1 = 255 - clamp255(a + ((-22554 * cb + 32768 - 46802 * cr) >> 16));
+      c2 = 255 - clamp255(a + ((116130 * cb + 32768) >> 16));
+    }
+    w[i] = (unsigned)c0 | ((unsigned)c1 << 8) | ((unsigned)c2 << 16) | ((unsigned)c3 << 24);
+  }
+  uint4 v;
+  v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
+  *reinterpret_cast<uint4 *>(pixels + (size_t)img * P.image_stride + (size_t)yo * P.row_pitch + (size_t)x0 * 4) = v;
+}
+
 void mjh_launch_idct(const MjhConst &C, const MjhIdctQ &Q, int comps, const int16_t *coef_q, uint8_t *planes, const unsigned *status, int n, hipStream_t s)
 {
   int nblk = 1;
@@ -438,6 +474,12 @@ void mjh_launch_upcolor_565(const MjhPixOut &P, int dither, const uint8_t *plane
 {
   const int groups = (P.W + 3) / 4;
   hipLaunchKernelGGL(k_upcolor_565, dim3((groups + 255) / 256, P.H, n), dim3(256), 0, s, P, dither, planes, pixels, status);
+}
+
+void mjh_launch_upcolor4(const MjhPixOut4 &P, const uint8_t *planes, uint8_t *pixels, const unsigned *status, int n, hipStream_t s)
+{
+  const int groups = (P.W + 3) / 4;
+  hipLaunchKernelGGL(k_upcolor4, dim3((groups + 255) / 256, P.H, n), dim3(256), 0, s, P, planes, pixels, status);
 }
 
 void mjh_launch_idct_scaled(const MjhConst &C, const MjhIdctQ &Q, int ci, int N, int pitch, const int16_t *coef_q, uint8_t *planes, const unsigned *status, int n, hipStream_t s)

@@ -96,8 +96,10 @@ static int probe_walk(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_i
           return pfail(MJH_EINVAL, "Unsupported JPEG data precision %d (JERR_BAD_PRECISION)", info->data_precision);
       } else
       if (info->data_precision != 8) return pfail(MJH_EUNSUPPORTED, "%d-bit source file: only 8-bit samples", info->data_precision);
-      if (info->num_components != 1 && info->num_components != 3)
-        return pfail(MJH_EUNSUPPORTED, "%d components in the source file: 1 or 3 are supported", info->num_components);
+      if (lossless && info->num_components == 4)
+        return pfail(MJH_EUNSUPPORTED, "4 components in a lossless source file: 1 or 3 are supported (four components are decoded from DCT files only)");
+      if (info->num_components != 1 && info->num_components != 3 && info->num_components != 4)
+        return pfail(MJH_EUNSUPPORTED, "%d components in the source file: 1, 3 or 4 are supported", info->num_components);
       for (int c = 0; c < info->num_components; c++) {
         info->component_id[c] = s[6 + 3 * c];
         info->h_samp_factor[c] = s[7 + 3 * c] >> 4;
@@ -286,6 +288,13 @@ static int probe_walk(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_i
   if (num_ex) *num_ex = nex;
   // default_decompress_parms (jdapimin.c:130-205)
   if (info->num_components == 1) info->jpeg_color_space = MJH_CS_GRAYSCALE;
+  else if (info->num_components == 4) {
+    // :183-201: the Adobe transform alone decides, a JFIF marker says nothing; where the reference warns (JWRN_ADOBE_XFORM) and
+    // assumes YCCK, the file is refused
+    if (info->saw_Adobe_marker && info->Adobe_transform != 0 && info->Adobe_transform != 2)
+      return pfail(MJH_EUNSUPPORTED, "Unknown Adobe color transform code %d (JWRN_ADOBE_XFORM) in a four-component file: 0 (CMYK) and 2 (YCCK) are decoded", info->Adobe_transform);
+    info->jpeg_color_space = info->saw_Adobe_marker && info->Adobe_transform == 2 ? MJH_CS_YCCK : MJH_CS_CMYK;
+  }
   else if (info->saw_JFIF_marker) info->jpeg_color_space = MJH_CS_YCbCr;
   else if (info->saw_Adobe_marker) info->jpeg_color_space = info->Adobe_transform == 0 ? MJH_CS_RGB : MJH_CS_YCbCr;
   else info->jpeg_color_space = (info->component_id[0] == 82 && info->component_id[1] == 71 && info->component_id[2] == 66) ? MJH_CS_RGB : MJH_CS_YCbCr;
@@ -316,7 +325,36 @@ extern "C" int mjh_params_from_jpeg(const mjh_jpeg_info *info, int compress_prof
 {
   if (!info || !p) return pfail(MJH_EINVAL, "bad arguments");
   const int nc = info->num_components;
-  if (nc != 1 && nc != 3) return pfail(MJH_EUNSUPPORTED, "%d components", nc);
+  if (nc != 1 && nc != 3 && nc != 4) return pfail(MJH_EUNSUPPORTED, "%d components", nc);
+  if (nc == 4) {
+    // A CMYK / YCCK file: the parameters of an encoder that owns the geometry and the tables of decode calls on such files and
+    // writes nothing -- jpeg_set_colorspace(JCS_CMYK / JCS_YCCK)'s table numbers (jcparam.c:624-645), the file's own ids, factors
+    // and quantization tables, a sequential script whatever the profile (no scan script exists for four components here)
+    if (info->sof_type == 3) return pfail(MJH_EUNSUPPORTED, "4 components in a lossless source file");
+    if (info->jpeg_color_space != MJH_CS_CMYK && info->jpeg_color_space != MJH_CS_YCCK) return pfail(MJH_EINVAL, "a four-component file whose colour space is %d (MJH_CS_CMYK or MJH_CS_YCCK)", info->jpeg_color_space);
+    int rc = mjh_params_defaults(p, info->image_width, info->image_height, 3, 0, compress_profile, 1, 1);
+    if (rc) return rc;
+    const bool ycck = info->jpeg_color_space == MJH_CS_YCCK;
+    p->trellis_quant = 0;
+    p->data_precision = info->data_precision;
+    p->input_components = 4;
+    p->input_pixel_size = 4;
+    p->num_components = 4;
+    p->color_transform = ycck ? MJH_COLOR_YCCK : MJH_COLOR_CMYK;
+    p->write_JFIF_header = 0;
+    for (int t = 0; t < 4; t++)
+      if ((info->quant_defined >> t) & 1) memcpy(p->quantval[t], info->quantval[t], sizeof(p->quantval[t]));
+    for (int c = 0; c < 4; c++) {
+      p->component_id[c] = info->component_id[c];
+      p->h_samp_factor[c] = info->h_samp_factor[c];
+      p->v_samp_factor[c] = info->v_samp_factor[c];
+      p->quant_tbl_no[c] = info->quant_tbl_no[c];
+      p->dc_tbl_no[c] = p->ac_tbl_no[c] = ycck && (c == 1 || c == 2);
+      if (p->quant_tbl_no[c] < 0 || p->quant_tbl_no[c] > 3 || !((info->quant_defined >> p->quant_tbl_no[c]) & 1))
+        return pfail(MJH_EINVAL, "Quantization table 0x%02x was not defined (JERR_NO_QUANT_TABLE)", p->quant_tbl_no[c]);
+    }
+    return MJH_OK;
+  }
   if (info->sof_type == 3) {
     // A lossless file (mjh_jpeg_probe_ex with MJH_SRC_LOSSLESS): the parameters of an encoder that writes such files and owns the
     // geometry its decode calls need -- jpeg_enable_lossless(predictor, point transform) of the file's first scan as a script of one
@@ -430,6 +468,7 @@ int mjh_transform_plan(const mjh_jpeg_info *f, const mjh_transform *t, MjhXformP
     return pfail(t->transform == 8 || t->transform == 9 ? MJH_EUNSUPPORTED : MJH_EINVAL, "transform %d (MJH_XFORM_NONE .. MJH_XFORM_ROT_270; -wipe and -drop are not built)", t->transform);
   if (t->transform == MJH_XFORM_NONE && !t->crop && !t->grayscale) return MJH_OK;      // (-trim / -perfect alone change nothing)
   const int nc = f->num_components;
+  if (nc == 4) return pfail(MJH_EUNSUPPORTED, "four-component files (CMYK, YCCK) are decoded, not written: no lossless transform of them");
   if (nc != 1 && nc != 3) return pfail(MJH_EUNSUPPORTED, "%d components", nc);
   if (t->crop)
     for (int s : { t->crop_width_set, t->crop_height_set })

@@ -20,7 +20,7 @@
  * The LEGACY tjCompress2 selects the fast DCT (JDCT_IFAST, jfdctfst.c) unless quality >= 96 or TJFLAG_ACCURATEDCT is given
  * (processFlags turbojpeg.c:522-527), the 3.x API through TJPARAM_FASTDCT: mjh_params.dct_method, coded bit-exactly like the
  * accurate one, 8- and 12-bit samples; lossless mode (TJPARAM_LOSSLESS*, 8 / 12 / 16 bits, tj3Compress16).  Outside the GPU path (an
- * ERROR, never a CPU fallback): CMYK / YCCK.
+ * ERROR, never a CPU fallback): writing CMYK / YCCK files (decompress instances read them, see the second half of this file).
  */
 #define _GNU_SOURCE
 #include <dlfcn.h>
@@ -629,12 +629,15 @@ DLLEXPORT int tjCompressFromYUV(tjhandle handle, const unsigned char *srcBuf, in
 
 /* ==== decompress instances ==========================================================================================================
  * The rule of the compress half holds: the reference's bytes or an error, never a CPU fallback and never a different picture.
- * - A file mjh_jpeg_probe refuses (progressive, arithmetic, 12-bit, lossless, four components, DNL) fails at the header or the
+ * - A file mjh_jpeg_probe refuses (progressive, arithmetic, 12-bit, lossless, two components, DNL) fails at the header or the
  *   decompress call with the probe's text.
+ * - Four-component files (CMYK, YCCK) report TJCS_CMYK / TJCS_YCCK and the reference's subsampling (TJSAMP_UNKNOWN when K is
+ *   sampled unlike Y) and decode to TJPF_CMYK alone; TJPF_CMYK of any other file, any other format of these, and their planar
+ *   YUV output fail as in the reference ("Unsupported color conversion request", "JPEG image must have 3 or fewer components").
  * - All 16 scaling factors of the reference are accepted and chosen (tjDecompress2) as there; a decompress call at a factor other
  *   than 1/1, 1/2, 1/4, 1/8 fails with a text naming the factor.
  * - Damaged entropy-coded data is a FATAL error and the destination is left untouched (the reference: a warning and a partial
- *   image).  Cropping regions other than TJUNCROPPED, TJPF_CMYK and 12- / 16-bit output are refused.
+ *   image).  Cropping regions other than TJUNCROPPED and 12- / 16-bit output are refused.
  * A handle keeps one mjh_encoder made from mjh_params_from_jpeg (the 'revert' profile, one file per call) and remakes it when
  * a file's parameters differ, as the compress half does. */
 #define NUMSF 16
@@ -684,27 +687,29 @@ DLLEXPORT int tj3SetCroppingRegion(tjhandle handle, tjregion croppingRegion)
   return fail(t, "tj3SetCroppingRegion", "partial decompression (a cropping region other than TJUNCROPPED) is not built on the GPU path");
 }
 
-/* getSubsamp turbojpeg.c:400-478 for the files that get this far (one or three components) */
+/* getSubsamp turbojpeg.c:400-478 for the files that get this far (one, three or four components).  In a CMYK / YCCK file the
+ * fourth component (K) is expected with the factors of the first; a K sampled otherwise leaves TJSAMP_UNKNOWN. */
 static int subsamp_of(const mjh_jpeg_info *in)
 {
   int i, k;
-  const int *h = in->h_samp_factor, *v = in->v_samp_factor;
-  if (in->num_components == 1 && in->jpeg_color_space == MJH_CS_GRAYSCALE) return TJSAMP_GRAY;
-  if (in->num_components != 3) return TJSAMP_UNKNOWN;
+  const int *h = in->h_samp_factor, *v = in->v_samp_factor, nc = in->num_components;
+  const int four = nc == 4 && (in->jpeg_color_space == MJH_CS_CMYK || in->jpeg_color_space == MJH_CS_YCCK);
+  if (nc == 1 && in->jpeg_color_space == MJH_CS_GRAYSCALE) return TJSAMP_GRAY;
+  if (nc != 3 && !four) return TJSAMP_UNKNOWN;
   for (i = 0; i < TJ_NUMSAMP; i++) {
     int match;
     if (i == TJSAMP_GRAY) continue;
     if (h[0] == kMcuW[i] / 8 && v[0] == kMcuH[i] / 8) {               /* the standard way: luma carries the factors, chroma 1x1 */
-      for (match = 0, k = 1; k < 3; k++) if (h[k] == 1 && v[k] == 1) match++;
-      if (match == 2) return i;
+      for (match = 0, k = 1; k < nc; k++) if (h[k] == (k == 3 ? kMcuW[i] / 8 : 1) && v[k] == (k == 3 ? kMcuH[i] / 8 : 1)) match++;
+      if (match == nc - 1) return i;
     }
     if (h[0] == 2 && v[0] == 2 && (i == TJSAMP_422 || i == TJSAMP_440)) {       /* 4:2:2 and 4:4:0 under a 2x2 luma */
-      for (match = 0, k = 1; k < 3; k++) if (h[k] == kMcuH[i] / 8 && v[k] == kMcuW[i] / 8) match++;
-      if (match == 2) return i;
+      for (match = 0, k = 1; k < nc; k++) if (h[k] == (k == 3 ? 2 : kMcuH[i] / 8) && v[k] == (k == 3 ? 2 : kMcuW[i] / 8)) match++;
+      if (match == nc - 1) return i;
     }
     if (h[0] * v[0] <= 10 / 3 && i == TJSAMP_444) {                   /* 4:4:4 with equal factors above 1 (D_MAX_BLOCKS_IN_MCU / 3) */
-      for (match = 0, k = 1; k < 3; k++) if (h[k] == h[0] && v[k] == v[0]) match++;
-      if (match == 2) return i;
+      for (match = 0, k = 1; k < nc; k++) if (h[k] == h[0] && v[k] == v[0]) match++;
+      if (match == nc - 1) return i;
     }
   }
   return TJSAMP_UNKNOWN;
@@ -717,7 +722,8 @@ static int read_header(tjs *t, const char *fn, const unsigned char *jpegBuf, siz
   t->subsamp = subsamp_of(in);
   t->jpeg_width = in->image_width; t->jpeg_height = in->image_height;
   t->precision = in->data_precision;
-  t->colorspace = in->jpeg_color_space == MJH_CS_GRAYSCALE ? TJCS_GRAY : in->jpeg_color_space == MJH_CS_RGB ? TJCS_RGB : in->jpeg_color_space == MJH_CS_YCbCr ? TJCS_YCbCr : -1;
+  t->colorspace = in->jpeg_color_space == MJH_CS_GRAYSCALE ? TJCS_GRAY : in->jpeg_color_space == MJH_CS_RGB ? TJCS_RGB : in->jpeg_color_space == MJH_CS_YCbCr ? TJCS_YCbCr :
+                  in->jpeg_color_space == MJH_CS_CMYK ? TJCS_CMYK : in->jpeg_color_space == MJH_CS_YCCK ? TJCS_YCCK : -1;
   t->progressive = t->arithmetic = t->lossless = 0;          /* (such files do not get this far) */
   t->lossless_psv = 0; t->lossless_pt = 0;                   /* Ss and Al of a sequential scan */
   if (in->saw_JFIF_marker) { t->xdensity = in->X_density; t->ydensity = in->Y_density; t->density_units = in->density_unit; }
@@ -790,8 +796,12 @@ static int decompress_pixels(tjs *t, const char *fn, const unsigned char *jpegBu
   int W, H;
   if (jpegBuf == NULL || jpegSize <= 0 || dstBuf == NULL || pitch < 0 || pixelFormat < 0 || pixelFormat >= TJ_NUMPF) return fail(t, fn, "Invalid argument");
   if (decode_setup(t, fn, jpegBuf, jpegSize, &in, &o, &W, &H)) return -1;
-  if (pixelFormat == TJPF_CMYK) return fail(t, fn, "CMYK / YCCK are outside the GPU path (no CPU fallback)");
-  if (pixelFormat == TJPF_GRAY) { o.out_color_space = MJH_CS_GRAYSCALE; o.pixel_size = 1; }
+  /* jinit_color_deconverter (jdcolor.c:784-931): TJPF_CMYK of CMYK and YCCK files, and of nothing else; nothing else of them */
+  if ((pixelFormat == TJPF_CMYK) != (in.num_components == 4))
+    return fail(t, fn, pixelFormat == TJPF_CMYK ? "Unsupported color conversion request: TJPF_CMYK pixels come from CMYK and YCCK files only"
+                                                : "Unsupported color conversion request: a CMYK or YCCK file decodes to TJPF_CMYK only");
+  if (pixelFormat == TJPF_CMYK) { o.out_color_space = MJH_CS_CMYK; o.pixel_size = 4; }
+  else if (pixelFormat == TJPF_GRAY) { o.out_color_space = MJH_CS_GRAYSCALE; o.pixel_size = 1; }
   else {
     o.out_color_space = MJH_CS_RGB; o.pixel_size = kPixelSize[pixelFormat];
     o.rgb_offset[0] = kRed[pixelFormat]; o.rgb_offset[1] = kGreen[pixelFormat]; o.rgb_offset[2] = kBlue[pixelFormat];
@@ -872,6 +882,7 @@ static int decompress_planes(tjs *t, const char *fn, const unsigned char *jpegBu
   if (decode_setup(t, fn, jpegBuf, jpegSize, &in, &o, &W, &H)) return -1;
   if (t->subsamp == TJSAMP_UNKNOWN) return fail(t, fn, "Could not determine subsampling level of JPEG image");
   if (t->subsamp != TJSAMP_GRAY && (!dstPlanes[1] || !dstPlanes[2])) return fail(t, fn, "Invalid argument");
+  if (in.num_components > 3) return fail(t, fn, "JPEG image must have 3 or fewer components");      /* turbojpeg.c:2089 */
   nc = t->subsamp == TJSAMP_GRAY ? 1 : 3;
   for (i = 0; i < nc; i++) {
     pw[i] = tj3YUVPlaneWidth(i, W, t->subsamp); ph[i] = tj3YUVPlaneHeight(i, H, t->subsamp);

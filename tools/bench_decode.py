@@ -20,7 +20,12 @@ of workload A from one thread -- one image per call, each call synchronises -- n
 in the same process, alternating rounds; the two libraries' pixels are compared first.
 --progressive default|simple: the workloads' images as progressive files (the reference's cjpeg with its default switches, or with
 -revert -progressive), decoded with Encoder.set_sources(progressive=True); phase_ms then holds "refinement", the refinement levels' time.
-usage: python tools/bench_decode.py [--progressive default|simple] [--workloads A,B] [--scale 1/1] [--dct fast] [--color rgb565] [--tj] [--seconds 2] [--repeats 3] [--out profiles/decode_bench]"""
+--source ycck420: instead of the above, workload A's 64 frames as four-component files -- 4K YCCK 4:2:0 with K sampled 2x2, made by the
+reference's tj3Compress8(TJPF_CMYK, TJCS_YCCK, TJSAMP_420) from the synthetic frames (inverted) plus a K plane -- decoded to CMYK pixels
+(k_upcolor4): files/s to device and to pinned host memory, the phase times, the reference's djpeg from 16 processes on the same files,
+and the YCbCr files of the same frames decoded in the same run for k_upcolor's time per pixel; every file's pixels are first compared
+with the reference's tj3Decompress8(TJPF_CMYK).
+usage: python tools/bench_decode.py [--progressive default|simple] [--source ycck420] [--workloads A,B] [--scale 1/1] [--dct fast] [--color rgb565] [--tj] [--seconds 2] [--repeats 3] [--out profiles/decode_bench]"""
 import argparse
 import json
 import os
@@ -188,6 +193,76 @@ def bench_tj(a, isa):
     return res
 
 
+def bench_ycck(a, isa):
+    """the 64 x 4K frames as YCCK 4:2:0 files -> CMYK pixels, next to the same frames as YCbCr 4:2:0 files -> RGB pixels"""
+    import cmyk_cases as K
+    import oracle_lib as O
+    import transcode_cases as TC
+    n = 64
+    with ThreadPoolExecutor(16) as ex:
+        imgs = list(ex.map(lambda i: O.synthetic_frame(3840, 2160, seed=1234 + i), range(n)))
+        cmyk = lambda im: np.ascontiguousarray(np.concatenate([255 - im, np.roll(im[..., 1:2], (540, 960), (0, 1))], axis=-1))
+        files = list(ex.map(lambda im: K.tj_compress(cmyk(im), K.TJCS_YCCK, K.TJSAMP_420, quality=75), imgs))
+        ycc = list(ex.map(lambda im: TC.cjpeg(im, ["-revert", "-quality", "75", "-sample", "2x2"]), imgs))
+    del imgs
+    info = M.jpeg_info(files[0])
+    w, h = info.image_width, info.image_height
+    assert info.jpeg_color_space == M.CS_YCCK and [info.h_samp_factor[c] for c in range(4)] == [2, 1, 1, 2]
+    res = {"files": n, "width": w, "height": h, "source_bytes": sum(len(f) for f in files), "ycbcr_source_bytes": sum(len(f) for f in ycc),
+           "kernel_sha": {k: isa[k]["sha"] for k in ("k_dec_sync", "k_dec_store", "k_idct", "k_upcolor", "k_upcolor4")},
+           "vgpr": {k: isa[k]["vgpr"] for k in ("k_upcolor", "k_upcolor4")}}
+    enc = M.Encoder(M.params_from_jpeg(files[0], revert=True), max_batch=n)
+    opts = M.decode_opts()
+    outs = enc.decode_host(files, opts=opts)
+    assert outs[0].shape == (h, w, 4)
+    with ThreadPoolExecutor(16) as ex:
+        same = list(ex.map(lambda i: bool(np.array_equal(outs[i], K.tj_pixels(files[i])[1])), range(n)))
+    del outs
+    res["identical_to_reference"] = all(same)
+    res["reference_files_per_s"], res["reference_on_ramdisk"] = reference_rate(files)
+    res["reference_ycbcr_files_per_s"] = reference_rate(ycc)[0]
+    host = M.pinned_empty((n, h, w, 4))
+    paths = {"device": None, "host": host}
+    res["paths"] = {}
+    for name, dst in paths.items():
+        timed(enc, files, 0.0, dst, opts)              # warm-up
+        res["paths"][name] = {"files_per_s": []}
+    for _ in range(a.repeats):                         # alternating
+        for name, dst in paths.items():
+            res["paths"][name]["files_per_s"].append(timed(enc, files, a.seconds, dst, opts))
+    for name in paths:
+        c = res["paths"][name]
+        v = c["files_per_s"]
+        c["median_files_per_s"] = median(v)
+        c["median_mpixels_per_s"] = c["median_files_per_s"] * w * h / 1e6
+        c["spread"] = (max(v) - min(v)) / c["median_files_per_s"]
+        c["ratio_to_reference"] = c["median_files_per_s"] / res["reference_files_per_s"]
+    del host
+    # the phases of both kinds of file, alternating calls under the profiler (two warm-up rounds, the median of 7)
+    enc3 = M.Encoder(M.params_from_jpeg(ycc[0], revert=True), max_batch=n)
+    ms = {"ycck": [], "ycbcr": []}
+    for e in (enc, enc3):
+        e.set_profiling(1)
+    for r in range(9):
+        for name, e, fs in (("ycck", enc, files), ("ycbcr", enc3, ycc)):
+            e.submit_decode(fs, opts=opts)
+            e.sync()
+            if r >= 2:
+                ms[name].append(dict(e.transcode_stats()["ms"], **e.decode_stats()["ms"]))
+    stats = {"ycck": {k: v for k, v in enc.transcode_stats().items() if k != "ms"}, "ycbcr": {k: v for k, v in enc3.transcode_stats().items() if k != "ms"}}
+    enc.close()
+    enc3.close()
+    res["phase_ms"] = {name: {k: median([m[k] for m in v]) for k in v[0]} for name, v in ms.items()}
+    res["stats"] = stats
+    px = n * w * h
+    # algorithmic bytes per pixel of the colour kernels: 2.25 samples in and 4 bytes out against 1.5 in and 3 out
+    res["k_upcolor4_gbytes_per_s"] = px * 6.25 / res["phase_ms"]["ycck"]["upcolor"] / 1e6
+    res["k_upcolor_gbytes_per_s"] = px * 4.5 / res["phase_ms"]["ycbcr"]["upcolor"] / 1e6
+    res["upcolor4_over_upcolor_time_per_pixel"] = res["phase_ms"]["ycck"]["upcolor"] / res["phase_ms"]["ycbcr"]["upcolor"]
+    res["bytes_ratio"] = 6.25 / 4.5
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", default="A,B")
@@ -199,9 +274,10 @@ def main():
     ap.add_argument("--tj", action="store_true")
     ap.add_argument("--color", default=None, choices=["rgb565"])
     ap.add_argument("--progressive", default=None, choices=["default", "simple"])
+    ap.add_argument("--source", default=None, choices=["ycck420"])
     a = ap.parse_args()
     prog = a.progressive is not None
-    if a.dct or a.tj or a.color:
+    if a.dct or a.tj or a.color or a.source:
         isa = json.load(open(os.path.join(ROOT, "mozjpeg_amd", "kernel_isa.json")))
         result = {"source_stamp": isa.get("source_stamp")}
         if a.dct:
@@ -213,6 +289,9 @@ def main():
         if a.tj:
             result["tj"] = bench_tj(a, isa["kernels"])
             print(json.dumps({"tj": result["tj"]}), flush=True)
+        if a.source:
+            result["ycck420"] = bench_ycck(a, isa["kernels"])
+            print(json.dumps({"ycck420": result["ycck420"]}), flush=True)
         if a.out:
             with open(a.out + ".json", "w") as f:
                 json.dump(result, f, indent=1)
