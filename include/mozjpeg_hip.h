@@ -326,7 +326,8 @@ int mjh_encoder_sync(mjh_encoder *e);
  * Accepted: Huffman-coded sequential DCT files (SOF0, SOF1), 8-bit, 1 or 3 components, one interleaved scan or several
  * scans (every component in exactly one), any restart intervals.  MJH_EUNSUPPORTED: progressive (unless asked for, see
  * mjh_encoder_set_sources below), arithmetic, lossless (decoded to samples when asked for, MJH_SRC_LOSSLESS below; never re-compressed),
- * 12-bit, 2 components, DNL.  COM / APPn markers are not copied (-copy none).
+ * 12-bit, 2 components, DNL.  COM / APPn markers are not copied (-copy none) unless mjh_encoder_set_copy_markers asks for
+ * them (-copy comments / all / icc, below).
  * Four components (Adobe-style CMYK and YCCK files) are read by the marker walk and DECODED (mjh_decode_host: pixels, planes,
  * coefficients), never written: mjh_params_from_jpeg gives parameters an encoder can be created from (color_transform
  * MJH_COLOR_CMYK / MJH_COLOR_YCCK), and mjh_transcode_host, mjh_encoder_set_transform and every mjh_encode_* call on such an
@@ -466,6 +467,39 @@ int mjh_transcode_batch_size(mjh_encoder *e);
  * milliseconds of the decoder's phases: [0] first pass + synchronisation rounds, [1] block indices, [2] storing pass,
  * [3] DC sums + scrub.  Any pointer may be NULL. */
 int mjh_transcode_stats(mjh_encoder *e, int *subseq, int *rounds, int *host_syncs, float ms[4]);
+/* ---- COM / APPn markers kept (jpegtran -copy), ICC profiles written (cjpeg -icc, jpegtran -icc) ----
+ * The copy modes are JCOPY_OPTION's (transupp.h): MJH_COPY_NONE is the state of a new encoder and everything above without change. */
+#define MJH_COPY_NONE           0
+#define MJH_COPY_COMMENTS       1   /* COM only (jpegtran's own default) */
+#define MJH_COPY_ALL            2   /* COM + APP0..15 */
+#define MJH_COPY_ALL_EXCEPT_ICC 3   /* all but APP2 */
+#define MJH_COPY_ICC            4   /* APP2 only */
+typedef struct {
+  int marker;                /* 0xFE (COM) or 0xE0..0xEF (APPn) */
+  size_t data_offset;        /* of the segment's data in the file: the segment itself begins 4 bytes in front, FF xx len len */
+  unsigned data_length;      /* without the two length bytes */
+} mjh_jpeg_marker;
+/* The reference's marker_list of a file under one copy mode (jcopy_markers_setup, transupp.c:2312-2336): every COM / APPn segment
+ * the mode saves, in file order -- those between the scans and behind the last one too (jpeg_read_coefficients reads the whole
+ * file before anything is written), and JFIF / Adobe segments, which only the writing side may leave out.  accept: the MJH_SRC_*
+ * mask of mjh_jpeg_probe_ex; a file the probe refuses is refused here in the same words.  At most `cap` entries are written to
+ * list (may be NULL with cap 0); more markers than that: MJH_EINVAL with the number in *count. */
+int mjh_jpeg_markers(const void *jpeg, size_t size, unsigned accept, int copy_mode, mjh_jpeg_marker *list, int cap, int *count);
+/* The copy mode of the following mjh_transcode_host calls on e (unknown: MJH_EINVAL).  The saved markers go out right behind the
+ * SOI / JFIF APP0 / Adobe APP14 the encoder writes, in file order (jcopy_markers_execute, transupp.c:2345-2388): a JFIF APP0 is
+ * left out when the encoder writes its own, an Adobe APP14 likewise; a JFXX APP0 is copied.  When the FIRST saved marker is an
+ * APP1 that begins "Exif\0\0" (transupp.c:2115-2143) the encoder's JFIF APP0 is not written -- the file begins SOI, APP1 -- and,
+ * where the destination's size differs from the source's (crop, trim, a transposing transform), ExifImageWidth / ExifImageHeight
+ * of its ExifSubIFD are rewritten (adjust_exif_parameters; in the library's copy, never in the caller's buffer).
+ * The markers are inserted where the finished files are handed to the host (k_pack_results_spliced); the files in device memory
+ * never hold them.  On an encoder made for four-component files the call is accepted; the calls that write stay refused. */
+int mjh_encoder_set_copy_markers(mjh_encoder *e, int copy_mode);
+/* An ICC profile for every file the encoder produces from now on (jpeg_write_icc_profile, jcicc.c:49-80: APP2 segments of at
+ * most 65519 profile bytes, each "ICC_PROFILE\0", sequence number, count): every mjh_encode_* call of every coder family, where
+ * it stands right behind the SOI / APP0 / APP14 (cjpeg.c:957-992), and mjh_transcode_host, where it follows the copied markers
+ * and MJH_COPY_ALL acts as MJH_COPY_ALL_EXCEPT_ICC, MJH_COPY_ICC as MJH_COPY_NONE (jpegtran.c:601-604).  NULL, 0 clears it.
+ * MJH_EINVAL: a non-NULL pointer with length 0, or more than 255 segments.  The bytes are copied.  Synchronises with the device. */
+int mjh_encoder_set_icc_profile(mjh_encoder *e, const void *icc, size_t len);
 
 /* ---- lossless transforms while re-compressing (jpegtran -rotate / -flip / -transpose / -transverse / -crop / -grayscale) ----
  * The semantics are transupp.c's as jpegtran.c drives them: the bytes of `jpegtran -copy none <transform> <coding switches>`.
@@ -636,12 +670,14 @@ int mjh_enc_onepass_stats(mjh_encoder *e, int *enabled, unsigned long long *long
  * 3 the general kernel, 4 the speculative pair of one- and two-frame calls. */
 int mjh_get_dc_path(mjh_encoder *e, int *path);
 
-/* Size in bytes of JPEG i of the last batch (synchronises). */
+/* Size in bytes of JPEG i of the last batch (synchronises): with a copy mode or an ICC profile set, of the file with its markers. */
 int mjh_get_jpeg_size(mjh_encoder *e, int i, size_t *size);
 /* Copy JPEG i of the last batch to host memory (synchronises). */
 int mjh_get_jpeg(mjh_encoder *e, int i, void *dst, size_t cap, size_t *size);
 /* Device-side view of the outputs of the last batch: file i starts at base + i*stride and is
- * sizes[i] bytes long (sizes is a device pointer to uint32). */
+ * sizes[i] bytes long (sizes is a device pointer to uint32).  These are the files BEFORE the hand-over: while a copy mode
+ * (mjh_encoder_set_copy_markers) or an ICC profile (mjh_encoder_set_icc_profile) is set the call is MJH_EUNSUPPORTED, since
+ * the markers go in at the hand-over and the device buffer never holds the files the other accessors return. */
 int mjh_get_output_device(mjh_encoder *e, void **d_base, size_t *stride, void **d_sizes);
 
 /* The Huffman table entry `scan` of the scan script was coded with in image `image` of the last batch: bits[0..16] (counts per

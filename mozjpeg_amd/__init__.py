@@ -74,6 +74,21 @@ class JpegScanEx(C.Structure):
 SRC_PROGRESSIVE = 1         # MJH_SRC_PROGRESSIVE
 SRC_LOSSLESS = 2            # MJH_SRC_LOSSLESS
 MAX_SRC_SCANS = 64          # MJH_MAX_SRC_SCANS: the cap on the scans of one progressive file
+COPY_MODES = {"none": 0, "comments": 1, "all": 2, "all_except_icc": 3, "icc": 4}      # MJH_COPY_*: jpegtran -copy
+
+
+class JpegMarker(C.Structure):
+    """mjh_jpeg_marker: one saved COM / APPn segment of a source file (mjh_jpeg_markers)"""
+    _fields_ = [("marker", C.c_int), ("data_offset", C.c_size_t), ("data_length", C.c_uint)]
+
+
+def copy_mode(mode):
+    """MJH_COPY_* of a -copy name ("none", "comments", "all", "all_except_icc", "icc") or of the number itself"""
+    if isinstance(mode, str):
+        if mode not in COPY_MODES:
+            raise MjhError(EINVAL, "copy mode %r (one of %s)" % (mode, ", ".join(COPY_MODES)))
+        return COPY_MODES[mode]
+    return int(mode)
 
 
 class Transform(C.Structure):
@@ -183,6 +198,10 @@ def lib():
         L.mjh_params_from_jpeg_transform.argtypes = [C.POINTER(JpegInfo), C.POINTER(Transform), C.c_int, C.POINTER(Params)]
         L.mjh_encoder_set_transform.argtypes = [C.c_void_p, C.POINTER(Transform)]
         L.mjh_transcode_host.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int]
+        if hasattr(L, "mjh_jpeg_markers"):      # (absent from an older library loaded for an A/B run)
+            L.mjh_jpeg_markers.argtypes = [C.c_char_p, C.c_size_t, C.c_uint, C.c_int, C.POINTER(JpegMarker), C.c_int, C.POINTER(C.c_int)]
+            L.mjh_encoder_set_copy_markers.argtypes = [C.c_void_p, C.c_int]
+            L.mjh_encoder_set_icc_profile.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
         L.mjh_transcode_status.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p)]
         L.mjh_transcode_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float)]
         if hasattr(L, "mjh_decode_host"):             # (absent from an older MOZJPEG_AMD_LIB variant, as below)
@@ -371,6 +390,25 @@ def jpeg_info(data, progressive_sources=False, lossless_sources=False):
     return info
 
 
+def jpeg_markers(data, copy="all", progressive_sources=False, lossless_sources=False, cap=None):
+    """The COM / APPn segments of a file that a -copy mode saves (mjh_jpeg_markers = the reference's marker_list), in file order:
+    [(marker code, data bytes), ...] -- those between the scans and behind the last one too, and JFIF / Adobe segments, which only
+    the writing side leaves out.  A file jpeg_info() refuses is refused in the same words.  cap: room for that many (None: as
+    many as there are); more raise MjhError(EINVAL) naming the count."""
+    data = bytes(data)
+    mode, accept = copy_mode(copy), _src_accept(progressive_sources, lossless_sources)
+    n = C.c_int()
+    room = 64 if cap is None else int(cap)
+    while True:
+        lst = (JpegMarker * max(room, 1))()
+        rc = lib().mjh_jpeg_markers(data, len(data), accept, mode, lst, room, C.byref(n))
+        if rc == EINVAL and cap is None and n.value > room:
+            room = n.value
+            continue
+        _chk(rc)
+        return [(m.marker, data[m.data_offset:m.data_offset + m.data_length]) for m in lst[:n.value]]
+
+
 TRANSFORMS = {"flip_h": 1, "flip_v": 2, "transpose": 3, "transverse": 4, "rot90": 5, "rot180": 6, "rot270": 7}   # JXFORM_CODE
 
 
@@ -444,9 +482,12 @@ _recompress_encoders = {}
 _LOSSLESS_NO_COEFS = "lossless source file (SOF3): it has no DCT coefficients (jpeg_copy_critical_parameters refuses it as well: JERR_NOTIMPL, jctrans.c:83)"
 
 
-def recompress(files, *, max_batch=64, device=0, progressive_sources=False, lossless_sources=False, **switches):
+def recompress(files, *, max_batch=64, device=0, progressive_sources=False, lossless_sources=False, copy="none", icc=None, **switches):
     """Re-compress JPEG files on the GPU: what `jpegtran -copy none` + the switches (revert, optimize, progressive, fastcrush,
-    restart) writes for each of them, in input order.  The files are grouped by what a batch must have in common; one encoder
+    restart) writes for each of them, in input order.  copy: jpegtran's -copy ("none", "comments", "all", "icc": the COM / APPn
+    markers of every source that its result keeps, Encoder.set_copy); icc: the bytes of an ICC profile written into every result
+    (jpegtran -icc FILE, Encoder.set_icc_profile), in place of the sources' own under "all".  A source is compared with its result
+    as it is returned, markers included.  The files are grouped by what a batch must have in common; one encoder
     per group is kept for later calls.  In the max-compression profile without `revert` / `progressive` a source that is
     smaller than its re-coded file is returned as it came (jpegtran.c:171, :774-777).  A file that cannot be re-coded
     (unsupported type, malformed headers, damaged entropy-coded data) gets the MjhError in its slot; the others are unaffected.
@@ -475,8 +516,9 @@ def recompress(files, *, max_batch=64, device=0, progressive_sources=False, loss
     if transforming:
         prefer_smallest = False
     key_sw = tuple(sorted((k, bytes(v) if isinstance(v, Transform) else v) for k, v in switches.items()))
+    mode, icc = copy_mode(copy), None if icc is None else bytes(icc)
     for sig, (info, idx) in groups.items():
-        key = (sig, key_sw, device, LIB_PATH)
+        key = (sig, key_sw, device, LIB_PATH, mode, icc)
         enc = _recompress_encoders.get(key)
         if enc is not None:
             enc.set_sources(progressive=progressive_sources)
@@ -486,6 +528,10 @@ def recompress(files, *, max_batch=64, device=0, progressive_sources=False, loss
             try:
                 enc = _recompress_encoders[key] = Encoder(params_from_jpeg(info, **switches), max_batch=min(max_batch, len(idx)), device=device)
                 enc.set_sources(progressive=progressive_sources)
+                if mode:
+                    enc.set_copy(mode)
+                if icc is not None:
+                    enc.set_icc_profile(icc)
             except MjhError as exc:         # a transform this group's geometry refuses (perfect, a crop outside the image, ...)
                 _recompress_encoders.pop(key, None)
                 if not (transforming or switches.get("perfect") or exc.code == EUNSUPPORTED):      # (a frame no encoder exists for)
@@ -814,6 +860,20 @@ class Encoder:
         self._progressive = bool(progressive)
         self._lossless = bool(lossless)
         _chk(lib().mjh_encoder_set_sources(self._h, _src_accept(progressive, lossless)))
+
+    def set_copy(self, mode):
+        """The COM / APPn markers the following transcode calls keep (mjh_encoder_set_copy_markers): jpegtran's -copy name
+        ("none", "comments", "all", "all_except_icc", "icc") or the MJH_COPY_* number."""
+        _chk(lib().mjh_encoder_set_copy_markers(self._h, copy_mode(mode)))
+
+    def set_icc_profile(self, profile):
+        """An ICC profile for every file the encoder produces from now on (mjh_encoder_set_icc_profile: cjpeg -icc, jpegtran -icc);
+        None clears it."""
+        if profile is None:
+            _chk(lib().mjh_encoder_set_icc_profile(self._h, None, 0))
+        else:
+            profile = bytes(profile)
+            _chk(lib().mjh_encoder_set_icc_profile(self._h, profile if profile else b"\0", len(profile)))
 
     def prog_stats(self):
         """levels of scans in the last call's progressive files (first scans are level 0 and count; 0: no progressive file) and the

@@ -441,6 +441,21 @@ struct mjh_encoder {
   unsigned src_accept = 0;
   int pg_levels = 0;                    // levels of scans in the last call's progressive files (0: none in the call)
   hipEvent_t pg_ev[2] = { nullptr, nullptr }; bool pg_timed = false;
+  // mjh_encoder_set_copy_markers / mjh_encoder_set_icc_profile: the settings (a twin reads its owner's), the profile's APP2 segments
+  // as they are written (host + device), and what the files of the LAST batch get at the hand-over -- `sp`, written by the call
+  // that queued the batch: per file the bytes of the encoder's SOI / APP0 / APP14 that stay and its runs of source markers in
+  // h_tc / d_tc (MjhSpliceFile; nothing per file for an encode call: the profile alone).  d_splan[b]: the plan of the batch in arena b.
+  int copy_mode = MJH_COPY_NONE;
+  std::shared_ptr<const std::vector<uint8_t>> icc;
+  uint8_t *d_icc = nullptr;
+  struct Splice {
+    bool on = false, runs_stale = false;      // runs_stale: a later decode call has staged other files over the runs' bytes
+    std::shared_ptr<const std::vector<uint8_t>> icc;
+    std::vector<MjhSpliceFile> files;
+    std::vector<MjhSpliceRun> runs;
+  } sp;
+  uint8_t *d_splan[2] = { nullptr, nullptr }, *h_splan[2] = { nullptr, nullptr }; size_t splan_cap[2] = { 0, 0 };
+  int sp_reads_tc = -1;                 // the arena whose queued hand-over reads d_tc (-1: none): nothing may be staged over it before that
   // lossless files (mjh_decode_lossless.hip), decoded by a lossless encoder: one plane of differences per component and image, which
   // the undifferencing kernels turn into samples in place, and the column-0 chains of the predictor 1 planes (made by the first call)
   int16_t *d_lldiff = nullptr; unsigned *d_llabove = nullptr;
@@ -937,6 +952,8 @@ static void free_all(mjh_encoder *e)
   if (e->h_cfin) (void)hipHostFree(e->h_cfin);
   for (void *q : { (void *)e->d_tc, (void *)e->d_tdesc, e->d_tsub, (void *)e->d_tdiff, (void *)e->d_tdiff_x, (void *)e->d_tstat, (void *)e->d_tchanged, (void *)e->d_lldiff, (void *)e->d_llabove }) if (q) (void)mjh_guard_free(q);
   for (void *q : { (void *)e->h_tc, (void *)e->h_tdesc, (void *)e->h_tstat[0], (void *)e->h_tstat[1], (void *)e->h_tflag }) if (q) (void)hipHostFree(q);
+  for (void *q : { (void *)e->d_icc, (void *)e->d_splan[0], (void *)e->d_splan[1] }) if (q) (void)mjh_guard_free(q);
+  for (void *q : { (void *)e->h_splan[0], (void *)e->h_splan[1] }) if (q) (void)hipHostFree(q);
   for (hipEvent_t ev : e->tc_ev) if (ev) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : e->pg_ev) if (ev) (void)hipEventDestroy(ev);
   if (e->d_pixout) (void)mjh_guard_free(e->d_pixout);
@@ -1668,6 +1685,45 @@ static MjhConst dc_chain_view(const mjh_encoder *e, const MjhConst &CV)
 static int run_lossless(mjh_encoder *e, const void *d_pixels, size_t row_pitch, size_t image_stride, int n, hipStream_t s,
                         hipEvent_t input_read, hipEvent_t before_output);
 
+// ---- markers at the hand-over (mjh_encoder_set_copy_markers, mjh_encoder_set_icc_profile) -----------------------------------------
+static const mjh_encoder *settings_of(const mjh_encoder *e) { return e->owner ? e->owner : e; }
+// the copy mode of a transcode call: with a profile to write, the source's own APP2 segments are not copied (jpegtran.c:601-604)
+static int splice_mode(const mjh_encoder *e)
+{
+  const mjh_encoder *r = settings_of(e);
+  if (!r->icc) return r->copy_mode;
+  return r->copy_mode == MJH_COPY_ALL ? MJH_COPY_ALL_EXCEPT_ICC : r->copy_mode == MJH_COPY_ICC ? MJH_COPY_NONE : r->copy_mode;
+}
+// an encode call (pixels, planes, coefficients): its files get the profile, if there is one, and nothing else
+static void splice_plan_encode(mjh_encoder *e, int n)
+{
+  mjh_encoder::Splice &sp = e->sp;
+  sp.icc = settings_of(e)->icc;
+  sp.on = sp.icc != nullptr;
+  sp.runs_stale = false;
+  sp.runs.clear();
+  sp.files.assign(sp.on ? (size_t)n : 0, MjhSpliceFile{ (unsigned)e->file_hdr_len, 0u, 0u, 0u });
+}
+// file i of the last batch as it leaves, from the `raw` bytes of its slot in d_out (the files the pack kernel left to the host,
+// and every file of a batch that was not handed over through an arena)
+static size_t spliced_size(const mjh_encoder *e, int i, size_t raw)
+{
+  const mjh_encoder::Splice &sp = e->sp;
+  if (!sp.on) return raw;
+  const size_t hdr = (size_t)e->file_hdr_len;
+  return sp.files[(size_t)i].keep + sp.files[(size_t)i].ins + (sp.icc ? sp.icc->size() : 0) + (raw > hdr ? raw - hdr : 0);
+}
+static void splice_host(const mjh_encoder *e, int i, const uint8_t *raw, size_t raw_len, uint8_t *dst)
+{
+  const mjh_encoder::Splice &sp = e->sp;
+  const MjhSpliceFile &f = sp.files[(size_t)i];
+  const size_t hdr = (size_t)e->file_hdr_len;
+  memcpy(dst, raw, f.keep); dst += f.keep;
+  for (unsigned k = 0; k < f.nrun; k++) { const MjhSpliceRun &r = sp.runs[f.run0 + k]; memcpy(dst, e->h_tc + r.off, r.len); dst += r.len; }
+  if (sp.icc) { memcpy(dst, sp.icc->data(), sp.icc->size()); dst += sp.icc->size(); }
+  if (raw_len > hdr) memcpy(dst, raw + hdr, raw_len - hdr);
+}
+
 static int run_pipeline(mjh_encoder *e, const void *d_pixels, size_t row_pitch, size_t image_stride, int n, hipStream_t s,
                         const MjhPlaneSrc *plane_src = nullptr, const MjhCoefSrc *coef_src = nullptr,
                         hipEvent_t input_read = nullptr, hipEvent_t before_output = nullptr)
@@ -1682,6 +1738,7 @@ static int run_pipeline(mjh_encoder *e, const void *d_pixels, size_t row_pitch, 
   e->res_buf = -1;
   e->coef_input = coef_src != nullptr;
   e->last_stream = s;
+  if (!e->tc_preloaded) splice_plan_encode(e, n);      // (a transcode call has made its files' plan: decode_front)
   if (!e->owner) e->last = nullptr;      // (mjh_encode_device names the twin afterwards when it ran the batch)
   // two batches in flight: the other buffer set's AC trellis kernel has the chip for itself -- nothing of this batch starts before it has ended
   mjh_encoder *const peer = e->owner ? e->owner : e->twin;
@@ -2399,8 +2456,31 @@ static int queue_pack(mjh_encoder *e, int b, int n)
   void *d_res = nullptr, *d_tab = nullptr;
   HIPCHK(hipHostGetDevicePointer(&d_res, e->h_res[b], 0));
   HIPCHK(hipHostGetDevicePointer(&d_tab, e->h_tab[b], 0));
-  mjh_launch_pack_results(e->d_out, e->out_stride, e->d_sizes, (e->progressive || e->arith) ? nullptr : e->d_meta, (e->progressive || e->arith) ? e->d_prog_ctl : nullptr,
-                          n, d_res, e->res_cap, d_tab, ps);
+  const void *pk_meta = (e->progressive || e->arith) ? nullptr : e->d_meta, *pk_ctl = (e->progressive || e->arith) ? e->d_prog_ctl : nullptr;
+  if (!e->sp.on) mjh_launch_pack_results(e->d_out, e->out_stride, e->d_sizes, pk_meta, pk_ctl, n, d_res, e->res_cap, d_tab, ps);
+  else {
+    // the batch's plan travels in front of the kernel on the same stream (arena b's previous hand-over lies behind it in stream order)
+    const mjh_encoder::Splice &sp = e->sp;
+    const size_t fbytes = (size_t)n * sizeof(MjhSpliceFile), rbytes = sp.runs.size() * sizeof(MjhSpliceRun);
+    // (pinned staging, so that the copy is queued and not waited for; its previous copy belongs to the batch of two calls ago,
+    // whose files the caller has normally collected by now)
+    if (e->res_n[b] && !e->res_waited[b]) HIPCHK(hipEventSynchronize(e->ev_packed[b]));
+    if (fbytes + rbytes > e->splan_cap[b]) {
+      if (e->d_splan[b]) { (void)mjh_guard_free(e->d_splan[b]); e->d_splan[b] = nullptr; }
+      if (e->h_splan[b]) { (void)hipHostFree(e->h_splan[b]); e->h_splan[b] = nullptr; }
+      e->splan_cap[b] = 0;
+      HIPCHK(mjh_dmalloc((void **)&e->d_splan[b], 2 * (fbytes + rbytes)));
+      HIPCHK(mjh_numa_host_alloc((void **)&e->h_splan[b], 2 * (fbytes + rbytes), hipHostMallocDefault, e->device));
+      e->splan_cap[b] = 2 * (fbytes + rbytes);
+    }
+    memcpy(e->h_splan[b], sp.files.data(), fbytes);
+    if (rbytes) memcpy(e->h_splan[b] + fbytes, sp.runs.data(), rbytes);
+    HIPCHK(hipMemcpyAsync(e->d_splan[b], e->h_splan[b], fbytes + rbytes, hipMemcpyHostToDevice, ps));
+    mjh_launch_pack_results_spliced(e->d_out, e->out_stride, e->d_sizes, pk_meta, pk_ctl, n, (const MjhSpliceFile *)e->d_splan[b],
+                                    (const MjhSpliceRun *)(e->d_splan[b] + fbytes), e->d_tc, sp.icc ? e->d_icc : nullptr,
+                                    sp.icc ? (unsigned)sp.icc->size() : 0u, (unsigned)e->file_hdr_len, d_res, e->res_cap, d_tab, ps);
+    if (rbytes) e->sp_reads_tc = b;
+  }
   HIPCHK(hipEventRecord(e->ev_packed[b], ps));
   e->res_buf = b;
   e->res_n[b] = n;
@@ -2782,6 +2862,47 @@ static bool make_dec_table(const uint8_t bits[17], const uint8_t vals[256], bool
 static size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 int mjh_transform_plan(const mjh_jpeg_info *f, const mjh_transform *t, MjhXformPlan *g);   // mjh_jpeg_parse.cpp
+int mjh_probe_markers(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_info *info, mjh_jpeg_scan_ex *scans, int cap, int *num_scans,
+                      int copy_mode, std::vector<mjh_jpeg_marker> *saved);                  // mjh_jpeg_parse.cpp
+
+// What adjust_exif_parameters (transupp.c:1880-2028) does to the TIFF structure of an Exif segment (t: behind "Exif\0\0"): the
+// entries ExifImageWidth (0xA002) and ExifImageHeight (0xA003) of the ExifSubIFD that IFD0's entry 0x8769 points to become LONG,
+// count 1, with the low 16 bits of the new size.  Offsets are followed only when their upper 16 bits are zero, every read is
+// checked against the segment as the reference checks it, and anything that does not fit leaves the segment as it was from
+// there on (entries already rewritten stay rewritten, as in the reference).
+static void adjust_exif_parameters(uint8_t *t, unsigned length, unsigned new_w, unsigned new_h)
+{
+  if (length < 12) return;
+  const bool be = t[0] == 'M' && t[1] == 'M';
+  if (!be && !(t[0] == 'I' && t[1] == 'I')) return;
+  auto u16 = [&](unsigned o) { return be ? ((unsigned)t[o] << 8) | t[o + 1] : ((unsigned)t[o + 1] << 8) | t[o]; };
+  auto put16 = [&](unsigned o, unsigned v) { t[o + (be ? 0 : 1)] = (uint8_t)(v >> 8); t[o + (be ? 1 : 0)] = (uint8_t)v; };
+  // a 32-bit offset whose upper half must be zero: its lower half, or -1
+  auto off32 = [&](unsigned o) { return u16(be ? o : o + 2) != 0 ? -1 : (int)u16(be ? o + 2 : o); };
+  if (u16(2) != 0x2A) return;
+  const int ifd0 = off32(4);
+  if (ifd0 < 0 || (unsigned)ifd0 > length - 2) return;
+  unsigned ntags = u16((unsigned)ifd0), pos = (unsigned)ifd0 + 2;
+  if (ntags == 0) return;
+  for (;; pos += 12) {
+    if (pos > length - 12) return;
+    if (u16(pos) == 0x8769) break;
+    if (--ntags == 0) return;
+  }
+  const int sub = off32(pos + 8);
+  if (sub < 0 || (unsigned)sub > length - 2) return;
+  ntags = u16((unsigned)sub);
+  if (ntags < 2) return;
+  pos = (unsigned)sub + 2;
+  for (; ntags; ntags--, pos += 12) {
+    if (pos > length - 12) return;
+    const unsigned tag = u16(pos);
+    if (tag != 0xA002 && tag != 0xA003) continue;
+    put16(pos + 2, 4);                                       // LONG
+    put16(be ? pos + 4 : pos + 6, 0); put16(be ? pos + 6 : pos + 4, 1);      // count 1
+    put16(be ? pos + 8 : pos + 10, 0); put16(be ? pos + 10 : pos + 8, (tag == 0xA002 ? new_w : new_h) & 0xFFFFu);
+  }
+}
 
 extern "C" int mjh_encoder_set_transform(mjh_encoder *e, const mjh_transform *t)
 {
@@ -2980,15 +3101,20 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
   std::vector<mjh_jpeg_info> infos((size_t)n);
   std::vector<std::vector<mjh_jpeg_scan_ex>> pscans((size_t)n);      // the scans of the call's progressive files
   e->pg_levels = 0; e->pg_timed = false;
+  // a transcode call with a copy mode: the same walk lists the COM / APPn segments the mode saves (the reference's marker_list)
+  const int cmode = pixels ? MJH_COPY_NONE : splice_mode(e);
+  std::vector<std::vector<mjh_jpeg_marker>> marks(cmode != MJH_COPY_NONE ? (size_t)n : 0);
   CopyPool::get().run(n, [&](int i) {
     int rc;
     if (!jpegs[i] || !sizes[i]) rc = fail(MJH_EINVAL, "empty file");
-    else if (!e->src_accept) rc = mjh_jpeg_probe(jpegs[i], sizes[i], &infos[i]);
+    else if (!e->src_accept) rc = cmode != MJH_COPY_NONE ? mjh_probe_markers(jpegs[i], sizes[i], 0u, &infos[i], nullptr, 0, nullptr, cmode, &marks[(size_t)i])
+                                                       : mjh_jpeg_probe(jpegs[i], sizes[i], &infos[i]);
     else {
       static thread_local std::vector<mjh_jpeg_scan_ex> room;
       room.resize(MJH_MAX_SRC_SCANS);
       int ns = 0;
-      rc = mjh_jpeg_probe_ex(jpegs[i], sizes[i], e->src_accept, &infos[i], room.data(), MJH_MAX_SRC_SCANS, &ns);
+      rc = cmode != MJH_COPY_NONE ? mjh_probe_markers(jpegs[i], sizes[i], e->src_accept, &infos[i], room.data(), MJH_MAX_SRC_SCANS, &ns, cmode, &marks[(size_t)i])
+                                  : mjh_jpeg_probe_ex(jpegs[i], sizes[i], e->src_accept, &infos[i], room.data(), MJH_MAX_SRC_SCANS, &ns);
       if (rc == MJH_OK && infos[i].sof_type == 3)
         rc = fail(MJH_EUNSUPPORTED, "lossless source file (SOF3): it has no DCT coefficients (jpeg_copy_critical_parameters refuses it as well: JERR_NOTIMPL, jctrans.c:83); "
                                     "mjh_decode_host decodes it on an encoder made from its own parameters (mjh_params_from_jpeg)");
@@ -3191,6 +3317,45 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
       e->tc_code[(size_t)i] = MJH_EINVAL; e->tc_text[(size_t)i] = why;
     } else if (file_levels > levels) levels = file_levels;
   }
+  // ---- 2b. what every file of a transcode call gets at the hand-over (jcopy_markers_execute, transupp.c:2345-2388; the Exif rule
+  // of jtransform_adjust_parameters, :2115-2143): the bytes of the encoder's SOI / APP0 / APP14 that stay, and the saved segments
+  // as runs of the staging buffer -- a run is a whole segment with its FF xx and length, segments that lie back to back are one run
+  mjh_encoder::Splice plan_sp;
+  std::vector<int> exif_fix((size_t)n, 0);      // 1: the file's first saved marker is an Exif APP1 whose dimension tags are rewritten
+  if (!pixels) {
+    plan_sp.icc = settings_of(e)->icc;
+    plan_sp.on = cmode != MJH_COPY_NONE || plan_sp.icc != nullptr;
+    const unsigned hdr = (unsigned)e->file_hdr_len;
+    const bool own_adobe = e->p.color_transform == MJH_COLOR_NONE && e->p.num_components == 3;      // (build_prefix)
+    if (plan_sp.on) plan_sp.files.assign((size_t)n, MjhSpliceFile{ hdr, 0u, 0u, 0u });
+    for (int i = 0; i < n && cmode != MJH_COPY_NONE; i++) {
+      if (e->tc_code[(size_t)i] != MJH_OK) continue;
+      const uint8_t *d = (const uint8_t *)jpegs[i];
+      const std::vector<mjh_jpeg_marker> &mk = marks[(size_t)i];
+      MjhSpliceFile &pf = plan_sp.files[(size_t)i];
+      const bool exif_first = !mk.empty() && mk[0].marker == 0xE1 && mk[0].data_length >= 6 && memcmp(d + mk[0].data_offset, "Exif\0\0", 6) == 0;
+      const bool own_jfif = e->p.write_JFIF_header && !exif_first;
+      if (exif_first && e->p.write_JFIF_header) {
+        if (own_adobe) {
+          e->tc_code[(size_t)i] = MJH_EUNSUPPORTED; e->tc_text[(size_t)i] = "an Exif APP1 in front of everything else on an encoder that writes both a JFIF APP0 and an Adobe APP14";
+          continue;
+        }
+        pf.keep = 2;      // SOI alone: the file begins SOI, APP1
+      }
+      exif_fix[(size_t)i] = exif_first && (e->p.image_width != infos[(size_t)i].image_width || e->p.image_height != infos[(size_t)i].image_height);
+      pf.run0 = (unsigned)plan_sp.runs.size();
+      for (const mjh_jpeg_marker &m : mk) {
+        const uint8_t *s = d + m.data_offset;
+        if (own_jfif && m.marker == 0xE0 && m.data_length >= 5 && memcmp(s, "JFIF\0", 5) == 0) continue;      // reject duplicate JFIF
+        if (own_adobe && m.marker == 0xEE && m.data_length >= 5 && memcmp(s, "Adobe", 5) == 0) continue;     // reject duplicate Adobe
+        const unsigned long long off = file_off[(size_t)i] + m.data_offset - 4;
+        const unsigned len = m.data_length + 4;
+        if (pf.nrun && plan_sp.runs.back().off + plan_sp.runs.back().len == off) plan_sp.runs.back().len += len;
+        else { plan_sp.runs.push_back(MjhSpliceRun{ off, len, 0u }); pf.nrun++; }
+        pf.ins += len;
+      }
+    }
+  }
   for (int i = 0; i < n; i++)
     if (e->tc_code[(size_t)i] != MJH_OK) return fail(e->tc_code[(size_t)i], "file %d: %s", i, e->tc_text[(size_t)i].c_str());
   const bool has_prog = levels > 0;
@@ -3230,7 +3395,18 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
     }
     memcpy(e->h_tdesc + o_xf, &X, sizeof(X));
   }
+  // the hand-over of an earlier batch that reads its markers out of d_tc has to be through before other files land there
+  if (e->sp_reads_tc >= 0) { HIPCHK(hipStreamWaitEvent(e->stream, e->ev_packed[e->sp_reads_tc], 0)); e->sp_reads_tc = -1; }
   CopyPool::get().run(n, [&](int i) { memcpy(e->h_tc + file_off[(size_t)i], jpegs[i], sizes[i]); });
+  if (pixels) e->sp.runs_stale = !e->sp.runs.empty();      // (the last transcode batch's runs lay in h_tc)
+  else {
+    for (int i = 0; i < n; i++)
+      if (exif_fix[(size_t)i]) {
+        const mjh_jpeg_marker &m = marks[(size_t)i][0];
+        adjust_exif_parameters(e->h_tc + file_off[(size_t)i] + m.data_offset + 6, m.data_length - 6, (unsigned)e->p.image_width, (unsigned)e->p.image_height);
+      }
+    e->sp = std::move(plan_sp);
+  }
   for (const DecDescSet &D : sets) {
     memcpy(e->h_tdesc + D.o_scans, D.scans.data(), D.scans.size() * sizeof(MjhDecScan));
     memcpy(e->h_tdesc + D.o_ps, D.ps.data(), D.ps.size() * sizeof(MjhDecProg));
@@ -3349,6 +3525,42 @@ extern "C" int mjh_encoder_set_sources(mjh_encoder *e, unsigned accept)
   if (!e) return fail(MJH_EINVAL, "null encoder");
   if (accept & ~(MJH_SRC_PROGRESSIVE | MJH_SRC_LOSSLESS)) return fail(MJH_EINVAL, "unknown source kinds 0x%x (MJH_SRC_PROGRESSIVE | MJH_SRC_LOSSLESS)", accept);
   e->src_accept = accept;
+  return MJH_OK;
+}
+
+extern "C" int mjh_encoder_set_copy_markers(mjh_encoder *e, int copy_mode)
+{
+  if (!e) return fail(MJH_EINVAL, "null encoder");
+  if (copy_mode < MJH_COPY_NONE || copy_mode > MJH_COPY_ICC) return fail(MJH_EINVAL, "unknown copy mode %d (MJH_COPY_NONE .. MJH_COPY_ICC)", copy_mode);
+  e->copy_mode = copy_mode;
+  return MJH_OK;
+}
+
+// jpeg_write_icc_profile (jcicc.c:49-80): segments of at most 65533 - 14 profile bytes behind "ICC_PROFILE\0", number, count
+extern "C" int mjh_encoder_set_icc_profile(mjh_encoder *e, const void *icc, size_t len)
+{
+  if (!e) return fail(MJH_EINVAL, "null encoder");
+  if ((icc == nullptr) != (len == 0)) return fail(MJH_EINVAL, "an ICC profile of %zu bytes at %s (NULL, 0 clears the profile)", len, icc ? "a non-NULL address" : "NULL");
+  const size_t per = 65533 - 14, nseg = (len + per - 1) / per;
+  if (nseg > 255) return fail(MJH_EINVAL, "an ICC profile of %zu bytes needs %zu APP2 segments: at most 255 exist", len, nseg);
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipDeviceSynchronize());      // a queued hand-over may still read the profile that goes
+  if (e->d_icc) { (void)mjh_guard_free(e->d_icc); e->d_icc = nullptr; }
+  e->icc.reset();
+  if (!icc) return MJH_OK;
+  std::vector<uint8_t> seg;
+  seg.reserve(len + nseg * 18);
+  const uint8_t *src = (const uint8_t *)icc;
+  for (size_t k = 0; k < nseg; k++) {
+    const size_t part = len - k * per < per ? len - k * per : per;
+    seg.push_back(0xFF); seg.push_back(0xE2); put2(seg, (int)(part + 14 + 2));
+    const uint8_t id[] = { 'I', 'C', 'C', '_', 'P', 'R', 'O', 'F', 'I', 'L', 'E', 0, (uint8_t)(k + 1), (uint8_t)nseg };
+    seg.insert(seg.end(), id, id + sizeof(id));
+    seg.insert(seg.end(), src + k * per, src + k * per + part);
+  }
+  HIPCHK(mjh_dmalloc((void **)&e->d_icc, up16(seg.size())));      // (the hand-over kernel reads whole aligned vectors)
+  HIPCHK(hipMemcpy(e->d_icc, seg.data(), seg.size(), hipMemcpyHostToDevice));
+  e->icc = std::make_shared<const std::vector<uint8_t>>(std::move(seg));
   return MJH_OK;
 }
 
@@ -4128,6 +4340,7 @@ static int fetch_sizes(mjh_encoder *e)
     for (int i = 0; i < e->last_n; i++)
       if (mt[i].bad_coef) return fail(MJH_EINVAL, "image %d holds a DCT coefficient out of range (JERR_BAD_DCT_COEF, jchuff.c:489,596,624)", i);
   }
+  for (int i = 0; i < e->last_n; i++) e->h_sizes[i] = (unsigned)spliced_size(e, i, e->h_sizes[i]);      // (no hand-over kernel ran: mjh_get_jpeg puts the profile in)
   e->sizes_valid = true;
   return MJH_OK;
 }
@@ -4156,12 +4369,25 @@ extern "C" int mjh_get_jpeg(mjh_encoder *e, int i, void *dst, size_t cap, size_t
     return MJH_OK;
   }
   HIPCHK(hipSetDevice(e->device));
+  if (e->sp.on) {
+    // the slot holds the file without its markers: the host puts them in (the slow path of files the arena has no room for)
+    const MjhSpliceFile &f = e->sp.files[(size_t)i];
+    if (f.nrun && e->sp.runs_stale) return fail(MJH_EINVAL, "the source files of this batch have left the staging buffer (a later decode call): file %d can no longer be put together", i);
+    const size_t raw = n - (spliced_size(e, i, (size_t)e->file_hdr_len) - (size_t)e->file_hdr_len);
+    std::vector<uint8_t> tmp(raw);
+    HIPCHK(hipMemcpy(tmp.data(), e->d_out + (size_t)i * e->out_stride, raw, hipMemcpyDeviceToHost));
+    splice_host(e, i, tmp.data(), raw, (uint8_t *)dst);
+    return MJH_OK;
+  }
   HIPCHK(hipMemcpy(dst, e->d_out + (size_t)i * e->out_stride, n, hipMemcpyDeviceToHost));
   return MJH_OK;
 }
 
 extern "C" int mjh_get_output_device(mjh_encoder *e, void **d_base, size_t *stride, void **d_sizes)
 {
+  if (e && (e->copy_mode != MJH_COPY_NONE || e->icc))
+    return fail(MJH_EUNSUPPORTED, "a copy mode or an ICC profile is set: the markers go in at the hand-over to the host (mjh_get_jpeg, mjh_collect), "
+                                  "the files in device memory do not hold them");
   e = cur(e);
   if (!e) return fail(MJH_EINVAL, "null encoder");
   if (d_base) *d_base = e->d_out;
@@ -4554,6 +4780,7 @@ static int run_lossless(mjh_encoder *e, const void *d_pixels, size_t row_pitch, 
   e->res_buf = -1;
   e->coef_input = false;
   e->last_stream = s;
+  splice_plan_encode(e, n);
   if (!e->owner) e->last = nullptr;
   Prof pr{ e, s };
   if (e->profiling && e->prof_calls < 256) {

@@ -137,6 +137,12 @@ struct MjhImageMeta {
   unsigned bad_coef;       // coefficient input only: a value no Huffman symbol exists for (JERR_BAD_DCT_COEF, jchuff.c:489,596,624)
 };
 
+// The hand-over with markers (k_pack_results_spliced): what the host decided for one file of the batch.  The file that leaves is
+//   slot[0 : keep] ++ run[run0] ++ .. ++ run[run0 + nrun - 1] ++ the ICC segments ++ slot[file_hdr_len : size]
+// where a run is a whole COM / APPn segment (or several that lie back to back) of the source file in the batch's staging buffer.
+#define MJH_SPLICE_RUNS 60               // runs of one file the kernel takes (its piece table has 64 entries); a file with more is left to the host (mjh_get_jpeg), as one that does not fit the arena
+struct MjhSpliceFile { unsigned keep, ins, run0, nrun; };      // ins: bytes of the file's runs together
+struct MjhSpliceRun { unsigned long long off; unsigned len, pad; };   // off: into the staging buffer of source files
 
 // ---- progressive mode (jcphuff.c, scan scripts jcparam.c:733-1004, scan search jcmaster.c:773-962) ----
 #define MJH_MAX_PROG_SCANS 72   // 64 script scans + the 3 per-component trellis statistics passes

@@ -6,6 +6,7 @@
 #include <stddef.h>
 #include <stdio.h>
 #include <string.h>
+#include <vector>
 
 #include "../../include/mozjpeg_hip.h"
 #include "mjh_internal.h"
@@ -36,7 +37,19 @@ static const int kNatural[64] = {
 // MJH_SRC_LOSSLESS) is reported the same way: its scans in ex[] with Ss = the predictor and Al = the point transform, checked as
 // start_pass_lossless (jdlossls.c:249-258) and start_input_pass (jddiffct.c:104-110) check them.
 static_assert(offsetof(mjh_jpeg_scan_ex, Ss) == sizeof(mjh_jpeg_scan), "mjh_jpeg_scan_ex begins with the fields of mjh_jpeg_scan");
-static int probe_walk(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_info *info, mjh_jpeg_scan_ex *ex, int cap, int *num_ex)
+// saves(mode, m): jcopy_markers_setup (transupp.c:2312-2336) -- does copy mode `mode` save marker code m
+static bool copy_mode_saves(int mode, int m)
+{
+  if (m == 0xFE) return mode != MJH_COPY_NONE && mode != MJH_COPY_ICC;
+  if (m < 0xE0 || m > 0xEF) return false;
+  if (mode == MJH_COPY_ALL) return true;
+  if (mode == MJH_COPY_ALL_EXCEPT_ICC) return m != 0xE2;
+  return mode == MJH_COPY_ICC && m == 0xE2;
+}
+
+// copy_mode / saved: the walk also lists the COM / APPn segments that mode saves (mjh_jpeg_markers), wherever they stand
+static int probe_walk(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_info *info, mjh_jpeg_scan_ex *ex, int cap, int *num_ex,
+                      int copy_mode = MJH_COPY_NONE, std::vector<mjh_jpeg_marker> *saved = nullptr)
 {
   const uint8_t *d = (const uint8_t *)jpeg;
   memset(info, 0, sizeof(*info));
@@ -71,6 +84,7 @@ static int probe_walk(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_i
     const uint8_t *s = d + pos + 2;
     const size_t n = len - 2;
     pos += len;
+    if (saved && copy_mode_saves(copy_mode, m)) saved->push_back(mjh_jpeg_marker{ m, (size_t)(s - d), (unsigned)n });
     switch (m) {
     case 0xC0: case 0xC1: case 0xC2: case 0xC3: case 0xC9: case 0xCA: case 0xCB:
     case 0xC5: case 0xC6: case 0xC7: case 0xCD: case 0xCE: case 0xCF: {
@@ -276,7 +290,7 @@ static int probe_walk(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_i
       }
       break;
     }
-    default:              // APPn, COM and the rest: skipped (-copy none)
+    default:              // APPn, COM and the rest: nothing to learn from them (a copy mode lists them above)
       break;
     }
   }
@@ -319,6 +333,35 @@ extern "C" int mjh_jpeg_probe_ex(const void *jpeg, size_t size, unsigned accept,
   if (!accept) { if (num_scans) *num_scans = 0; return probe_walk(jpeg, size, 0u, info, nullptr, 0, nullptr); }
   if (!scans || !num_scans || cap < 1) return pfail(MJH_EINVAL, "bad arguments: MJH_SRC_PROGRESSIVE and MJH_SRC_LOSSLESS need room for the scans");
   return probe_walk(jpeg, size, accept, info, scans, cap < MJH_MAX_SRC_SCANS ? cap : MJH_MAX_SRC_SCANS, num_scans);
+}
+
+// mjh_jpeg_probe / mjh_jpeg_probe_ex and the marker list of one copy mode in the same walk (mjh_encoder.cpp: a transcode call
+// with a copy mode reads every file once)
+int mjh_probe_markers(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_info *info, mjh_jpeg_scan_ex *scans, int cap, int *num_scans,
+                      int copy_mode, std::vector<mjh_jpeg_marker> *saved)
+{
+  saved->clear();
+  if (!accept) { if (num_scans) *num_scans = 0; return probe_walk(jpeg, size, 0u, info, nullptr, 0, nullptr, copy_mode, saved); }
+  return probe_walk(jpeg, size, accept, info, scans, cap < MJH_MAX_SRC_SCANS ? cap : MJH_MAX_SRC_SCANS, num_scans, copy_mode, saved);
+}
+
+extern "C" int mjh_jpeg_markers(const void *jpeg, size_t size, unsigned accept, int copy_mode, mjh_jpeg_marker *list, int cap, int *count)
+{
+  if (count) *count = 0;
+  if (!jpeg || cap < 0 || (cap > 0 && !list)) return pfail(MJH_EINVAL, "bad arguments");
+  if (accept & ~(MJH_SRC_PROGRESSIVE | MJH_SRC_LOSSLESS)) return pfail(MJH_EINVAL, "unknown source kinds 0x%x (MJH_SRC_PROGRESSIVE | MJH_SRC_LOSSLESS)", accept);
+  if (copy_mode < MJH_COPY_NONE || copy_mode > MJH_COPY_ICC) return pfail(MJH_EINVAL, "unknown copy mode %d (MJH_COPY_NONE .. MJH_COPY_ICC)", copy_mode);
+  static thread_local mjh_jpeg_info info;
+  static thread_local std::vector<mjh_jpeg_scan_ex> room;
+  static thread_local std::vector<mjh_jpeg_marker> saved;
+  if (accept) room.resize(MJH_MAX_SRC_SCANS);
+  int ns = 0;
+  const int rc = mjh_probe_markers(jpeg, size, accept, &info, accept ? room.data() : nullptr, MJH_MAX_SRC_SCANS, &ns, copy_mode, &saved);
+  if (rc) return rc;
+  if (count) *count = (int)saved.size();
+  if (saved.size() > (size_t)cap) return pfail(MJH_EINVAL, "%zu markers in the file, room for %d", saved.size(), cap);
+  for (size_t i = 0; i < saved.size(); i++) list[i] = saved[i];
+  return MJH_OK;
 }
 
 extern "C" int mjh_params_from_jpeg(const mjh_jpeg_info *info, int compress_profile, mjh_params *p)

@@ -2659,6 +2659,120 @@ k_pack_results(const uint8_t *__restrict__ out, size_t out_stride, const unsigne
   for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < nvec; i += gridDim.x * 256) d[i] = src[i];
 }
 
+// The same hand-over with COM / APPn markers and an ICC profile put in behind the file's first bytes (mjh_encoder_set_copy_markers,
+// mjh_encoder_set_icc_profile): file img leaves as the pieces
+//   slot[0 : keep] ++ run 0 ++ run 1 ++ ... ++ icc[0 : icc_len] ++ slot[hdr : size]
+// (MjhSpliceFile / MjhSpliceRun: the runs are segments of the source files in `tc`).  What is inserted has any length, so every
+// piece lands at its own shift against the 16-byte grid of the arena.  A workgroup keeps the file's pieces in LDS -- where each
+// begins in the output and where its bytes lie -- and walks them one by one: the output vectors that lie wholly inside a piece
+// are each put together from the two aligned source vectors they straddle (the shift is the same for all of them, a wave-uniform
+// value) and stored whole; the few vectors that hold the end of a piece, at most one per piece, are gathered byte by byte from
+// the pieces they span by the first lanes of the file's first workgroup and stored whole as well.  Nothing is stored in units
+// smaller than an aligned vector and nothing is read back over the host link.  Table and error flags: as k_pack_results.
+#define SPLICE_PIECES (MJH_SPLICE_RUNS + 3)
+__device__ __forceinline__ unsigned long long splice_size(const MjhSpliceFile &f, unsigned sz, unsigned hdr, unsigned icc_len)
+{
+  return (unsigned long long)f.keep + f.ins + icc_len + (sz > hdr ? sz - hdr : 0u);
+}
+
+__global__ void __launch_bounds__(256)
+k_pack_results_spliced(const uint8_t *__restrict__ out, size_t out_stride, const unsigned *__restrict__ sizes,
+                       const MjhImageMeta *__restrict__ meta, const MjhProgCtl *__restrict__ ctl, int n,
+                       const MjhSpliceFile *__restrict__ files, const MjhSpliceRun *__restrict__ runs, const uint8_t *__restrict__ tc,
+                       const uint8_t *__restrict__ icc, unsigned icc_len, unsigned hdr,
+                       uint8_t *__restrict__ dst, size_t cap, unsigned long long *__restrict__ table)
+{
+  __shared__ unsigned long long s_src[SPLICE_PIECES];      // address of the piece's first byte
+  __shared__ unsigned s_beg[SPLICE_PIECES + 1];            // output offset of the piece's first byte; [np]: the file's size
+  const int img = blockIdx.y;
+  unsigned long long off = 0;
+  for (int j = 0; j < img; j++) {
+    const unsigned long long r = (splice_size(files[j], sizes[j], hdr, icc_len) + 15ull) & ~15ull;
+    if (files[j].nrun <= MJH_SPLICE_RUNS && off + r <= cap) off += r;   // a file that does not fit (or is left to the host) takes no room
+  }
+  const MjhSpliceFile f = files[img];
+  const unsigned sz = sizes[img];
+  const unsigned long long total = splice_size(f, sz, hdr, icc_len);
+  const unsigned long long r = (total + 15ull) & ~15ull;
+  const bool fits = f.keep <= hdr && f.nrun <= MJH_SPLICE_RUNS && off + r <= cap && total < 0xFFFFFFF0ull;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    table[2 + 2 * img] = fits ? off : ~0ull;
+    table[3 + 2 * img] = total;
+    if (img == n - 1) table[0] = off + (fits ? r : 0ull);
+    if (img == 0) {
+      unsigned long long err = 0;
+      for (int j = 0; j < n; j++) {
+        if (meta && meta[j].total_bits == 0xFFFFFFFFu) err |= 1ull;
+        if (meta && meta[j].bad_coef) err |= 4ull;
+        if (ctl && ctl[j].error) err |= ctl[j].error == 1 ? 1ull : 2ull;
+      }
+      table[1] = err;
+    }
+  }
+  if (!fits) return;
+  // the piece table: head, runs, profile, body (an empty piece stays in the table with its length of 0)
+  const uint8_t *slot = out + (size_t)img * out_stride;
+  const int np = (int)f.nrun + 3;
+  if (threadIdx.x == 0) {
+    unsigned o = 0;
+    s_src[0] = (unsigned long long)(uintptr_t)slot; s_beg[0] = 0; o = f.keep;
+    for (unsigned k = 0; k < f.nrun; k++) {
+      const MjhSpliceRun rn = runs[f.run0 + k];
+      s_src[1 + k] = (unsigned long long)(uintptr_t)(tc + rn.off); s_beg[1 + k] = o; o += rn.len;
+    }
+    s_src[np - 2] = (unsigned long long)(uintptr_t)icc; s_beg[np - 2] = o; o += icc_len;
+    s_src[np - 1] = (unsigned long long)(uintptr_t)(slot + hdr); s_beg[np - 1] = o;
+    s_beg[np] = (unsigned)total;
+  }
+  __syncthreads();
+  uint4 *d = reinterpret_cast<uint4 *>(dst + off);
+  const unsigned lane = blockIdx.x * 256 + threadIdx.x, lanes = gridDim.x * 256;
+  for (int p = 0; p < np; p++) {
+    const unsigned b0 = s_beg[p], b1 = s_beg[p + 1];
+    const unsigned v0 = (b0 + 15u) >> 4, v1 = b1 >> 4;       // output vectors [v0, v1) lie wholly inside the piece
+    if (v0 >= v1) continue;
+    const unsigned long long a0 = s_src[p] + ((unsigned long long)v0 * 16u - b0);   // source address of vector v0's first byte
+    const unsigned sh = (unsigned)(a0 & 15ull), q = sh >> 2, rb = (sh & 3u) * 8u;
+    const uint4 *sv = reinterpret_cast<const uint4 *>((uintptr_t)(a0 - sh));
+    for (unsigned i = lane; i < v1 - v0; i += lanes) {
+      const uint4 lo = sv[i];
+      if (sh == 0) { d[v0 + i] = lo; continue; }
+      const uint4 hi = sv[i + 1];      // (holds the vector's last byte: inside the piece)
+      unsigned w0, w1, w2, w3, w4;
+      if (q == 0) { w0 = lo.x; w1 = lo.y; w2 = lo.z; w3 = lo.w; w4 = hi.x; }
+      else if (q == 1) { w0 = lo.y; w1 = lo.z; w2 = lo.w; w3 = hi.x; w4 = hi.y; }
+      else if (q == 2) { w0 = lo.z; w1 = lo.w; w2 = hi.x; w3 = hi.y; w4 = hi.z; }
+      else { w0 = lo.w; w1 = hi.x; w2 = hi.y; w3 = hi.z; w4 = hi.w; }
+      uint4 o;
+      o.x = (unsigned)(((((unsigned long long)w1) << 32) | w0) >> rb);
+      o.y = (unsigned)(((((unsigned long long)w2) << 32) | w1) >> rb);
+      o.z = (unsigned)(((((unsigned long long)w3) << 32) | w2) >> rb);
+      o.w = (unsigned)(((((unsigned long long)w4) << 32) | w3) >> rb);
+      d[v0 + i] = o;
+    }
+  }
+  // the vectors that hold a piece's end: lane t looks after the end of piece t, unless a later piece ends in the same vector
+  if (blockIdx.x == 0 && (int)threadIdx.x < np) {
+    const int t = (int)threadIdx.x;
+    const unsigned e = s_beg[t + 1], v = e >> 4;
+    const bool mine = (e & 15u) != 0 && (t == np - 1 || (s_beg[t + 2] >> 4) != v);
+    if (mine) {
+      int p = t;
+      while (p > 0 && s_beg[p] > v * 16u) p--;               // the piece that holds the vector's first byte
+      unsigned long long wl = 0, wh = 0;
+      const unsigned tot = s_beg[np];
+      for (unsigned k = 0; k < 16u && v * 16u + k < tot; k++) {
+        const unsigned pos = v * 16u + k;
+        while (pos >= s_beg[p + 1]) p++;
+        const uint8_t *sp = reinterpret_cast<const uint8_t *>((uintptr_t)s_src[p]);
+        const unsigned long long byte = sp[pos - s_beg[p]];
+        if (k < 8u) wl |= byte << (8u * k); else wh |= byte << (8u * (k - 8u));
+      }
+      d[v] = make_uint4((unsigned)wl, (unsigned)(wl >> 32), (unsigned)wh, (unsigned)(wh >> 32));
+    }
+  }
+}
+
 // =============================================================================================
 // host-callable launch wrappers (C++ linkage, used by mjh_encoder.cpp)
 // =============================================================================================
@@ -2671,6 +2785,15 @@ void mjh_launch_pack_results(const void *out, size_t out_stride, const unsigned 
 {
   hipLaunchKernelGGL(k_pack_results, dim3(16, n), dim3(256), 0, s, (const uint8_t *)out, out_stride, sizes, (const MjhImageMeta *)meta,
                      (const MjhProgCtl *)prog_ctl, n, (uint8_t *)dst, cap, (unsigned long long *)table);
+}
+
+void mjh_launch_pack_results_spliced(const void *out, size_t out_stride, const unsigned *sizes, const void *meta, const void *prog_ctl, int n,
+                                     const MjhSpliceFile *files, const MjhSpliceRun *runs, const void *tc, const void *icc, unsigned icc_len, unsigned hdr,
+                                     void *dst, size_t cap, void *table, hipStream_t s)
+{
+  hipLaunchKernelGGL(k_pack_results_spliced, dim3(16, n), dim3(256), 0, s, (const uint8_t *)out, out_stride, sizes, (const MjhImageMeta *)meta,
+                     (const MjhProgCtl *)prog_ctl, n, files, runs, (const uint8_t *)tc, (const uint8_t *)icc, icc_len, hdr,
+                     (uint8_t *)dst, cap, (unsigned long long *)table);
 }
 
 void mjh_launch_import_coefs(const MjhConst &C, const MjhCoefSrc &S, void *coef_q, void *meta, int n, hipStream_t s)

@@ -56,6 +56,10 @@ void mjh_launch_stuff(const unsigned *stream, size_t stream_words_per_image, con
                       unsigned *ff_totals, void *out, size_t out_stride, void *meta, unsigned *sizes, const unsigned *mpos, int nseg, int n, hipStream_t s);
 void mjh_launch_pack_results(const void *out, size_t out_stride, const unsigned *sizes, const void *meta, const void *prog_ctl, int n,
                              void *dst, size_t cap, void *table, hipStream_t s);
+// the same with markers put in behind the files' first bytes (MjhSpliceFile, mjh_internal.h): hdr = the encoder's SOI + APP0 / APP14
+void mjh_launch_pack_results_spliced(const void *out, size_t out_stride, const unsigned *sizes, const void *meta, const void *prog_ctl, int n,
+                                     const MjhSpliceFile *files, const MjhSpliceRun *runs, const void *tc, const void *icc, unsigned icc_len, unsigned hdr,
+                                     void *dst, size_t cap, void *table, hipStream_t s);
 void mjh_launch_spin(unsigned long long ticks_100mhz, hipStream_t s);   // one wave busy for that long (hardware-queue probe)
 void mjh_launch_gen_tables_list(MjhHuffTable *tabs, int spi, const int *d_slots, int nslots, int n, hipStream_t s);
 // progressive mode (mjh_prog.hip)

@@ -13,7 +13,8 @@ switch), and next to the decoder's phase times what a plain device-to-device cop
 (the yardstick a separate permutation pass would have to be measured against).
 --progressive default|simple: the same images as progressive files, written by the reference's cjpeg with its default switches or with
 -revert -progressive, decoded with Encoder.set_sources(progressive=True); the refinement levels' time is reported next to the phases.
-usage: python tools/bench_transcode.py [--progressive default|simple] [--workloads A,B] [--seconds 2] [--repeats 3] [--subseq 512,0] [--transform rot90 [--trim]]
+--copy MODE: both workloads with a 12 KB Exif APP1 and a 3 KB ICC APP2 added to every file, under copy="none" and copy=MODE.
+usage: python tools/bench_transcode.py [--copy all] [--progressive default|simple] [--workloads A,B] [--seconds 2] [--repeats 3] [--subseq 512,0] [--transform rot90 [--trim]]
                                        [--out profiles/transcode_bench]"""
 import argparse
 import json
@@ -108,8 +109,54 @@ def timed(enc, files, seconds):
             return calls * len(files) / dt
 
 
+def with_markers(jpeg, seed):
+    """the file with a 12 KB Exif APP1 and a 3 KB ICC profile (one APP2) behind its JFIF APP0: what a camera file carries"""
+    import copy_cases as CC
+    exif = CC.seg(0xE1, b"Exif\0\0" + CC.blob(12 * 1024, seed))       # (no TIFF header in it: nothing to adjust, as without a transform)
+    return CC.behind_app0(jpeg, exif + CC.icc_segments(CC.blob(3 * 1024, seed + 1)))
+
+
+def copy_bench(a):
+    """--copy MODE: workloads A and B with markers added to every file, re-coded under copy="none" and copy=MODE by two encoders
+    of one process, alternating; the reference is jpegtran -copy MODE, 16 processes at a time.  MOZJPEG_AMD_LIB naming a library
+    that predates the copy modes: only copy="none" is measured (the parent's figure for the same files)."""
+    result = {"copy": a.copy, "library": M.LIB_PATH, "workloads": {}}
+    old = not hasattr(M.lib(), "mjh_encoder_set_copy_markers")
+    modes = ["none"] if old or a.copy == "none" else ["none", a.copy]      # (--copy none: the one encoder of a run on an older library, for a like-for-like pair)
+    for wl in a.workloads.split(","):
+        files = [with_markers(f, 500 + i) for i, f in enumerate(sources(wl))]
+        r = {"files": len(files), "source_bytes": sum(len(f) for f in files), "configs": {}}
+        encs = {}
+        for m in modes:
+            ref_rate, ref_outs, _ = reference_rate(files, switches=["-copy", m, "-revert", "-optimize"])
+            enc = encs[m] = M.Encoder(M.params_from_jpeg(files[0], revert=True, optimize=True), max_batch=len(files))
+            if m != "none":
+                enc.set_copy(m)
+            outs = enc.transcode_host(files)
+            r["configs"][m] = {"reference_files_per_s": ref_rate, "identical_to_reference": outs == ref_outs, "files_per_s": [],
+                               "output_bytes": sum(len(o) for o in outs)}
+            enc.submit_transcode(files)
+            enc.collect(0)                      # warm-up
+        for _ in range(a.repeats):             # alternating
+            for m, enc in encs.items():
+                r["configs"][m]["files_per_s"].append(timed(enc, files, a.seconds))
+        for m, enc in encs.items():
+            c = r["configs"][m]
+            v = c["files_per_s"]
+            c["median_files_per_s"] = sorted(v)[len(v) // 2]
+            c["spread"] = (max(v) - min(v)) / c["median_files_per_s"]
+            enc.close()
+        result["workloads"][wl] = r
+        print(json.dumps({wl: r}), flush=True)
+    if a.out:
+        with open(a.out + ".json", "w") as f:
+            json.dump(result, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--copy", default=None, choices=["none", "comments", "all", "icc"],
+                    help="markers added to every file; copy=none against this mode (see copy_bench)")
     ap.add_argument("--workloads", default="A,B")
     ap.add_argument("--seconds", type=float, default=2.0)
     ap.add_argument("--repeats", type=int, default=3)
@@ -119,6 +166,8 @@ def main():
     ap.add_argument("--progressive", default=None, choices=["default", "simple"])
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.copy:
+        return copy_bench(a)
     prog = a.progressive is not None
     xf = dict(transform=a.transform, trim=a.trim) if a.transform else {}
     switches = SWITCHES[:2] + XC.jpegtran_args(**xf) + SWITCHES[2:]
