@@ -325,7 +325,7 @@ int mjh_encoder_sync(mjh_encoder *e);
  * (mjh_decode.hip), whose output feeds the entropy-coding passes of mjh_encode_coefficients_*.
  * Accepted: Huffman-coded sequential DCT files (SOF0, SOF1), 8-bit, 1 or 3 components, one interleaved scan or several
  * scans (every component in exactly one), any restart intervals.  MJH_EUNSUPPORTED: progressive (unless asked for, see
- * mjh_encoder_set_sources below), arithmetic, lossless (decoded to samples when asked for, MJH_SRC_LOSSLESS below; never re-compressed),
+ * mjh_encoder_set_sources below), arithmetic (unless MJH_SRC_ARITHMETIC, below), lossless (decoded to samples when asked for, MJH_SRC_LOSSLESS below; never re-compressed),
  * 12-bit, 2 components, DNL.  COM / APPn markers are not copied (-copy none) unless mjh_encoder_set_copy_markers asks for
  * them (-copy comments / all / icc, below).
  * Four components (Adobe-style CMYK and YCCK files) are read by the marker walk and DECODED (mjh_decode_host: pixels, planes,
@@ -355,7 +355,7 @@ typedef struct {
   uint8_t huff_vals[8][256];
 } mjh_jpeg_scan;
 typedef struct {
-  int sof_type;                                     /* 0 = SOF0 (baseline), 1 = SOF1 (extended sequential), 2 = SOF2, 3 = SOF3 (both mjh_jpeg_probe_ex only) */
+  int sof_type;                                     /* 0 = SOF0 (baseline), 1 = SOF1 (extended sequential), 2 = SOF2, 3 = SOF3, 9 = SOF9, 10 = SOF10 (2 and above: mjh_jpeg_probe_ex only) */
   int data_precision;
   int image_width, image_height;
   int num_components;
@@ -377,7 +377,7 @@ int mjh_jpeg_probe(const void *jpeg, size_t size, mjh_jpeg_info *info);
  * With nothing set every entry point refuses a progressive file as the list above says.  mjh_jpeg_probe_ex with
  * MJH_SRC_PROGRESSIVE in `accept`, and the calls of an encoder that mjh_encoder_set_sources(e, MJH_SRC_PROGRESSIVE) was called on
  * (mjh_transcode_host, mjh_decode_host with and without raw_coefs), accept 8-bit SOF2 files of 1, 3 or (mjh_decode_host only) 4
- * components; SOF9 / SOF10, 12-bit, lossless, two components and DNL stay refused in the same words.
+ * components; SOF9 / SOF10 (unless MJH_SRC_ARITHMETIC, below), 12-bit, lossless, two components and DNL stay refused in the same words.
  * A progressive file has more scans than mjh_jpeg_info holds: info->sof_type is 2, info->num_scans is 0 and the scans go to
  * scans[0 .. *num_scans), each with its spectral selection (Ss, Se), its successive approximation (Ah, Al) and the Huffman tables
  * and restart interval in force at its SOS (DHT and DRI between scans are normal in these files).  More than
@@ -414,6 +414,38 @@ int mjh_jpeg_probe(const void *jpeg, size_t size, mjh_jpeg_info *info);
  * 16-byte aligned as ever.  Damaged entropy-coded data is fatal for that file alone, as on the other decode paths, and its pixels
  * are zeros.  mjh_transcode_host refuses a lossless file whatever is set (jpegtran does: JERR_NOTIMPL, jctrans.c:83). */
 #define MJH_SRC_LOSSLESS 2u
+/* ---- arithmetic-coded source files (SOF9, SOF10), opt-in ----
+ * With nothing set, and with MJH_SRC_PROGRESSIVE alone, every entry point refuses an arithmetic-coded file and a DAC marker in
+ * the words it always used.  With MJH_SRC_ARITHMETIC in `accept` (mjh_jpeg_probe_ex, mjh_jpeg_markers, mjh_jpeg_arith_cond) and on
+ * an encoder that mjh_encoder_set_sources(e, MJH_SRC_ARITHMETIC [| MJH_SRC_PROGRESSIVE]) was called on, these are accepted and
+ * decoded on the device (jdarith.c; mjh_decode_arith.hip):
+ *   SOF9  sequential DCT, 8-bit, 1, 3 or (mjh_decode_host only) 4 components, one interleaved scan or several scans with every
+ *         component in exactly one, any restart interval.  info->sof_type is 9, the scans are in info->scans[] as for SOF0.
+ *   SOF10 progressive DCT, when MJH_SRC_PROGRESSIVE is set as well (with MJH_SRC_ARITHMETIC alone: MJH_EUNSUPPORTED naming the
+ *         missing flag).  info->sof_type is 10, the scans go to scans[] as for SOF2 with the same validation, progression
+ *         tracking and cap (jdarith.c:638-690 does what jdphuff.c does).
+ * In an arithmetic scan huff_defined is 0 and dc_tbl_no / ac_tbl_no hold the conditioning table numbers (Td / Ta).  DAC markers
+ * are read as get_dac reads them (jdmarker.c:388-428): any number of (Tc|Tb, value) pairs; a DC entry is L = value & 15,
+ * U = value >> 4 with L > U MJH_EINVAL (JERR_DAC_VALUE), an AC entry Kx = value; an index outside 0..15 / 16..31 is MJH_EINVAL
+ * (JERR_DAC_INDEX).  Defaults L 0, U 1, K 5; a table keeps its conditioning from scan to scan until a DAC redefines it.  Tables
+ * 0..3 are decoded: Td / Ta above 3 in an SOS is MJH_EUNSUPPORTED naming the number (the reference takes 0..15).  With the flag a
+ * DAC in a Huffman-coded file is read and ignored.  Still MJH_EUNSUPPORTED with their reason: an SOF9 scan that is not Ss = 0,
+ * Se = 63, Ah = Al = 0 (the reference warns JWRN_NOT_SEQUENTIAL), SOF11, 12-bit, two components, DNL.
+ * Served: mjh_decode_host (pixels with every option, raw_planes, raw_coefs), mjh_transcode_host with every switch, the probes.
+ * Refused with an arithmetic file in the call: a lossless transform (mjh_encoder_set_transform) and, on the way to pixels or
+ * planes, an SOF10 file whose blocks the reference would smooth (as for SOF2).  A segment that ends early is not an error
+ * (arith_decode feeds zeros behind a marker, jdarith.c:126-145) and decodes as in the reference; what the reference warns about
+ * with JWRN_ARITH_BAD_CODE (a spectral or magnitude overflow) damages that file alone, like a bad Huffman code.  The drop-in
+ * libraries (libjpeg, the interposing library, TurboJPEG) do not set the flag and keep refusing these files. */
+#define MJH_SRC_ARITHMETIC 4u
+struct mjh_jpeg_arith_cond {                        /* (a struct tag: the call below bears the same name) */
+  int dc_L[4], dc_U[4], ac_K[4];                    /* conditioning of tables 0..3 in force at one SOS */
+};
+/* The arithmetic conditioning in force at every SOS of a file, in file order: entry i belongs to scan i (info->scans[i] of an
+ * SOF9 file, scans[i] of an SOF10 file).  accept: the MJH_SRC_* mask of mjh_jpeg_probe_ex; a file the probe refuses is refused
+ * here in the same words; a Huffman-coded file lists what its DAC markers, if any, left.  At most `cap` entries are written
+ * (list may be NULL with cap 0); more scans than that: MJH_EINVAL with the number in *count. */
+int mjh_jpeg_arith_cond(const void *jpeg, size_t size, unsigned accept, struct mjh_jpeg_arith_cond *list, int cap, int *count);
 typedef struct {
   int comps_in_scan;                                /* the fields of mjh_jpeg_scan, in its order */
   int component_index[MJH_MAX_COMPS];
@@ -428,7 +460,8 @@ typedef struct {
 } mjh_jpeg_scan_ex;
 int mjh_jpeg_probe_ex(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_info *info, mjh_jpeg_scan_ex *scans, int cap, int *num_scans);
 /* The kinds of source file the encoder's mjh_transcode_host / mjh_decode_host calls take beyond the sequential ones: 0 (the state
- * of a new encoder), MJH_SRC_PROGRESSIVE, MJH_SRC_LOSSLESS or both.  Files of one call may differ in scan script, and progressive and sequential files of
+ * of a new encoder) or any of MJH_SRC_PROGRESSIVE, MJH_SRC_LOSSLESS, MJH_SRC_ARITHMETIC OR-ed together (any other bit: MJH_EINVAL; so is
+ * MJH_SRC_ARITHMETIC on an encoder made from lossless parameters, which decodes lossless files alone -- SOF11 is not decoded).  Files of one call may differ in scan script, and progressive and sequential files of
  * one geometry may share a call.  Refused with a progressive file in the call (MJH_EUNSUPPORTED): a lossless transform
  * (mjh_encoder_set_transform), and -- on the way to pixels or planes only -- a file at whose end the reference would smooth blocks
  * (jdcoefct.c smoothing_ok: some AC coefficient of positions 1..9 never sent or not refined to the last bit). */
@@ -438,6 +471,11 @@ int mjh_encoder_set_sources(mjh_encoder *e, unsigned accept);
  * coefficient range; 0 = no progressive file in the call) and, with mjh_set_profiling(e, 1), the milliseconds the levels above 0
  * took together.  The four phases of mjh_transcode_stats cover the first scans.  Any pointer may be NULL. */
 int mjh_decode_prog_stats(mjh_encoder *e, int *levels, float *ms);
+/* The arithmetic-coded files of the last call: how many chains -- (image, scan, restart segment), one wave each -- were decoded,
+ * in how many launches (one for all SOF9 scans, one per scan ordinal of the SOF10 files) and, with mjh_set_profiling(e, 1), the
+ * milliseconds they took together.  mjh_transcode_stats and mjh_decode_prog_stats keep their meaning for the Huffman-coded files
+ * of the call.  Any pointer may be NULL. */
+int mjh_decode_arith_stats(mjh_encoder *e, int *chains, int *launches, float *ms);
 /* What jpeg_copy_critical_parameters (jctrans.c:75-171) leaves in the destination object: the profile's defaults
  * (the max-compression profile: optimal tables, progressive with scan search), trellis_quant = 0, and the source's size,
  * colour space, precision, component ids, sampling factors, quantization-table numbers and tables -- not its Huffman tables,

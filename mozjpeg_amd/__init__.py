@@ -73,8 +73,14 @@ class JpegScanEx(C.Structure):
 
 SRC_PROGRESSIVE = 1         # MJH_SRC_PROGRESSIVE
 SRC_LOSSLESS = 2            # MJH_SRC_LOSSLESS
+SRC_ARITHMETIC = 4          # MJH_SRC_ARITHMETIC
 MAX_SRC_SCANS = 64          # MJH_MAX_SRC_SCANS: the cap on the scans of one progressive file
 COPY_MODES = {"none": 0, "comments": 1, "all": 2, "all_except_icc": 3, "icc": 4}      # MJH_COPY_*: jpegtran -copy
+
+
+class JpegArithCond(C.Structure):
+    """struct mjh_jpeg_arith_cond: the arithmetic conditioning of tables 0..3 in force at one SOS (mjh_jpeg_arith_cond)"""
+    _fields_ = [("dc_L", C.c_int * 4), ("dc_U", C.c_int * 4), ("ac_K", C.c_int * 4)]
 
 
 class JpegMarker(C.Structure):
@@ -202,6 +208,9 @@ def lib():
             L.mjh_jpeg_markers.argtypes = [C.c_char_p, C.c_size_t, C.c_uint, C.c_int, C.POINTER(JpegMarker), C.c_int, C.POINTER(C.c_int)]
             L.mjh_encoder_set_copy_markers.argtypes = [C.c_void_p, C.c_int]
             L.mjh_encoder_set_icc_profile.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+        if hasattr(L, "mjh_jpeg_arith_cond"):
+            L.mjh_jpeg_arith_cond.argtypes = [C.c_char_p, C.c_size_t, C.c_uint, C.POINTER(JpegArithCond), C.c_int, C.POINTER(C.c_int)]
+            L.mjh_decode_arith_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float)]
         L.mjh_transcode_status.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p)]
         L.mjh_transcode_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float)]
         if hasattr(L, "mjh_decode_host"):             # (absent from an older MOZJPEG_AMD_LIB variant, as below)
@@ -361,11 +370,11 @@ def make_params(width, height, *, quality=75, baseline=False, revert=False, opti
     return p
 
 
-def _src_accept(progressive_sources, lossless_sources):
-    return (SRC_PROGRESSIVE if progressive_sources else 0) | (SRC_LOSSLESS if lossless_sources else 0)
+def _src_accept(progressive_sources, lossless_sources, arithmetic_sources=False):
+    return (SRC_PROGRESSIVE if progressive_sources else 0) | (SRC_LOSSLESS if lossless_sources else 0) | (SRC_ARITHMETIC if arithmetic_sources else 0)
 
 
-def jpeg_info(data, progressive_sources=False, lossless_sources=False):
+def jpeg_info(data, progressive_sources=False, lossless_sources=False, arithmetic_sources=False):
     """The marker segments of a JPEG file (mjh_jpeg_probe): frame, tables, colour space, JFIF / Adobe fields, and per scan its
     components, Huffman tables, restart interval and the byte range of its entropy-coded data.  Raises MjhError (EUNSUPPORTED:
     progressive, arithmetic, lossless, 12-bit, 2 components, a four-component file with an Adobe transform other than 0 or 2;
@@ -375,28 +384,44 @@ def jpeg_info(data, progressive_sources=False, lossless_sources=False):
     JpegInfo has sof_type 2 and num_scans 0, and its scans are the list `prog_scans` of JpegScanEx (empty for a sequential file).
     lossless_sources=True (MJH_SRC_LOSSLESS): a Huffman-coded lossless file of 8, 12 or 16 bits is accepted; its JpegInfo has
     sof_type 3 and num_scans 0, and its scans are the list `lossless_scans` of JpegScanEx, Ss the predictor and Al the point
-    transform (empty for any other file)."""
+    transform (empty for any other file).
+    arithmetic_sources=True (MJH_SRC_ARITHMETIC): an arithmetic-coded file is accepted -- SOF9 (sof_type 9, its scans in `scans`
+    as for a Huffman-coded sequential file) and, together with progressive_sources=True, SOF10 (sof_type 10, its scans in
+    `prog_scans`).  dc_tbl_no / ac_tbl_no of such a scan are its conditioning table numbers and huff_defined is 0; `arith_cond`
+    lists the conditioning in force at every SOS (jpeg_arith_cond)."""
     info = JpegInfo()
     data = bytes(data)
-    accept = _src_accept(progressive_sources, lossless_sources)
+    accept = _src_accept(progressive_sources, lossless_sources, arithmetic_sources)
     if not accept:
         _chk(lib().mjh_jpeg_probe(data, len(data), C.byref(info)))
         return info
     scans, n = (JpegScanEx * MAX_SRC_SCANS)(), C.c_int()
     _chk(lib().mjh_jpeg_probe_ex(data, len(data), accept, C.byref(info), scans, MAX_SRC_SCANS, C.byref(n)))
-    info.prog_scans = [scans[i] for i in range(n.value)] if info.sof_type == 2 else []
+    info.prog_scans = [scans[i] for i in range(n.value)] if info.sof_type in (2, 10) else []
+    if arithmetic_sources:
+        info.arith_cond = jpeg_arith_cond(data, progressive_sources, lossless_sources) if info.sof_type in (9, 10) else []
     info.lossless_scans = [scans[i] for i in range(n.value)] if info.sof_type == 3 else []
     info._prog_keep = scans         # (the list's entries are views of this array)
     return info
 
 
-def jpeg_markers(data, copy="all", progressive_sources=False, lossless_sources=False, cap=None):
+def jpeg_arith_cond(data, progressive_sources=False, lossless_sources=False):
+    """The arithmetic conditioning in force at every SOS of a file (mjh_jpeg_arith_cond with MJH_SRC_ARITHMETIC), in file order:
+    [dict(dc_L=[4], dc_U=[4], ac_K=[4]), ...] for tables 0..3.  A file jpeg_info(arithmetic_sources=True) refuses is refused in
+    the same words."""
+    data = bytes(data)
+    lst, n = (JpegArithCond * MAX_SRC_SCANS)(), C.c_int()
+    _chk(lib().mjh_jpeg_arith_cond(data, len(data), _src_accept(progressive_sources, lossless_sources, True), lst, MAX_SRC_SCANS, C.byref(n)))
+    return [dict(dc_L=list(c.dc_L), dc_U=list(c.dc_U), ac_K=list(c.ac_K)) for c in lst[:n.value]]
+
+
+def jpeg_markers(data, copy="all", progressive_sources=False, lossless_sources=False, cap=None, arithmetic_sources=False):
     """The COM / APPn segments of a file that a -copy mode saves (mjh_jpeg_markers = the reference's marker_list), in file order:
     [(marker code, data bytes), ...] -- those between the scans and behind the last one too, and JFIF / Adobe segments, which only
     the writing side leaves out.  A file jpeg_info() refuses is refused in the same words.  cap: room for that many (None: as
     many as there are); more raise MjhError(EINVAL) naming the count."""
     data = bytes(data)
-    mode, accept = copy_mode(copy), _src_accept(progressive_sources, lossless_sources)
+    mode, accept = copy_mode(copy), _src_accept(progressive_sources, lossless_sources, arithmetic_sources)
     n = C.c_int()
     room = 64 if cap is None else int(cap)
     while True:
@@ -432,7 +457,7 @@ def transform_spec(transform=None, trim=False, perfect=False, crop=None, graysca
 
 def params_from_jpeg(data, *, revert=False, optimize=False, progressive=None, fastcrush=False, restart=0,
                      transform=None, trim=False, perfect=False, crop=None, grayscale=False, progressive_sources=False,
-                     lossless_sources=False):
+                     lossless_sources=False, arithmetic_sources=False, arithmetic=False):
     """Parameters of a `jpegtran -copy none` run on this file (mjh_params_from_jpeg = jpeg_copy_critical_parameters) plus
     jpegtran's switches in make_params' vocabulary.  `data`: the file's bytes or a JpegInfo.
     transform / trim / perfect / crop / grayscale (transform_spec): the parameters of the DESTINATION of that lossless transform
@@ -440,8 +465,10 @@ def params_from_jpeg(data, *, revert=False, optimize=False, progressive=None, fa
     applies it in transcode_host.  progressive_sources=True: bytes of a progressive file are accepted (jpeg_info); jpegtran copies
     no scan script, so its parameters are those of a sequential file of the same frame.  lossless_sources=True: bytes of a
     lossless file are accepted; its parameters are the lossless ones of the file (make_params(lossless=(psv, pt)) of its first
-    scan, its precision and components), for an Encoder that decodes such files -- jpegtran refuses them."""
-    info = data if isinstance(data, JpegInfo) else jpeg_info(data, progressive_sources, lossless_sources)
+    scan, its precision and components), for an Encoder that decodes such files -- jpegtran refuses them.
+    arithmetic_sources=True: bytes of an arithmetic-coded file are accepted (jpeg_info).  arithmetic=True: jpegtran -arithmetic,
+    the result is arithmetic-coded (arith_code), whatever the source was."""
+    info = data if isinstance(data, JpegInfo) else jpeg_info(data, progressive_sources, lossless_sources, arithmetic_sources)
     p = Params()
     L = lib()
     t = transform_spec(transform, trim, perfect, crop, grayscale)
@@ -453,6 +480,8 @@ def params_from_jpeg(data, *, revert=False, optimize=False, progressive=None, fa
         p.transform = t
     if optimize:
         p.optimize_coding = 1
+    if arithmetic:
+        p.arith_code = 1
     if restart:
         if isinstance(restart, str) and restart.lower().endswith("b"):
             p.restart_interval = int(restart[:-1])
@@ -482,7 +511,8 @@ _recompress_encoders = {}
 _LOSSLESS_NO_COEFS = "lossless source file (SOF3): it has no DCT coefficients (jpeg_copy_critical_parameters refuses it as well: JERR_NOTIMPL, jctrans.c:83)"
 
 
-def recompress(files, *, max_batch=64, device=0, progressive_sources=False, lossless_sources=False, copy="none", icc=None, **switches):
+def recompress(files, *, max_batch=64, device=0, progressive_sources=False, lossless_sources=False, arithmetic_sources=False, copy="none", icc=None,
+               **switches):
     """Re-compress JPEG files on the GPU: what `jpegtran -copy none` + the switches (revert, optimize, progressive, fastcrush,
     restart) writes for each of them, in input order.  copy: jpegtran's -copy ("none", "comments", "all", "icc": the COM / APPn
     markers of every source that its result keeps, Encoder.set_copy); icc: the bytes of an ICC profile written into every result
@@ -496,13 +526,14 @@ def recompress(files, *, max_batch=64, device=0, progressive_sources=False, loss
     geometry refuses the request (not perfect, a crop outside the image) gets that MjhError in its slot.
     progressive_sources=True: progressive files are decoded too (Encoder.set_sources); they share batches with sequential files
     of the same frame.  lossless_sources=True is accepted for symmetry with decode(): a lossless file is refused all the same
-    (EUNSUPPORTED in its slot), as jpegtran refuses it."""
+    (EUNSUPPORTED in its slot), as jpegtran refuses it.  arithmetic_sources=True: arithmetic-coded files (SOF9; SOF10 together
+    with progressive_sources=True) are decoded too -- jpegtran from arithmetic to Huffman coding, or to arithmetic again."""
     files = [bytes(f) for f in files]
     out = [None] * len(files)
     groups = {}
     for i, f in enumerate(files):
         try:
-            info = jpeg_info(f, progressive_sources, lossless_sources)
+            info = jpeg_info(f, progressive_sources, lossless_sources, arithmetic_sources)
         except MjhError as exc:
             out[i] = exc
             continue
@@ -521,13 +552,13 @@ def recompress(files, *, max_batch=64, device=0, progressive_sources=False, loss
         key = (sig, key_sw, device, LIB_PATH, mode, icc)
         enc = _recompress_encoders.get(key)
         if enc is not None:
-            enc.set_sources(progressive=progressive_sources)
+            enc.set_sources(progressive=progressive_sources, arithmetic=arithmetic_sources)
         if enc is None or enc.max_batch < min(max_batch, len(idx)):
             if enc is not None:
                 enc.close()
             try:
                 enc = _recompress_encoders[key] = Encoder(params_from_jpeg(info, **switches), max_batch=min(max_batch, len(idx)), device=device)
-                enc.set_sources(progressive=progressive_sources)
+                enc.set_sources(progressive=progressive_sources, arithmetic=arithmetic_sources)
                 if mode:
                     enc.set_copy(mode)
                 if icc is not None:
@@ -673,7 +704,7 @@ def decode_opts(color=None, layout=None, pixel_size=0, rgb_offset=None, fancy_up
 _decode_encoders = {}
 
 
-def decode(files, *, max_batch=64, device=0, progressive_sources=False, lossless_sources=False, **opts):
+def decode(files, *, max_batch=64, device=0, progressive_sources=False, lossless_sources=False, arithmetic_sources=False, **opts):
     """Decode JPEG files to pixels on the GPU: the bytes `djpeg` (+ -grayscale / -rgb / -nosmooth / -scale / -dct fast, see
     decode_opts) writes for each of them, as numpy arrays [H, W, C] ([H, W] for gray) in input order.  A four-component file
     (Adobe-style CMYK or YCCK) gives [H, W, 4], C, M, Y, K -- what tj3Decompress8 gives for TJPF_CMYK, a CMYK file's samples as
@@ -688,8 +719,10 @@ def decode(files, *, max_batch=64, device=0, progressive_sources=False, lossless
     lossless_sources=True: lossless files (SOF3, 8 / 12 / 16 bits, predictors 1..7, any point transform) are decoded too, to the
     samples djpeg writes: uint8 arrays for 8-bit files, uint16 for 12 and 16 bits, [H, W] or [H, W, 3] ([H, W, 4] for the
     4-sample layouts, the fourth sample 2^precision - 1).  djpeg converts and scales nothing for these files: color= other than
-    the file's own is EUNSUPPORTED in the file's slot, scale / dct / fancy_upsampling are ignored."""
-    return _decode_grouped(files, max_batch, device, decode_opts(**opts), progressive_sources, lossless_sources)
+    the file's own is EUNSUPPORTED in the file's slot, scale / dct / fancy_upsampling are ignored.
+    arithmetic_sources=True: arithmetic-coded files are decoded too -- SOF9, and SOF10 together with progressive_sources=True
+    (the same block-smoothing refusal as for SOF2)."""
+    return _decode_grouped(files, max_batch, device, decode_opts(**opts), progressive_sources, lossless_sources, arithmetic_sources)
 
 
 def yuv_plane_size(info, comp, k=8):
@@ -704,30 +737,30 @@ def yuv_plane_size(info, comp, k=8):
     return ph * info.v_samp_factor[comp] // maxv, pw * info.h_samp_factor[comp] // maxh
 
 
-def decode_planes(files, scale=None, dct=None, *, max_batch=64, device=0, progressive_sources=False, lossless_sources=False):
+def decode_planes(files, scale=None, dct=None, *, max_batch=64, device=0, progressive_sources=False, lossless_sources=False, arithmetic_sources=False):
     """Decode JPEG files to their sample planes on the GPU, without upsampling or colour conversion (TurboJPEG's
     tj3DecompressToYUVPlanes8): per file a list of uint8 arrays [h, w], one per component, of yuv_plane_size(), or the MjhError.
     Every component is transformed at the scale's own size (mjh_decode_opts.raw_planes), so the planes keep the file's
     subsampling at every scale.  A lossless file has no such planes: with lossless_sources=True, EUNSUPPORTED in its slot."""
-    return _decode_grouped(files, max_batch, device, decode_opts(scale=scale, dct=dct, raw_planes=True), progressive_sources, lossless_sources)
+    return _decode_grouped(files, max_batch, device, decode_opts(scale=scale, dct=dct, raw_planes=True), progressive_sources, lossless_sources, arithmetic_sources)
 
 
-def decode_coefficients(files, *, max_batch=64, device=0, progressive_sources=False, lossless_sources=False):
+def decode_coefficients(files, *, max_batch=64, device=0, progressive_sources=False, lossless_sources=False, arithmetic_sources=False):
     """Decode JPEG files to their quantized DCT coefficients on the GPU (jpeg_read_coefficients): per file a list of int16 arrays
     [height_in_blocks, width_in_blocks, 64], one per component, block-major and in natural order -- what
     Encoder.encode_coefficients_host takes -- or the MjhError in its slot.  The values are the file's own (no limit of +-1023 is
     applied; the entropy coder refuses what it cannot code).  The quantization tables they belong to: jpeg_info(f).quantval.
     A lossless file has no coefficients: with lossless_sources=True, EUNSUPPORTED in its slot."""
-    return _decode_grouped(files, max_batch, device, decode_opts(raw_coefs=True), progressive_sources, lossless_sources)
+    return _decode_grouped(files, max_batch, device, decode_opts(raw_coefs=True), progressive_sources, lossless_sources, arithmetic_sources)
 
 
-def _decode_grouped(files, max_batch, device, o, progressive_sources=False, lossless_sources=False):
+def _decode_grouped(files, max_batch, device, o, progressive_sources=False, lossless_sources=False, arithmetic_sources=False):
     files = [bytes(f) for f in files]
     out = [None] * len(files)
     groups = {}
     for i, f in enumerate(files):
         try:
-            info = jpeg_info(f, progressive_sources, lossless_sources)
+            info = jpeg_info(f, progressive_sources, lossless_sources, arithmetic_sources)
         except MjhError as exc:
             out[i] = exc
             continue
@@ -736,13 +769,13 @@ def _decode_grouped(files, max_batch, device, o, progressive_sources=False, loss
         key = (sig, device, LIB_PATH)
         enc = _decode_encoders.get(key)
         if enc is not None:
-            enc.set_sources(progressive=progressive_sources, lossless=lossless_sources)
+            enc.set_sources(progressive=progressive_sources, lossless=lossless_sources, arithmetic=arithmetic_sources and info.sof_type != 3)
         if enc is None or enc.max_batch < min(max_batch, len(idx)):
             if enc is not None:
                 enc.close()
             try:
                 enc = _decode_encoders[key] = Encoder(params_from_jpeg(info, revert=True), max_batch=min(max_batch, len(idx)), device=device)
-                enc.set_sources(progressive=progressive_sources, lossless=lossless_sources)
+                enc.set_sources(progressive=progressive_sources, lossless=lossless_sources, arithmetic=arithmetic_sources and info.sof_type != 3)
             except MjhError as exc:         # a frame no encoder exists for (fractional sampling ratios): this group's files alone
                 _decode_encoders.pop(key, None)
                 if exc.code != EUNSUPPORTED:
@@ -853,13 +886,16 @@ class Encoder:
         t = transform_spec(transform, **spec)
         _chk(lib().mjh_encoder_set_transform(self._h, C.byref(t) if t is not None else None))
 
-    def set_sources(self, progressive=True, lossless=False):
+    def set_sources(self, progressive=True, lossless=False, arithmetic=False):
         """The kinds of source file the following transcode / decode calls take beyond the sequential ones
         (mjh_encoder_set_sources): progressive=True accepts Huffman-coded progressive files, lossless=True lossless ones (decode
-        calls of an encoder made from params_from_jpeg of such a file); both False is the state of a new encoder."""
+        calls of an encoder made from params_from_jpeg of such a file), arithmetic=True arithmetic-coded ones (SOF9; SOF10 when
+        progressive is set as well; EINVAL on an encoder made from a lossless file's parameters, which decodes lossless files
+        alone); all False is the state of a new encoder."""
         self._progressive = bool(progressive)
         self._lossless = bool(lossless)
-        _chk(lib().mjh_encoder_set_sources(self._h, _src_accept(progressive, lossless)))
+        self._arithmetic = bool(arithmetic)
+        _chk(lib().mjh_encoder_set_sources(self._h, _src_accept(progressive, lossless, arithmetic)))
 
     def set_copy(self, mode):
         """The COM / APPn markers the following transcode calls keep (mjh_encoder_set_copy_markers): jpegtran's -copy name
@@ -881,6 +917,13 @@ class Encoder:
         lv, ms = C.c_int(), C.c_float()
         _chk(lib().mjh_decode_prog_stats(self._h, C.byref(lv), C.byref(ms)))
         return dict(levels=lv.value, ms=float(ms.value))
+
+    def arith_stats(self):
+        """chains (image, scan, restart segment) of the last call's arithmetic-coded files, the launches they took and, with
+        profiling, the milliseconds (mjh_decode_arith_stats)"""
+        ch, la, ms = C.c_int(), C.c_int(), C.c_float()
+        _chk(lib().mjh_decode_arith_stats(self._h, C.byref(ch), C.byref(la), C.byref(ms)))
+        return dict(chains=ch.value, launches=la.value, ms=float(ms.value))
 
     def close(self):
         if self._h:
@@ -1169,7 +1212,7 @@ class Encoder:
                 return [self.get_coefficients(i) for i in range(n)]
             if o.raw_planes:
                 k = 8 if o.scale_num == 0 and o.scale_denom == 0 else scale_idct_size(o.scale_num, o.scale_denom)
-                return [self.get_planes(i, jpeg_info(files[i], getattr(self, "_progressive", False), getattr(self, "_lossless", False)), k) for i in range(n)]
+                return [self.get_planes(i, jpeg_info(files[i], getattr(self, "_progressive", False), getattr(self, "_lossless", False), getattr(self, "_arithmetic", False)), k) for i in range(n)]
             return [self.get_pixels(i) for i in range(n)]
         except MjhError:
             if errors != "return":

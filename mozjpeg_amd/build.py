@@ -13,7 +13,7 @@ LIB = os.path.join(HERE, "libmozjpeg_hip.so")
 SHIM = os.path.join(HERE, "libmozjpeg_hip_jpeg62.so")
 STANDALONE = os.path.join(HERE, "standalone", "libjpeg.so.62")
 TJSHIM = os.path.join(HERE, "libmozjpeg_hip_turbojpeg.so")
-SOURCES = ["mjh_kernels.hip", "mjh_trellis.hip", "mjh_prog.hip", "mjh_arith.hip", "mjh_lossless.hip", "mjh_decode.hip", "mjh_decode_prog.hip", "mjh_decode_lossless.hip", "mjh_idct.hip", "mjh_encoder.cpp", "mjh_jpeg_parse.cpp", "mjh_pool.cpp", "mjh_guard.cpp", "mjh_numa.cpp"]
+SOURCES = ["mjh_kernels.hip", "mjh_trellis.hip", "mjh_prog.hip", "mjh_arith.hip", "mjh_lossless.hip", "mjh_decode.hip", "mjh_decode_prog.hip", "mjh_decode_lossless.hip", "mjh_decode_arith.hip", "mjh_idct.hip", "mjh_encoder.cpp", "mjh_jpeg_parse.cpp", "mjh_pool.cpp", "mjh_guard.cpp", "mjh_numa.cpp"]
 # -ffp-contract=off: the trellis / deringing float recipes must not be fused into FMAs
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fno-fast-math",
          "-Wall", "-Wno-unused-function"]

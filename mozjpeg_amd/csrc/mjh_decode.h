@@ -74,6 +74,11 @@ struct MjhDecBatch {
 // refinement of bit Al
 struct MjhDecProg { int Ss, Se, Ah, Al; };
 
+// Arithmetic-coded files (SOF9, SOF10; mjh_decode_arith.hip): entry i of a parallel array belongs to scan i of the same batch and holds
+// the conditioning in force at its SOS for tables 0..3; MjhDecScan::dctab / actab then hold the scan's conditioning table NUMBERS
+// (Td / Ta) and canon, diff_off and the subsequence arrays are not looked at
+struct MjhDecArith { int dc_L[4], dc_U[4], ac_K[4]; };
+
 // Lossless files (SOF3, mjh_decode_lossless.hip).  The entropy-coded data of a scan is one difference symbol per sample, so a scan
 // goes through the phases above with "block" = sample: MjhDecScan::nb is 1 for every component, mcus = W * H, mcus_per_row = W, and
 // the scan-order difference array becomes one plane of 16-bit differences per component, rows MjhLlGeom::Wp elements apart (component
@@ -140,6 +145,10 @@ void mjh_launch_ldec_store(const MjhConst &C, const MjhDecBatch &B, hipStream_t 
 // (above: n * ncomp * H words of scratch, the column-0 chain of the predictor 1 planes)
 void mjh_launch_ll_undiff(const MjhLlGeom &G, const MjhLlPlane *planes, int16_t *diff, unsigned *above, int n, hipStream_t s);
 void mjh_launch_ll_pixels(const MjhLlGeom &G, const MjhLlPlane *planes, const int16_t *diff, const MjhLlOut &O, uint8_t *pixels, const unsigned *status, int n, hipStream_t s);
+// arithmetic-coded scans: one wave per restart segment of B.segs[0 .. B.nseg), decoded and stored in one go (no other phase; the
+// scrub follows as for the other kinds).  whole_blocks: the scans of sequential files (PS may be nullptr); else PS[i] belongs to
+// B.scans[i] and the launch holds ONE scan ordinal of every progressive file.  AR[i]: the conditioning of B.scans[i]
+void mjh_launch_adec_scans(const MjhConst &C, const MjhDecBatch &B, const MjhDecProg *PS, const MjhDecArith *AR, int whole_blocks, int16_t *coef_q, hipStream_t s);
 void mjh_launch_dec_scrub(const MjhConst &C, const MjhDecBatch &B, int16_t *coef_q, void *meta, hipStream_t s);
 // after the encode: image i's JFIF version / density bytes (7 bytes at file offset 11) and its status from the encoder's own checks
 void mjh_launch_dec_finish(const uint8_t *jfif7, int patch, uint8_t *out, size_t out_stride, const void *meta, unsigned *status, int n, hipStream_t s);

@@ -11,6 +11,7 @@
 #include "../../include/mozjpeg_hip.h"
 #include "mjh_internal.h"
 
+typedef struct mjh_jpeg_arith_cond MjhArithCond;      // (the public header spells the type with its tag: the call bears the same name)
 int mjh_transform_plan(const mjh_jpeg_info *f, const mjh_transform *t, MjhXformPlan *g);   // (also used by mjh_encoder.cpp)
 int mjh_internal_fail(int code, const char *msg);
 
@@ -36,6 +37,7 @@ static const int kNatural[64] = {
 // device decoder then never meets a refinement of something that was not sent.  A lossless file (SOF3, accepted with
 // MJH_SRC_LOSSLESS) is reported the same way: its scans in ex[] with Ss = the predictor and Al = the point transform, checked as
 // start_pass_lossless (jdlossls.c:249-258) and start_input_pass (jddiffct.c:104-110) check them.
+#define MJH_SRC_ALL (MJH_SRC_PROGRESSIVE | MJH_SRC_LOSSLESS | MJH_SRC_ARITHMETIC)
 static_assert(offsetof(mjh_jpeg_scan_ex, Ss) == sizeof(mjh_jpeg_scan), "mjh_jpeg_scan_ex begins with the fields of mjh_jpeg_scan");
 // saves(mode, m): jcopy_markers_setup (transupp.c:2312-2336) -- does copy mode `mode` save marker code m
 static bool copy_mode_saves(int mode, int m)
@@ -48,13 +50,18 @@ static bool copy_mode_saves(int mode, int m)
 }
 
 // copy_mode / saved: the walk also lists the COM / APPn segments that mode saves (mjh_jpeg_markers), wherever they stand
+// cond: the arithmetic conditioning in force at every SOS, in file order (mjh_jpeg_arith_cond)
 static int probe_walk(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_info *info, mjh_jpeg_scan_ex *ex, int cap, int *num_ex,
-                      int copy_mode = MJH_COPY_NONE, std::vector<mjh_jpeg_marker> *saved = nullptr)
+                      int copy_mode = MJH_COPY_NONE, std::vector<mjh_jpeg_marker> *saved = nullptr, std::vector<MjhArithCond> *cond = nullptr)
 {
   const uint8_t *d = (const uint8_t *)jpeg;
   memset(info, 0, sizeof(*info));
   if (num_ex) *num_ex = 0;
-  bool prog = false, lossless = false;
+  bool prog = false, lossless = false, arith = false;
+  const bool take_arith = (accept & MJH_SRC_ARITHMETIC) != 0;
+  int dac_L[16], dac_U[16], dac_K[16];      // (jdmarker.c:203-207: L 0, U 1, K 5 at every SOI)
+  for (int t = 0; t < 16; t++) { dac_L[t] = 0; dac_U[t] = 1; dac_K[t] = 5; }
+  if (cond) cond->clear();
   int nex = 0;
   int coef_bits[MJH_MAX_COMPS][64];
   for (int c = 0; c < MJH_MAX_COMPS; c++) for (int k = 0; k < 64; k++) coef_bits[c][k] = -1;
@@ -91,9 +98,13 @@ static int probe_walk(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_i
       if (m == 0xC2 && !(accept & MJH_SRC_PROGRESSIVE))
         return pfail(MJH_EUNSUPPORTED, "progressive source file (SOF2): only sequential Huffman-coded files are decoded on the device");
       if (m == 0xC3 && !(accept & MJH_SRC_LOSSLESS)) return pfail(MJH_EUNSUPPORTED, "lossless source file (SOF3): jpeg_copy_critical_parameters refuses it as well (JERR_NOTIMPL, jctrans.c:83)");
-      if (m == 0xC9 || m == 0xCA || m == 0xCB) return pfail(MJH_EUNSUPPORTED, "arithmetic-coded source file (SOF%d)", m - 0xC0);
-      if (m != 0xC0 && m != 0xC1 && m != 0xC2 && m != 0xC3) return pfail(MJH_EUNSUPPORTED, "Unsupported JPEG process: SOF type 0x%02x (JERR_SOF_UNSUPPORTED)", m);
-      prog = m == 0xC2;
+      if ((m == 0xC9 || m == 0xCA || m == 0xCB) && !take_arith) return pfail(MJH_EUNSUPPORTED, "arithmetic-coded source file (SOF%d)", m - 0xC0);
+      if (m == 0xCB) return pfail(MJH_EUNSUPPORTED, "arithmetic-coded lossless source file (SOF11): SOF9 and SOF10 are decoded");
+      if (m == 0xCA && !(accept & MJH_SRC_PROGRESSIVE))
+        return pfail(MJH_EUNSUPPORTED, "progressive arithmetic-coded source file (SOF10): MJH_SRC_PROGRESSIVE is not set next to MJH_SRC_ARITHMETIC");
+      if (m != 0xC0 && m != 0xC1 && m != 0xC2 && m != 0xC3 && m != 0xC9 && m != 0xCA) return pfail(MJH_EUNSUPPORTED, "Unsupported JPEG process: SOF type 0x%02x (JERR_SOF_UNSUPPORTED)", m);
+      prog = m == 0xC2 || m == 0xCA;
+      arith = m == 0xC9 || m == 0xCA;
       lossless = m == 0xC3;
       if (saw_sof) return pfail(MJH_EINVAL, "Invalid JPEG file structure: two SOF markers (JERR_SOF_DUPLICATE)");
       if (n < 6) return pfail(MJH_EINVAL, "Bogus marker length (JERR_BAD_LENGTH)");
@@ -149,7 +160,20 @@ static int probe_walk(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_i
       }
       break;
     }
-    case 0xCC: return pfail(MJH_EUNSUPPORTED, "arithmetic-coding conditioning (DAC) in the source file");
+    case 0xCC: {          // DAC (get_dac jdmarker.c:388-428): any number of (Tc|Tb, value) pairs
+      if (!take_arith) return pfail(MJH_EUNSUPPORTED, "arithmetic-coding conditioning (DAC) in the source file");
+      if (n & 1) return pfail(MJH_EINVAL, "Bogus marker length (JERR_BAD_LENGTH)");
+      for (size_t o = 0; o < n; o += 2) {
+        const int idx = s[o], val = s[o + 1];
+        if (idx >= 32) return pfail(MJH_EINVAL, "Bogus DAC index %d (JERR_DAC_INDEX)", idx);
+        if (idx >= 16) dac_K[idx - 16] = val;
+        else {
+          dac_L[idx] = val & 15; dac_U[idx] = val >> 4;
+          if (dac_L[idx] > dac_U[idx]) return pfail(MJH_EINVAL, "Bogus DAC value 0x%x (JERR_DAC_VALUE)", val);
+        }
+      }
+      break;
+    }
     case 0xDB: {          // DQT (get_dqt jdmarker.c:536-620)
       size_t o = 0;
       while (o < n) {
@@ -227,6 +251,13 @@ static int probe_walk(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_i
         sc->component_index[i] = ci;
         sc->dc_tbl_no[i] = s[2 + 2 * i] >> 4;
         sc->ac_tbl_no[i] = s[2 + 2 * i] & 15;
+        if (arith) {       // conditioning tables 0..3 are decoded: the one a scan of this kind uses (a DC refinement: none)
+          const bool use_dc = !prog || (Ss == 0 && Ah == 0), use_ac = !prog || Ss != 0;
+          if (use_dc && sc->dc_tbl_no[i] > 3)
+            return pfail(MJH_EUNSUPPORTED, "arithmetic conditioning table %d (DC) in an SOS: tables 0..3 are decoded", sc->dc_tbl_no[i]);
+          if (use_ac && sc->ac_tbl_no[i] > 3)
+            return pfail(MJH_EUNSUPPORTED, "arithmetic conditioning table %d (AC) in an SOS: tables 0..3 are decoded", sc->ac_tbl_no[i]);
+        }
         if (prog) {
           // jdphuff.c:126-144: where the reference warns, the file is refused
           if (Ss != 0 && coef_bits[ci][0] < 0)
@@ -239,7 +270,7 @@ static int probe_walk(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_i
             coef_bits[ci][k] = Al;
           }
           // only the table the scan decodes with (jdphuff.c:159-176): DC first its DC table, an AC scan its AC table, DC refinement none
-          const bool need_dc = Ss == 0 && Ah == 0, need_ac = Ss != 0;
+          const bool need_dc = !arith && Ss == 0 && Ah == 0, need_ac = !arith && Ss != 0;
           if ((need_dc && (sc->dc_tbl_no[i] > 3 || !((hdef >> (2 * sc->dc_tbl_no[i])) & 1))) || (need_ac && (sc->ac_tbl_no[i] > 3 || !((hdef >> (2 * sc->ac_tbl_no[i] + 1)) & 1))))
             return pfail(MJH_EINVAL, "Huffman table 0x%02x was not defined (JERR_NO_HUFF_TABLE)", s[2 + 2 * i]);
         } else if (lossless) {         // the DC table alone (jdlhuff.c start_pass_lhuff_decoder); a lossless frame has no quantization tables
@@ -247,17 +278,26 @@ static int probe_walk(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_i
             return pfail(MJH_EINVAL, "Huffman table 0x%02x was not defined (JERR_NO_HUFF_TABLE)", s[2 + 2 * i]);
           continue;
         } else
-        if (sc->dc_tbl_no[i] > 3 || sc->ac_tbl_no[i] > 3 || !((hdef >> (2 * sc->dc_tbl_no[i])) & 1) || !((hdef >> (2 * sc->ac_tbl_no[i] + 1)) & 1))
+        if (!arith && (sc->dc_tbl_no[i] > 3 || sc->ac_tbl_no[i] > 3 || !((hdef >> (2 * sc->dc_tbl_no[i])) & 1) || !((hdef >> (2 * sc->ac_tbl_no[i] + 1)) & 1)))
           return pfail(MJH_EINVAL, "Huffman table 0x%02x was not defined (JERR_NO_HUFF_TABLE)", s[2 + 2 * i]);
         if (!((info->quant_defined >> info->quant_tbl_no[ci]) & 1))
           return pfail(MJH_EINVAL, "Quantization table 0x%02x was not defined (JERR_NO_QUANT_TABLE)", info->quant_tbl_no[ci]);
       }
+      if (!to_ex && arith && (t[0] != 0 || t[1] != 63 || t[2] != 0))
+        return pfail(MJH_EUNSUPPORTED, "a scan with Ss=%d Se=%d Ah=%d Al=%d in a sequential arithmetic-coded file (the reference warns JWRN_NOT_SEQUENTIAL and decodes whole blocks): only Ss=0 Se=63 Ah=Al=0 is decoded", t[0], t[1], t[2] >> 4, t[2] & 15);
       if (!to_ex && (t[0] != 0 || t[1] != 63 || t[2] != 0))
         return pfail(MJH_EINVAL, "Invalid progressive parameters Ss=%d Se=%d Ah=%d Al=%d in a sequential file (JERR_BAD_PROGRESSION)", t[0], t[1], t[2] >> 4, t[2] & 15);
       sc->restart_interval = ri;
-      sc->huff_defined = hdef;
-      memcpy(sc->huff_bits, hbits, sizeof(hbits));
-      memcpy(sc->huff_vals, hvals, sizeof(hvals));
+      sc->huff_defined = arith ? 0 : hdef;
+      if (!arith) {
+        memcpy(sc->huff_bits, hbits, sizeof(hbits));
+        memcpy(sc->huff_vals, hvals, sizeof(hvals));
+      } else if (!to_ex) { memset(sc->huff_bits, 0, sizeof(sc->huff_bits)); memset(sc->huff_vals, 0, sizeof(sc->huff_vals)); }
+      if (cond) {
+        MjhArithCond ac;
+        for (int tb = 0; tb < 4; tb++) { ac.dc_L[tb] = dac_L[tb]; ac.dc_U[tb] = dac_U[tb]; ac.ac_K[tb] = dac_K[tb]; }
+        cond->push_back(ac);
+      }
       sc->data_offset = pos;
       // the segment ends at the first 0xFF that is followed by neither 0x00 nor RSTn (fill bytes 0xFF 0xFF belong to that marker)
       size_t q = pos;
@@ -329,34 +369,52 @@ extern "C" int mjh_jpeg_probe(const void *jpeg, size_t size, mjh_jpeg_info *info
 extern "C" int mjh_jpeg_probe_ex(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_info *info, mjh_jpeg_scan_ex *scans, int cap, int *num_scans)
 {
   if (!jpeg || !info) return pfail(MJH_EINVAL, "bad arguments");
-  if (accept & ~(MJH_SRC_PROGRESSIVE | MJH_SRC_LOSSLESS)) return pfail(MJH_EINVAL, "unknown source kinds 0x%x (MJH_SRC_PROGRESSIVE | MJH_SRC_LOSSLESS)", accept);
+  if (accept & ~MJH_SRC_ALL) return pfail(MJH_EINVAL, "unknown source kinds 0x%x (MJH_SRC_PROGRESSIVE | MJH_SRC_LOSSLESS | MJH_SRC_ARITHMETIC)", accept);
   if (!accept) { if (num_scans) *num_scans = 0; return probe_walk(jpeg, size, 0u, info, nullptr, 0, nullptr); }
-  if (!scans || !num_scans || cap < 1) return pfail(MJH_EINVAL, "bad arguments: MJH_SRC_PROGRESSIVE and MJH_SRC_LOSSLESS need room for the scans");
+  if (!scans || !num_scans || cap < 1) return pfail(MJH_EINVAL, "bad arguments: MJH_SRC_PROGRESSIVE, MJH_SRC_LOSSLESS and MJH_SRC_ARITHMETIC need room for the scans");
   return probe_walk(jpeg, size, accept, info, scans, cap < MJH_MAX_SRC_SCANS ? cap : MJH_MAX_SRC_SCANS, num_scans);
 }
 
 // mjh_jpeg_probe / mjh_jpeg_probe_ex and the marker list of one copy mode in the same walk (mjh_encoder.cpp: a transcode call
 // with a copy mode reads every file once)
 int mjh_probe_markers(const void *jpeg, size_t size, unsigned accept, mjh_jpeg_info *info, mjh_jpeg_scan_ex *scans, int cap, int *num_scans,
-                      int copy_mode, std::vector<mjh_jpeg_marker> *saved)
+                      int copy_mode, std::vector<mjh_jpeg_marker> *saved, std::vector<MjhArithCond> *cond)
 {
-  saved->clear();
-  if (!accept) { if (num_scans) *num_scans = 0; return probe_walk(jpeg, size, 0u, info, nullptr, 0, nullptr, copy_mode, saved); }
-  return probe_walk(jpeg, size, accept, info, scans, cap < MJH_MAX_SRC_SCANS ? cap : MJH_MAX_SRC_SCANS, num_scans, copy_mode, saved);
+  if (saved) saved->clear();
+  if (!accept) { if (num_scans) *num_scans = 0; return probe_walk(jpeg, size, 0u, info, nullptr, 0, nullptr, copy_mode, saved, cond); }
+  return probe_walk(jpeg, size, accept, info, scans, cap < MJH_MAX_SRC_SCANS ? cap : MJH_MAX_SRC_SCANS, num_scans, copy_mode, saved, cond);
+}
+
+extern "C" int mjh_jpeg_arith_cond(const void *jpeg, size_t size, unsigned accept, struct mjh_jpeg_arith_cond *list, int cap, int *count)
+{
+  if (count) *count = 0;
+  if (!jpeg || cap < 0 || (cap > 0 && !list)) return pfail(MJH_EINVAL, "bad arguments");
+  if (accept & ~MJH_SRC_ALL) return pfail(MJH_EINVAL, "unknown source kinds 0x%x (MJH_SRC_PROGRESSIVE | MJH_SRC_LOSSLESS | MJH_SRC_ARITHMETIC)", accept);
+  static thread_local mjh_jpeg_info info;
+  static thread_local std::vector<mjh_jpeg_scan_ex> room;
+  static thread_local std::vector<MjhArithCond> conds;
+  if (accept) room.resize(MJH_MAX_SRC_SCANS);
+  int ns = 0;
+  const int rc = mjh_probe_markers(jpeg, size, accept, &info, accept ? room.data() : nullptr, MJH_MAX_SRC_SCANS, &ns, MJH_COPY_NONE, nullptr, &conds);
+  if (rc) return rc;
+  if (count) *count = (int)conds.size();
+  if (conds.size() > (size_t)cap) return pfail(MJH_EINVAL, "%zu scans in the file, room for %d", conds.size(), cap);
+  for (size_t i = 0; i < conds.size(); i++) list[i] = conds[i];
+  return MJH_OK;
 }
 
 extern "C" int mjh_jpeg_markers(const void *jpeg, size_t size, unsigned accept, int copy_mode, mjh_jpeg_marker *list, int cap, int *count)
 {
   if (count) *count = 0;
   if (!jpeg || cap < 0 || (cap > 0 && !list)) return pfail(MJH_EINVAL, "bad arguments");
-  if (accept & ~(MJH_SRC_PROGRESSIVE | MJH_SRC_LOSSLESS)) return pfail(MJH_EINVAL, "unknown source kinds 0x%x (MJH_SRC_PROGRESSIVE | MJH_SRC_LOSSLESS)", accept);
+  if (accept & ~MJH_SRC_ALL) return pfail(MJH_EINVAL, "unknown source kinds 0x%x (MJH_SRC_PROGRESSIVE | MJH_SRC_LOSSLESS | MJH_SRC_ARITHMETIC)", accept);
   if (copy_mode < MJH_COPY_NONE || copy_mode > MJH_COPY_ICC) return pfail(MJH_EINVAL, "unknown copy mode %d (MJH_COPY_NONE .. MJH_COPY_ICC)", copy_mode);
   static thread_local mjh_jpeg_info info;
   static thread_local std::vector<mjh_jpeg_scan_ex> room;
   static thread_local std::vector<mjh_jpeg_marker> saved;
   if (accept) room.resize(MJH_MAX_SRC_SCANS);
   int ns = 0;
-  const int rc = mjh_probe_markers(jpeg, size, accept, &info, accept ? room.data() : nullptr, MJH_MAX_SRC_SCANS, &ns, copy_mode, &saved);
+  const int rc = mjh_probe_markers(jpeg, size, accept, &info, accept ? room.data() : nullptr, MJH_MAX_SRC_SCANS, &ns, copy_mode, &saved, nullptr);
   if (rc) return rc;
   if (count) *count = (int)saved.size();
   if (saved.size() > (size_t)cap) return pfail(MJH_EINVAL, "%zu markers in the file, room for %d", saved.size(), cap);

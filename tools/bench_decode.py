@@ -25,7 +25,10 @@ reference's tj3Compress8(TJPF_CMYK, TJCS_YCCK, TJSAMP_420) from the synthetic fr
 (k_upcolor4): files/s to device and to pinned host memory, the phase times, the reference's djpeg from 16 processes on the same files,
 and the YCbCr files of the same frames decoded in the same run for k_upcolor's time per pixel; every file's pixels are first compared
 with the reference's tj3Decompress8(TJPF_CMYK).
-usage: python tools/bench_decode.py [--progressive default|simple] [--source ycck420] [--workloads A,B] [--scale 1/1] [--dct fast] [--color rgb565] [--tj] [--seconds 2] [--repeats 3] [--out profiles/decode_bench]"""
+--source arith420: workload A's 64 frames as arithmetic-coded files (cjpeg -revert -arithmetic, with and without a restart interval),
+decoded with Encoder.set_sources(arithmetic=True) against the reference's djpeg on the same files.
+
+usage: python tools/bench_decode.py [--progressive default|simple] [--source ycck420|arith420] [--workloads A,B] [--scale 1/1] [--dct fast] [--color rgb565] [--tj] [--seconds 2] [--repeats 3] [--out profiles/decode_bench]"""
 import argparse
 import json
 import os
@@ -263,6 +266,50 @@ def bench_ycck(a, isa):
     return res
 
 
+def bench_arith(a, isa):
+    """workload A's 64 x 4K frames as arithmetic-coded 4:2:0 files (cjpeg -revert -arithmetic, SOF9) -> RGB pixels, once with a
+    restart interval of one MCU row (135 chains per file) and once without (one chain per file); the reference: djpeg on the same
+    files, 16 processes.  One wave decodes one chain, so the files/s follow the chains in flight, not the bytes."""
+    import oracle_lib as O
+    import transcode_cases as TC
+    n = 64
+    res = {"files": n, "kernel_sha": {"k_adec_scans": isa["k_adec_scans"]["sha"]}, "vgpr": isa["k_adec_scans"]["vgpr"], "variants": {}}
+    with ThreadPoolExecutor(16) as ex:
+        imgs = list(ex.map(lambda i: O.synthetic_frame(3840, 2160, seed=1234 + i), range(n)))
+        variants = {"restart_1_row": list(ex.map(lambda im: TC.cjpeg(im, ["-revert", "-quality", "75", "-sample", "2x2", "-restart", "1", "-arithmetic"]), imgs)),
+                    "no_restart": list(ex.map(lambda im: TC.cjpeg(im, ["-revert", "-quality", "75", "-sample", "2x2", "-arithmetic"]), imgs))}
+    del imgs
+    opts = M.decode_opts()
+    for name, files in variants.items():
+        info = M.jpeg_info(files[0], arithmetic_sources=True)
+        w, h = info.image_width, info.image_height
+        assert info.sof_type == 9
+        enc = M.Encoder(M.params_from_jpeg(info, revert=True), max_batch=n)
+        enc.set_sources(progressive=False, arithmetic=True)
+        outs = enc.decode_host(files, opts=opts)
+        with ThreadPoolExecutor(16) as ex:
+            same = list(ex.map(lambda i: bool(np.array_equal(outs[i], DC.djpeg(files[i]))), range(n)))
+        del outs
+        r = {"width": w, "height": h, "source_bytes": sum(len(f) for f in files), "identical_to_reference": all(same)}
+        r["reference_files_per_s"], r["reference_on_ramdisk"] = reference_rate(files)
+        timed(enc, files, 0.0, None, opts)                # warm-up
+        v = [timed(enc, files, a.seconds, None, opts) for _ in range(a.repeats)]
+        r["files_per_s"] = v
+        r["median_files_per_s"] = median(v)
+        r["spread"] = (max(v) - min(v)) / median(v)
+        r["ratio_to_reference"] = median(v) / r["reference_files_per_s"]
+        enc.set_profiling(1)
+        ms = []
+        for _ in range(3):
+            enc.submit_decode(files, opts=opts)
+            enc.sync()
+            ms.append(enc.arith_stats())
+        r["arith"] = dict(ms[0], ms=median([m["ms"] for m in ms]))
+        enc.close()
+        res["variants"][name] = r
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", default="A,B")
@@ -274,7 +321,7 @@ def main():
     ap.add_argument("--tj", action="store_true")
     ap.add_argument("--color", default=None, choices=["rgb565"])
     ap.add_argument("--progressive", default=None, choices=["default", "simple"])
-    ap.add_argument("--source", default=None, choices=["ycck420"])
+    ap.add_argument("--source", default=None, choices=["ycck420", "arith420"])
     a = ap.parse_args()
     prog = a.progressive is not None
     if a.dct or a.tj or a.color or a.source:
@@ -289,9 +336,12 @@ def main():
         if a.tj:
             result["tj"] = bench_tj(a, isa["kernels"])
             print(json.dumps({"tj": result["tj"]}), flush=True)
-        if a.source:
+        if a.source == "ycck420":
             result["ycck420"] = bench_ycck(a, isa["kernels"])
             print(json.dumps({"ycck420": result["ycck420"]}), flush=True)
+        if a.source == "arith420":
+            result["arith420"] = bench_arith(a, isa["kernels"])
+            print(json.dumps({"arith420": result["arith420"]}), flush=True)
         if a.out:
             with open(a.out + ".json", "w") as f:
                 json.dump(result, f, indent=1)

@@ -14,7 +14,7 @@ switch), and next to the decoder's phase times what a plain device-to-device cop
 --progressive default|simple: the same images as progressive files, written by the reference's cjpeg with its default switches or with
 -revert -progressive, decoded with Encoder.set_sources(progressive=True); the refinement levels' time is reported next to the phases.
 --copy MODE: both workloads with a 12 KB Exif APP1 and a 3 KB ICC APP2 added to every file, under copy="none" and copy=MODE.
-usage: python tools/bench_transcode.py [--copy all] [--progressive default|simple] [--workloads A,B] [--seconds 2] [--repeats 3] [--subseq 512,0] [--transform rot90 [--trim]]
+usage: python tools/bench_transcode.py [--copy all] [--progressive default|simple] [--source arith420] [--workloads A,B] [--seconds 2] [--repeats 3] [--subseq 512,0] [--transform rot90 [--trim]]
                                        [--out profiles/transcode_bench]"""
 import argparse
 import json
@@ -66,9 +66,12 @@ def plane_probe(p, n, rounds=5):
 # --progressive: the sources as the reference's cjpeg writes them with its default switches (the max-compression profile: progressive
 # with scan search and trellis quantization, its own quantization tables) or with -revert -progressive (jpeg_simple_progression)
 PROGRESSIVE_ARGS = {None: ["-revert"], "default": [], "simple": ["-revert", "-progressive"]}
+# --source arith420: the same images as arithmetic-coded sequential files with a restart interval of one MCU row (cjpeg -revert
+# -restart 1 -arithmetic), decoded with Encoder.set_sources(arithmetic=True): jpegtran from arithmetic to optimised Huffman coding
+ARITH_ARGS = ["-restart", "1", "-arithmetic"]
 
 
-def sources(workload, progressive=None):
+def sources(workload, progressive=None, arith=False):
     if workload == "A":
         imgs = [O.synthetic_frame(3840, 2160, seed=1234 + i) for i in range(64)]
     else:
@@ -76,7 +79,7 @@ def sources(workload, progressive=None):
         imgs = [big[i % 4][y:y + 240, x:x + 320] for i, (y, x) in enumerate((y, x) for y in range(0, 1920, 120) for x in range(0, 3520, 55))][:1024]
         assert len(imgs) == 1024
     with ThreadPoolExecutor(16) as ex:
-        return list(ex.map(lambda a: TC.cjpeg(a, PROGRESSIVE_ARGS[progressive] + ["-quality", "75", "-sample", "2x2"]), imgs))
+        return list(ex.map(lambda a: TC.cjpeg(a, PROGRESSIVE_ARGS[progressive] + ["-quality", "75", "-sample", "2x2"] + (ARITH_ARGS if arith else [])), imgs))
 
 
 def reference_rate(files, procs=16, switches=None):
@@ -164,23 +167,25 @@ def main():
     ap.add_argument("--transform", default=None, choices=sorted(M.TRANSFORMS))
     ap.add_argument("--trim", action="store_true")
     ap.add_argument("--progressive", default=None, choices=["default", "simple"])
+    ap.add_argument("--source", default=None, choices=["arith420"])
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    arith = a.source == "arith420"
     if a.copy:
         return copy_bench(a)
     prog = a.progressive is not None
     xf = dict(transform=a.transform, trim=a.trim) if a.transform else {}
     switches = SWITCHES[:2] + XC.jpegtran_args(**xf) + SWITCHES[2:]
-    result = {"switches": switches, "progressive_sources": a.progressive, "workloads": {}}
+    result = {"switches": switches, "progressive_sources": a.progressive, "arithmetic_sources": arith, "workloads": {}}
     for wl in a.workloads.split(","):
-        files = sources(wl, a.progressive)
+        files = sources(wl, a.progressive, arith)
         ref_rate, ref_outs, ramdisk = reference_rate(files, switches=switches)
         r = {"files": len(files), "source_bytes": sum(len(f) for f in files), "reference_files_per_s": ref_rate, "reference_on_ramdisk": ramdisk, "configs": {}}
         encs = {}
         for s in a.subseq.split(","):
             os.environ["MJH_DECODE_SUBSEQ"] = s
-            encs[s] = M.Encoder(M.params_from_jpeg(files[0], revert=True, optimize=True, progressive_sources=prog, **xf), max_batch=len(files))
-            encs[s].set_sources(progressive=prog)
+            encs[s] = M.Encoder(M.params_from_jpeg(files[0], revert=True, optimize=True, progressive_sources=prog, arithmetic_sources=arith, **xf), max_batch=len(files))
+            encs[s].set_sources(progressive=prog, arithmetic=arith)
         os.environ.pop("MJH_DECODE_SUBSEQ", None)
         for s, enc in encs.items():
             outs = enc.transcode_host(files)
@@ -201,6 +206,8 @@ def main():
                 enc.submit_transcode(files)
                 enc.collect(0)
             c["decoder_ms"] = enc.transcode_stats()["ms"]
+            if arith:
+                c["arith"] = enc.arith_stats()               # chains, launches, and the milliseconds of K-DA
             if prog:
                 c["refinement"] = enc.prog_stats()          # levels of scans, and the milliseconds of the levels above 0
             c["kernel_ms"] = enc.kernel_times()
