@@ -704,6 +704,10 @@ int mjh_decode_stats(mjh_encoder *e, int *width, int *height, int *pixel_size, f
  * groups of 256 blocks whose bits outgrew their window (64 Kbit) and were coded by the direct path -- both counted since
  * the encoder was made.  Any pointer may be NULL.  Synchronises with the device. */
 int mjh_enc_onepass_stats(mjh_encoder *e, int *enabled, unsigned long long *long_blocks, unsigned long long *big_groups);
+/* How many consecutive groups of 256 blocks a workgroup of that walk codes (MJH_ENCP_GROUPS in the environment of
+ * mjh_encoder_create, 1 to 64; the files do not depend on it): the encoder's setting, and that of its second buffer set
+ * (-1 while none has been made).  Either pointer may be NULL. */
+int mjh_enc_pack_groups(mjh_encoder *e, int *groups, int *twin_groups);
 /* Which DC trellis kernels the latest call launched: 0 none, 1 one lane per chain (MJH_DC_LANES), 2 the sliding-window kernel,
  * 3 the general kernel, 4 the speculative pair of one- and two-frame calls. */
 int mjh_get_dc_path(mjh_encoder *e, int *path);

@@ -233,6 +233,9 @@ def lib():
             L.mjh_get_dc_path.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         if hasattr(L, "mjh_enc_onepass_stats"):       # (absent from a MOZJPEG_AMD_LIB variant built from an older tree: A/B runs against it)
             L.mjh_enc_onepass_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
+        if hasattr(L, "mjh_enc_pack_groups"):
+            L.mjh_enc_pack_groups.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+            L.mjh_enc_scan_positions.argtypes = [C.c_int] + [C.POINTER(C.c_int)] * 4 + [C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]
         _lib = L
     return _lib
 
@@ -1069,6 +1072,12 @@ class Encoder:
         on, a, b = C.c_int(), C.c_ulonglong(), C.c_ulonglong()
         _chk(lib().mjh_enc_onepass_stats(self._h, C.byref(on), C.byref(a), C.byref(b)))
         return dict(enabled=bool(on.value), long_blocks=a.value, big_groups=b.value)
+
+    def enc_pack_groups(self):
+        """groups of 256 blocks per workgroup of the one-walk coder (MJH_ENCP_GROUPS): (the encoder's, its second buffer set's or None)"""
+        g, t = C.c_int(), C.c_int()
+        _chk(lib().mjh_enc_pack_groups(self._h, C.byref(g), C.byref(t)))
+        return g.value, (None if t.value < 0 else t.value)
 
     def dc_path(self):
         """the DC trellis kernels of the latest call: None (no DC trellis), "lane" (one lane per chain, MJH_DC_LANES), "dc3", "dc2" or "speculative"""

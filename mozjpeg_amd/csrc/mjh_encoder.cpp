@@ -356,6 +356,7 @@ struct mjh_encoder {
   int enc_onepass = 1;             // MJH_ENC_ONEPASS: scans without restart intervals are coded in one walk (k_enc_write_pack / _place)
   unsigned *d_pack = nullptr;      // the one-walk coder's workgroup slots (pack_words per image)
   size_t pack_words = 0;
+  int encp_groups = MJH_ENCP_GROUPS_DEFAULT;   // MJH_ENCP_GROUPS: consecutive groups of 256 scan positions per workgroup of k_enc_write_pack
   unsigned *d_enc_slow = nullptr;  // its two slow-path counters (mjh_enc_onepass_stats)
   int chunks = 0, ff_chunks = 0;
   uint8_t *d_out = nullptr;
@@ -1025,6 +1026,7 @@ static int mjh_streams_overlap(hipStream_t a, hipStream_t b)
 }
 
 static thread_local bool g_create_twin = false;
+static thread_local int g_twin_encp_groups = MJH_ENCP_GROUPS_DEFAULT;   // (the same for MJH_ENCP_GROUPS)
 static thread_local int g_twin_onepass = 1;     // the twin takes the primary's setting (the environment is read once, for the primary)
 static thread_local int g_twin_dc_lanes = 0, g_twin_dc_lanes_set = 0;    // (the same for MJH_DC_LANES)
 static thread_local hipStream_t g_twin_avoid[2] = { nullptr, nullptr };   // make_twin: the primary's main and side stream     // mjh_encoder_create is making the second buffer set of an encoder (make_twin)
@@ -1210,6 +1212,8 @@ extern "C" int mjh_encoder_create(const mjh_params *p, int max_batch, int device
   e->chunks = (C.total_mcu_blocks + 2047) / 2048;
   if (g_create_twin) e->enc_onepass = g_twin_onepass;
   else if (const char *v = getenv("MJH_ENC_ONEPASS")) e->enc_onepass = atoi(v) != 0;   // A/B knob: 0 = length pass + offsets + k_enc_write_mcu for every scan
+  if (g_create_twin) e->encp_groups = g_twin_encp_groups;
+  else if (const char *v = getenv("MJH_ENCP_GROUPS")) { e->encp_groups = atoi(v); if (e->encp_groups < 1 || e->encp_groups > 64) e->encp_groups = MJH_ENCP_GROUPS_DEFAULT; }   // A/B knob; the files do not depend on it
   if (e->enc_onepass) {
     e->pack_words = mjh_encode_pack_words(C);
     HIPCHK_E(mjh_dmalloc((void **)&e->d_pack, B * e->pack_words * 4));
@@ -2162,7 +2166,7 @@ static int run_pipeline(mjh_encoder *e, const void *d_pixels, size_t row_pitch, 
       pr.mark("huff_encode");
       mjh_launch_encode(V, e->d_q, nzm, e->d_tabs, spi, v_dc, v_ac, e->d_len16, e->d_off32, e->d_sums, e->chunks, e->d_totals,
                         e->d_stream, e->stream_words, e->d_meta, e->d_seg_x, e->d_seg_E, e->d_seg_sums, e->d_seg_totals, e->d_mpos, q.nseg, n, s,
-                        e->d_pack, e->pack_words, e->d_enc_slow);
+                        e->d_pack, e->pack_words, e->d_enc_slow, e->encp_groups);
       pr.mark("byte_stuff");
       mjh_launch_stuff(e->d_stream, e->stream_words, e->d_totals, e->d_ffsums, e->ff_chunks, e->d_fftotals, e->d_out, e->out_stride,
                        e->d_meta, e->d_sizes, e->d_mpos, q.nseg, n, s);
@@ -2191,7 +2195,7 @@ static int run_pipeline(mjh_encoder *e, const void *d_pixels, size_t row_pitch, 
     pr.mark("huff_encode");
     mjh_launch_encode(C, e->d_q, nzm, e->d_tabs, spi, fin_dc, fin_ac, e->d_len16, e->d_off32, e->d_sums, e->chunks, e->d_totals,
                       e->d_stream, e->stream_words, e->d_meta, e->d_seg_x, e->d_seg_E, e->d_seg_sums, e->d_seg_totals, e->d_mpos, e->nseg, n, s,
-                      e->d_pack, e->pack_words, e->d_enc_slow);
+                      e->d_pack, e->pack_words, e->d_enc_slow, e->encp_groups);
     if (if_mode == 2) { HIPCHK(hipEventRecord(e->ev_done, s)); e->ev_done_set = true; }      // (the bit writer is the tail's last VALU-bound kernel)
     pr.mark("byte_stuff");
     mjh_launch_stuff(e->d_stream, e->stream_words, e->d_totals, e->d_ffsums, e->ff_chunks, e->d_fftotals, e->d_out, e->out_stride,
@@ -2228,6 +2232,7 @@ static int make_twin(mjh_encoder *e)
   mjh_encoder *t = nullptr;
   g_create_twin = true;
   g_twin_onepass = e->enc_onepass;
+  g_twin_encp_groups = e->encp_groups;
   g_twin_dc_lanes = e->dc_lanes; g_twin_dc_lanes_set = e->dc_lanes_set;
   g_twin_avoid[0] = e->stream; g_twin_avoid[1] = e->side_stream;
   const int rc = mjh_encoder_create(&e->p_created, e->max_batch, e->device, &t);
@@ -4375,6 +4380,15 @@ extern "C" int mjh_enc_onepass_stats(mjh_encoder *e, int *enabled, unsigned long
   }
   if (long_blocks) *long_blocks = a;
   if (big_groups) *big_groups = b;
+  return MJH_OK;
+}
+
+// MJH_ENCP_GROUPS as the encoder took it, and as its second buffer set did (-1: none has been made)
+extern "C" int mjh_enc_pack_groups(mjh_encoder *e, int *groups, int *twin_groups)
+{
+  if (!e) return fail(MJH_EINVAL, "null encoder");
+  if (groups) *groups = e->encp_groups;
+  if (twin_groups) *twin_groups = e->twin ? e->twin->encp_groups : -1;
   return MJH_OK;
 }
 

@@ -860,6 +860,35 @@ __device__ __forceinline__ void for_each_nonzero(const int16_t *__restrict__ qb,
   }
 }
 
+// the same with the first burst already in registers: v0[j] = plane j + 1 of the block, loaded by the caller whatever the mask
+// says (planes 1 to 8 exist for every block) -- a kernel that walks several blocks per lane issues them one block ahead
+template <class F>
+__device__ __forceinline__ void for_each_nonzero_from(const int *v0, const int16_t *__restrict__ qb, size_t kstride, unsigned long long mask, bool active, F &&f)
+{
+  const int n = active ? __popcll(mask) : 0;
+#pragma unroll
+  for (int j = 0; j < 8; j++)
+    if (j < n) {
+      const int pos = __builtin_ctzll(mask);
+      mask &= mask - 1ull;
+      f(pos, v0[j]);
+    }
+#pragma unroll 1
+  for (int base = 8; base < 63; base += 8) {
+    if (__builtin_amdgcn_ballot_w64(base < n) == 0ull) break;
+    int v[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) v[j] = (base + j < n) ? (int)qb[(size_t)(base + j + 1) * kstride] : 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++)
+      if (base + j < n) {
+        const int pos = __builtin_ctzll(mask);
+        mask &= mask - 1ull;
+        f(pos, v[j]);
+      }
+  }
+}
+
 // k_stats_ac on compact records (the final statistics of the sequential scan)
 #define STATS_AC_ITER 4
 __global__ void __launch_bounds__(256)
@@ -2128,11 +2157,72 @@ struct MarkerCursor {
 #define ENCW_WIN 4096
 // (BitSink<LDSW>: mjh_device.h)
 
+// the DC difference of a block: its size category's code, then its bits
+template <class W>
+__device__ __forceinline__ void enc_put_dc(W &bw, const unsigned *s_dc, int df, int *dc_nbits)
+{
+  const int a = df < 0 ? -df : df;
+  const int nb = bitlen((unsigned)a);
+  if (dc_nbits) *dc_nbits = nb;
+  const unsigned e = s_dc[nb];
+  bw.put(e & 0xFFFF, (int)(e >> 16));
+  if (nb) bw.put((unsigned)(df < 0 ? df - 1 : df), nb);
+}
+
+// the AC coefficients of block b of a component (q: its planes, kstride elements apart; m: its mask, compact records only; a dummy block codes one EOB).
+// v0: the block's first eight record values, loaded by the caller (nullptr: loaded here)
+template <bool COMPACT, class W>
+__device__ __forceinline__ void enc_put_ac(int kstride, W &bw, const unsigned *s_ac, const int16_t *__restrict__ q, unsigned long long m, bool real, int b,
+                                           const int *v0 = nullptr)
+{
+  if (COMPACT) {
+    int prev = 0;
+    auto sym = [&](int pos, int v) {
+      int run = pos - prev - 1;
+      prev = pos;
+      while (run > 15) { const unsigned e = s_ac[0xF0]; bw.put(e & 0xFFFF, (int)(e >> 16)); run -= 16; }
+      const int a = v < 0 ? -v : v;
+      const int nbv = bitlen((unsigned)a);
+      const unsigned e = s_ac[(run << 4) + nbv];
+      bw.put_sym(e, (unsigned)(v < 0 ? v - 1 : v), nbv);
+    };
+    if (v0) for_each_nonzero_from(v0, q + b, (size_t)kstride, m, real, sym);
+    else for_each_nonzero(q + b, (size_t)kstride, m, real, sym);
+    if (!real || prev < 63) { const unsigned e = s_ac[0]; bw.put(e & 0xFFFF, (int)(e >> 16)); }
+  } else {
+    int x[64];
+#pragma unroll
+    for (int k = 1; k < 64; k++) x[k] = q[(size_t)k * kstride + b];
+    if (real) {
+      int run = 0;
+#pragma unroll
+      for (int k = 1; k < 64; k++) {
+        const int v = x[k];
+        if (v == 0) run++;
+        else {
+          while (run > 15) { const unsigned e = s_ac[0xF0]; bw.put(e & 0xFFFF, (int)(e >> 16)); run -= 16; }
+          const int a = v < 0 ? -v : v;
+          const int nb = bitlen((unsigned)a);
+          const unsigned e = s_ac[(run << 4) + nb];
+          bw.put_sym(e, (unsigned)(v < 0 ? v - 1 : v), nb);
+          run = 0;
+        }
+      }
+      if (run > 0) { const unsigned e = s_ac[0]; bw.put(e & 0xFFFF, (int)(e >> 16)); }
+    } else {
+      const unsigned e = s_ac[0];
+      bw.put(e & 0xFFFF, (int)(e >> 16));
+    }
+  }
+}
+
 template <bool COMPACT, class W>
 __device__ __forceinline__ void enc_write_block(const MjhConst &C, const MjhComp &cc, W &bw, const unsigned *s_ac, const unsigned *s_dc,
                                                 const int16_t *__restrict__ q, const unsigned long long *__restrict__ nzmask_img, int r, int c,
                                                 int *dc_nbits = nullptr)   // dc_nbits: the size category of the DC difference (the caller's range check)
 {
+  // (k_enc_write_mcu and k_enc_write_big: written out as it was before enc_put_dc / enc_put_ac were cut from it for k_enc_write_pack, so
+  // that those kernels keep the machine code their profiles were taken on)
   const int dc = q[dc_source_block(cc, r, c)];
   int pr, pc, pred = 0;
   if (mcu_prev_block(C, cc, r, c, pr, pc)) pred = q[dc_source_block(cc, pr, pc)];
@@ -2273,7 +2363,14 @@ k_enc_write_mcu(MjhConst C, const int16_t *__restrict__ coef_q, const unsigned l
 //   * a workgroup whose bits do not fit the window (ENCP_WIN words): it stores its total only, and k_enc_write_big walks its blocks
 //     again (count, scan, then straight into the zeroed stream)
 // ---------------------------------------------------------------------------------------------
+#ifndef ENCP_DEPTH
 #define ENCP_DEPTH 8      // 256 bits per block
+#endif
+#ifdef ENCP_MIN_WAVES     // waves per SIMD the compiler must leave registers for (variants: tools/build_variant.sh)
+#define ENCP_BOUNDS __launch_bounds__(256, ENCP_MIN_WAVES)
+#else
+#define ENCP_BOUNDS __launch_bounds__(256)
+#endif
 #define ENCP_WIN 2048     // 256 bits per block on average
 
 __device__ __forceinline__ void enc_load_tables(unsigned (*s_ac)[256], unsigned (*s_dc)[32], const MjhConst &C, const MjhHuffTable *__restrict__ tabs_img,
@@ -2304,68 +2401,209 @@ __device__ __forceinline__ int enc_scan_position(const MjhConst &C, int p, int &
   return comp;
 }
 
+// The same for the walk of k_enc_write_pack (a scan without restart intervals), with no integer division: the two quotients that
+// are not small come from a multiply-high by constants of the host (mjh_enc_div_magic), the row inside the MCU from a byte table, and
+// the predecessor in MCU order from the position's own MCU row / column instead of mcu_prev_block's way back from (r, c).
+// exact floor(n / d) for 0 <= n < 2^31 and d >= 1: m = ceil(2^(31 + s) / d), s = ceil(log2 d).  With m = (2^(31 + s) + e) / d, 0 <= e < d <= 2^s:
+// n m / 2^(31 + s) = n / d + n e / (d 2^(31 + s)), and the second term is below 1 / d; 2n and m fit 32 bits (tests/test_enc_pack_index.py
+// checks every divisor the kernel can meet)
+__host__ __device__ __forceinline__ int udiv_m31(int n, unsigned m, unsigned s)
+{
+  return (int)((unsigned)(((unsigned long long)((unsigned)n << 1) * m) >> 32) >> s);
+}
+
+static void mjh_enc_div_magic(unsigned d, unsigned *m, unsigned *s)
+{
+  unsigned sh = 0;
+  while ((1u << sh) < d) sh++;
+  *m = (unsigned)((((unsigned long long)1 << (31 + sh)) + d - 1) / d);
+  *s = sh;
+}
+
+// what the walk needs of a component, per lane: a copy in LDS (a lane's component is not uniform, and MjhConst is kernel
+// arguments: indexing it by lane is a trip to memory in front of every other load of the position)
+struct EncComp { int h, v, wib, hib, mcu_blk0, kstride; long long coef_off, blk_off; };
+__host__ __device__ __forceinline__ EncComp enc_comp(const MjhComp &m)
+{
+  EncComp e;
+  e.h = m.h; e.v = m.v; e.wib = m.wib; e.hib = m.hib; e.mcu_blk0 = m.mcu_blk0; e.kstride = m.kstride; e.coef_off = m.coef_off; e.blk_off = m.blk_off;
+  return e;
+}
+
+__host__ __device__ __forceinline__ int enc_dc_source(const EncComp &cc, int r, int c, int mcol)   // dc_source_block for a block of MCU column mcol
+{
+  if (r >= cc.hib) { c = mcol * cc.h + cc.h - 1; r = cc.hib - 1; }
+  if (c > cc.wib - 1) c = cc.wib - 1;
+  return r * cc.wib + c;
+}
+
+// cs: enc_comp of the scan's components; dv = (m, s) of blocks_per_mcu, (m, s) of mcus_per_row.  dc_blk: the block whose DC the position codes (a dummy block copies one);
+// pred_blk: the same for its predecessor, -1 when it has none (the first block of a component)
+__host__ __device__ __forceinline__ int enc_scan_position_nodiv(const MjhConst &C, const EncComp *cs, const uint4 &dv, int p, int &r, int &c, int &dc_blk, int &pred_blk)
+{
+  const int mcu = udiv_m31(p, dv.x, dv.y), bi = p - mcu * C.blocks_per_mcu;
+  int comp = 0;
+  for (int ci = 1; ci < C.ncomp; ci++) if (bi >= C.c[ci].mcu_blk0) comp = ci;
+  const EncComp cc = cs[comp];
+  const int h = cc.h, v = cc.v;
+  const int local = bi - cc.mcu_blk0;                                       // < 16
+  const int yi = (local * (int)((0x10162040u >> (8 * (h - 1))) & 0xFFu)) >> 6, xi = local - yi * h;   // ceil(64 / h) for h = 1..4
+  const int mrow = udiv_m31(mcu, dv.z, dv.w), mcol = mcu - mrow * C.mcus_per_row;
+  r = mrow * v + yi;
+  c = mcol * h + xi;
+  dc_blk = enc_dc_source(cc, r, c, mcol);
+  int pr = r, pc = c - 1, pmcol = mcol;                                     // xi > 0: the block to the left
+  bool has = true;
+  if (xi == 0) {
+    if (yi > 0) { pr = r - 1; pc = c + h - 1; }                             // the last block of the row above, same MCU
+    else if (mcu == 0) has = false;
+    else {                                                                  // the last block of the MCU before
+      const bool wrap = mcol == 0;
+      pmcol = wrap ? C.mcus_per_row - 1 : mcol - 1;
+      pr = (wrap ? mrow - 1 : mrow) * v + v - 1;
+      pc = pmcol * h + h - 1;
+    }
+  }
+  pred_blk = has ? enc_dc_source(cc, pr, pc, pmcol) : -1;
+  return comp;
+}
+
+// host-side view of the arithmetic above for the tests: np positions of a scan of ncomp components (sampling factors h, v; wib x hib
+// real blocks) with mcus_per_row MCUs per row -> out[5 i ..] = component, r, c, dc_blk, pred_blk
+extern "C" int mjh_enc_scan_positions(int ncomp, const int *h, const int *v, const int *wib, const int *hib, int mcus_per_row,
+                                      const int *p, int np, int *out)
+{
+  if (ncomp < 1 || ncomp > MJH_MAXC || mcus_per_row < 1) return -1;
+  MjhConst C{};
+  C.ncomp = ncomp;
+  C.mcus_per_row = mcus_per_row;
+  for (int i = 0; i < ncomp; i++) {
+    if (h[i] < 1 || h[i] > 4 || v[i] < 1 || v[i] > 4) return -1;
+    C.c[i].h = h[i]; C.c[i].v = v[i]; C.c[i].wib = wib[i]; C.c[i].hib = hib[i];
+    C.c[i].mcu_blk0 = C.blocks_per_mcu;
+    C.blocks_per_mcu += h[i] * v[i];
+  }
+  EncComp cs[MJH_MAXC];
+  for (int i = 0; i < ncomp; i++) cs[i] = enc_comp(C.c[i]);
+  uint4 dv;
+  mjh_enc_div_magic((unsigned)C.blocks_per_mcu, &dv.x, &dv.y);
+  mjh_enc_div_magic((unsigned)C.mcus_per_row, &dv.z, &dv.w);
+  for (int i = 0; i < np; i++) {
+    int *o = out + 5 * (size_t)i;
+    o[0] = enc_scan_position_nodiv(C, cs, dv, p[i], o[1], o[2], o[3], o[4]);
+  }
+  return 0;
+}
+
+// A workgroup walks `groups` consecutive groups of 256 scan positions of ONE image (MJH_ENCP_GROUPS): the tables are staged and the
+// window is zeroed once, and while a group is scanned, shifted and stored the loads of the next one are under way (ENCP_AHEAD: the
+// lane's mask, its two DC values and its first eight record values).  The window is zero again when a group has left: every lane
+// clears the words it has stored, and the next group's lanes touch the window only behind their scan's barrier.
+#ifndef ENCP_AHEAD
+#define ENCP_AHEAD 1
+#endif
+#ifndef ENCP_EARLY
+#define ENCP_EARLY 1
+#endif
 template <bool COMPACT>
-__global__ void __launch_bounds__(256)
+__global__ void ENCP_BOUNDS
 k_enc_write_pack(MjhConst C, const int16_t *__restrict__ coef_q, const unsigned long long *__restrict__ nzmask, const MjhHuffTable *__restrict__ tabs,
                  int slots_per_image, int4 dc_slot_of_comp, int4 ac_slot_of_comp,
                  unsigned *__restrict__ pack, size_t pack_words_per_image, unsigned *__restrict__ sums, int segs_per_image,
-                 MjhImageMeta *__restrict__ meta, unsigned *__restrict__ slow)
+                 MjhImageMeta *__restrict__ meta, unsigned *__restrict__ slow, int groups, uint4 dv)
 {
   __shared__ unsigned s_ac[MJH_MAXC][256];   // size << 16 | code, per component
   __shared__ unsigned s_dc[MJH_MAXC][32];
   __shared__ unsigned s_stage[ENCP_DEPTH * 256];
   __shared__ uint4 s_win4[ENCP_WIN / 4];
   __shared__ unsigned sh[8];
+  __shared__ EncComp s_cc[MJH_MAXC];
   unsigned *s_win = reinterpret_cast<unsigned *>(s_win4);
+  constexpr bool AHEAD = COMPACT && ENCP_AHEAD;
   const int img = blockIdx.y, tid = threadIdx.x;
-  const int N = C.total_mcu_blocks, p = blockIdx.x * 256 + tid;
+  const int N = C.total_mcu_blocks;
+  if (tid < C.ncomp) s_cc[tid] = enc_comp(C.c[tid]);
+  if (AHEAD && ENCP_EARLY) __syncthreads();      // (a barrier of their own: the first group's loads then go out in front of the tables')
+  const int16_t *qimg = coef_q + (size_t)img * C.coefs_per_image;
+  const unsigned long long *nzi = COMPACT ? nzmask + (size_t)img * C.total_real_blocks : nullptr;
+  const int max_nb = C.precision == 12 ? 15 : 11;      // MAX_COEF_BITS + 1 (jchuff.c:489)
+  const int seg0 = blockIdx.x * groups, seg1 = min(seg0 + groups, segs_per_image);
+  // a lane's position in a group and everything the walk loads first
+  struct Pos { int comp, b, df, kstride; bool real; const int16_t *q; unsigned long long m; int v0[8]; };
+  auto fetch = [&](int seg, Pos &P) {
+    const int p = seg * 256 + tid;
+    int r, c, dcb, pdb;
+    P.comp = enc_scan_position_nodiv(C, s_cc, dv, p < N ? p : 0, r, c, dcb, pdb);
+    const EncComp cc = s_cc[P.comp];
+    P.q = qimg + cc.coef_off;
+    P.real = r < cc.hib && c < cc.wib;
+    P.b = P.real ? r * cc.wib + c : 0;
+    P.kstride = cc.kstride;
+    P.m = 0ull;
+    if (COMPACT) P.m = nzi[cc.blk_off + P.b];
+    if (AHEAD) {
+#pragma unroll
+      for (int j = 0; j < 8; j++) P.v0[j] = (int)P.q[(size_t)(j + 1) * cc.kstride + P.b];
+    }
+    const int dc = P.q[dcb], pred = P.q[pdb < 0 ? dcb : pdb];
+    P.df = dc - (pdb < 0 ? 0 : pred);
+  };
+  Pos P;
+  if (AHEAD && ENCP_EARLY) fetch(seg0, P);
   enc_load_tables(s_ac, s_dc, C, tabs + (size_t)img * slots_per_image, dc_slot_of_comp, ac_slot_of_comp);
   for (int i = tid; i < ENCP_WIN / 4; i += 256) s_win4[i] = make_uint4(0u, 0u, 0u, 0u);   // (the whole window, two stores per lane: no barrier of its own behind the scan)
   __syncthreads();
-  int r = 0, c = 0;
-  const int comp = enc_scan_position(C, p < N ? p : 0, r, c);
-  const MjhComp cc = C.c[comp];
-  const int16_t *q = coef_q + (size_t)img * C.coefs_per_image + cc.coef_off;
-  const unsigned long long *nzi = COMPACT ? nzmask + (size_t)img * C.total_real_blocks : nullptr;
-  unsigned bits = 0;
-  if (p < N) {
-    MJH_DIVERGENT_SCOPE;      // (the ballot of for_each_nonzero)
-    StageSink<ENCP_DEPTH, 256> bw;
-    bw.init(s_stage + tid);
-    int nb = 0;
-    enc_write_block<COMPACT>(C, cc, bw, s_ac[comp], s_dc[comp], q, nzi, r, c, &nb);
-    bw.flush();
-    bits = bw.bitpos();
-    if (nb > (C.precision == 12 ? 15 : 11)) meta[img].bad_coef = 1u;   // MAX_COEF_BITS + 1 (jchuff.c:489)
-  }
-  unsigned tot;
-  const unsigned ex = block_excl_scan_256_1b(bits, sh, 0, &tot);
-  if (tid == 0) sums[(size_t)img * segs_per_image + blockIdx.x] = tot;
-  const unsigned nw = (tot + 31u) >> 5;
-  if (nw > (unsigned)ENCP_WIN) {          // left to k_enc_write_big
-    if (tid == 0) atomicAdd(&slow[1], 1u);
-    return;
-  }
-  if (bits > ENCP_DEPTH * 32u) {
-    MJH_DIVERGENT_SCOPE;
-    atomicAdd(&slow[0], 1u);
-    BitSink<true, false> bw;
-    bw.init(s_win, ex);
-    enc_write_block<COMPACT>(C, cc, bw, s_ac[comp], s_dc[comp], q, nzi, r, c);
-    bw.flush();
-  } else {
-    const unsigned s = ex & 31u, w0 = ex >> 5, nsw = (bits + 31u) >> 5, ndw = (s + bits + 31u) >> 5;
-    unsigned prev = 0u;
-    for (unsigned k = 0; k < ndw; k++) {
-      const unsigned cur = k < nsw ? s_stage[k * 256 + tid] : 0u;
-      const unsigned v = funnel_shift(prev, cur, s);
-      if (v) atomicOr(&s_win[w0 + k], v);
-      prev = cur;
+  if (AHEAD && !ENCP_EARLY) fetch(seg0, P);
+#pragma unroll 1
+  for (int seg = seg0; seg < seg1; seg++) {
+    if (!AHEAD) fetch(seg, P);
+    const int p = seg * 256 + tid, comp = P.comp, kstride = P.kstride;
+    unsigned bits = 0;
+    if (p < N) {
+      MJH_DIVERGENT_SCOPE;      // (the ballot of for_each_nonzero)
+      StageSink<ENCP_DEPTH, 256> bw;
+      bw.init(s_stage + tid);
+      int nb = 0;
+      enc_put_dc(bw, s_dc[comp], P.df, &nb);
+      enc_put_ac<COMPACT>(kstride, bw, s_ac[comp], P.q, P.m, P.real, P.b, AHEAD ? P.v0 : nullptr);
+      bw.flush();
+      bits = bw.bitpos();
+      if (nb > max_nb) meta[img].bad_coef = 1u;
     }
+    if (AHEAD && seg + 1 < seg1) fetch(seg + 1, P);      // in flight during the scan, the shift and the store
+    unsigned tot;
+    const unsigned ex = block_excl_scan_256_1b(bits, sh, (seg - seg0) & 1, &tot);   // (a group that is left to k_enc_write_big has this barrier only: hence the parity)
+    if (tid == 0) sums[(size_t)img * segs_per_image + seg] = tot;
+    const unsigned nw = (tot + 31u) >> 5;
+    if (nw > (unsigned)ENCP_WIN) {          // left to k_enc_write_big; the window has not been touched
+      if (tid == 0) atomicAdd(&slow[1], 1u);
+      continue;
+    }
+    if (bits > ENCP_DEPTH * 32u) {          // the block again, into the window (its position is fetched again: nothing of it is kept for this)
+      MJH_DIVERGENT_SCOPE;
+      atomicAdd(&slow[0], 1u);
+      Pos Q;
+      fetch(seg, Q);
+      BitSink<true, false> bw;
+      bw.init(s_win, ex);
+      enc_put_dc(bw, s_dc[comp], Q.df, nullptr);
+      enc_put_ac<COMPACT>(Q.kstride, bw, s_ac[comp], Q.q, Q.m, Q.real, Q.b);
+      bw.flush();
+    } else {
+      const unsigned s = ex & 31u, w0 = ex >> 5, nsw = (bits + 31u) >> 5, ndw = (s + bits + 31u) >> 5;
+      unsigned prev = 0u;
+      for (unsigned k = 0; k < ndw; k++) {
+        const unsigned cw = k < nsw ? s_stage[k * 256 + tid] : 0u;
+        const unsigned v = funnel_shift(prev, cw, s);
+        if (v) atomicOr(&s_win[w0 + k], v);
+        prev = cw;
+      }
+    }
+    __syncthreads();
+    // the window leaves, and is zero again behind it (four words per lane: the slot is ENCP_WIN words, the words behind nw are zero)
+    uint4 *g = reinterpret_cast<uint4 *>(pack + (size_t)img * pack_words_per_image + (size_t)seg * ENCP_WIN);
+    for (unsigned i = tid; i < (nw + 3u) >> 2; i += 256) { g[i] = s_win4[i]; s_win4[i] = make_uint4(0u, 0u, 0u, 0u); }
   }
-  __syncthreads();
-  unsigned *g = pack + (size_t)img * pack_words_per_image + (size_t)blockIdx.x * ENCP_WIN;
-  for (unsigned i = tid; i < nw; i += 256) g[i] = s_win[i];
 }
 
 // sums: the exclusive prefix of the workgroup totals (k_scan_sums).  One wave per slot; the first and the last word of a slot's
@@ -2984,18 +3222,23 @@ void mjh_launch_encode(const MjhConst &C, const void *q, const unsigned long lon
                        void *len16, void *off32, unsigned *sums, int chunks_per_image, unsigned *totals,
                        unsigned *stream, size_t stream_words_per_image, void *meta,
                        unsigned *seg_x, unsigned *seg_E, unsigned *seg_sums, unsigned *seg_totals, unsigned *mpos, int nseg,
-                       int n, hipStream_t s, unsigned *pack, size_t pack_words_per_image, unsigned *slow)
+                       int n, hipStream_t s, unsigned *pack, size_t pack_words_per_image, unsigned *slow, int pack_groups)
 {
   const int4 ds = make_int4(dc_slot[0], dc_slot[1], dc_slot[2], dc_slot[3]);
   const int4 as = make_int4(ac_slot[0], ac_slot[1], ac_slot[2], ac_slot[3]);
   if (pack && C.restart_interval == 0) {
-    // the one-walk schedule: every block is walked once (k_enc_write_pack), the workgroups' slots are placed by their totals' scan
+    // the one-walk schedule: every block is walked once (k_enc_write_pack, pack_groups groups of 256 positions per workgroup), the
+    // groups' slots are placed by their totals' scan
     const int segs = mjh_encode_segments(C);
-    dim3 gridp(segs, n);
+    const int G = pack_groups < 1 ? 1 : pack_groups;
+    dim3 gridp((segs + G - 1) / G, n);
+    uint4 dv;
+    mjh_enc_div_magic((unsigned)C.blocks_per_mcu, &dv.x, &dv.y);
+    mjh_enc_div_magic((unsigned)C.mcus_per_row, &dv.z, &dv.w);
     if (nzmask) hipLaunchKernelGGL((k_enc_write_pack<true>), gridp, dim3(256), 0, s, C, (const int16_t *)q, nzmask, tabs, spi, ds, as, pack, pack_words_per_image, sums, segs,
-                                   (MjhImageMeta *)meta, slow);
+                                   (MjhImageMeta *)meta, slow, G, dv);
     else hipLaunchKernelGGL((k_enc_write_pack<false>), gridp, dim3(256), 0, s, C, (const int16_t *)q, nzmask, tabs, spi, ds, as, pack, pack_words_per_image, sums, segs,
-                            (MjhImageMeta *)meta, slow);
+                            (MjhImageMeta *)meta, slow, G, dv);
     hipLaunchKernelGGL(k_scan_sums, dim3(n), dim3(256), 0, s, sums, segs, totals, (const unsigned *)nullptr);
     hipLaunchKernelGGL(k_zero_stream, dim3(64, n), dim3(256), 0, s, stream, stream_words_per_image, (const unsigned *)totals, (const unsigned *)nullptr);
     hipLaunchKernelGGL(k_enc_write_place, dim3((segs + 3) / 4, n), dim3(256), 0, s, (const unsigned *)pack, pack_words_per_image, (const unsigned *)sums, segs,

@@ -42,10 +42,12 @@ void mjh_launch_encode(const MjhConst &C, const void *q, const unsigned long lon
                        void *len16, void *off32, unsigned *sums, int chunks_per_image, unsigned *totals,
                        unsigned *stream, size_t stream_words_per_image, void *meta,
                        unsigned *seg_x, unsigned *seg_E, unsigned *seg_sums, unsigned *seg_totals, unsigned *mpos, int nseg,
-                       int n, hipStream_t s, unsigned *pack = nullptr, size_t pack_words_per_image = 0, unsigned *slow = nullptr);
+                       int n, hipStream_t s, unsigned *pack = nullptr, size_t pack_words_per_image = 0, unsigned *slow = nullptr, int pack_groups = 1);
 // pack != nullptr and a scan without restart intervals: the one-walk schedule (k_enc_write_pack / _place / _big).  pack: mjh_encode_pack_words(C)
 // words per image; sums: at least mjh_encode_segments(C) words per image; slow: two counters (blocks longer than their staging column,
-// workgroups larger than their window), only ever added to.  len16 / off32 are not touched then.
+// groups larger than their window), only ever added to.  len16 / off32 are not touched then.  pack_groups: consecutive groups of 256
+// positions a workgroup of k_enc_write_pack walks (MJH_ENCP_GROUPS); the files do not depend on it.
+#define MJH_ENCP_GROUPS_DEFAULT 4
 int mjh_encode_segments(const MjhConst &C);
 size_t mjh_encode_pack_words(const MjhConst &C);
 void mjh_launch_header(const void *prefix, int prefix_len, const void *sos, int sos_len, const MjhHuffTable *tabs, int spi,
