@@ -708,6 +708,10 @@ int mjh_enc_onepass_stats(mjh_encoder *e, int *enabled, unsigned long long *long
  * mjh_encoder_create, 1 to 64; the files do not depend on it): the encoder's setting, and that of its second buffer set
  * (-1 while none has been made).  Either pointer may be NULL. */
 int mjh_enc_pack_groups(mjh_encoder *e, int *groups, int *twin_groups);
+/* Whether the latest batch counted its final AC symbol statistics inside the AC trellis kernels instead of in a pass of
+ * their own (1 / 0; MJH_FUSE_FINAL_AC=0 in the environment of mjh_encoder_create keeps the pass; the files do not depend
+ * on it), and the same of the second buffer set's latest batch (-1 while none has been made).  Either pointer may be NULL. */
+int mjh_final_ac_fused(mjh_encoder *e, int *fused, int *twin_fused);
 /* Which DC trellis kernels the latest call launched: 0 none, 1 one lane per chain (MJH_DC_LANES), 2 the sliding-window kernel,
  * 3 the general kernel, 4 the speculative pair of one- and two-frame calls. */
 int mjh_get_dc_path(mjh_encoder *e, int *path);
@@ -739,8 +743,10 @@ enum {
   MJH_TAP_HUFF_VALS = 6, /* uint8  [4][256]                                                  */
   MJH_TAP_PROG_SCAN_US = 7, /* uint32 [2][64] progressive: microseconds the statistics [0] / encode [1]
                               workgroup of each scan-script entry ran (0 = not run)              */
-  MJH_TAP_LL_COUNTS = 8  /* uint32 [17] lossless: symbol histogram (difference categories 0..16) of the table (a script of several
+  MJH_TAP_LL_COUNTS = 8, /* uint32 [17] lossless: symbol histogram (difference categories 0..16) of the table (a script of several
                             scans: of the LAST scan's table, the one the object holds as DC table 0 afterwards; so MJH_TAP_HUFF_BITS / VALS) */
+  MJH_TAP_FINAL_COUNTS = 9 /* diagnostic, for the test suite (no caller needs it to encode): uint32 [4 slots: DC0,AC0,DC1,AC1][256]
+                              symbol histograms the image's final tables were made from; only what the LAST scan of a script counted */
 };
 int mjh_set_debug_taps(mjh_encoder *e, int on);
 int mjh_read_tap(mjh_encoder *e, int what, int image, int component, void *dst, size_t cap, size_t *size);

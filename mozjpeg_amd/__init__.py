@@ -22,6 +22,7 @@ CS_CMYK, CS_YCCK = 4, 5                       # four-component files (Adobe-styl
 CS_RGB565 = 16                                # JCS_RGB565: DecodeOpts.out_color_space only
 OK, EINVAL, EUNSUPPORTED, EHIP, ENOMEM, ETOOSMALL = 0, -1, -2, -3, -4, -5
 TAP_PLANE, TAP_COEF_UQ, TAP_COEF_Q, TAP_COEF_Q0, TAP_HUFF_BITS, TAP_HUFF_VALS, TAP_PROG_SCAN_US, TAP_LL_COUNTS = 1, 2, 3, 4, 5, 6, 7, 8
+TAP_FINAL_COUNTS = 9
 
 
 class MjhError(RuntimeError):
@@ -233,6 +234,8 @@ def lib():
             L.mjh_get_dc_path.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         if hasattr(L, "mjh_enc_onepass_stats"):       # (absent from a MOZJPEG_AMD_LIB variant built from an older tree: A/B runs against it)
             L.mjh_enc_onepass_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
+        if hasattr(L, "mjh_final_ac_fused"):
+            L.mjh_final_ac_fused.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         if hasattr(L, "mjh_enc_pack_groups"):
             L.mjh_enc_pack_groups.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
             L.mjh_enc_scan_positions.argtypes = [C.c_int] + [C.POINTER(C.c_int)] * 4 + [C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]
@@ -1078,6 +1081,20 @@ class Encoder:
         g, t = C.c_int(), C.c_int()
         _chk(lib().mjh_enc_pack_groups(self._h, C.byref(g), C.byref(t)))
         return g.value, (None if t.value < 0 else t.value)
+
+    def final_ac_fused(self):
+        """whether the latest batch counted its final AC statistics inside the AC trellis kernels (MJH_FUSE_FINAL_AC): (the encoder's
+        latest batch, its second buffer set's or None)"""
+        f, t = C.c_int(), C.c_int()
+        _chk(lib().mjh_final_ac_fused(self._h, C.byref(f), C.byref(t)))
+        return bool(f.value), (None if t.value < 0 else bool(t.value))
+
+    def final_counts(self, image=0):
+        """uint32 [4 slots: DC0, AC0, DC1, AC1][256]: the symbol histograms the image's final tables were made from"""
+        out = np.empty((4, 256), np.uint32)
+        n = C.c_size_t()
+        _chk(lib().mjh_read_tap(self._h, TAP_FINAL_COUNTS, image, 0, out.ctypes.data, out.nbytes, C.byref(n)))
+        return out
 
     def dc_path(self):
         """the DC trellis kernels of the latest call: None (no DC trellis), "lane" (one lane per chain, MJH_DC_LANES), "dc3", "dc2" or "speculative"""

@@ -309,6 +309,7 @@ struct mjh_encoder {
   size_t small_batch = 400000;       // batches of fewer blocks run the AC trellis' first tier with one pass per tile
   uint8_t *d_nq8 = nullptr;          // per block: non-zero conventionally quantized AC coefficients (FDCT kernel) = tile-sort key of the AC trellis
   int fastdiv_all = 0;               // every table in use has q <= 255: the kernels divide by 8q with one multiply-high (MjhQuant.mdiv)
+  bool dc_late_set = false;          // MJH_DC_LATE given: dc_late as it says; otherwise 2 where the AC trellis counts the final AC symbols (the tail it hid under is shorter by that pass: Cb next to the AC kernel again, profiles/final_ac_fused_ab.md), 1 elsewhere
   int dc_late = 1;                   // large sequential batches: the DC chains of components >= dc_late (1: both chroma components, 2: Cr only) run behind the AC kernel, under the tail of small kernels (MJH_DC_LATE=0: all next to it)
   int dc_lanes = 12000;              // MJH_DC_LANES: the DC trellis runs one lane per chain (k_trellis_dc_lane) in a call with at least this many chains per component (frames x iMCU rows) that meets dc_window_ok's conditions (0: never, 1: whenever they hold; the default: profiles/dc_lanes_ab.md)
   int dc_lanes_set = 0;              // MJH_DC_LANES was given: only then may the lane kernel take a call of one or two frames from the speculative pair
@@ -356,6 +357,8 @@ struct mjh_encoder {
   int enc_onepass = 1;             // MJH_ENC_ONEPASS: scans without restart intervals are coded in one walk (k_enc_write_pack / _place)
   unsigned *d_pack = nullptr;      // the one-walk coder's workgroup slots (pack_words per image)
   size_t pack_words = 0;
+  bool fuse_final_ac = true;   // MJH_FUSE_FINAL_AC=0: the final AC statistics as a pass of their own behind the AC trellis (A/B knob; the files do not depend on it)
+  bool final_ac_fused = false; // what the last batch did (mjh_final_ac_fused)
   int encp_groups = MJH_ENCP_GROUPS_DEFAULT;   // MJH_ENCP_GROUPS: consecutive groups of 256 scan positions per workgroup of k_enc_write_pack
   unsigned *d_enc_slow = nullptr;  // its two slow-path counters (mjh_enc_onepass_stats)
   int chunks = 0, ff_chunks = 0;
@@ -1027,6 +1030,7 @@ static int mjh_streams_overlap(hipStream_t a, hipStream_t b)
 
 static thread_local bool g_create_twin = false;
 static thread_local int g_twin_encp_groups = MJH_ENCP_GROUPS_DEFAULT;   // (the same for MJH_ENCP_GROUPS)
+static thread_local bool g_twin_fuse_final_ac = true;                   // (the same for MJH_FUSE_FINAL_AC)
 static thread_local int g_twin_onepass = 1;     // the twin takes the primary's setting (the environment is read once, for the primary)
 static thread_local int g_twin_dc_lanes = 0, g_twin_dc_lanes_set = 0;    // (the same for MJH_DC_LANES)
 static thread_local hipStream_t g_twin_avoid[2] = { nullptr, nullptr };   // make_twin: the primary's main and side stream     // mjh_encoder_create is making the second buffer set of an encoder (make_twin)
@@ -1200,7 +1204,7 @@ extern "C" int mjh_encoder_create(const mjh_params *p, int max_batch, int device
   if (const char *v = getenv("MJH_SMALL_BATCH")) e->small_batch = (size_t)atoll(v);      // tests: the large-batch schedule on small images
   if (const char *v = getenv("MJH_TRELLIS_CHUNKS")) { e->trellis_chunks = atoi(v); if (e->trellis_chunks < 0 || e->trellis_chunks > 4) e->trellis_chunks = 0; }
   for (int i = 0; i < 4; i++) HIPCHK_E(hipEventCreateWithFlags(&e->ev_chunk[i], hipEventDisableTiming));
-  if (const char *v = getenv("MJH_DC_LATE")) { e->dc_late = atoi(v); if (e->dc_late < 0 || e->dc_late > 2) e->dc_late = 1; }   // A/B knob
+  if (const char *v = getenv("MJH_DC_LATE")) { e->dc_late = atoi(v); if (e->dc_late < 0 || e->dc_late > 2) e->dc_late = 1; e->dc_late_set = true; }   // A/B knob
   if (g_create_twin) { e->dc_lanes = g_twin_dc_lanes; e->dc_lanes_set = g_twin_dc_lanes_set; }
   else if (const char *v = getenv("MJH_DC_LANES")) { e->dc_lanes = atoi(v); if (e->dc_lanes < 0) e->dc_lanes = 0; e->dc_lanes_set = 1; }   // A/B knob
   e->dc_window_ok = 1;
@@ -1214,6 +1218,8 @@ extern "C" int mjh_encoder_create(const mjh_params *p, int max_batch, int device
   else if (const char *v = getenv("MJH_ENC_ONEPASS")) e->enc_onepass = atoi(v) != 0;   // A/B knob: 0 = length pass + offsets + k_enc_write_mcu for every scan
   if (g_create_twin) e->encp_groups = g_twin_encp_groups;
   else if (const char *v = getenv("MJH_ENCP_GROUPS")) { e->encp_groups = atoi(v); if (e->encp_groups < 1 || e->encp_groups > 64) e->encp_groups = MJH_ENCP_GROUPS_DEFAULT; }   // A/B knob; the files do not depend on it
+  if (g_create_twin) e->fuse_final_ac = g_twin_fuse_final_ac;
+  else if (const char *v = getenv("MJH_FUSE_FINAL_AC")) e->fuse_final_ac = atoi(v) != 0;      // A/B knob; the files do not depend on it
   if (e->enc_onepass) {
     e->pack_words = mjh_encode_pack_words(C);
     HIPCHK_E(mjh_dmalloc((void **)&e->d_pack, B * e->pack_words * 4));
@@ -1794,7 +1800,9 @@ static int run_pipeline(mjh_encoder *e, const void *d_pixels, size_t row_pitch, 
   // The pre-trellis AC statistics are gathered inside the FDCT kernel (debug taps expose the pre-trellis quantized planes, so
   // they keep the unfused schedule).  Measured: the fused FDCT kernel costs what the separate statistics pass cost (7.19 vs
   // 7.23 ms per 64 4K frames) but moves 3.2 GB less.  The FINAL statistics inside either trellis kernel cost more than their
-  // own pass over the compact records (rounds 2 and 3: 3.83 vs 3.36 + 0.38 ms; 2.77 vs 2.36 + 0.33 ms) and were removed in round 5.
+  // own pass over the compact records in rounds 2 and 3 (a full multi-copy histogram: 3.83 vs 3.36 + 0.38 ms; 2.77 vs 2.36 + 0.33 ms) and
+  // were removed in round 5; they are back in another form -- the kernels that count the final symbols (mjh_trellis.hip, "CF") with a
+  // compact histogram that keeps the occupancy -- for the schedule final_ac_wanted / final_ac_here below describe.
   // band-limited passes (use_scans_in_trellis) keep the other band's quantized planes, and the block-row
   // pass of trellis_eob_opt changes coefficients behind the per-block DP: neither fusion applies then
   const bool ext_eob = p.trellis_quant && p.trellis_eob_opt, ext_qopt = p.trellis_quant && p.trellis_q_opt;
@@ -1912,6 +1920,12 @@ static int run_pipeline(mjh_encoder *e, const void *d_pixels, size_t row_pitch, 
   const int nloops = p.trellis_quant && !e->arith ? (p.trellis_num_loops > 1 ? p.trellis_num_loops : 1) : 0;   // (the arithmetic coder has its own trellis pass below)
   bool join_late = false;            // the side stream (late DC chains + final DC statistics) is joined in front of the final tables
   bool final_dc_counted = false;     // ... and the side stream the DC statistics, right behind the DC trellis (under the AC kernel)
+  // (every tile flushes its bins into the histograms of ITS image: one very large image funnels all of them into two or three tables,
+  // and the atomics on the same words cost more than the pass -- one 8192 x 8192 4:4:4 frame: 2.76 -> 2.82 ms per step,
+  // profiles/final_ac_fused_ab.md -- so an image of more than 2048 tiles per component on average keeps the pass)
+  const bool final_ac_wanted = e->fuse_final_ac && e->fastdiv_all && p.optimize_coding && C.total_real_blocks <= 3 * 2048 * 256;
+  bool final_ac_counted = false;     // the AC trellis kernels counted the final AC symbols of the blocks they finished (no stats_ac(final))
+  e->final_ac_fused = false;
   auto trellis_pass = [&](const MjhConst &CV, const int *sl_dc_seq, const int *sl_dc_prog, const int *sl_ac, const int *crst,
                           const mjh_encoder::PList *plt, int Ss, int Se, bool first_pass, bool last_loop, int qstride) -> int {
     if (!first_pass)   // fresh (zero) statistics for this pass
@@ -1952,6 +1966,7 @@ static int run_pipeline(mjh_encoder *e, const void *d_pixels, size_t row_pitch, 
     // DC kernel runs on a side stream underneath the AC kernel.
     e->side_timed = false;
     bool dc_late = false;
+    int late_from_used = 1;
     if (p.trellis_quant_dc) {
       HIPCHK(hipEventRecord(e->ev_fork, s));
       HIPCHK(hipStreamWaitEvent(e->side_stream, e->ev_fork, 0));
@@ -1981,11 +1996,14 @@ static int run_pipeline(mjh_encoder *e, const void *d_pixels, size_t row_pitch, 
       // (the late chains hang on the tile-sorted AC kernel's event: without that kernel -- MJH_TRELLIS_V3=0, a capacity beyond its tiers --
       // every chain starts here, the older schedule)
       const bool sorted_tier = nzm && e->d_nq8 && e->trellis_v3 > 0 && e->trellis_variant <= 4;
-      dc_late = e->dc_late > 0 && sorted_tier && !spec && final_dc_here && nloops == 1 && CV.ncomp == 3 && !e->debug_taps && (size_t)n * C.total_real_blocks >= e->small_batch;
+      // (without the final AC statistics the main stream's tail no longer covers both chroma launches: only Cr stays late then)
+      const int late_from = e->dc_late_set ? e->dc_late : (final_ac_wanted ? 2 : 1);
+      late_from_used = late_from;
+      dc_late = late_from > 0 && sorted_tier && !spec && final_dc_here && nloops == 1 && CV.ncomp == 3 && !e->debug_taps && (size_t)n * C.total_real_blocks >= e->small_batch;
       if (spec) { mjh_launch_trellis_dc_speculative(CV, e->d_quant, e->d_uq, e->d_q, e->d_tabs, spi, sl_dc, e->d_lambda, e->d_back9, e->d_jfin, e->d_qspec, n, e->side_stream); e->dc_path = MJH_DC_PATH_SPEC; }
       else
       e->dc_path = mjh_launch_trellis_dc(dc_chain_view(e, CV), e->d_quant, e->d_uq, e->d_q, e->d_tabs, spi, sl_dc, e->d_lambda, e->d_back, n, e->side_stream, e->dc_window_ok,
-                            0, dc_late ? e->dc_late * CV.mcu_rows : -1, e->dc_lanes);   // (the DC entries never change: image 0's tables serve all)
+                            0, dc_late ? late_from * CV.mcu_rows : -1, e->dc_lanes);   // (the DC entries never change: image 0's tables serve all)
       if (pr.enabled && e->profiling == 1) { HIPCHK(hipEventRecord(e->side_events[2 * e->prof_calls + 1], e->side_stream)); e->side_timed = true; }
       if (final_dc_here && !dc_late) {
         // the final DC statistics need nothing but the DC trellis's result: counted here, they cost no time of their own
@@ -2009,18 +2027,26 @@ static int run_pipeline(mjh_encoder *e, const void *d_pixels, size_t row_pitch, 
                                : !e->progressive && (size_t)n * C.total_real_blocks >= (size_t)6000000 ? 2 : 1;
     // the record counts the first tier's capacity is chosen by: from one tile in eight of a large batch (scaled back below)
     const int count_mask = v3 && (size_t)n * C.total_real_blocks >= (size_t)2000000 ? 7 : 0;
+    // The final AC statistics, counted where the final coefficients are made: the pass whose result the one interleaved scan codes
+    // (what final_dc_here says of the DC side) writing compact records.  Everything else -- a progressive or multi-scan script,
+    // every loop but the last (the tables are reset in front of each later pass), band-limited passes, trellis_eob_opt (it zeroes
+    // bands behind the kernels), trellis_q_opt, debug taps, tables the fast division does not cover, very large images (above) --
+    // keeps stats_ac(final).
+    const bool final_ac_here = final_ac_wanted && !e->progressive && last_loop && !extended && nzm && e->seq_scans.empty() && !e->debug_taps;
     pr.mark("trellis_ac");
+    const bool ac_counted =
     mjh_launch_trellis_ac(CV, e->d_quant, e->d_uq, e->d_q, e->d_tabs, spi, sl_ac, e->d_lambda, e->d_worklist, e->d_worklist2, e->d_dense, e->dense_cap,
                           e->trellis_variant,
                           Ss, Se, ext_eob ? e->d_eob_cost : nullptr, ext_eob ? e->d_eob_has : nullptr, nzm, qstride, n, s,
                           e->d_nq8, v3 ? ((size_t)n * C.total_real_blocks < e->small_batch ? 1 : e->trellis_v3) : 0,   // (a small batch: one pass per tile -- four times the workgroups, a quarter of their length: latency matters more than the sorting)
                           e->fastdiv_all, dc_late ? e->ev_side0 : nullptr, excl ? e->ev_tier1 : nullptr,
-                          trellis_ranges, e->side_stream, e->ev_chunk, count_mask);
+                          trellis_ranges, e->side_stream, e->ev_chunk, count_mask, final_ac_here ? fin_ac : nullptr);
+    if (ac_counted) { final_ac_counted = true; e->final_ac_fused = true; }      // (else stats_ac(final) below)
     if (excl) e->ev_tier1_set = true;
     if (dc_late) {
       if (!v3) return fail(MJH_EINVAL, "internal: the late DC chains need the tile-sorted trellis' event");
       HIPCHK(hipStreamWaitEvent(e->side_stream, e->ev_side0, 0));
-      mjh_launch_trellis_dc(CV, e->d_quant, e->d_uq, e->d_q, e->d_tabs, spi, sl_dc, e->d_lambda, e->d_back, n, e->side_stream, e->dc_window_ok, e->dc_late * CV.mcu_rows, -1, e->dc_lanes);
+      mjh_launch_trellis_dc(CV, e->d_quant, e->d_uq, e->d_q, e->d_tabs, spi, sl_dc, e->d_lambda, e->d_back, n, e->side_stream, e->dc_window_ok, late_from_used * CV.mcu_rows, -1, e->dc_lanes);
       mjh_launch_stats_dc(C, e->d_q, e->d_tabs, spi, fin_dc, 1, zero4, n, e->side_stream);
       final_dc_counted = true;
       HIPCHK(hipEventRecord(e->ev_join, e->side_stream));
@@ -2174,8 +2200,10 @@ static int run_pipeline(mjh_encoder *e, const void *d_pixels, size_t row_pitch, 
   } else {
     if (p.optimize_coding) {
       // pass 6: statistics of the interleaved scan (dummy blocks included) -> final tables
-      pr.mark("stats_ac(final)");
-      mjh_launch_stats_ac(C, e->d_q, nzm, e->d_tabs, spi, fin_ac, 1, n, s);
+      if (!final_ac_counted) {
+        pr.mark("stats_ac(final)");
+        mjh_launch_stats_ac(C, e->d_q, nzm, e->d_tabs, spi, fin_ac, 1, n, s);
+      }
       if (!final_dc_counted) {
         pr.mark("stats_dc(final)");
         mjh_launch_stats_dc(C, e->d_q, e->d_tabs, spi, fin_dc, 1, zero4, n, s);
@@ -2233,6 +2261,7 @@ static int make_twin(mjh_encoder *e)
   g_create_twin = true;
   g_twin_onepass = e->enc_onepass;
   g_twin_encp_groups = e->encp_groups;
+  g_twin_fuse_final_ac = e->fuse_final_ac;
   g_twin_dc_lanes = e->dc_lanes; g_twin_dc_lanes_set = e->dc_lanes_set;
   g_twin_avoid[0] = e->stream; g_twin_avoid[1] = e->side_stream;
   const int rc = mjh_encoder_create(&e->p_created, e->max_batch, e->device, &t);
@@ -4383,6 +4412,16 @@ extern "C" int mjh_enc_onepass_stats(mjh_encoder *e, int *enabled, unsigned long
   return MJH_OK;
 }
 
+// whether the last batch counted its final AC symbols inside the AC trellis kernels (MJH_FUSE_FINAL_AC and the schedule's
+// conditions), and the same of the second buffer set (-1: none has been made)
+extern "C" int mjh_final_ac_fused(mjh_encoder *e, int *fused, int *twin_fused)
+{
+  if (!e) return fail(MJH_EINVAL, "null encoder");
+  if (fused) *fused = e->final_ac_fused ? 1 : 0;
+  if (twin_fused) *twin_fused = e->twin ? (e->twin->final_ac_fused ? 1 : 0) : -1;
+  return MJH_OK;
+}
+
 // MJH_ENCP_GROUPS as the encoder took it, and as its second buffer set did (-1: none has been made)
 extern "C" int mjh_enc_pack_groups(mjh_encoder *e, int *groups, int *twin_groups)
 {
@@ -4617,6 +4656,14 @@ extern "C" int mjh_read_tap(mjh_encoder *e, int what, int image, int comp, void 
     const size_t need = 17 * sizeof(uint32_t);
     if (cap < need) return fail(MJH_ETOOSMALL, "need %zu bytes", need);
     HIPCHK(hipMemcpy(dst, (const uint8_t *)(e->d_tabs + (size_t)image * e->spi + SLOT_FINAL) + offsetof(MjhHuffTable, counts), need, hipMemcpyDeviceToHost));
+    if (size) *size = need;
+    return MJH_OK;
+  }
+  if (what == MJH_TAP_FINAL_COUNTS) {      // counts[0..255] of the four final table slots (DC 0, AC 0, DC 1, AC 1) of the image
+    const size_t need = 4 * 256 * sizeof(uint32_t);
+    if (cap < need) return fail(MJH_ETOOSMALL, "need %zu bytes", need);
+    for (int i = 0; i < 4; i++)
+      HIPCHK(hipMemcpy((uint8_t *)dst + (size_t)i * 1024, (const uint8_t *)(e->d_tabs + (size_t)image * e->spi + SLOT_FINAL + i) + offsetof(MjhHuffTable, counts), 1024, hipMemcpyDeviceToHost));
     if (size) *size = need;
     return MJH_OK;
   }

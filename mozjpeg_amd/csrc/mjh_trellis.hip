@@ -222,14 +222,17 @@ __device__ __forceinline__ int trellis_q_phase1(const short (&xs)[64], const int
 // *nz_out = 64-bit mask of its non-zero positions, plane i+1 of the block = its i-th non-zero value in position order --
 // which is all the statistics / bit-length / bit-writing passes behind the trellis need: they then touch as many
 // planes as the busiest block of a wave has non-zero coefficients (~20 at q75) instead of 63.
-template <int QN, bool LDS_ROWS, bool EXT = false, bool COMPACT = false>
+template <int QN, bool LDS_ROWS, bool EXT = false, bool COMPACT = false, bool REC = false>
 __device__ __forceinline__ void trellis_q_walk(const uint4 *si_rows, const float4 *rate_rows, const int (*dqT)[64], const float (*ltT)[64],
                                                int qrow, int nq_in, float azd63, float lambda, bool active, int16_t *__restrict__ qo,
                                                int kstride, uint2 (*col)[64], unsigned short (*e_pk)[64], int lane,
                                                int Ss = 1, int Se = 63, float2 *__restrict__ eob_out = nullptr, int *__restrict__ eob_has = nullptr,
                                                unsigned long long *__restrict__ nz_out = nullptr,
-                                               const int *__restrict__ dq_lane = nullptr, const float *__restrict__ lt_lane = nullptr)
+                                               const int *__restrict__ dq_lane = nullptr, const float *__restrict__ lt_lane = nullptr,
+                                               unsigned long long *rec_mask = nullptr, int *rec_cnt = nullptr)
 {
+  // rec_mask / rec_cnt (REC: COMPACT, the kernels that count the final symbols): the record of a block this call finished, for
+  // count_final_records -- its values stay in the lane's LDS column, slot j = the j-th non-zero from the END of the block
   // dq_lane / lt_lane (EXT only): this lane's own quantizer rows in global memory instead of the LDS copies (per-image tables)
   static_assert(!(COMPACT && EXT), "compact records exist for the plain pass");
   const int vstart = EXT ? Ss - 1 : 0;          // position of the virtual start entry
@@ -394,6 +397,7 @@ __device__ __forceinline__ void trellis_q_walk(const uint4 *si_rows, const float
     }
     if (COMPACT) {
       *nz_out = pmask;
+      if (REC) { *rec_mask = pmask; *rec_cnt = cnt; }
       // plane i+1 <- the i-th non-zero in position order = slot cnt-1-i (per-lane LDS address); a plane is stored only
       // while some block of the wave still has a value for it
 #pragma unroll
@@ -723,6 +727,55 @@ struct MjhTrellisExt {
   int qstride;        // EXT instantiations: 1 = one MjhQuant per image (trellis_q_opt re-estimates the tables between passes), 0 = shared
 };
 
+// CF instantiations of the general tiers (count final symbols, see k_trellis_ac_v3): the (run, size) symbols of the records the
+// wave has just written, added to counts[] of the FINAL AC slot of each block's image and component.  Called with the whole wave.
+// `worked`: the lane finished a block (a block handed on to the next list is counted by the tier that takes it); `key` = table
+// index (image * slots per image + final slot) of the lane's block -- the lanes of a work-list wave come from several images and
+// components, so the wave counts key by key in ONE full-alphabet histogram (256 bins, sizes up to 10; 1 KB on the back-pointer
+// columns, which are dead behind the walk) and flushes the non-empty bins after each: a key's blocks sit next to each other in the
+// list (a first-tier wave appends its blocks together), so a wave has a handful of keys.
+__device__ __forceinline__ void count_final_records(bool worked, unsigned long long pmask, int cnt, const uint2 (*col)[64], unsigned *hist,
+                                                    MjhHuffTable *__restrict__ fin_tabs, unsigned key, int lane)
+{
+  typedef unsigned short __attribute__((may_alias)) us_alias;
+  const us_alias *colh = reinterpret_cast<const us_alias *>(&col[0][0]);
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < 4; j++) hist[lane + 64 * j] = 0u;
+  __syncthreads();
+  bool pending = worked;
+  for (;;) {
+    const unsigned long long pb = __builtin_amdgcn_ballot_w64(pending);
+    if (pb == 0ull) break;
+    const unsigned k0 = (unsigned)__shfl((int)key, __builtin_ctzll(pb), 64);
+    if (pending && key == k0) {
+      unsigned long long m = pmask;
+      int prev = 0;
+      for (int i = 0; i < cnt; i++) {
+        const int pos = __builtin_ctzll(m);
+        m &= m - 1ull;
+        const int s2 = cnt - 1 - i;
+        const int v = (int)(short)colh[((s2 >> 2) * 64 + lane) * 4 + (s2 & 3)];
+        int r = pos - prev - 1;
+        prev = pos;
+        if (r > 15) { atomicAdd(&hist[0xF0], (unsigned)(r >> 4)); r &= 15; }
+        atomicAdd(&hist[(r << 4) + bitlen((unsigned)(v < 0 ? -v : v))], 1u);
+      }
+      if (prev < 63) atomicAdd(&hist[0], 1u);
+      pending = false;
+    }
+    __syncthreads();
+    unsigned *dst = (fin_tabs + k0)->counts;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const unsigned c = hist[lane + 64 * j];
+      if (c) { atomicAdd(&dst[lane + 64 * j], c); hist[lane + 64 * j] = 0u; }
+    }
+    __syncthreads();
+  }
+}
+
+// (the body is mjh_trellis_q_body.inc, included by the plain kernel and by the one that counts the final AC symbols)
 template <int QN, bool EXT = false, bool COMPACT = false>
 __global__ void __launch_bounds__(64)
 k_trellis_ac_q(MjhConst C, const MjhQuant *__restrict__ Q, const int16_t *__restrict__ coef_uq,
@@ -730,51 +783,23 @@ k_trellis_ac_q(MjhConst C, const MjhQuant *__restrict__ Q, const int16_t *__rest
                int4 ac_slot_of_comp, int4 wave0_of_comp, const float *__restrict__ lambda_in, unsigned *__restrict__ worklist,
                int16_t *__restrict__ dense, unsigned dense_cap, MjhTrellisExt ext)
 {
-  static_assert(QN >= 16 && QN <= 63, "queue capacity");
-  __shared__ uint2 col[QN][64];                  // queue records, then live entries {azd, acc}, then the value column
-  __shared__ unsigned short e_pk[QN + 1][64];    // back position | magnitude << 6 of live entry e
-  __shared__ uint4 si_rows[16];
-  __shared__ float4 rate_rows[16];
-  __shared__ int dqT[1][64];
-  __shared__ float ltT[1][64];
-  // flattened grid: blockIdx.x counts the waves of all components of one image (wave0_of_comp = first wave of each)
-  const int img = blockIdx.y;
-  const int wv = blockIdx.x;
-  const int comp = wv >= wave0_of_comp.w ? 3 : wv >= wave0_of_comp.z ? 2 : wv >= wave0_of_comp.y ? 1 : 0;
-  const int w0 = comp == 0 ? 0 : comp == 1 ? wave0_of_comp.y : comp == 2 ? wave0_of_comp.z : wave0_of_comp.w;
-  const MjhComp cc = C.c[comp];
-  const int lane = threadIdx.x;
-  const int slot = comp == 0 ? ac_slot_of_comp.x : comp == 1 ? ac_slot_of_comp.y : comp == 2 ? ac_slot_of_comp.z : ac_slot_of_comp.w;
-  const MjhHuffTable *T = tabs + (size_t)img * slots_per_image + slot;
-  const int blk = (wv - w0) * 64 + lane;
-  const bool inside = blk < cc.nblk;
-  const float lambda = lambda_in[(size_t)img * C.total_real_blocks + cc.blk_off + (inside ? blk : cc.nblk - 1)];
-  if (lane < 16) {
-    const uint4 r = reinterpret_cast<const uint4 *>(T->ehufsi)[lane];
-    si_rows[lane] = r;
-    rate_rows[lane] = rate_row(r);
-  }
-  if (EXT) Q += (size_t)img * ext.qstride;
-  dqT[0][lane] = Q->dq8[cc.qtbl][lane];
-  ltT[0][lane] = Q->lambda_tbl[cc.qtbl][lane];
-  int nq;
-  float azd63;
-  {
-    // all 63 raw coefficients at once (coalesced lines, one burst); they are dead after phase 1 / the dense copy
-    const int16_t *uq = coef_uq + (size_t)img * C.coefs_per_image + cc.coef_off + (inside ? blk : cc.nblk - 1);
-    short xs[64];
-#pragma unroll
-    for (int k = 1; k < 64; k++) xs[k] = uq[(size_t)k * cc.kstride];
-    nq = trellis_q_phase1<QN, EXT>(xs, Q->dq8[cc.qtbl], Q->rcp8q[cc.qtbl], Q->lambda_tbl[cc.qtbl], lambda, col, lane, azd63, ext.Ss, ext.Se);
-    defer_blocks(inside && nq > QN, worklist, (unsigned)img, ((unsigned)comp << 28) | (unsigned)blk, 0u, xs, dense, dense_cap, true, lane);
-    if (!EXT) count_heavy(worklist, inside, nq, lane);
-  }
-  __syncthreads();
-  int16_t *qo = coef_q + (size_t)img * C.coefs_per_image + cc.coef_off + blk;
-  const size_t gblk = (size_t)img * C.total_real_blocks + cc.blk_off + (inside ? blk : 0);
-  trellis_q_walk<QN, true, EXT, COMPACT>(si_rows, rate_rows, dqT, ltT, 0, nq, azd63, lambda, inside, qo, cc.kstride, col, e_pk, lane,
-                                         ext.Ss, ext.Se, EXT && ext.eob_cost ? ext.eob_cost + gblk : nullptr, EXT && ext.eob_cost ? ext.eob_has + gblk : nullptr,
-                                         COMPACT ? ext.nzmask + gblk : nullptr);
+  constexpr bool CF = false;
+  MjhHuffTable *const fin_tabs = nullptr;
+  const int4 fin_slot_of_comp = make_int4(0, 0, 0, 0);
+#include "mjh_trellis_q_body.inc"
+}
+
+// the compact first tier that counts the final AC symbols (and the dummy blocks' EOBs) into the final slots: the same body
+template <int QN>
+__global__ void __launch_bounds__(64)
+k_trellis_ac_q_cf(MjhConst C, const MjhQuant *__restrict__ Q, const int16_t *__restrict__ coef_uq,
+                  int16_t *__restrict__ coef_q, const MjhHuffTable *__restrict__ tabs, int slots_per_image,
+                  int4 ac_slot_of_comp, int4 wave0_of_comp, const float *__restrict__ lambda_in, unsigned *__restrict__ worklist,
+                  int16_t *__restrict__ dense, unsigned dense_cap, MjhTrellisExt ext,
+                  MjhHuffTable *__restrict__ fin_tabs, int4 fin_slot_of_comp)
+{
+  constexpr bool CF = true, EXT = false, COMPACT = true;
+#include "mjh_trellis_q_body.inc"
 }
 
 // Deferred blocks (any image / component per lane), same walk with a longer queue: raw coefficients come from the dense
@@ -787,62 +812,23 @@ k_trellis_ac_qd(MjhConst C, const MjhQuant *__restrict__ Q, const int16_t *__res
                 int4 ac_slot_of_comp, const float *__restrict__ lambda_in, const unsigned *__restrict__ worklist,
                 unsigned *__restrict__ worklist_next, const int16_t *__restrict__ dense, unsigned dense_cap, MjhTrellisExt ext)
 {
-  __shared__ uint2 col[QN2][64];
-  __shared__ unsigned short e_pk[QN2 + 1][64];
-  __shared__ int dqT[4][64];
-  __shared__ float ltT[4][64];
-  const int lane = threadIdx.x;
-#pragma unroll
-  for (int t = 0; t < 4; t++) { dqT[t][lane] = Q->dq8[t][lane]; ltT[t][lane] = Q->lambda_tbl[t][lane]; }
-  __syncthreads();
-  const unsigned count = worklist[0];
-  for (unsigned base = blockIdx.x * 64; base < count; base += gridDim.x * 64) {   // wave-uniform trip count
-    const unsigned it = base + lane;
-    const bool active = it < count;
-    const unsigned ii = active ? it : count - 1;
-    const int img = (int)worklist[4 + 3 * (size_t)ii];
-    const unsigned w = worklist[5 + 3 * (size_t)ii];
-    const unsigned ds = worklist[6 + 3 * (size_t)ii];
-    const int comp = (int)(w >> 28);
-    const MjhComp cc = C.c[comp];
-    const int blk = (int)(w & 0x0FFFFFFFu);
-    const int slot = comp == 0 ? ac_slot_of_comp.x : comp == 1 ? ac_slot_of_comp.y : comp == 2 ? ac_slot_of_comp.z : ac_slot_of_comp.w;
-    const MjhHuffTable *T = tabs + (size_t)img * slots_per_image + slot;
-    const float lambda = lambda_in[(size_t)img * C.total_real_blocks + cc.blk_off + blk];
-    int nq;
-    float azd63;
-    {
-      short xs[64];
-      if (ds < dense_cap) {
-        const uint4 *d = reinterpret_cast<const uint4 *>(dense + (size_t)ds * 64);
-#pragma unroll
-        for (int v = 0; v < 8; v++) {
-          const uint4 q4 = d[v];
-          const unsigned ww[4] = { q4.x, q4.y, q4.z, q4.w };
-#pragma unroll
-          for (int j = 0; j < 4; j++) { xs[8 * v + 2 * j] = (short)(ww[j] & 0xFFFFu); xs[8 * v + 2 * j + 1] = (short)(ww[j] >> 16); }
-        }
-      } else {
-        const int16_t *uq = coef_uq + (size_t)img * C.coefs_per_image + cc.coef_off + blk;
-#pragma unroll
-        for (int k = 1; k < 64; k++) xs[k] = uq[(size_t)k * cc.kstride];
-      }
-      if (EXT && ext.qstride) {
-        const MjhQuant *Qi = Q + (size_t)img * ext.qstride;   // per-lane image: vector loads of its own rows
-        nq = trellis_q_phase1<QN2, EXT>(xs, Qi->dq8[cc.qtbl], Qi->rcp8q[cc.qtbl], Qi->lambda_tbl[cc.qtbl], lambda, col, lane, azd63, ext.Ss, ext.Se);
-      } else
-      nq = trellis_q_phase1<QN2, EXT>(xs, dqT[cc.qtbl], Q->rcp8q[cc.qtbl], ltT[cc.qtbl], lambda, col, lane, azd63, ext.Ss, ext.Se);
-      if (QN2 < 63) defer_blocks(active && nq > QN2, worklist_next, (unsigned)img, w, ds, xs, nullptr, 0u, false, lane);
-    }
-    int16_t *qo = coef_q + (size_t)img * C.coefs_per_image + cc.coef_off + blk;
-    const size_t gblk = (size_t)img * C.total_real_blocks + cc.blk_off + blk;
-    trellis_q_walk<QN2, false, EXT, COMPACT>(reinterpret_cast<const uint4 *>(T->ehufsi), nullptr, dqT, ltT, cc.qtbl, nq, azd63, lambda, active, qo, cc.kstride,
-                                                              col, e_pk, lane, ext.Ss, ext.Se, EXT && ext.eob_cost ? ext.eob_cost + gblk : nullptr,
-                                                              EXT && ext.eob_cost ? ext.eob_has + gblk : nullptr, COMPACT ? ext.nzmask + gblk : nullptr,
-                                                              EXT && ext.qstride ? (Q + (size_t)img * ext.qstride)->dq8[cc.qtbl] : nullptr,
-                                                              EXT && ext.qstride ? (Q + (size_t)img * ext.qstride)->lambda_tbl[cc.qtbl] : nullptr);
-    __syncthreads();   // the LDS columns are reused by the next round
-  }
+  constexpr bool CF = false;
+  MjhHuffTable *const fin_tabs = nullptr;
+  const int4 fin_slot_of_comp = make_int4(0, 0, 0, 0);
+#include "mjh_trellis_qd_body.inc"
+}
+
+// the compact general tiers that count the final AC symbols of the blocks they finish: the same body
+template <int QN2>
+__global__ void __launch_bounds__(64)
+k_trellis_ac_qd_cf(MjhConst C, const MjhQuant *__restrict__ Q, const int16_t *__restrict__ coef_uq,
+                   int16_t *__restrict__ coef_q, const MjhHuffTable *__restrict__ tabs, int slots_per_image,
+                   int4 ac_slot_of_comp, const float *__restrict__ lambda_in, const unsigned *__restrict__ worklist,
+                   unsigned *__restrict__ worklist_next, const int16_t *__restrict__ dense, unsigned dense_cap, MjhTrellisExt ext,
+                   MjhHuffTable *__restrict__ fin_tabs, int4 fin_slot_of_comp)
+{
+  constexpr bool CF = true, EXT = false, COMPACT = true;
+#include "mjh_trellis_qd_body.inc"
 }
 
 // =============================================================================================
@@ -940,8 +926,18 @@ __device__ __forceinline__ void v3_scan(const uint2 (*col)[64], const IT (*info)
   } while (e > 0 && !(gap_old > best));
 }
 
-// (Round 3 also counted the AC symbol statistics of the final coefficients in this kernel's back-track, MJH_FUSE bit 4: the
-// trellis paid 0.4 ms for the 0.33 ms of the separate pass over the compact records; removed in round 5.)
+// (Round 3 counted the AC symbol statistics of the final coefficients in this kernel's back-track into a full multi-copy histogram,
+// MJH_FUSE bit 4: the trellis paid 0.4 ms for the 0.33 ms of the separate pass over the compact records; removed in round 5.  The CF
+// form below is what came back.)
+// The body is mjh_trellis_v3_body.inc, included by the plain kernel and by k_trellis_ac_v3_cf.
+// CF (count final symbols): the (run, size) symbols of the blocks this kernel finishes are counted in the back-track, where the
+// position, the magnitude and the entry the path came from are in registers, and added to counts[] of the component's FINAL AC
+// slot -- the schedule then launches no k_stats_ac_compact (mjh_encoder.cpp, fuse_final_ac).  Unlike round 3's full histogram
+// this one is COMPACT: magnitudes below 16 mean sizes 1..4, so 64 (run & 15, size) bins + EOB + ZRL; as 16-bit bins, two to a
+// word (a tile of 512 blocks has at most 32 256 symbols), it is 132 bytes: 10 180 with the rest, still 16 waves per CU at 16
+// records.  Copies of 32-bit bins (1 / 2 / 4: 15 / 15 / 14 waves) all measured slower, profiles/final_ac_fused_ab.md.  Deferred blocks are counted by the tier that finishes them.
+#define MJH_FH_EOB 64
+#define MJH_FH_ZRL 65
 template <int QN, int NPASS, bool FD>
 __global__ void __launch_bounds__(64)
 k_trellis_ac_v3(MjhConst C, const MjhQuant *__restrict__ Q, const int16_t *__restrict__ coef_uq, int16_t *__restrict__ coef_q,
@@ -949,271 +945,33 @@ k_trellis_ac_v3(MjhConst C, const MjhQuant *__restrict__ Q, const int16_t *__res
                 const float *__restrict__ lambda_in, uint8_t *__restrict__ nq8, unsigned *__restrict__ worklist,
                 int16_t *__restrict__ dense, unsigned dense_cap, unsigned long long *__restrict__ nzmask, int img0, unsigned *__restrict__ counts, int count_mask)
 {
-  static_assert(QN >= 16 && QN <= 63 && NPASS >= 1 && NPASS <= 8, "queue capacity / passes");
-  constexpr int TILE = 64 * NPASS;
-  __shared__ uint2 col[QN + 1][64];      // tile sort scratch; per pass: queue records (record r in slot r) -> live entries {azd, acc} (entry e in slot e; 0 = the virtual start) -> value column
-  // live entry e at [e]: position | back entry << 6 | magnitude (< 16) << 12 (the signs: one bit per position in a register).
-  // SLIM (up to 16 records): the word keeps the position only -- ONE byte -- and the back entry (< 16) and the magnitude (< 16) of
-  // entry e are nibble e - 1 of two 64-bit registers.  17 slots of 9 instead of 10 bytes per lane + the rate rows = 10 048 bytes:
-  // 16 waves per CU instead of 14 (the kernel follows its occupancy, profiles/r06g_occupancy.md: T(w) ~ 0.52 + 13.3 / w), and the
-  // scan loop loses the two masks of its position fields.  Same operations on the same values per lane: the files do not change.
-  constexpr bool SLIM = QN <= 16;
-  typedef typename std::conditional<SLIM, unsigned char, unsigned short>::type info_t;
-  __shared__ info_t info[QN + 1][64];
-  __shared__ float4 rate_rows[16];
-  typedef unsigned __attribute__((may_alias)) u_alias;
-  typedef unsigned short __attribute__((may_alias)) us_alias;
-  const int img = blockIdx.y + img0, tl = blockIdx.x, lane = threadIdx.x;      // (img0: first image of this launch's range of the batch)
-  const int comp = tl >= tile0_of_comp.w ? 3 : tl >= tile0_of_comp.z ? 2 : tl >= tile0_of_comp.y ? 1 : 0;
-  const int t0 = comp == 0 ? 0 : comp == 1 ? tile0_of_comp.y : comp == 2 ? tile0_of_comp.z : tile0_of_comp.w;
-  const MjhComp cc = C.c[comp];
-  const int tile_base = (tl - t0) * TILE;
-  const int slot = comp == 0 ? ac_slot_of_comp.x : comp == 1 ? ac_slot_of_comp.y : comp == 2 ? ac_slot_of_comp.z : ac_slot_of_comp.w;
-  const MjhHuffTable *T = tabs + (size_t)img * slots_per_image + slot;
-  const size_t gblk0 = (size_t)img * C.total_real_blocks + cc.blk_off;
-  if (lane < 16) rate_rows[lane] = rate_row(reinterpret_cast<const uint4 *>(T->ehufsi)[lane]);
-  const int si_f0 = (int)T->ehufsi[0xF0], si_eob = (int)T->ehufsi[0];
-  const float f0f = si_f0 ? (float)si_f0 : 3e38f, eobf = (float)si_eob;
-  const int dq_lane = Q->dq8[cc.qtbl][lane];                    // lane k holds the row entry of position k (ds_bpermute lookups)
-  const float lt_lane = Q->lambda_tbl[cc.qtbl][lane];
+  constexpr bool CF = false;
+  MjhHuffTable *const fin_tabs = nullptr;
+  const int4 fin_slot_of_comp = make_int4(0, 0, 0, 0);
+#include "mjh_trellis_v3_body.inc"
+}
 
-  // ---- tile sort: descending key; perm entry = index in tile | key << 9 ----
-  unsigned long long mine0 = 0ull, mine1 = 0ull;
-  {
-    u_alias *hist = reinterpret_cast<u_alias *>(&col[0][0]);              // [64]
-    us_alias *perm = reinterpret_cast<us_alias *>(&col[0][0]) + 128;      // [TILE], behind the histogram
-    hist[lane] = 0u;
-    __syncthreads();
-    unsigned key[NPASS], rank[NPASS];
-#pragma unroll
-    for (int j = 0; j < NPASS; j++) {
-      const int b = tile_base + j * 64 + lane;
-      unsigned k = b < cc.nblk ? (unsigned)nq8[gblk0 + b] : 0u;
-      key[j] = k > 63u ? 63u : k;
-      rank[j] = atomicAdd(&hist[key[j]], 1u);
-    }
-    __syncthreads();
-    const unsigned h = hist[63 - lane];     // lane L: blocks with key 63-L; blocks with a larger key come first
-    unsigned inc = h;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned n = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += n;
-    }
-    __syncthreads();
-    hist[63 - lane] = inc - h;
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < NPASS; j++) perm[hist[key[j]] + rank[j]] = (unsigned short)((unsigned)(j * 64 + lane) | (key[j] << 9));
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < NPASS; j++) {
-      const unsigned long long v = perm[j * 64 + lane];
-      if (j < 4) mine0 |= v << (16 * j); else mine1 |= v << (16 * (j - 4));
-    }
-    __syncthreads();
-  }
-
-  us_alias *colh = reinterpret_cast<us_alias *>(&col[0][0]);   // value of slot s: row s>>2, half-word s&3 of the lane's uint2
-#pragma unroll 1
-  for (int pass = 0; pass < NPASS; pass++) {
-    const unsigned pe = (unsigned)(((pass < 4 ? mine0 : mine1) >> (16 * (pass & 3))) & 0xFFFFull);
-    const int blk = tile_base + (int)(pe & 511u);
-    const bool inside = blk < cc.nblk;
-    const size_t gblk = gblk0 + (inside ? blk : 0);
-    if (__builtin_amdgcn_ballot_w64(inside && (pe >> 9) != 0u) == 0ull) {   // nothing quantizes to non-zero: all-zero blocks
-      if (inside) nzmask[gblk] = 0ull;
-      continue;
-    }
-    const float lambda = lambda_in[gblk0 + (inside ? blk : cc.nblk - 1)];
-    int nq = 0, qmax = 0;
-    float azd63;
-    {
-      const int16_t *uq = coef_uq + (size_t)img * C.coefs_per_image + cc.coef_off + (inside ? blk : cc.nblk - 1);
-      short xs[64];
-#pragma unroll
-      for (int k = 1; k < 64; k++) xs[k] = uq[(size_t)k * cc.kstride];
-      // (the rows' wave-uniform constants: fetched for eight positions at a time, outside the per-position branch -- one scalar-memory
-      // round trip per eight positions instead of two per position; see dct_quant_body)
-      constexpr int QCH = 8;
-      int dq_c[QCH], sdiv_c[QCH];
-      unsigned mdiv_c[QCH];
-      float lt_c[QCH], rcp_c[QCH], thr_c[QCH];
-      float azd = 0.0f;
-#pragma unroll
-      for (int k = 1; k < 64; k++) {
-        if (k == 1 || (k % QCH) == 0) {
-#pragma unroll
-          for (int j = 0; j < QCH; j++) {
-            const int kk = (k / QCH) * QCH + j;
-            dq_c[j] = Q->dq8[cc.qtbl][kk];
-            lt_c[j] = Q->lambda_tbl[cc.qtbl][kk];
-            thr_c[j] = Q->thr8[cc.qtbl][kk];
-            if (FD) { sdiv_c[j] = Q->sdiv[cc.qtbl][kk]; mdiv_c[j] = Q->mdiv[cc.qtbl][kk]; }
-            else rcp_c[j] = Q->rcp8q[cc.qtbl][kk];
-          }
-        }
-        // The position's share of the all-zero distortion needs x^2 only: from the SIGNED coefficient converted to float -- xf * xf is
-        // the correctly rounded x^2, which is what (float)(x * x) is (one rounding of the same exact integer either way) -- and
-        // "quantizes to non-zero" is a compare of |xf| (a source modifier) with the table's float threshold: six VALU instructions per
-        // position instead of nine; |x| as an integer exists only inside the branch few positions take.
-        const int xsg = xs[k];
-        const float xf = (float)xsg;
-        float t = (xf * xf) * lambda;
-        t = t * lt_c[k % QCH];
-        const float azd_cur = t + azd;
-        if (__builtin_fabsf(xf) >= thr_c[k % QCH]) {
-          const int x = (int)__builtin_fabsf(xf);      // (one conversion with a source modifier)
-          const int dq = dq_c[k % QCH];
-          int qval = FD ? udiv_mh(x + (dq >> 1), sdiv_c[k % QCH], mdiv_c[k % QCH]) : udiv_exact(x + (dq >> 1), dq, rcp_c[k % QCH]);
-          if (qval >= 1024) qval = 1023;
-          qmax = qval > qmax ? qval : qmax;
-          // (a block with more than QN records is deferred: what its surplus records overwrite in the last slot is never read)
-          col[nq < QN ? nq : QN - 1][lane] = make_uint2((unsigned)k | ((__float_as_uint(xf) >> 25) & 64u) | ((unsigned)qval << 7) | ((unsigned)x << 17), __float_as_uint(azd));      // (the sign: the float's)
-          nq++;
-        }
-        azd = azd_cur;
-      }
-      azd63 = azd;
-      defer_blocks(inside && (nq > QN || qmax >= 16), worklist, (unsigned)img, ((unsigned)comp << 28) | (unsigned)blk, 0u, xs, dense, dense_cap, true, lane);
-      // (the whole batch's counts: the first range's header.  A large batch counts in every (count_mask + 1)-th tile only -- the host
-      // scales: three more atomics per pass on the line of the work-list counter, which one word's ~88 operations per microsecond make
-      // ~1.3 % of the kernel, profiles/r06g_occupancy.md)
-      if ((tl & count_mask) == 0) count_heavy(counts, inside, nq, lane);
-    }
-    const bool work = inside && nq <= QN && qmax < 16;
-
-    // ---- the walk: every lane consumes its own records, one record per round; the next record is always one load ahead ----
-    int nlive = 1, qi = 0, last = 0;
-    unsigned long long neg = 0ull;          // positions whose coefficient is negative (of the entries created so far)
-    bool act = work && nq > 0;
-    int i = 0, x = 0, qval = 0, ncd = 0, sgn = 0, e = 0, beste = -1, bestk = 0;
-    float azd_prev = 0.0f, azd_cur = 0.0f, d0 = 0.0f, d1 = 0.0f, d2 = 0.0f, d3 = 0.0f, best = 1e38f;
-    float end_best = azd63 + eobf;
-    uint2 rec_n = col[0][lane];
-    col[0][lane] = make_uint2(0u, 0u);     // record 0 is in registers: its slot becomes entry 0, the virtual start (position 0, azd 0, cost 0)
-    info[0][lane] = (info_t)0;
-    unsigned long long back4 = 0ull, mag4 = 0ull;      // SLIM: nibble e - 1 = back entry / magnitude of live entry e
-    // quantizer constants of the NEXT record's position: lane k holds entry k of the component's rows, fetched with ds_bpermute
-    // at a point where every lane of the wave is enabled (a disabled source lane would read as 0)
-    int dq_n = 1;
-    float lt_n = 0.0f;
-    auto lookup = [&]() {
-      const int a = (int)(rec_n.x & 63u) << 2;
-      dq_n = __builtin_amdgcn_ds_bpermute(a, dq_lane) & 0x3FFFF;      // 8q <= 8 * 32767: tells the compiler the 24-bit multiplies are exact
-      lt_n = __int_as_float(__builtin_amdgcn_ds_bpermute(a, __float_as_int(lt_lane)));
-    };
-    lookup();
-    // `wide`: some lane of the round has a record with more than two candidates (quantized magnitude >= 4); without one, the
-    // round's steps evaluate two candidates and the distortions of the other two are not computed
-    auto setup = [&](bool wide) {
-      const uint2 rec = rec_n;
-      qi++;
-      rec_n = col[qi][lane];      // qi <= nq <= QN: slot QN exists (a slot is overwritten only after its record was consumed: entry e lives in slot e <= qi - 1 when it is written, and record qi - 1 is in registers by then)
-      i = (int)(rec.x & 63u); sgn = (int)((rec.x >> 6) & 1u); qval = (int)((rec.x >> 7) & 1023u); x = (int)(rec.x >> 17);
-      azd_prev = __uint_as_float(rec.y);
-      const int dq = dq_n;
-      const float lti = lt_n;
-      float t = squaref(x) * lambda;      // ((float)x * (float)x == (float)(x * x): one rounding of the same exact integer)
-      t = t * lti;
-      azd_cur = t + azd_prev;
-      ncd = bitlen((unsigned)qval);
-      float dd[4] = { 3e38f, 3e38f, 3e38f, 3e38f };
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        if (k >= 2 && !wide) break;      // uniform
-        const int cand = (k < ncd - 1) ? (2 << k) - 1 : qval;
-        const int delta = mul24(cand, dq) - x;
-        const float d = squaref(delta) * lambda;      // (|delta| <= x < 2^15)
-        dd[k] = k < ncd ? d * lti : 3e38f;
-      }
-      d0 = dd[0]; d1 = dd[1]; d2 = dd[2]; d3 = dd[3];
-      e = nlive; best = 1e38f; beste = -1; bestk = 0;
-    };
-    auto next_wide = [&]() { return __builtin_amdgcn_ballot_w64(act && qi < nq && ((rec_n.x >> 7) & 1023u) >= 4u) != 0ull; };   // of the records about to be set up
-    bool wide = next_wide();
-    if (act) setup(wide);
-    // One ROUND per queue record.  A round is the scan of the lane's live entries for its current record (pair steps, run
-    // until the last lane's scan has ended) and then, at a point where the wave is whole again, the commit of the new entry and
-    // the setup of the next record for every working lane at once.  (Until round 5 a lane committed and set up as soon as its own
-    // scan ended: with 64 lanes some lane nearly always did, so those ~100 instructions were issued in almost every iteration
-    // for a handful of lanes -- tools/model_sched.py: 0.74 of the issued instructions this way.)  The same operations per lane
-    // in the same order: the files do not change.  Every working lane is at record `qi` of its queue in the same round.
-    while (__builtin_amdgcn_ballot_w64(act) != 0ull) {
-      if (act) {
-        // (a plain divergent loop: lanes whose scan has ended wait masked until the last one is done.  Written as
-        // `while (ballot(scan)) if (scan) {..}` until late in round 5, the loop carried its state through a bypass block: eight
-        // register copies plus a flag materialised and re-tested per pair step, 10 of its ~75 instructions)
-        if (!wide) v3_scan<QN, 2, info_t>(col, info, rate_rows, lane, e, i - 1, azd_prev, f0f, d0, d1, d2, d3, best, beste, bestk);
-        else v3_scan<QN, 4, info_t>(col, info, rate_rows, lane, e, i - 1, azd_prev, f0f, d0, d1, d2, d3, best, beste, bestk);
-      }
-      lookup();
-      const bool wide_n = next_wide();
-      if (act) {
-        if (beste >= 0) {
-          const int mag = (bestk < ncd - 1) ? (2 << bestk) - 1 : qval;
-          col[nlive][lane] = make_uint2(__float_as_uint(azd_cur), __float_as_uint(best));     // live entry nlive
-          if (SLIM) {
-            info[nlive][lane] = (info_t)i;
-            const int sh = 4 * (nlive - 1);      // (nlive >= 1; beste < nlive <= 16)
-            back4 |= (unsigned long long)(unsigned)beste << sh;
-            mag4 |= (unsigned long long)(unsigned)mag << sh;
-          } else
-          info[nlive][lane] = (info_t)((unsigned)i | ((unsigned)beste << 6) | ((unsigned)mag << 12));
-          neg |= (unsigned long long)sgn << i;
-          // end-of-block choice (jcdctmgr.c:1187-1207): entries appear in position order, strict '<' keeps the first minimum
-          float c = best + azd63;
-          c = c - azd_cur;
-          if (i < 63) c = c + eobf;
-          if (c < end_best) { end_best = c; last = nlive; }
-          nlive++;
-        }
-        if (qi >= nq) act = false;
-        else setup(wide_n);
-      }
-      wide = wide_n;
-    }
-
-    // ---- back-track (jcdctmgr.c:1211-1222) along the entry indices; values in visiting (descending position) order ----
-    unsigned long long pmask = 0ull;
-    int cnt = 0, e2 = work ? last : 0;
-    while (__builtin_amdgcn_ballot_w64(e2 > 0) != 0ull) {
-      if (e2 > 0) {
-        const unsigned inf = info[e2][lane];
-        const int sh = 4 * (e2 - 1);
-        const int mag = SLIM ? (int)((mag4 >> sh) & 15ull) : (int)(inf >> 12), pos = SLIM ? (int)inf : (int)(inf & 63u);
-        const int v = ((neg >> pos) & 1ull) ? -mag : mag;
-        colh[((cnt >> 2) * 64 + lane) * 4 + (cnt & 3)] = (unsigned short)v;
-        pmask |= 1ull << pos;
-        cnt++;
-        e2 = SLIM ? (int)((back4 >> sh) & 15ull) : (int)((inf >> 6) & 63u);
-      }
-    }
-    if (work) nzmask[gblk] = pmask;
-    {
-      int16_t *qo = coef_q + (size_t)img * C.coefs_per_image + cc.coef_off + blk;
-      // plane i+1 <- the i-th non-zero in position order = slot cnt-1-i; a plane is stored only while some block has a value for it
-#pragma unroll
-      for (int i2 = 0; i2 < QN; i2++) {
-        if (__builtin_amdgcn_ballot_w64(i2 < cnt) == 0ull) break;
-        if (i2 < cnt) {
-          const int s2 = cnt - 1 - i2;
-          qo[(size_t)(i2 + 1) * cc.kstride] = (int16_t)colh[((s2 >> 2) * 64 + lane) * 4 + (s2 & 3)];
-        }
-      }
-    }
-    __syncthreads();
-  }
+// ... and the kernel that counts: the same body
+template <int QN, int NPASS>
+__global__ void __launch_bounds__(64)
+k_trellis_ac_v3_cf(MjhConst C, const MjhQuant *__restrict__ Q, const int16_t *__restrict__ coef_uq, int16_t *__restrict__ coef_q,
+                   const MjhHuffTable *__restrict__ tabs, int slots_per_image, int4 ac_slot_of_comp, int4 tile0_of_comp,
+                   const float *__restrict__ lambda_in, uint8_t *__restrict__ nq8, unsigned *__restrict__ worklist,
+                   int16_t *__restrict__ dense, unsigned dense_cap, unsigned long long *__restrict__ nzmask, int img0, unsigned *__restrict__ counts, int count_mask,
+                   MjhHuffTable *__restrict__ fin_tabs, int4 fin_slot_of_comp)
+{
+  constexpr bool CF = true, FD = true;      // (the schedule asks for the count with the fast division only)
+#include "mjh_trellis_v3_body.inc"
 }
 
 // =============================================================================================
 // host-side launch wrappers
 // =============================================================================================
-void mjh_launch_trellis_ac(const MjhConst &C, const MjhQuant *Q, const void *uq, void *q, MjhHuffTable *tabs, int spi, const int ac_slot[4], const float *lambda,
+bool mjh_launch_trellis_ac(const MjhConst &C, const MjhQuant *Q, const void *uq, void *q, MjhHuffTable *tabs, int spi, const int ac_slot[4], const float *lambda,
                            unsigned *worklist, unsigned *worklist2, void *dense, unsigned dense_cap, int variant,
                            int Ss, int Se, void *eob_cost, int *eob_has, unsigned long long *nzmask, int qstride, int n, hipStream_t s,
                            uint8_t *nq8, int v3_passes, int fastdiv, hipEvent_t after_first_tier, hipEvent_t after_first_tier2,
-                           int chunks, hipStream_t side, hipEvent_t *ev_chunk, int count_mask)
+                           int chunks, hipStream_t side, hipEvent_t *ev_chunk, int count_mask, const int *fin_ac_slot)
 {
   // band-limited pass (use_scans_in_trellis), the per-block outputs of trellis_eob_opt, per-image tables (trellis_q_opt):
   // the EXT instantiations
@@ -1222,6 +980,12 @@ void mjh_launch_trellis_ac(const MjhConst &C, const MjhQuant *Q, const void *uq,
   ext.Ss = Ss; ext.Se = Se; ext.eob_cost = (float2 *)eob_cost; ext.eob_has = eob_has; ext.nzmask = nzmask; ext.qstride = qstride;
   const int4 sl = make_int4(ac_slot[0], ac_slot[1], ac_slot[2], ac_slot[3]);
   const bool sorted = !extended && nzmask && nq8 && v3_passes > 0 && variant <= 4;
+  // fin_ac_slot (not null: the result of this pass is final): EVERY tier counts the final AC symbols of the blocks it finishes into
+  // these slots, or none does -- the return value tells the caller, who launches k_stats_ac_compact where it is false.  The tiers
+  // count from compact records of a plain pass only, and the tile-sorted tier has counting kernels for the fast division only.
+  const bool cf = fin_ac_slot != nullptr && nzmask && !extended && (!sorted || fastdiv);
+  const int4 fsl = cf ? make_int4(fin_ac_slot[0], fin_ac_slot[1], fin_ac_slot[2], fin_ac_slot[3]) : make_int4(0, 0, 0, 0);
+  MjhHuffTable *const ftabs = cf ? tabs : nullptr;
   // Image ranges of the tile-sorted tier (see below): range c owns the work-list pair at word offset wo[c] (its own 16-byte
   // header; room for every block of its images) and its share of the dense copies
   const int nch = sorted && chunks > 1 && chunks <= 4 && side && ev_chunk && n >= 2 * chunks ? chunks : 1;
@@ -1245,8 +1009,13 @@ void mjh_launch_trellis_ac(const MjhConst &C, const MjhQuant *Q, const void *uq,
   const int4 wv = make_int4(w0[0], w0[1], w0[2], w0[3]);
   // the general tiers behind a first tier: blocks with more than its capacity (then 32) queue records, from their dense copies
 #define LQ(QN, EXTV, CMP) hipLaunchKernelGGL((k_trellis_ac_q<QN, EXTV, CMP>), gridq, dim3(64), 0, s, C, Q, (const int16_t *)uq, (int16_t *)q, (const MjhHuffTable *)tabs, spi, sl, wv, lambda, worklist, (int16_t *)dense, dense_cap, ext)
+#define LQF(QN) hipLaunchKernelGGL((k_trellis_ac_q_cf<QN>), gridq, dim3(64), 0, s, C, Q, (const int16_t *)uq, (int16_t *)q, (const MjhHuffTable *)tabs, spi, sl, wv, lambda, worklist, (int16_t *)dense, dense_cap, ext, ftabs, fsl)
+#define LQC(QN) do { if (cf) LQF(QN); else LQ(QN, false, true); } while (0)      // compact first tier
 #define LDX(QN, EXTV, CMP, GRID, WL, WLN, ST, DN, DCAP) hipLaunchKernelGGL((k_trellis_ac_qd<QN, EXTV, CMP>), dim3(GRID), dim3(64), 0, ST, C, Q, (const int16_t *)uq, (int16_t *)q, (const MjhHuffTable *)tabs, spi, sl, lambda, (const unsigned *)WL, WLN, (const int16_t *)DN, DCAP, ext)
+#define LDXF(QN, GRID, WL, WLN, ST, DN, DCAP) hipLaunchKernelGGL((k_trellis_ac_qd_cf<QN>), dim3(GRID), dim3(64), 0, ST, C, Q, (const int16_t *)uq, (int16_t *)q, (const MjhHuffTable *)tabs, spi, sl, lambda, (const unsigned *)WL, WLN, (const int16_t *)DN, DCAP, ext, ftabs, fsl)
+#define LDXC(QN, GRID, WL, WLN, ST, DN, DCAP) do { if (cf) LDXF(QN, GRID, WL, WLN, ST, DN, DCAP); else LDX(QN, false, true, GRID, WL, WLN, ST, DN, DCAP); } while (0)      // compact general tiers
 #define LD(QN, EXTV, CMP, GRID, WL, WLN) LDX(QN, EXTV, CMP, GRID, WL, WLN, s, dense, dense_cap)
+#define LDC(QN, GRID, WL, WLN) LDXC(QN, GRID, WL, WLN, s, dense, dense_cap)
   if (extended) {   // the rarely used options take one fixed tiering (16 -> 32 -> 63)
     LQ(16, true, false);
     LD(32, true, false, 2048, worklist, worklist2);
@@ -1278,13 +1047,17 @@ void mjh_launch_trellis_ac(const MjhConst &C, const MjhQuant *Q, const void *uq,
       int16_t *dn = (int16_t *)dense + (size_t)c * capc * 64;
       const int img0 = n0[c];
 #define LV3(QN, NP, FDV) hipLaunchKernelGGL((k_trellis_ac_v3<QN, NP, FDV>), gridt, dim3(64), 0, s, C, Q, (const int16_t *)uq, (int16_t *)q, (const MjhHuffTable *)tabs, spi, sl, tv, lambda, nq8, wl, dn, capc, nzmask, img0, worklist, count_mask)
-      if (small24) LV3(24, 1, true);
-      else if (variant >= 4) { if (fastdiv) LV3(48, 4, true); else LV3(48, 4, false); }      // q90 and up: 32 / 48 records (21 / 31 KB of LDS per wave)
-      else if (variant == 3) { if (fastdiv) LV3(32, 4, true); else LV3(32, 4, false); }
-      else if (variant > 0) { if (fastdiv) LV3(24, 4, true); else LV3(24, 4, false); }       // more records per block (higher qualities)
+#define LV3F(QN, NP) hipLaunchKernelGGL((k_trellis_ac_v3_cf<QN, NP>), gridt, dim3(64), 0, s, C, Q, (const int16_t *)uq, (int16_t *)q, (const MjhHuffTable *)tabs, spi, sl, tv, lambda, nq8, wl, dn, capc, nzmask, img0, worklist, count_mask, ftabs, fsl)
+#define LV3C(QN, NP) do { if (cf) LV3F(QN, NP); else LV3(QN, NP, true); } while (0)      // (cf implies fastdiv here, see above)
+      if (small24) LV3C(24, 1);
+      else if (variant >= 4) { if (fastdiv) LV3C(48, 4); else LV3(48, 4, false); }      // q90 and up: 32 / 48 records (21 / 31 KB of LDS per wave)
+      else if (variant == 3) { if (fastdiv) LV3C(32, 4); else LV3(32, 4, false); }
+      else if (variant > 0) { if (fastdiv) LV3C(24, 4); else LV3(24, 4, false); }       // more records per block (higher qualities)
       else if (!fastdiv) LV3(16, 4, false);
-      else switch (np) { case 8: LV3(16, 8, true); break; case 4: LV3(16, 4, true); break; case 2: LV3(16, 2, true); break; default: LV3(16, 1, true); break; }
+      else switch (np) { case 8: LV3C(16, 8); break; case 4: LV3C(16, 4); break; case 2: LV3C(16, 2); break; default: LV3C(16, 1); break; }
+#undef LV3C
 #undef LV3
+#undef LV3F
       const bool last = c == nch - 1;
       hipStream_t st = last ? s : side;
       if (last) {
@@ -1294,8 +1067,8 @@ void mjh_launch_trellis_ac(const MjhConst &C, const MjhQuant *Q, const void *uq,
         (void)hipEventRecord(ev_chunk[c], s);
         (void)hipStreamWaitEvent(side, ev_chunk[c], 0);
       }
-      if (variant >= 3) LDX(63, false, true, qd_grid, wl, (unsigned *)nullptr, st, dn, capc);   // what is left has more than 32 records or a magnitude >= 16: one general tier that takes everything
-      else { LDX(32, false, true, qd_grid, wl, wl2, st, dn, capc); LDX(63, false, true, 1024, wl2, (unsigned *)nullptr, st, dn, capc); }
+      if (variant >= 3) LDXC(63, qd_grid, wl, (unsigned *)nullptr, st, dn, capc);   // what is left has more than 32 records or a magnitude >= 16: one general tier that takes everything
+      else { LDXC(32, qd_grid, wl, wl2, st, dn, capc); LDXC(63, 1024, wl2, (unsigned *)nullptr, st, dn, capc); }
     }
     if (nch > 1) {
       (void)hipEventRecord(ev_chunk[nch - 1], side);
@@ -1303,9 +1076,9 @@ void mjh_launch_trellis_ac(const MjhConst &C, const MjhQuant *Q, const void *uq,
     }
   } else if (nzmask) {   // compact records out of the general first tier (the caller guarantees: plain pass)
     if (variant > 3) variant = 3;   // (the general first tier stops at 32 records)
-    switch (variant) { case 1: LQ(20, false, true); break; case 2: LQ(24, false, true); break; case 3: LQ(32, false, true); break; default: LQ(16, false, true); break; }
-    if (variant == 3) LD(63, false, true, 2048, worklist, (unsigned *)nullptr);
-    else { LD(32, false, true, 2048, worklist, worklist2); LD(63, false, true, 1024, worklist2, (unsigned *)nullptr); }
+    switch (variant) { case 1: LQC(20); break; case 2: LQC(24); break; case 3: LQC(32); break; default: LQC(16); break; }
+    if (variant == 3) LDC(63, 2048, worklist, (unsigned *)nullptr);
+    else { LDC(32, 2048, worklist, worklist2); LDC(63, 1024, worklist2, (unsigned *)nullptr); }
   } else {               // one plane per position (trellis loops, progressive scans with restart intervals ...)
     if (variant > 3) variant = 3;
     switch (variant) { case 1: LQ(20, false, false); break; case 2: LQ(24, false, false); break; case 3: LQ(32, false, false); break; default: LQ(16, false, false); break; }
@@ -1313,8 +1086,14 @@ void mjh_launch_trellis_ac(const MjhConst &C, const MjhQuant *Q, const void *uq,
     else { LD(32, false, false, 2048, worklist, worklist2); LD(63, false, false, 1024, worklist2, (unsigned *)nullptr); }
   }
 #undef LQ
+#undef LQC
+#undef LQF
 #undef LD
+#undef LDC
 #undef LDX
+#undef LDXC
+#undef LDXF
+  return cf;
 }
 
 void mjh_launch_trellis_eob_chain(const MjhConst &C, void *q, const MjhHuffTable *tabs, int spi, const int ac_slot[4], const void *eob_cost, const int *eob_has,

@@ -52,7 +52,7 @@ def build(force=False, verbose=False):
     os.makedirs(OUT, exist_ok=True)
     csrc = _sources()
     flags = [f for f in FLAGS if f != "-I" + CSRC] + ["-I" + csrc]
-    hdrs = [os.path.join(csrc, h) for h in os.listdir(csrc) if h.endswith(".h")] + \
+    hdrs = [os.path.join(csrc, h) for h in os.listdir(csrc) if h.endswith((".h", ".inc"))] + \
         [os.path.join(HERE, "include", "hip", "hip_runtime.h"), os.path.join(ROOT, "include", "mozjpeg_hip.h")]
     jobs = []
     for s in SOURCES + ["simt.cpp"]:
