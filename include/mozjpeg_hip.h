@@ -611,8 +611,14 @@ int mjh_encoder_set_transform(mjh_encoder *e, const mjh_transform *t);
  * (it takes the matrix row from output_scanline at the time of the call).  no_dither 1: plain (-dither none).
  * scale_num / scale_denom: djpeg -scale M/N, decoding at a reduced size inside the inverse DCT (jidctred.c).  The fraction is
  * resolved as jpeg_core_output_dimensions does (jdmaster.c:105ff): to k / 8 with the smallest k in 1..16 for which
- * scale_num * 8 <= scale_denom * k, 16 if there is none -- 1/5 decodes at 2/8.  k = 1, 2, 4 and 8 are built; 8 is the
- * full-size path, which 1/1 and 0/0 (a zeroed struct) name.  The output is ceil(W k / 8) x ceil(H k / 8): mjh_decode_stats
+ * scale_num * 8 <= scale_denom * k, 16 if there is none -- 1/5 decodes at 2/8.  Every k is built: 1, 2 and 4 (jidctred.c), 8
+ * (the full-size path, which 1/1 and 0/0, a zeroed struct, name) and, with all_scales, 3, 5, 6, 7 and 9 to 16 (jpeg_idct_3x3 to
+ * jpeg_idct_16x16 of jidctint.c: djpeg -scale 3/8 ... 16/8, enlarging included).
+ * all_scales: 0 = a scale that resolves to a k other than 1, 2, 4 or 8 is refused with MJH_EUNSUPPORTED, as it was before those
+ * sizes were built (the refusal and its text are part of the tested contract, so the new sizes are an opt-in); 1 = every k in
+ * 1..16 decodes.  Components are transformed at k, doubled while it is below 8 and the sampling ratios allow it (jdmaster.c:
+ * 287-320), so a 4:2:0 file at k = 5, 6, 7 has its chroma at 10, 12, 14; a call with a component above 8 keeps its sample
+ * planes in a buffer of its own (made by the first such call), every other call where they always were.  The output is ceil(W k / 8) x ceil(H k / 8): mjh_decode_stats
  * reports that size, mjh_get_pixels and mjh_get_pixels_device address that image.  The encoder is still the one made from
  * mjh_params_from_jpeg at the file's own size, and serves calls at different scales one after the other.
  * dct_method: the numbers of mjh_params.dct_method -- 0 = JDCT_ISLOW (jidctint.c), 1 = JDCT_IFAST (jidctfst.c: djpeg -dct fast,
@@ -633,9 +639,10 @@ int mjh_encoder_set_transform(mjh_encoder *e, const mjh_transform *t);
  * mjh_encode_coefficients_host / _device read.  The values are the 16 bits the reference's JCOEF holds; no +-1023 limit is
  * applied (that is the entropy coder's: a file with a larger value decodes here and is refused when it is coded again).  Every
  * other field of the struct is ignored, raw_planes too.  The files accepted are those of mjh_transcode_host.
- * dct_method, bottom_up, raw_planes, no_dither and raw_coefs were appended; 0 in all of them is the behaviour of the struct without them.
+ * dct_method, bottom_up, raw_planes, no_dither, raw_coefs and all_scales were appended; 0 in all of them is the behaviour of the struct without them.
  * MJH_EINVAL: an unknown colour space, pixel size, offsets or dct_method; a pixel size other than 0 or 2 or an offset with RGB565; a scale_num or scale_denom below 1 (other than 0/0).
- * MJH_EUNSUPPORTED: a lossless transform set on the encoder; a scale that resolves to an IDCT size of 3, 5, 6, 7 or 9 to 16;
+ * MJH_EUNSUPPORTED: a lossless transform set on the encoder; without all_scales, a scale that resolves to an IDCT size of 3, 5,
+ * 6, 7 or 9 to 16;
  * the float IDCT, cropping and colour quantization have no option here. */
 typedef struct {
   int out_color_space;
@@ -648,6 +655,7 @@ typedef struct {
   int raw_planes;
   int no_dither;
   int raw_coefs;
+  int all_scales;
 } mjh_decode_opts;
 void mjh_decode_opts_defaults(mjh_decode_opts *o);
 /* Decodes n files (opts == NULL: the defaults).  Queued on the encoder's stream; the bytes need not stay valid after the call.

@@ -122,7 +122,7 @@ class DecodeOpts(C.Structure):
     bottom-up rows, and the raw sample planes or the DCT coefficients instead of pixels"""
     _fields_ = [("out_color_space", C.c_int), ("pixel_size", C.c_int), ("rgb_offset", C.c_int * 3), ("fancy_upsampling", C.c_int),
                 ("scale_num", C.c_int), ("scale_denom", C.c_int), ("dct_method", C.c_int), ("bottom_up", C.c_int), ("raw_planes", C.c_int),
-                ("no_dither", C.c_int), ("raw_coefs", C.c_int)]
+                ("no_dither", C.c_int), ("raw_coefs", C.c_int), ("all_scales", C.c_int)]
 
 
 class Result(C.Structure):
@@ -602,7 +602,8 @@ PIXEL_LAYOUTS = {"rgb": (3, (0, 1, 2)), "bgr": (3, (2, 1, 0)), "rgbx": (4, (0, 1
                  "xbgr": (4, (3, 2, 1)), "xrgb": (4, (1, 2, 3))}      # name -> pixel_size, rgb_offset (the extended colour spaces)
 
 
-SCALED_IDCT_SIZES = (1, 2, 4, 8)      # the k of output = input * k / 8 that the pixel kernels are built for
+SCALED_IDCT_SIZES = (1, 2, 4, 8)      # the k of output = input * k / 8 that decode without all_scales=True
+ALL_IDCT_SIZES = tuple(range(1, 17))  # with it: the twelve other sizes of jidctint.c as well
 
 
 def scale_idct_size(num, denom):
@@ -614,8 +615,8 @@ def scale_idct_size(num, denom):
     return k
 
 
-def _parse_scale(scale):
-    """(num, denom) of a pair or a string "M/N"; None is 1/1"""
+def _parse_scale(scale, all_scales=False):
+    """(num, denom) of a pair or a string "M/N"; None is 1/1.  all_scales: every IDCT size in 1..16, not only 1, 2, 4 and 8"""
     if scale is None:
         return 1, 1
     try:
@@ -631,7 +632,7 @@ def _parse_scale(scale):
     if not (-2 ** 31 <= num < 2 ** 31 and -2 ** 31 <= denom < 2 ** 31):
         raise MjhError(EINVAL, "scale %d/%d (beyond an int)" % (num, denom))
     k = scale_idct_size(num, denom)
-    if k not in SCALED_IDCT_SIZES:
+    if k not in (ALL_IDCT_SIZES if all_scales else SCALED_IDCT_SIZES):
         raise MjhError(EUNSUPPORTED, "scale %d/%d decodes with the %dx%d inverse DCT; the sizes built are 1x1, 2x2, 4x4 and 8x8" % (num, denom, k, k))
     return num, denom
 
@@ -640,13 +641,14 @@ DCT_METHODS = {None: 0, "int": 0, "islow": 0, "fast": 1, "ifast": 1}     # djpeg
 
 
 def decode_opts(color=None, layout=None, pixel_size=0, rgb_offset=None, fancy_upsampling=True, scale=None, dct=None, bottom_up=False,
-                raw_planes=False, dither=True, raw_coefs=False):
+                raw_planes=False, dither=True, raw_coefs=False, all_scales=False):
     """DecodeOpts from djpeg's vocabulary.  color: None (the file's default: gray stays gray, a CMYK or YCCK file gives CMYK,
     everything else RGB), "gray" / "grayscale" (-grayscale), "rgb" (-rgb), "rgb565" (-rgb565: 16-bit pixels, with dither=False
     -dither none), "cmyk" (the one output of four-component files: [H, W, 4], C, M, Y, K; pixel_size 0 or 4, rgb_offset is
     ignored) or a CS_* number; layout: a name out of PIXEL_LAYOUTS, or pixel_size and rgb_offset;
     fancy_upsampling=False: -nosmooth; scale: -scale, a pair (num, denom) or a string "M/N" that resolves to 1/8, 2/8, 4/8 or
-    8/8 as djpeg resolves it (scale_idct_size); dct: "int" (the default) or "fast" (-dct fast, TurboJPEG's FASTDCT);
+    8/8 as djpeg resolves it (scale_idct_size) -- with all_scales=True to any k / 8, k in 1..16 (the other sizes of jidctint.c;
+    an opt-in because the refusal of those sizes is part of the tested contract); dct: "int" (the default) or "fast" (-dct fast, TurboJPEG's FASTDCT);
     bottom_up=True: the rows last to first (TurboJPEG's BOTTOMUP); raw_planes=True: no pixels, the sample planes (decode_planes);
     raw_coefs=True: nothing of the above, the quantized DCT coefficients (decode_coefficients)."""
     o = DecodeOpts()
@@ -668,7 +670,8 @@ def decode_opts(color=None, layout=None, pixel_size=0, rgb_offset=None, fancy_up
     elif o.out_color_space == CS_RGB565:
         o.rgb_offset[:] = [0, 0, 0]     # (the defaults name 0, 1, 2; a 16-bit pixel has no byte offsets)
     o.fancy_upsampling = int(bool(fancy_upsampling))
-    o.scale_num, o.scale_denom = _parse_scale(scale)
+    o.scale_num, o.scale_denom = _parse_scale(scale, all_scales)
+    o.all_scales = int(bool(all_scales))
     if isinstance(dct, int) and not isinstance(dct, bool):
         o.dct_method = dct
     elif dct in DCT_METHODS:
@@ -743,12 +746,13 @@ def yuv_plane_size(info, comp, k=8):
     return ph * info.v_samp_factor[comp] // maxv, pw * info.h_samp_factor[comp] // maxh
 
 
-def decode_planes(files, scale=None, dct=None, *, max_batch=64, device=0, progressive_sources=False, lossless_sources=False, arithmetic_sources=False):
+def decode_planes(files, scale=None, dct=None, *, max_batch=64, device=0, progressive_sources=False, lossless_sources=False, arithmetic_sources=False,
+                  all_scales=False):
     """Decode JPEG files to their sample planes on the GPU, without upsampling or colour conversion (TurboJPEG's
     tj3DecompressToYUVPlanes8): per file a list of uint8 arrays [h, w], one per component, of yuv_plane_size(), or the MjhError.
     Every component is transformed at the scale's own size (mjh_decode_opts.raw_planes), so the planes keep the file's
     subsampling at every scale.  A lossless file has no such planes: with lossless_sources=True, EUNSUPPORTED in its slot."""
-    return _decode_grouped(files, max_batch, device, decode_opts(scale=scale, dct=dct, raw_planes=True), progressive_sources, lossless_sources, arithmetic_sources)
+    return _decode_grouped(files, max_batch, device, decode_opts(scale=scale, dct=dct, raw_planes=True, all_scales=all_scales), progressive_sources, lossless_sources, arithmetic_sources)
 
 
 def decode_coefficients(files, *, max_batch=64, device=0, progressive_sources=False, lossless_sources=False, arithmetic_sources=False):

@@ -1120,7 +1120,7 @@ boolean jpeg_start_decompress(j_decompress_ptr cinfo)
 {
   d_master *m = DM(cinfo);
   mjh_decode_opts o;
-  int ci, k, rc, off[3], px;
+  int ci, k, rc, off[3], px, every;
   double t0 = 0.0;
   if (cinfo->global_state != DSTATE_READY) ERREXIT1(cinfo, JERR_BAD_STATE, cinfo->global_state);
   if (cinfo->buffered_image) refuse(cinfo, "buffered-image mode is not built (the GPU path decodes a whole file at once)");
@@ -1128,13 +1128,19 @@ boolean jpeg_start_decompress(j_decompress_ptr cinfo)
   if (cinfo->dct_method != JDCT_ISLOW && cinfo->dct_method != JDCT_IFAST) refuse(cinfo, "the float inverse DCT (djpeg -dct float) is not built on the GPU path (no CPU fallback)");
   calc_output_dimensions(cinfo);
   k = cinfo->min_DCT_scaled_size;
-  if (k != 1 && k != 2 && k != 4 && k != 8) {
+  /* MOZJPEG_HIP_ALL_SCALES=1: every size of jidctint.c decodes (mjh_decode_opts.all_scales); read here, per file, not at load */
+  {
+    const char *v = getenv("MOZJPEG_HIP_ALL_SCALES");
+    every = v && v[0] == '1' && v[1] == 0;
+  }
+  if (!every && k != 1 && k != 2 && k != 4 && k != 8) {
     char why[160];
     snprintf(why, sizeof(why), "scale %u/%u decodes with the %dx%d inverse DCT; the sizes built on the GPU path are 1x1, 2x2, 4x4 and 8x8", cinfo->scale_num, cinfo->scale_denom, k, k);
     refuse(cinfo, why);
   }
   mjh_decode_opts_defaults(&o);
   o.scale_num = k; o.scale_denom = 8;
+  o.all_scales = every;
   o.dct_method = cinfo->dct_method == JDCT_IFAST ? 1 : 0;
   o.fancy_upsampling = cinfo->do_fancy_upsampling ? 1 : 0;
   px = 0;

@@ -28,6 +28,7 @@
 #include "mjh_lossless.h"
 #include "mjh_decode.h"
 #include "mjh_idct.h"
+#include "mjh_scale_layout.h"
 #include "mjh_guard.h"
 #include "mjh_numa.h"
 #include "mjh_arith_table.h"
@@ -468,6 +469,9 @@ struct mjh_encoder {
   // mjh_decode_host (mjh_idct.hip): the interleaved pixels of the last decoded batch (made at the first call, grown when a later
   // call asks for larger pixels), its layout, its status words on the host and the event behind everything it queued
   uint8_t *d_pixout = nullptr; size_t pixout_cap = 0;
+  // the sample planes of a decode call with a component at an IDCT size above 8 (all_scales; MjhPlaneLayout.own): made by the
+  // first such call, grown like d_pixout.  Every other call keeps its samples in d_planes.
+  uint8_t *d_planes_big = nullptr; size_t planes_big_cap = 0;
   DecOut dp{};
   unsigned *h_dstat = nullptr;
   hipEvent_t dp_ev[3] = { nullptr, nullptr, nullptr }, dp_done = nullptr; bool dp_timed = false;
@@ -478,6 +482,9 @@ struct mjh_encoder {
   // at plane_off, rows rp_pitch[c] apart)
   bool dp_raw = false;
   int rp_ncomp = 0, rp_w[MJH_MAXC] = {}, rp_h[MJH_MAXC] = {}, rp_pitch[MJH_MAXC] = {};
+  // where they lie: component c of image i at rp_base + i * rp_stride + rp_off[c] (d_planes with the encoder's own offsets, or
+  // d_planes_big with the call's layout)
+  uint8_t *rp_base = nullptr; size_t rp_off[MJH_MAXC] = {}, rp_stride = 0;
   // raw_coefs: the batch stopped after K-D; k_export_coefs put its coefficients into d_coefx as block-major natural-order arrays
   // (cx: component c's array of image 0, its row pitch in blocks, the bytes between images).  The buffer is made by the first
   // raw_coefs call.
@@ -964,6 +971,7 @@ static void free_all(mjh_encoder *e)
   for (hipEvent_t ev : e->pg_ev) if (ev) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : e->ar_ev) if (ev) (void)hipEventDestroy(ev);
   if (e->d_pixout) (void)mjh_guard_free(e->d_pixout);
+  if (e->d_planes_big) (void)mjh_guard_free(e->d_planes_big);
   if (e->d_coefx) (void)mjh_guard_free(e->d_coefx);
   for (hipEvent_t ev : e->cx_ev) if (ev) (void)hipEventDestroy(ev);
   if (e->h_dstat) (void)hipHostFree(e->h_dstat);
@@ -3755,15 +3763,15 @@ extern "C" void mjh_decode_opts_defaults(mjh_decode_opts *o)
 }
 
 // the IDCT size k of djpeg -scale num/denom (output = input * k / 8), as jpeg_core_output_dimensions resolves the fraction
-// (jdmaster.c:105-235): the smallest k in 1..16 with num * 8 <= denom * k, else 16.  0/0 is 1/1.
+// (jdmaster.c:105-235): the smallest k in 1..16 with num * 8 <= denom * k, else 16.  0/0 is 1/1.  Without all_scales the sizes
+// beyond 1, 2, 4 and 8 are refused as they always were (the refusal and its text are pinned by tests).
 static int resolve_scale(const mjh_decode_opts *o, int *k)
 {
   *k = 8;
   if (o->scale_num == 0 && o->scale_denom == 0) return MJH_OK;
   if (o->scale_num < 1 || o->scale_denom < 1) return fail(MJH_EINVAL, "scale %d/%d (both at least 1, or 0/0 for 1/1)", o->scale_num, o->scale_denom);
-  int s = 1;
-  while (s < 16 && (long long)o->scale_num * 8 > (long long)o->scale_denom * s) s++;
-  if (s != 1 && s != 2 && s != 4 && s != 8)
+  const int s = mjh_scale_idct_size(o->scale_num, o->scale_denom);
+  if (!o->all_scales && !mjh_scale_size_is_classic(s))
     return fail(MJH_EUNSUPPORTED, "scale %d/%d decodes with the %dx%d inverse DCT (jidctint.c); the sizes built are 1x1, 2x2, 4x4 (jidctred.c) and 8x8", o->scale_num, o->scale_denom, s, s);
   *k = s;
   return MJH_OK;
@@ -3776,7 +3784,8 @@ static int resolve_scale(const mjh_decode_opts *o, int *k)
 // At k = 8 every component is at size 8 and this is the full-size plan.
 // *out: the output buffer's geometry.  Exactly one plan is made: *P4 for a four-component file (e->four, k_upcolor4), else *P
 // (k_upcolor, k_upcolor_565); the other stays zeroed.  up[c]: the upsampling of every component the plan reads, *ncomp of them.
-static int plan_pixels(const mjh_encoder *e, const mjh_decode_opts *o, int k, DecOut *out, MjhPixOut *P, MjhPixOut4 *P4, MjhUpComp up[MJH_MAXC], int *ncomp, int ssize[MJH_MAXC])
+// *L: where the planes lie (MjhPlaneLayout): the encoder's own offsets, or the call's where a component is larger than 8.
+static int plan_pixels(const mjh_encoder *e, const mjh_decode_opts *o, int k, DecOut *out, MjhPixOut *P, MjhPixOut4 *P4, MjhUpComp up[MJH_MAXC], int *ncomp, int ssize[MJH_MAXC], MjhPlaneLayout *L)
 {
   const MjhConst &C = e->C;
   memset(P, 0, sizeof(*P));
@@ -3829,13 +3838,13 @@ static int plan_pixels(const mjh_encoder *e, const mjh_decode_opts *o, int k, De
     MjhUpComp &u = up[c];
     memset(&u, 0, sizeof(u));
     if (C.maxh % cc.h || C.maxv % cc.v) return fail(MJH_EUNSUPPORTED, "fractional sampling ratios (JERR_FRACT_SAMPLE_NOTIMPL, jdsample.c:529)");
-    int ss = k;
-    while (ss < 8 && (C.maxh * k) % (cc.h * ss * 2) == 0 && (C.maxv * k) % (cc.v * ss * 2) == 0) ss *= 2;
+    const int ss = mjh_scaled_size(k, cc.h, cc.v, C.maxh, C.maxv);
     ssize[c] = ss;
     u.dw = (int)div_round_up((long)C.W * cc.h * ss, (long)C.maxh * 8);
     u.dh = (int)div_round_up((long)C.H * cc.v * ss, (long)C.maxv * 8);
-    // the reduced plane sits where the full-size one does; its rows hold whole words of k_idct_scaled's lanes (ss = 8: pw itself)
-    u.pw = (cc.wib * ss + 3) & ~3; u.plane_off = cc.plane_off;
+    // the reduced plane sits where the full-size one does; its rows hold whole words of k_idct_scaled's lanes (ss = 8: pw itself).
+    // (A call with a component above 8 moves all of them: below.)
+    u.pw = mjh_scaled_pitch(cc.wib, ss); u.plane_off = cc.plane_off;
     u.mode = MJH_UP_REPLICATE;
     // the upsampler's groups: h_in_group = h * ssize / k samples become h_out_group = max_h (jdsample.c:454-459)
     u.hexp = C.maxh * k / (cc.h * ss); u.vexp = C.maxv * k / (cc.v * ss);
@@ -3843,13 +3852,23 @@ static int plan_pixels(const mjh_encoder *e, const mjh_decode_opts *o, int k, De
     else if (u.hexp == 1 && u.vexp == 2) { if (fancy) u.mode = MJH_UP_H1V2_FANCY; }
     else if (u.hexp == 2 && u.vexp == 2) { if (fancy && u.dw > 2) u.mode = MJH_UP_H2V2_FANCY; }
   }
+  long long planes_per_image = C.planes_per_image;
+  {
+    int wib[MJH_MAXC], hib[MJH_MAXC];
+    for (int c = 0; c < *ncomp; c++) { wib[c] = C.c[c].wib; hib[c] = C.c[c].hib; }
+    mjh_plane_layout(*ncomp, wib, hib, ssize, L);
+    if (L->own) {
+      for (int c = 0; c < *ncomp; c++) up[c].plane_off = (long long)L->off[c];
+      planes_per_image = (long long)L->stride;
+    }
+  }
   if (src_four) {
     P4->W = out->W; P4->H = out->H;
-    P4->row_pitch = out->row_pitch; P4->image_stride = out->image_stride; P4->planes_per_image = C.planes_per_image;
+    P4->row_pitch = out->row_pitch; P4->image_stride = out->image_stride; P4->planes_per_image = planes_per_image;
     for (int c = 0; c < 4; c++) P4->c[c] = up[c];
   } else {
     P->W = out->W; P->H = out->H; P->px_size = px; P->ncomp = *ncomp;
-    P->row_pitch = out->row_pitch; P->image_stride = out->image_stride; P->planes_per_image = C.planes_per_image;
+    P->row_pitch = out->row_pitch; P->image_stride = out->image_stride; P->planes_per_image = planes_per_image;
     for (int c = 0; c < P->ncomp; c++) P->c[c] = up[c];
   }
   return MJH_OK;
@@ -4153,6 +4172,7 @@ extern "C" int mjh_decode_host(mjh_encoder *e, const void *const jpegs[], const 
   memset(&P, 0, sizeof(P));
   memset(&P4, 0, sizeof(P4));
   memset(up, 0, sizeof(up));
+  MjhPlaneLayout L;
   if (raw) {
     // the planes alone: every component at the scale's own size (what TurboJPEG forces for planar output, turbojpeg.c:2151-2167),
     // so that they keep the file's subsampling at every scale; nothing of the pixel options is looked at
@@ -4161,9 +4181,11 @@ extern "C" int mjh_decode_host(mjh_encoder *e, const void *const jpegs[], const 
     if (C0.precision != 8) return fail(MJH_EUNSUPPORTED, "decoding %d-bit files", C0.precision);
     out.W = (int)div_round_up((long)C0.W * k, 8); out.H = (int)div_round_up((long)C0.H * k, 8);
     ncomp = C0.ncomp;
-    for (int c = 0; c < ncomp; c++) { ssize[c] = k; up[c].pw = k == 8 ? C0.c[c].pw : (C0.c[c].wib * k + 3) & ~3; }
+    int wib[MJH_MAXC], hib[MJH_MAXC];
+    for (int c = 0; c < ncomp; c++) { ssize[c] = k; up[c].pw = k == 8 ? C0.c[c].pw : mjh_scaled_pitch(C0.c[c].wib, k); wib[c] = C0.c[c].wib; hib[c] = C0.c[c].hib; }
+    mjh_plane_layout(ncomp, wib, hib, ssize, &L);
   } else {
-    rc = plan_pixels(e, &o, k, &out, &P, &P4, up, &ncomp, ssize);
+    rc = plan_pixels(e, &o, k, &out, &P, &P4, up, &ncomp, ssize, &L);
     if (rc) return rc;
     P.bottom_up = P4.bottom_up = o.bottom_up != 0;
   }
@@ -4178,6 +4200,24 @@ extern "C" int mjh_decode_host(mjh_encoder *e, const void *const jpegs[], const 
     e->pixout_cap = 0;
     HIPCHK(mjh_dmalloc((void **)&e->d_pixout, need));
     e->pixout_cap = need;
+  }
+  // planes larger than the full-size ones: a buffer of the call's layout, made on demand and kept
+  uint8_t *planes = e->d_planes;
+  size_t plane_stride = (size_t)C.planes_per_image, plane_at[MJH_MAXC];
+  for (int c = 0; c < ncomp; c++) plane_at[c] = (size_t)C.c[c].plane_off;
+  if (L.own) {
+    const size_t need_planes = mjh_plane_layout_bytes(&L, e->max_batch);
+    if (!need_planes) return fail(MJH_ENOMEM, "the sample planes of %d images at the %dx%d inverse DCT do not fit the address space", e->max_batch, k, k);
+    if (need_planes > e->planes_big_cap) {
+      HIPCHK(hipStreamSynchronize(e->stream));
+      if (e->d_planes_big) { (void)mjh_guard_free(e->d_planes_big); e->d_planes_big = nullptr; }
+      e->planes_big_cap = 0;
+      HIPCHK(mjh_dmalloc((void **)&e->d_planes_big, need_planes));
+      e->planes_big_cap = need_planes;
+    }
+    planes = e->d_planes_big;
+    plane_stride = L.stride;
+    for (int c = 0; c < ncomp; c++) plane_at[c] = L.off[c];
   }
   rc = decode_host_state(e);
   if (rc) return rc;
@@ -4218,6 +4258,10 @@ extern "C" int mjh_decode_host(mjh_encoder *e, const void *const jpegs[], const 
         if (ss == 8) memcpy(QS.q[c], QF.q[c], sizeof(QS.q[c]));
       }
     for (int c = 0; c < ncomp; c++) {
+      if (ssize[c] != 8 && !mjh_scale_size_is_classic(ssize[c])) {       // a size of jidctint.c (all_scales): the planes may be the call's own
+        mjh_launch_idct_sized(C, QS, c, ssize[c], up[c].pw, (long long)plane_at[c], (long long)plane_stride, e->d_q, planes, e->d_tstat, n, s);
+        continue;
+      }
       if (ssize[c] != 8) { mjh_launch_idct_scaled(C, QS, c, ssize[c], up[c].pw, e->d_q, e->d_planes, e->d_tstat, n, s); continue; }
       C8.c[n8] = C.c[c];
       memcpy(Q8.q[n8], (ifast ? QF : Q).q[c], sizeof(Q8.q[n8]));
@@ -4228,10 +4272,11 @@ extern "C" int mjh_decode_host(mjh_encoder *e, const void *const jpegs[], const 
   if (timed) HIPCHK(hipEventRecord(e->dp_ev[1], s));
   if (raw) {
     e->rp_ncomp = ncomp;
-    for (int c = 0; c < ncomp; c++) { e->rp_w[c] = C.c[c].wib * k; e->rp_h[c] = C.c[c].hib * k; e->rp_pitch[c] = up[c].pw; }
-  } else if (e->four) mjh_launch_upcolor4(P4, e->d_planes, e->d_pixout, e->d_tstat, n, s);
-  else if (out.px_size == 2) mjh_launch_upcolor_565(P, o.no_dither == 0, e->d_planes, e->d_pixout, e->d_tstat, n, s);
-  else mjh_launch_upcolor(P, e->d_planes, e->d_pixout, e->d_tstat, n, s);
+    for (int c = 0; c < ncomp; c++) { e->rp_w[c] = C.c[c].wib * k; e->rp_h[c] = C.c[c].hib * k; e->rp_pitch[c] = up[c].pw; e->rp_off[c] = plane_at[c]; }
+    e->rp_base = planes; e->rp_stride = plane_stride;
+  } else if (e->four) mjh_launch_upcolor4(P4, planes, e->d_pixout, e->d_tstat, n, s);
+  else if (out.px_size == 2) mjh_launch_upcolor_565(P, o.no_dither == 0, planes, e->d_pixout, e->d_tstat, n, s);
+  else mjh_launch_upcolor(P, planes, e->d_pixout, e->d_tstat, n, s);
   if (timed) HIPCHK(hipEventRecord(e->dp_ev[2], s));
   e->dp_timed = timed;
   HIPCHK(hipGetLastError());
@@ -4303,7 +4348,7 @@ extern "C" int mjh_get_plane(mjh_encoder *e, int i, int comp, void *dst, size_t 
   if (width < 1 || height < 1 || width > e->rp_w[comp] || height > e->rp_h[comp])
     return fail(MJH_EINVAL, "%d x %d samples of component %d, whose plane holds %d x %d", width, height, comp, e->rp_w[comp], e->rp_h[comp]);
   if (row_pitch < (size_t)width) return fail(MJH_EINVAL, "row_pitch %zu is smaller than a row (%d bytes)", row_pitch, width);
-  HIPCHK(hipMemcpy2D(dst, row_pitch, e->d_planes + (size_t)i * (size_t)e->C.planes_per_image + (size_t)e->C.c[comp].plane_off, (size_t)e->rp_pitch[comp],
+  HIPCHK(hipMemcpy2D(dst, row_pitch, e->rp_base + (size_t)i * e->rp_stride + e->rp_off[comp], (size_t)e->rp_pitch[comp],
                      (size_t)width, (size_t)height, hipMemcpyDeviceToHost));
   return MJH_OK;
 }
@@ -4313,9 +4358,9 @@ extern "C" int mjh_get_planes_device(mjh_encoder *e, int comp, void **d_base, si
   if (!e) return fail(MJH_EINVAL, "null encoder");
   if (!e->dp_queued || !e->dp_raw) return fail(MJH_EINVAL, "the last batch was not decoded with raw_planes");
   if (comp < 0 || comp >= e->rp_ncomp) return fail(MJH_EINVAL, "component %d of %d", comp, e->rp_ncomp);
-  if (d_base) *d_base = e->d_planes + (size_t)e->C.c[comp].plane_off;
+  if (d_base) *d_base = e->rp_base + e->rp_off[comp];
   if (row_pitch) *row_pitch = (size_t)e->rp_pitch[comp];
-  if (image_stride) *image_stride = (size_t)e->C.planes_per_image;
+  if (image_stride) *image_stride = e->rp_stride;
   if (width) *width = e->rp_w[comp];
   if (height) *height = e->rp_h[comp];
   return MJH_OK;

@@ -63,6 +63,11 @@ void mjh_launch_idct_ifast(const MjhConst &C, const MjhIdctQ &Q, int comps, cons
 // jidctred.c), its N x N samples per block into a plane at the component's plane_off whose rows are `pitch` samples apart (a
 // multiple of 4, at least wib * N; never more than the full-size plane holds).  Components left at size 8: mjh_launch_idct.
 void mjh_launch_idct_scaled(const MjhConst &C, const MjhIdctQ &Q, int ci, int N, int pitch, const int16_t *coef_q, uint8_t *planes, const unsigned *status, int n, hipStream_t s);
+// K-I1 at every other size of jidctint.c (mjh_decode_opts.all_scales): component ci alone at DCT_scaled_size N of 3, 5, 6, 7 or
+// 9 to 16, its N x N samples per block into a plane at plane_off of an image's planes_per_image samples, rows `pitch` samples
+// apart ((wib * N + 3) & ~3).  The layout is the caller's: for N > 8 the plane is larger than the full-size one (mjh_scale_layout.h).
+void mjh_launch_idct_sized(const MjhConst &C, const MjhIdctQ &Q, int ci, int N, int pitch, long long plane_off, long long planes_per_image,
+                           const int16_t *coef_q, uint8_t *planes, const unsigned *status, int n, hipStream_t s);
 // K-I2: sample planes -> interleaved pixels.  Everything it knows of the planes and the image comes from P, so a scaled decode
 // is the same kernel given the reduced planes (dw, dh, pw), the group ratios of jdsample.c:454-459 and the scaled W x H.
 void mjh_launch_upcolor(const MjhPixOut &P, const uint8_t *planes, uint8_t *pixels, const unsigned *status, int n, hipStream_t s);

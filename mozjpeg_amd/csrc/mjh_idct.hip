@@ -18,6 +18,10 @@
 //   Fewer coefficient planes read, N x N samples per block written; see the kernel.  Components a scaled decode leaves at
 //   size 8 (and every component of an unscaled call) go through k_idct, or k_idct_ifast when the call asks for the fast method
 //   (jddctmgr.c start_pass consults dct_method at size 8 only).
+// K-I1n k_idct_sized<N>: the twelve other sizes of jidctint.c, N = 3, 5, 6, 7 and 9 to 16 (djpeg -scale N/8 with
+//   mjh_decode_opts.all_scales), one component per launch.  N x N samples per block, whose rows need not start at a word: a wave
+//   lays 64 blocks' worth of a sample row down in LDS and stores it as whole words; for N > 8 into planes of the call's own,
+//   larger than the full-size ones (mjh_scale_layout.h); see the kernel.
 // K-I2 k_upcolor: one lane per 4 output pixels of a row.  Per component the upsampler jinit_upsampler picks (jdsample.c:444-525),
 //   evaluated per output sample from the samples it reads, then the colour conversion of jdcolor.c / jdcolext.c, then one 4-byte,
 //   three 4-byte (12 contiguous bytes) or one 16-byte store (rows of the output hold whole groups of 4 pixels).
@@ -287,6 +291,480 @@ k_idct_scaled(MjhConst C, MjhIdctQ Q, int ci, int pitch, const int16_t *__restri
   for (int r = 0; r < N; r++) *reinterpret_cast<unsigned *>(out + (size_t)r * pitch) = w[r];
 }
 
+// ---- K-I1n: every other size of jidctint.c, N = 3, 5, 6, 7 and 9 to 16 (djpeg -scale N/8, mjh_decode_opts.all_scales) -----------
+// FIX() of jidctint.c: a constant at CONST_BITS 13
+__host__ __device__ constexpr long long fix13(double x) { return (long long)(x * 8192 + 0.5); }
+
+// The 1-D transforms of jpeg_idct_NxN, chosen by the number of outputs: the sums in front of the descaling shift, WITHOUT the
+// rounding term.  The reference adds that term (1 << 10 in pass 1, 1 << 17 in pass 2) to the DC term, which reaches every output
+// with the coefficient 1 -- the arithmetic is exact in 64 bits, so the callers add it to the sums instead.  Where the reference's
+// pass 1 shifts an even term alone and adds an odd term that was only scaled by 2^PASS1_BITS (6x6, 10x10, 14x14: "tmp11 =
+// RIGHT_SHIFT(...)", "tmp1 = LEFT_SHIFT(z1 - z2 - z3, PASS1_BITS)"), the odd term is a multiple of the shift's divisor once
+// brought to CONST_BITS, and floor((a + m 2^11) / 2^11) = floor(a / 2^11) + m: the sum shifted is the same number, which is
+// how pass 2 of the reference has it.  So both passes of a size are one function here as well.
+// x: sizes below 8 read x[0 .. N-1], the others all eight.
+__device__ __forceinline__ void idct_1d(const int (&x)[8], long long (&o)[3])     // jpeg_idct_3x3
+{
+  const long long tmp0 = (long long)x[0] * 8192, tmp12 = x[2] * fix13(0.707106781);
+  const long long tmp10 = tmp0 + tmp12, odd = x[1] * fix13(1.224744871);
+  o[0] = tmp10 + odd; o[2] = tmp10 - odd;
+  o[1] = tmp0 - tmp12 - tmp12;
+}
+__device__ __forceinline__ void idct_1d(const int (&x)[8], long long (&o)[5])     // jpeg_idct_5x5
+{
+  long long tmp12 = (long long)x[0] * 8192;
+  long long tmp0 = x[2], tmp1 = x[4];
+  long long z1 = (tmp0 + tmp1) * fix13(0.790569415), z2 = (tmp0 - tmp1) * fix13(0.353553391), z3 = tmp12 + z2;
+  const long long tmp10 = z3 + z1, tmp11 = z3 - z1;
+  tmp12 -= z2 * 4;
+  z2 = x[1]; z3 = x[3];
+  z1 = (z2 + z3) * fix13(0.831253876);
+  tmp0 = z1 + z2 * fix13(0.513743148);
+  tmp1 = z1 - z3 * fix13(2.176250899);
+  o[0] = tmp10 + tmp0; o[4] = tmp10 - tmp0;
+  o[1] = tmp11 + tmp1; o[3] = tmp11 - tmp1;
+  o[2] = tmp12;
+}
+__device__ __forceinline__ void idct_1d(const int (&x)[8], long long (&o)[6])     // jpeg_idct_6x6
+{
+  long long tmp0 = (long long)x[0] * 8192;
+  long long tmp10 = x[4] * fix13(0.707106781);
+  long long tmp1 = tmp0 + tmp10;
+  const long long tmp11 = tmp0 - tmp10 - tmp10;
+  tmp0 = x[2] * fix13(1.224744871);
+  tmp10 = tmp1 + tmp0;
+  const long long tmp12 = tmp1 - tmp0;
+  const long long z1 = x[1], z2 = x[3], z3 = x[5];
+  tmp1 = (z1 + z3) * fix13(0.366025404);
+  tmp0 = tmp1 + (z1 + z2) * 8192;
+  const long long tmp2 = tmp1 + (z3 - z2) * 8192;
+  tmp1 = (z1 - z2 - z3) * 8192;
+  o[0] = tmp10 + tmp0; o[5] = tmp10 - tmp0;
+  o[1] = tmp11 + tmp1; o[4] = tmp11 - tmp1;
+  o[2] = tmp12 + tmp2; o[3] = tmp12 - tmp2;
+}
+__device__ __forceinline__ void idct_1d(const int (&x)[8], long long (&o)[7])     // jpeg_idct_7x7
+{
+  long long tmp13 = (long long)x[0] * 8192;
+  long long z1 = x[2], z2 = x[4], z3 = x[6];
+  long long tmp10 = (z2 - z3) * fix13(0.881747734), tmp12 = (z1 - z2) * fix13(0.314692123);
+  const long long tmp11 = tmp10 + tmp12 + tmp13 - z2 * fix13(1.841218003);
+  long long tmp0 = z1 + z3;
+  z2 -= tmp0;
+  tmp0 = tmp0 * fix13(1.274162392) + tmp13;
+  tmp10 += tmp0 - z3 * fix13(0.077722536);
+  tmp12 += tmp0 - z1 * fix13(2.470602249);
+  tmp13 += z2 * fix13(1.414213562);
+  z1 = x[1]; z2 = x[3]; z3 = x[5];
+  long long tmp1 = (z1 + z2) * fix13(0.935414347), tmp2 = (z1 - z2) * fix13(0.170262339);
+  tmp0 = tmp1 - tmp2;
+  tmp1 += tmp2;
+  tmp2 = (z2 + z3) * -fix13(1.378756276);
+  tmp1 += tmp2;
+  z2 = (z1 + z3) * fix13(0.613604268);
+  tmp0 += z2;
+  tmp2 += z2 + z3 * fix13(1.870828693);
+  o[0] = tmp10 + tmp0; o[6] = tmp10 - tmp0;
+  o[1] = tmp11 + tmp1; o[5] = tmp11 - tmp1;
+  o[2] = tmp12 + tmp2; o[4] = tmp12 - tmp2;
+  o[3] = tmp13;
+}
+__device__ __forceinline__ void idct_1d(const int (&x)[8], long long (&o)[9])     // jpeg_idct_9x9
+{
+  long long tmp0 = (long long)x[0] * 8192;
+  long long z1 = x[2], z2 = x[4], z3 = x[6], z4;
+  long long tmp3 = z3 * fix13(0.707106781);
+  long long tmp1 = tmp0 + tmp3, tmp2 = tmp0 - tmp3 - tmp3;
+  tmp0 = (z1 - z2) * fix13(0.707106781);
+  const long long tmp11 = tmp2 + tmp0, tmp14 = tmp2 - tmp0 - tmp0;
+  tmp0 = (z1 + z2) * fix13(1.328926049);
+  tmp2 = z1 * fix13(1.083350441);
+  tmp3 = z2 * fix13(0.245575608);
+  const long long tmp10 = tmp1 + tmp0 - tmp3, tmp12 = tmp1 - tmp0 + tmp2, tmp13 = tmp1 - tmp2 + tmp3;
+  z1 = x[1]; z2 = x[3]; z3 = x[5]; z4 = x[7];
+  z2 = z2 * -fix13(1.224744871);
+  tmp2 = (z1 + z3) * fix13(0.909038955);
+  tmp3 = (z1 + z4) * fix13(0.483689525);
+  tmp0 = tmp2 + tmp3 - z2;
+  tmp1 = (z3 - z4) * fix13(1.392728481);
+  tmp2 += z2 - tmp1;
+  tmp3 += z2 + tmp1;
+  tmp1 = (z1 - z3 - z4) * fix13(1.224744871);
+  o[0] = tmp10 + tmp0; o[8] = tmp10 - tmp0;
+  o[1] = tmp11 + tmp1; o[7] = tmp11 - tmp1;
+  o[2] = tmp12 + tmp2; o[6] = tmp12 - tmp2;
+  o[3] = tmp13 + tmp3; o[5] = tmp13 - tmp3;
+  o[4] = tmp14;
+}
+__device__ __forceinline__ void idct_1d(const int (&x)[8], long long (&o)[10])    // jpeg_idct_10x10
+{
+  long long z3 = (long long)x[0] * 8192, z4 = x[4];
+  long long z1 = z4 * fix13(1.144122806), z2 = z4 * fix13(0.437016024);
+  long long tmp10 = z3 + z1, tmp11 = z3 - z2;
+  const long long tmp22 = z3 - (z1 - z2) * 2;
+  z2 = x[2]; z3 = x[6];
+  z1 = (z2 + z3) * fix13(0.831253876);
+  long long tmp12 = z1 + z2 * fix13(0.513743148), tmp13 = z1 - z3 * fix13(2.176250899);
+  const long long tmp20 = tmp10 + tmp12, tmp24 = tmp10 - tmp12, tmp21 = tmp11 + tmp13, tmp23 = tmp11 - tmp13;
+  z1 = x[1]; z2 = x[3]; z3 = x[5]; z4 = x[7];
+  tmp11 = z2 + z4;
+  tmp13 = z2 - z4;
+  tmp12 = tmp13 * fix13(0.309016994);
+  const long long z5 = z3 * 8192;
+  z2 = tmp11 * fix13(0.951056516);
+  z4 = z5 + tmp12;
+  tmp10 = z1 * fix13(1.396802247) + z2 + z4;
+  const long long tmp14 = z1 * fix13(0.221231742) - z2 + z4;
+  z2 = tmp11 * fix13(0.587785252);
+  z4 = z5 - tmp12 - tmp13 * 4096;
+  tmp12 = (z1 - tmp13 - z3) * 8192;
+  tmp11 = z1 * fix13(1.260073511) - z2 - z4;
+  tmp13 = z1 * fix13(0.642039522) - z2 + z4;
+  o[0] = tmp20 + tmp10; o[9] = tmp20 - tmp10;
+  o[1] = tmp21 + tmp11; o[8] = tmp21 - tmp11;
+  o[2] = tmp22 + tmp12; o[7] = tmp22 - tmp12;
+  o[3] = tmp23 + tmp13; o[6] = tmp23 - tmp13;
+  o[4] = tmp24 + tmp14; o[5] = tmp24 - tmp14;
+}
+__device__ __forceinline__ void idct_1d(const int (&x)[8], long long (&o)[11])    // jpeg_idct_11x11
+{
+  long long tmp10 = (long long)x[0] * 8192;
+  long long z1 = x[2], z2 = x[4], z3 = x[6];
+  long long tmp20 = (z2 - z3) * fix13(2.546640132), tmp23 = (z2 - z1) * fix13(0.430815045);
+  long long z4 = z1 + z3;
+  long long tmp24 = z4 * -fix13(1.155664402);
+  z4 -= z2;
+  long long tmp25 = tmp10 + z4 * fix13(1.356927976);
+  const long long tmp21 = tmp20 + tmp23 + tmp25 - z2 * fix13(1.821790775);
+  tmp20 += tmp25 + z3 * fix13(2.115825087);
+  tmp23 += tmp25 - z1 * fix13(1.513598477);
+  tmp24 += tmp25;
+  const long long tmp22 = tmp24 - z3 * fix13(0.788749120);
+  tmp24 += z2 * fix13(1.944413522) - z1 * fix13(1.390975730);
+  tmp25 = tmp10 - z4 * fix13(1.414213562);
+  z1 = x[1]; z2 = x[3]; z3 = x[5]; z4 = x[7];
+  long long tmp11 = z1 + z2;
+  long long tmp14 = (tmp11 + z3 + z4) * fix13(0.398430003);
+  tmp11 = tmp11 * fix13(0.887983902);
+  long long tmp12 = (z1 + z3) * fix13(0.670361295);
+  long long tmp13 = tmp14 + (z1 + z4) * fix13(0.366151574);
+  tmp10 = tmp11 + tmp12 + tmp13 - z1 * fix13(0.923107866);
+  z1 = tmp14 - (z2 + z3) * fix13(1.163011579);
+  tmp11 += z1 + z2 * fix13(2.073276588);
+  tmp12 += z1 - z3 * fix13(1.192193623);
+  z1 = (z2 + z4) * -fix13(1.798248910);
+  tmp11 += z1;
+  tmp13 += z1 + z4 * fix13(2.102458632);
+  tmp14 += z2 * -fix13(1.467221301) + z3 * fix13(1.001388905) - z4 * fix13(1.684843907);
+  o[0] = tmp20 + tmp10; o[10] = tmp20 - tmp10;
+  o[1] = tmp21 + tmp11; o[9] = tmp21 - tmp11;
+  o[2] = tmp22 + tmp12; o[8] = tmp22 - tmp12;
+  o[3] = tmp23 + tmp13; o[7] = tmp23 - tmp13;
+  o[4] = tmp24 + tmp14; o[6] = tmp24 - tmp14;
+  o[5] = tmp25;
+}
+__device__ __forceinline__ void idct_1d(const int (&x)[8], long long (&o)[12])    // jpeg_idct_12x12
+{
+  long long z3 = (long long)x[0] * 8192;
+  long long z4 = x[4] * fix13(1.224744871);
+  long long tmp10 = z3 + z4, tmp11 = z3 - z4;
+  long long z1 = x[2];
+  z4 = z1 * fix13(1.366025404);
+  z1 = z1 * 8192;
+  long long z2 = (long long)x[6] * 8192;
+  long long tmp12 = z1 - z2;
+  const long long tmp21 = z3 + tmp12, tmp24 = z3 - tmp12;
+  tmp12 = z4 + z2;
+  const long long tmp20 = tmp10 + tmp12, tmp25 = tmp10 - tmp12;
+  tmp12 = z4 - z1 - z2;
+  const long long tmp22 = tmp11 + tmp12, tmp23 = tmp11 - tmp12;
+  z1 = x[1]; z2 = x[3]; z3 = x[5]; z4 = x[7];
+  tmp11 = z2 * fix13(1.306562965);
+  long long tmp14 = z2 * -fix13(0.541196100);
+  tmp10 = z1 + z3;
+  long long tmp15 = (tmp10 + z4) * fix13(0.860918669);
+  tmp12 = tmp15 + tmp10 * fix13(0.261052384);
+  tmp10 = tmp12 + tmp11 + z1 * fix13(0.280143716);
+  long long tmp13 = (z3 + z4) * -fix13(1.045510580);
+  tmp12 += tmp13 + tmp14 - z3 * fix13(1.478575242);
+  tmp13 += tmp15 - tmp11 + z4 * fix13(1.586706681);
+  tmp15 += tmp14 - z1 * fix13(0.676326758) - z4 * fix13(1.982889723);
+  z1 -= z4;
+  z2 -= z3;
+  z3 = (z1 + z2) * fix13(0.541196100);
+  tmp11 = z3 + z1 * fix13(0.765366865);
+  tmp14 = z3 - z2 * fix13(1.847759065);
+  o[0] = tmp20 + tmp10; o[11] = tmp20 - tmp10;
+  o[1] = tmp21 + tmp11; o[10] = tmp21 - tmp11;
+  o[2] = tmp22 + tmp12; o[9] = tmp22 - tmp12;
+  o[3] = tmp23 + tmp13; o[8] = tmp23 - tmp13;
+  o[4] = tmp24 + tmp14; o[7] = tmp24 - tmp14;
+  o[5] = tmp25 + tmp15; o[6] = tmp25 - tmp15;
+}
+__device__ __forceinline__ void idct_1d(const int (&x)[8], long long (&o)[13])    // jpeg_idct_13x13
+{
+  long long z1 = (long long)x[0] * 8192;
+  long long z2 = x[2], z3 = x[4], z4 = x[6];
+  long long tmp10 = z3 + z4, tmp11 = z3 - z4;
+  long long tmp12 = tmp10 * fix13(1.155388986), tmp13 = tmp11 * fix13(0.096834934) + z1;
+  const long long tmp20 = z2 * fix13(1.373119086) + tmp12 + tmp13, tmp22 = z2 * fix13(0.501487041) - tmp12 + tmp13;
+  tmp12 = tmp10 * fix13(0.316450131);
+  tmp13 = tmp11 * fix13(0.486914739) + z1;
+  const long long tmp21 = z2 * fix13(1.058554052) - tmp12 + tmp13, tmp25 = z2 * -fix13(1.252223920) + tmp12 + tmp13;
+  tmp12 = tmp10 * fix13(0.435816023);
+  tmp13 = tmp11 * fix13(0.937303064) - z1;
+  const long long tmp23 = z2 * -fix13(0.170464608) - tmp12 - tmp13, tmp24 = z2 * -fix13(0.803364869) + tmp12 - tmp13;
+  const long long tmp26 = (tmp11 - z2) * fix13(1.414213562) + z1;
+  z1 = x[1]; z2 = x[3]; z3 = x[5]; z4 = x[7];
+  tmp11 = (z1 + z2) * fix13(1.322312651);
+  tmp12 = (z1 + z3) * fix13(1.163874945);
+  long long tmp15 = z1 + z4;
+  tmp13 = tmp15 * fix13(0.937797057);
+  tmp10 = tmp11 + tmp12 + tmp13 - z1 * fix13(2.020082300);
+  long long tmp14 = (z2 + z3) * -fix13(0.338443458);
+  tmp11 += tmp14 + z2 * fix13(0.837223564);
+  tmp12 += tmp14 - z3 * fix13(1.572116027);
+  tmp14 = (z2 + z4) * -fix13(1.163874945);
+  tmp11 += tmp14;
+  tmp13 += tmp14 + z4 * fix13(2.205608352);
+  tmp14 = (z3 + z4) * -fix13(0.657217813);
+  tmp12 += tmp14;
+  tmp13 += tmp14;
+  tmp15 = tmp15 * fix13(0.338443458);
+  tmp14 = tmp15 + z1 * fix13(0.318774355) - z2 * fix13(0.466105296);
+  z1 = (z3 - z2) * fix13(0.937797057);
+  tmp14 += z1;
+  tmp15 += z1 + z3 * fix13(0.384515595) - z4 * fix13(1.742345811);
+  o[0] = tmp20 + tmp10; o[12] = tmp20 - tmp10;
+  o[1] = tmp21 + tmp11; o[11] = tmp21 - tmp11;
+  o[2] = tmp22 + tmp12; o[10] = tmp22 - tmp12;
+  o[3] = tmp23 + tmp13; o[9] = tmp23 - tmp13;
+  o[4] = tmp24 + tmp14; o[8] = tmp24 - tmp14;
+  o[5] = tmp25 + tmp15; o[7] = tmp25 - tmp15;
+  o[6] = tmp26;
+}
+__device__ __forceinline__ void idct_1d(const int (&x)[8], long long (&o)[14])    // jpeg_idct_14x14
+{
+  long long z1 = (long long)x[0] * 8192, z4 = x[4];
+  long long z2 = z4 * fix13(1.274162392), z3 = z4 * fix13(0.314692123);
+  z4 = z4 * fix13(0.881747734);
+  long long tmp10 = z1 + z2, tmp11 = z1 + z3, tmp12 = z1 - z4;
+  const long long tmp23 = z1 - (z2 + z3 - z4) * 2;
+  z1 = x[2]; z2 = x[6];
+  z3 = (z1 + z2) * fix13(1.105676686);
+  long long tmp13 = z3 + z1 * fix13(0.273079590), tmp14 = z3 - z2 * fix13(1.719280954);
+  long long tmp15 = z1 * fix13(0.613604268) - z2 * fix13(1.378756276);
+  const long long tmp20 = tmp10 + tmp13, tmp26 = tmp10 - tmp13, tmp21 = tmp11 + tmp14, tmp25 = tmp11 - tmp14;
+  const long long tmp22 = tmp12 + tmp15, tmp24 = tmp12 - tmp15;
+  z1 = x[1]; z2 = x[3]; z3 = x[5]; z4 = x[7];
+  tmp13 = z4 * 8192;
+  tmp14 = z1 + z3;
+  tmp11 = (z1 + z2) * fix13(1.334852607);
+  tmp12 = tmp14 * fix13(1.197448846);
+  tmp10 = tmp11 + tmp12 + tmp13 - z1 * fix13(1.126980169);
+  tmp14 = tmp14 * fix13(0.752406978);
+  long long tmp16 = tmp14 - z1 * fix13(1.061150426);
+  z1 -= z2;
+  tmp15 = z1 * fix13(0.467085129) - tmp13;
+  tmp16 += tmp15;
+  z1 += z4;
+  z4 = (z2 + z3) * -fix13(0.158341681) - tmp13;
+  tmp11 += z4 - z2 * fix13(0.424103948);
+  tmp12 += z4 - z3 * fix13(2.373959773);
+  z4 = (z3 - z2) * fix13(1.405321284);
+  tmp14 += z4 + tmp13 - z3 * fix13(1.6906431334);
+  tmp15 += z4 + z2 * fix13(0.674957567);
+  tmp13 = (z1 - z3) * 8192;
+  o[0] = tmp20 + tmp10; o[13] = tmp20 - tmp10;
+  o[1] = tmp21 + tmp11; o[12] = tmp21 - tmp11;
+  o[2] = tmp22 + tmp12; o[11] = tmp22 - tmp12;
+  o[3] = tmp23 + tmp13; o[10] = tmp23 - tmp13;
+  o[4] = tmp24 + tmp14; o[9] = tmp24 - tmp14;
+  o[5] = tmp25 + tmp15; o[8] = tmp25 - tmp15;
+  o[6] = tmp26 + tmp16; o[7] = tmp26 - tmp16;
+}
+__device__ __forceinline__ void idct_1d(const int (&x)[8], long long (&o)[15])    // jpeg_idct_15x15
+{
+  long long z1 = (long long)x[0] * 8192;
+  long long z2 = x[2], z3 = x[4], z4 = x[6];
+  long long tmp10 = z4 * fix13(0.437016024), tmp11 = z4 * fix13(1.144122806);
+  const long long tmp12 = z1 - tmp10, tmp13 = z1 + tmp11;
+  z1 -= (tmp11 - tmp10) * 2;
+  z4 = z2 - z3;
+  z3 += z2;
+  tmp10 = z3 * fix13(1.337628990);
+  tmp11 = z4 * fix13(0.045680613);
+  z2 = z2 * fix13(1.439773946);
+  const long long tmp20 = tmp13 + tmp10 + tmp11, tmp23 = tmp12 - tmp10 + tmp11 + z2;
+  tmp10 = z3 * fix13(0.547059574);
+  tmp11 = z4 * fix13(0.399234004);
+  const long long tmp25 = tmp13 - tmp10 - tmp11, tmp26 = tmp12 + tmp10 - tmp11 - z2;
+  tmp10 = z3 * fix13(0.790569415);
+  tmp11 = z4 * fix13(0.353553391);
+  const long long tmp21 = tmp12 + tmp10 + tmp11, tmp24 = tmp13 - tmp10 + tmp11;
+  tmp11 += tmp11;
+  const long long tmp22 = z1 + tmp11, tmp27 = z1 - tmp11 - tmp11;
+  z1 = x[1]; z2 = x[3]; z4 = x[5];
+  z3 = z4 * fix13(1.224744871);
+  z4 = x[7];
+  long long t13 = z2 - z4;
+  long long tmp15 = (z1 + t13) * fix13(0.831253876);
+  tmp11 = tmp15 + z1 * fix13(0.513743148);
+  const long long tmp14 = tmp15 - t13 * fix13(2.176250899);
+  t13 = z2 * -fix13(0.831253876);
+  tmp15 = z2 * -fix13(1.344997024);
+  z2 = z1 - z4;
+  long long t12 = z3 + z2 * fix13(1.406466353);
+  tmp10 = t12 + z4 * fix13(2.457431844) - tmp15;
+  const long long tmp16 = t12 - z1 * fix13(1.112434820) + t13;
+  t12 = z2 * fix13(1.224744871) - z3;
+  z2 = (z1 + z4) * fix13(0.575212477);
+  t13 += z2 + z1 * fix13(0.475753014) - z3;
+  tmp15 += z2 - z4 * fix13(0.869244010) + z3;
+  o[0] = tmp20 + tmp10; o[14] = tmp20 - tmp10;
+  o[1] = tmp21 + tmp11; o[13] = tmp21 - tmp11;
+  o[2] = tmp22 + t12; o[12] = tmp22 - t12;
+  o[3] = tmp23 + t13; o[11] = tmp23 - t13;
+  o[4] = tmp24 + tmp14; o[10] = tmp24 - tmp14;
+  o[5] = tmp25 + tmp15; o[9] = tmp25 - tmp15;
+  o[6] = tmp26 + tmp16; o[8] = tmp26 - tmp16;
+  o[7] = tmp27;
+}
+__device__ __forceinline__ void idct_1d(const int (&x)[8], long long (&o)[16])    // jpeg_idct_16x16
+{
+  long long tmp0 = (long long)x[0] * 8192;
+  long long z1 = x[4];
+  long long tmp1 = z1 * fix13(1.306562965), tmp2 = z1 * fix13(0.541196100);
+  long long tmp10 = tmp0 + tmp1, tmp11 = tmp0 - tmp1, tmp12 = tmp0 + tmp2, tmp13 = tmp0 - tmp2;
+  z1 = x[2];
+  long long z2 = x[6];
+  long long z3 = z1 - z2;
+  long long z4 = z3 * fix13(0.275899379);
+  z3 = z3 * fix13(1.387039845);
+  tmp0 = z3 + z2 * fix13(2.562915447);
+  tmp1 = z4 + z1 * fix13(0.899976223);
+  tmp2 = z3 - z1 * fix13(0.601344887);
+  long long tmp3 = z4 - z2 * fix13(0.509795579);
+  const long long tmp20 = tmp10 + tmp0, tmp27 = tmp10 - tmp0, tmp21 = tmp12 + tmp1, tmp26 = tmp12 - tmp1;
+  const long long tmp22 = tmp13 + tmp2, tmp25 = tmp13 - tmp2, tmp23 = tmp11 + tmp3, tmp24 = tmp11 - tmp3;
+  z1 = x[1]; z2 = x[3]; z3 = x[5]; z4 = x[7];
+  tmp11 = z1 + z3;
+  tmp1 = (z1 + z2) * fix13(1.353318001);
+  tmp2 = tmp11 * fix13(1.247225013);
+  tmp3 = (z1 + z4) * fix13(1.093201867);
+  tmp10 = (z1 - z4) * fix13(0.897167586);
+  tmp11 = tmp11 * fix13(0.666655658);
+  tmp12 = (z1 - z2) * fix13(0.410524528);
+  tmp0 = tmp1 + tmp2 + tmp3 - z1 * fix13(2.286341144);
+  tmp13 = tmp10 + tmp11 + tmp12 - z1 * fix13(1.835730603);
+  z1 = (z2 + z3) * fix13(0.138617169);
+  tmp1 += z1 + z2 * fix13(0.071888074);
+  tmp2 += z1 - z3 * fix13(1.125726048);
+  z1 = (z3 - z2) * fix13(1.407403738);
+  tmp11 += z1 - z3 * fix13(0.766367282);
+  tmp12 += z1 + z2 * fix13(1.971951411);
+  z2 += z4;
+  z1 = z2 * -fix13(0.666655658);
+  tmp1 += z1;
+  tmp3 += z1 + z4 * fix13(1.065388962);
+  z2 = z2 * -fix13(1.247225013);
+  tmp10 += z2 + z4 * fix13(3.141271809);
+  tmp12 += z2;
+  z2 = (z3 + z4) * -fix13(1.353318001);
+  tmp2 += z2;
+  tmp3 += z2;
+  z2 = (z4 - z3) * fix13(0.410524528);
+  tmp10 += z2;
+  tmp11 += z2;
+  o[0] = tmp20 + tmp0; o[15] = tmp20 - tmp0;
+  o[1] = tmp21 + tmp1; o[14] = tmp21 - tmp1;
+  o[2] = tmp22 + tmp2; o[13] = tmp22 - tmp2;
+  o[3] = tmp23 + tmp3; o[12] = tmp23 - tmp3;
+  o[4] = tmp24 + tmp10; o[11] = tmp24 - tmp10;
+  o[5] = tmp25 + tmp11; o[10] = tmp25 - tmp11;
+  o[6] = tmp26 + tmp12; o[9] = tmp26 - tmp12;
+  o[7] = tmp27 + tmp13; o[8] = tmp27 - tmp13;
+}
+
+// One lane per block of component ci; a wave holds 64 horizontally adjacent blocks of one block row ("chunk"), whose first
+// sample byte, 64 * cx * N, is word-aligned for every N.  A block's row is N bytes at byte lane * N of the chunk's row -- not a
+// word boundary for odd N -- so the wave lays the 64 x N bytes of one sample row down in LDS and its lanes carry them out as
+// whole words: every store instruction writes one contiguous run of a sample row, and no byte store goes to memory.  Two LDS
+// rows take turns, so one barrier per sample row is enough (a row is read before the barrier of the next, and written again
+// only behind it).
+// plane_off, planes_per_image: the layout of the call's sample planes -- the encoder's own where every component fits its
+// full-size plane, a layout of the call's where a component is larger (N > 8); pitch: samples between rows, (wib * N + 3) & ~3.
+// The lanes a last chunk has beyond wib read nothing and lay down zeros, of which at most three reach the pitch pad.
+template <int N>
+__global__ void __launch_bounds__(256)
+k_idct_sized(MjhConst C, MjhIdctQ Q, int ci, int pitch, long long plane_off, long long planes_per_image,
+             const int16_t *__restrict__ coef_q, uint8_t *__restrict__ planes, const unsigned *__restrict__ status)
+{
+  constexpr int NI = N < 8 ? N : 8;                    // the coefficients a 1-D transform reads (the workspace is NI wide)
+  __shared__ unsigned seg[2][4][16 * N];
+  const int img = blockIdx.z;
+  if (status[img] != 0u) return;                       // (the same for every lane of the workgroup)
+  const MjhComp &cc = C.c[ci];
+  const int cpr = (cc.wib + 63) >> 6;                  // chunks per block row
+  const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63u);
+  const int chunk = (int)blockIdx.x * 4 + wave;
+  const int by = chunk / cpr, cx = chunk - by * cpr;
+  const int bx = cx * 64 + lane;
+  const bool row_live = by < cc.hib, live = row_live && bx < cc.wib;
+  int ws[N][8];
+  if (live) {
+    const int16_t *in = coef_q + (size_t)img * C.coefs_per_image + cc.coef_off + (size_t)by * cc.wib + bx;
+    const int *q = Q.q[ci];
+    // pass 1: NI columns to N values each, scaled up by 2^PASS1_BITS
+#pragma unroll
+    for (int c = 0; c < NI; c++) {
+      int x[8];
+#pragma unroll
+      for (int r = 0; r < 8; r++) x[r] = r < NI ? (int)in[(size_t)kZigOfNat[r * 8 + c] * cc.kstride] * q[r * 8 + c] : 0;
+      long long o[N];
+      idct_1d(x, o);
+#pragma unroll
+      for (int r = 0; r < N; r++) ws[r][c] = (int)((o[r] + 1024) >> 11);
+    }
+#pragma unroll
+    for (int r = 0; r < N; r++)
+#pragma unroll
+      for (int c = NI; c < 8; c++) ws[r][c] = 0;
+  }
+  // the words of the chunk's sample row that hold samples of real blocks
+  const int nb = cc.wib - cx * 64 < 64 ? cc.wib - cx * 64 : 64;
+  const int nw = row_live ? (nb * N + 3) >> 2 : 0;
+  unsigned *out = reinterpret_cast<unsigned *>(planes + (size_t)img * (size_t)planes_per_image + (size_t)plane_off + (size_t)(by * N) * pitch + (size_t)cx * 64 * N);
+  // pass 2: N rows; descale by 2^(CONST_BITS + PASS1_BITS + 3), then the range limit with the sample's centre added
+#pragma unroll
+  for (int r = 0; r < N; r++) {
+    unsigned s[N];
+#pragma unroll
+    for (int c = 0; c < N; c++) s[c] = 0u;
+    if (live) {
+      long long o[N];
+      idct_1d(ws[r], o);
+#pragma unroll
+      for (int c = 0; c < N; c++) s[c] = idct_range_limit((int)((o[c] + (1 << 17)) >> 18));
+    }
+    unsigned *row = seg[r & 1][wave];
+    if (N % 4 == 0) {
+#pragma unroll
+      for (int j = 0; j < N / 4; j++) row[lane * (N / 4) + j] = s[4 * j] | (s[4 * j + 1] << 8) | (s[4 * j + 2] << 16) | (s[4 * j + 3] << 24);
+    } else if (N % 2 == 0) {
+      unsigned short *row16 = reinterpret_cast<unsigned short *>(row) + lane * (N / 2);
+#pragma unroll
+      for (int j = 0; j < N / 2; j++) row16[j] = (unsigned short)(s[2 * j] | (s[2 * j + 1] << 8));
+    } else {
+      unsigned char *row8 = reinterpret_cast<unsigned char *>(row) + lane * N;
+#pragma unroll
+      for (int j = 0; j < N; j++) row8[j] = (unsigned char)s[j];
+    }
+    __syncthreads();
+    for (int i = lane; i < nw; i += 64) out[((size_t)r * pitch >> 2) + i] = row[i];
+  }
+}
+
 // one sample of component uc at output position (x, y), 0 <= x < W, 0 <= y < H
 __device__ __forceinline__ int up_sample(const MjhUpComp &uc, const uint8_t *__restrict__ pl, int x, int y)
 {
@@ -491,4 +969,18 @@ void mjh_launch_idct_scaled(const MjhConst &C, const MjhIdctQ &Q, int ci, int N,
   if (N == 4) hipLaunchKernelGGL((k_idct_scaled<4>), grid, dim3(256), 0, s, C, Q, ci, pitch, coef_q, planes, status);
   else if (N == 2) hipLaunchKernelGGL((k_idct_scaled<2>), grid, dim3(256), 0, s, C, Q, ci, pitch, coef_q, planes, status);
   else hipLaunchKernelGGL((k_idct_scaled<1>), grid, dim3(256), 0, s, C, Q, ci, pitch, coef_q, planes, status);
+}
+
+void mjh_launch_idct_sized(const MjhConst &C, const MjhIdctQ &Q, int ci, int N, int pitch, long long plane_off, long long planes_per_image,
+                           const int16_t *coef_q, uint8_t *planes, const unsigned *status, int n, hipStream_t s)
+{
+  const MjhComp &cc = C.c[ci];
+  const int chunks = (cc.wib + 63) / 64 * cc.hib;
+  const dim3 grid((chunks + 3) / 4, 1, n);
+#define MJH_SIZED(K) case K: hipLaunchKernelGGL((k_idct_sized<K>), grid, dim3(256), 0, s, C, Q, ci, pitch, plane_off, planes_per_image, coef_q, planes, status); break
+  switch (N) {
+    MJH_SIZED(3); MJH_SIZED(5); MJH_SIZED(6); MJH_SIZED(7); MJH_SIZED(9); MJH_SIZED(10); MJH_SIZED(11);
+    MJH_SIZED(12); MJH_SIZED(13); MJH_SIZED(14); MJH_SIZED(15); MJH_SIZED(16);
+  }
+#undef MJH_SIZED
 }

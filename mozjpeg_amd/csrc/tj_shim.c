@@ -88,6 +88,14 @@ static int serve_decompress(void)
   return !(v && v[0] == '0' && v[1] == 0);
 }
 
+/* MOZJPEG_HIP_ALL_SCALES=1: every one of the 16 scaling factors decodes (mjh_decode_opts.all_scales), not only 1/1, 1/2, 1/4 and
+ * 1/8.  Read when a decode call fills its options, so one process can decode with and without it. */
+static int all_scales(void)
+{
+  const char *v = getenv("MOZJPEG_HIP_ALL_SCALES");
+  return v && v[0] == '1' && v[1] == 0;
+}
+
 static int pick_device(void)
 {
   static int next = 0;
@@ -774,7 +782,8 @@ static int decode_setup(tjs *t, const char *fn, const unsigned char *jpegBuf, si
   char msg[160];
   if (read_header(t, fn, jpegBuf, jpegSize, in)) return -1;
   if (t->max_pixels && (unsigned long long)t->jpeg_width * (unsigned long long)t->jpeg_height > (unsigned long long)t->max_pixels) return fail(t, fn, "Image is too large");
-  if (!(t->sf.num == 1 && (t->sf.denom == 1 || t->sf.denom == 2 || t->sf.denom == 4 || t->sf.denom == 8))) {
+  const int every = all_scales();
+  if (!every && !(t->sf.num == 1 && (t->sf.denom == 1 || t->sf.denom == 2 || t->sf.denom == 4 || t->sf.denom == 8))) {
     snprintf(msg, sizeof(msg), "scaling factor %d/%d is not built on the GPU path (1/1, 1/2, 1/4 and 1/8 are; no CPU fallback)", t->sf.num, t->sf.denom);
     return fail(t, fn, msg);
   }
@@ -782,6 +791,7 @@ static int decode_setup(tjs *t, const char *fn, const unsigned char *jpegBuf, si
   if (get_encoder(t, fn, &p)) return -1;
   mjh_decode_opts_defaults(o);
   o->scale_num = t->sf.num; o->scale_denom = t->sf.denom;
+  o->all_scales = every;
   o->fancy_upsampling = !t->fast_upsample;
   o->dct_method = t->fast_dct ? 1 : 0;                       /* JDCT_FASTEST = JDCT_IFAST / JDCT_ISLOW, turbojpeg-mp.c:191 */
   *W = TJSCALED(t->jpeg_width, t->sf); *H = TJSCALED(t->jpeg_height, t->sf);

@@ -9,7 +9,10 @@ after a warm-up) with the run-to-run spread; the phase times of the Huffman deco
 (mjh_set_profiling(1), a separate pass) with the bytes per second the pixel kernels reach against their byte counts; and the
 yardstick: oracle/_ref/djpeg -pnm over the same files, 16 processes at a time, input on a RAM disk and output discarded (that
 figure includes process start and PPM formatting).  The first call's pixels are compared with djpeg's before anything is timed.
---scale M/N: both workloads decoded at that scale (1/2, 1/4, 1/8: the reduced inverse DCTs), the reference being djpeg -scale M/N.
+--scale M/N: both workloads decoded at that scale (all_scales=True: any of the sixteen IDCT sizes), the reference being djpeg -scale
+M/N.  At the twelve sizes of k_idct_sized one file per call is compared with djpeg (file 0), and above full size only the path to
+device memory is timed (64 enlarged 4K images do not belong in pinned host memory); the result then names the bytes of sample
+planes the transform writes per second.
 --dct fast: instead of the above, the K-I1 time of k_idct_ifast (mjh_decode_opts.dct_method 1) next to k_idct's on the same batch of
 workload A, alternating calls under mjh_set_profiling(1); the fast pixels of the first call are compared with djpeg -dct fast.
 --color rgb565: instead of the above, the K-I2 time of k_upcolor_565 (16-bit pixels, ordered dither and plain) next to k_upcolor's
@@ -346,11 +349,11 @@ def main():
             with open(a.out + ".json", "w") as f:
                 json.dump(result, f, indent=1)
         return
-    opts = M.decode_opts(scale=a.scale)
+    opts = M.decode_opts(scale=a.scale, all_scales=True)
     k = M.scale_idct_size(opts.scale_num, opts.scale_denom)
     dj_args = ["-scale", a.scale] if k != 8 else []
     isa = json.load(open(os.path.join(ROOT, "mozjpeg_amd", "kernel_isa.json")))["kernels"]
-    result = {"kernel_sha": {k: isa[k]["sha"] for k in isa if k in ("k_dec_sync", "k_dec_prefix", "k_dec_store", "k_dec_dc", "k_idct", "k_upcolor") or k.startswith("k_idct_scaled")},
+    result = {"kernel_sha": {k: isa[k]["sha"] for k in isa if k in ("k_dec_sync", "k_dec_prefix", "k_dec_store", "k_dec_dc", "k_idct", "k_upcolor") or k.startswith("k_idct_scaled") or k.startswith("k_idct_sized")},
               "scale": a.scale, "idct_size": k, "progressive_sources": a.progressive, "workloads": {}}
     for wl in a.workloads.split(","):
         files = sources(wl, a.progressive)
@@ -359,17 +362,24 @@ def main():
         w, h = info.image_width, info.image_height
         enc = M.Encoder(M.params_from_jpeg(files[0], revert=True, progressive_sources=prog), max_batch=n)
         enc.set_sources(progressive=prog)
-        outs = enc.decode_host(files, opts=opts)
         ow, oh = -(-w * k // 8), -(-h * k // 8)
-        assert outs[0].shape == (oh, ow, 3)
-        with ThreadPoolExecutor(16) as ex:
-            same = list(ex.map(lambda i: bool(np.array_equal(outs[i], DC.djpeg(files[i], dj_args))), range(n)))
-        del outs
+        if k in M.SCALED_IDCT_SIZES:
+            outs = enc.decode_host(files, opts=opts)
+            assert outs[0].shape == (oh, ow, 3)
+            with ThreadPoolExecutor(16) as ex:
+                same = list(ex.map(lambda i: bool(np.array_equal(outs[i], DC.djpeg(files[i], dj_args))), range(n)))
+            del outs
+        else:                                          # one file per call
+            enc.submit_decode(files, opts=opts)
+            out0 = enc.get_pixels(0)
+            assert out0.shape == (oh, ow, 3)
+            same = [bool(np.array_equal(out0, DC.djpeg(files[0], dj_args)))]
+            del out0
         ref_rate, ramdisk = reference_rate(files, dj_args)
         r = {"files": n, "width": w, "height": h, "out_width": ow, "out_height": oh, "source_bytes": sum(len(f) for f in files), "identical_to_reference": all(same),
              "reference_files_per_s": ref_rate, "reference_on_ramdisk": ramdisk, "stats": {k: v for k, v in enc.transcode_stats().items() if k != "ms"}, "paths": {}}
-        host = M.pinned_empty((n, oh, ow, 3))
-        paths = {"device": None, "host": host}
+        host = M.pinned_empty((n, oh, ow, 3)) if k <= 8 else None
+        paths = {"device": None, "host": host} if k <= 8 else {"device": None}
         for name, dst in paths.items():
             timed(enc, files, 0.0, dst, opts)          # warm-up
             r["paths"][name] = {"files_per_s": []}
@@ -400,6 +410,8 @@ def main():
             coef_bytes, plane_bytes, pix_bytes = n * w * h * 1.5 * 2, n * w * h * 1.5, n * w * h * 3
             r["idct_gbytes_per_s"] = (coef_bytes + plane_bytes) / r["phase_ms"]["idct"] / 1e6
             r["upcolor_gbytes_per_s"] = (plane_bytes + pix_bytes) / r["phase_ms"]["upcolor"] / 1e6
+        if k >= 8:                                     # (4:2:0: every component is at k itself from full size up)
+            r["idct_plane_gbytes_written_per_s"] = n * w * h * 1.5 * (k / 8.0) ** 2 / r["phase_ms"]["idct"] / 1e6
         kd = sum(r["phase_ms"][k] for k in ("sync", "prefix", "store", "dc"))
         r["pixel_kernels_to_huffman_decoder"] = (r["phase_ms"]["idct"] + r["phase_ms"]["upcolor"]) / kd
         enc.close()
