@@ -639,11 +639,32 @@ int mjh_encoder_set_transform(mjh_encoder *e, const mjh_transform *t);
  * mjh_encode_coefficients_host / _device read.  The values are the 16 bits the reference's JCOEF holds; no +-1023 limit is
  * applied (that is the entropy coder's: a file with a larger value decodes here and is refused when it is coded again).  Every
  * other field of the struct is ignored, raw_planes too.  The files accepted are those of mjh_transcode_host.
- * dct_method, bottom_up, raw_planes, no_dither, raw_coefs and all_scales were appended; 0 in all of them is the behaviour of the struct without them.
- * MJH_EINVAL: an unknown colour space, pixel size, offsets or dct_method; a pixel size other than 0 or 2 or an offset with RGB565; a scale_num or scale_denom below 1 (other than 0/0).
+ * crop_x, crop_y, crop_w, crop_h: a region of the image instead of the whole (jpeg_crop_scanline + jpeg_skip_scanlines, djpeg
+ * -crop WxH+X+Y), in pixels of the SCALED output image, one region for all files of the call.  All four 0: the whole image, bit for
+ * bit what the struct without them gives.  crop_w 0 / crop_h 0 beside a nonzero field: to the right / bottom edge.  The region
+ * must lie inside the scaled image, else MJH_EINVAL ("exceeds the scaled image dimensions").  crop_x is moved LEFT to a multiple
+ * of the iMCU column width -- k * max_h_samp_factor, k alone for a one-component file, k the IDCT size of the scale (16 for a
+ * 4:2:0 file at 1/1, 2 at 1/8) -- and the width grows by as much, as jpeg_crop_scanline does (jdapistd.c:237-252): the right
+ * edge stays where it was asked.  mjh_decode_region reports the region that was decoded; mjh_decode_stats, mjh_get_pixels and
+ * mjh_get_pixels_device address THAT image (the aligned width x crop_h), bottom_up flips inside it.  Only the region's blocks are
+ * inverse-transformed and only its pixels are made (K-IR).  The pixels are the reference's for the same calls: rows
+ * are those of its output for the same column crop, with the real image above and below as the context of fancy vertical
+ * upsampling; columns at the LEFT and RIGHT edge of the region may differ from the same columns of a whole decode, because the
+ * fancy h2v1 / h2v2 upsamplers of the reference treat the crop edges as image edges (libjpeg.txt, "jpeg_crop_scanline"); RGB565
+ * dither counts columns from the region's left edge and rows from the image's top, as there.
+ * Restart segments: a sequential Huffman file with restart markers has only the segments decoded that hold MCUs of the block
+ * rows the region reads (mjh_decode_region_stats tells how many).  A segment that is left out is NOT checked: a file damaged
+ * only there decodes clean, where the reference would at most warn.  Files without restart markers, progressive and
+ * arithmetic-coded files are entropy-decoded whole and get the region's pixel stage alone.
+ * A region is MJH_EUNSUPPORTED together with raw_planes or raw_coefs, on a four-component file, on a lossless file (as the
+ * reference: JERR_NOTIMPL), at an IDCT size other than 1, 2, 4 and 8 (the sizes of all_scales), and with a transform set on
+ * the encoder (as every decode call).
+ * dct_method, bottom_up, raw_planes, no_dither, raw_coefs, all_scales and crop_x .. crop_h were appended; 0 in all of them is the behaviour of the struct without them.
+ * MJH_EINVAL: an unknown colour space, pixel size, offsets or dct_method; a pixel size other than 0 or 2 or an offset with RGB565; a scale_num or scale_denom below 1 (other than 0/0);
+ * a region with a negative number or one that exceeds the scaled image dimensions.
  * MJH_EUNSUPPORTED: a lossless transform set on the encoder; without all_scales, a scale that resolves to an IDCT size of 3, 5,
- * 6, 7 or 9 to 16;
- * the float IDCT, cropping and colour quantization have no option here. */
+ * 6, 7 or 9 to 16; the region refusals above;
+ * the float IDCT and colour quantization have no option here. */
 typedef struct {
   int out_color_space;
   int pixel_size;
@@ -656,6 +677,7 @@ typedef struct {
   int no_dither;
   int raw_coefs;
   int all_scales;
+  int crop_x, crop_y, crop_w, crop_h;
 } mjh_decode_opts;
 void mjh_decode_opts_defaults(mjh_decode_opts *o);
 /* Decodes n files (opts == NULL: the defaults).  Queued on the encoder's stream; the bytes need not stay valid after the call.
@@ -705,6 +727,13 @@ int mjh_get_coefs_ms(mjh_encoder *e, float *ms);
  * After a batch of lossless files: pixel_size is in bytes (1, 2, 3, 4, 6 or 8), [0] is the undifferencing, [1] the samples into the
  * pixel layout, and of mjh_transcode_stats' four phases the last (DC sums) is 0.  Any pointer may be NULL. */
 int mjh_decode_stats(mjh_encoder *e, int *width, int *height, int *pixel_size, float ms[2]);
+/* The region of the (scaled) image the last decoded batch holds: x as it was aligned, y as asked, w the width grown by what x
+ * moved, h as asked -- w x h is what mjh_decode_stats reports.  A call without a region: 0, 0 and the whole size.  Any pointer
+ * may be NULL. */
+int mjh_decode_region(mjh_encoder *e, int *x, int *y, int *w, int *h);
+/* Restart segments (a scan without restart markers is one) of the last decoded batch's files, and how many of them were
+ * entropy-decoded: fewer only for a region call on sequential Huffman files with restart markers.  Any pointer may be NULL. */
+int mjh_decode_region_stats(mjh_encoder *e, long long *segments_decoded, long long *segments);
 
 /* The sequential Huffman coder writes a scan without restart intervals in one walk over its blocks (MJH_ENC_ONEPASS=0 in
  * the environment of mjh_encoder_create: the length pass and the second walk of the restart path for every scan).  enabled:

@@ -122,7 +122,8 @@ class DecodeOpts(C.Structure):
     bottom-up rows, and the raw sample planes or the DCT coefficients instead of pixels"""
     _fields_ = [("out_color_space", C.c_int), ("pixel_size", C.c_int), ("rgb_offset", C.c_int * 3), ("fancy_upsampling", C.c_int),
                 ("scale_num", C.c_int), ("scale_denom", C.c_int), ("dct_method", C.c_int), ("bottom_up", C.c_int), ("raw_planes", C.c_int),
-                ("no_dither", C.c_int), ("raw_coefs", C.c_int), ("all_scales", C.c_int)]
+                ("no_dither", C.c_int), ("raw_coefs", C.c_int), ("all_scales", C.c_int),
+                ("crop_x", C.c_int), ("crop_y", C.c_int), ("crop_w", C.c_int), ("crop_h", C.c_int)]
 
 
 class Result(C.Structure):
@@ -222,6 +223,8 @@ def lib():
             L.mjh_get_pixels_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
             L.mjh_decode_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float)]
             L.mjh_decode_wait.argtypes = [C.c_void_p]
+            L.mjh_decode_region.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 4
+            L.mjh_decode_region_stats.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
             L.mjh_get_plane.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int]
             L.mjh_get_planes_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                                 C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -640,8 +643,24 @@ def _parse_scale(scale, all_scales=False):
 DCT_METHODS = {None: 0, "int": 0, "islow": 0, "fast": 1, "ifast": 1}     # djpeg -dct int / fast -> mjh_decode_opts.dct_method
 
 
+def _parse_region(crop):
+    """(x, y, w, h) of a tuple (x, y, w, h) or of djpeg's -crop string "WxH+X+Y"; w or h 0: to the right / bottom edge"""
+    try:
+        if isinstance(crop, str):
+            size, x, y = crop.split("+")
+            w, h = size.lower().split("x")
+        else:
+            x, y, w, h = crop
+        x, y, w, h = int(x), int(y), int(w), int(h)
+    except (TypeError, ValueError):
+        raise MjhError(EINVAL, "crop %r (a tuple (x, y, w, h) or a string 'WxH+X+Y')" % (crop,))
+    if min(x, y, w, h) < 0 or max(x, y, w, h) >= 2 ** 31:
+        raise MjhError(EINVAL, "crop %r (no number may be negative or beyond an int)" % (crop,))
+    return x, y, w, h
+
+
 def decode_opts(color=None, layout=None, pixel_size=0, rgb_offset=None, fancy_upsampling=True, scale=None, dct=None, bottom_up=False,
-                raw_planes=False, dither=True, raw_coefs=False, all_scales=False):
+                raw_planes=False, dither=True, raw_coefs=False, all_scales=False, crop=None):
     """DecodeOpts from djpeg's vocabulary.  color: None (the file's default: gray stays gray, a CMYK or YCCK file gives CMYK,
     everything else RGB), "gray" / "grayscale" (-grayscale), "rgb" (-rgb), "rgb565" (-rgb565: 16-bit pixels, with dither=False
     -dither none), "cmyk" (the one output of four-component files: [H, W, 4], C, M, Y, K; pixel_size 0 or 4, rgb_offset is
@@ -650,9 +669,20 @@ def decode_opts(color=None, layout=None, pixel_size=0, rgb_offset=None, fancy_up
     8/8 as djpeg resolves it (scale_idct_size) -- with all_scales=True to any k / 8, k in 1..16 (the other sizes of jidctint.c;
     an opt-in because the refusal of those sizes is part of the tested contract); dct: "int" (the default) or "fast" (-dct fast, TurboJPEG's FASTDCT);
     bottom_up=True: the rows last to first (TurboJPEG's BOTTOMUP); raw_planes=True: no pixels, the sample planes (decode_planes);
-    raw_coefs=True: nothing of the above, the quantized DCT coefficients (decode_coefficients)."""
+    raw_coefs=True: nothing of the above, the quantized DCT coefficients (decode_coefficients);
+    crop: a region (x, y, w, h), or djpeg's -crop string "WxH+X+Y", in pixels of the scaled image (mjh_decode_opts.crop_*): x moves
+    left to a multiple of the iMCU column width as jpeg_crop_scanline moves it and the width grows by as much, so the arrays
+    are [h, w_eff, C] (Encoder.decode_region() tells); w or h 0: to the right / bottom edge; None or four zeros: the whole image."""
     o = DecodeOpts()
     lib().mjh_decode_opts_defaults(C.byref(o))
+    if crop is not None:
+        o.crop_x, o.crop_y, o.crop_w, o.crop_h = _parse_region(crop)
+        if (o.crop_x, o.crop_y, o.crop_w, o.crop_h) != (0, 0, 0, 0):
+            if raw_planes or raw_coefs:
+                raise MjhError(EUNSUPPORTED, "a region (crop) together with %s: they come for the whole image" % ("raw_planes" if raw_planes else "raw_coefs"))
+            if scale is not None and scale_idct_size(*_parse_scale(scale, True)) not in SCALED_IDCT_SIZES:
+                _parse_scale(scale, all_scales)         # (without all_scales: the refusal of the scale itself comes first)
+                raise MjhError(EUNSUPPORTED, "a region (crop) at a size of all_scales: regions are built for the sizes 1x1, 2x2, 4x4 and 8x8")
     if isinstance(color, str):
         names = {"gray": CS_GRAYSCALE, "grayscale": CS_GRAYSCALE, "rgb": CS_RGB, "rgb565": CS_RGB565, "cmyk": CS_CMYK}
         if color not in names:
@@ -802,7 +832,11 @@ def _decode_grouped(files, max_batch, device, o, progressive_sources=False, loss
                 pixels = not (o.raw_planes or o.raw_coefs)
                 four = info.num_components == 4
                 no_conversion = pixels and (o.out_color_space not in (0, CS_CMYK) if four else o.out_color_space == CS_CMYK)
-                if exc.code != EUNSUPPORTED or not (info.sof_type == 3 or no_conversion):
+                # ... and a region this group's files have none of: a four-component or lossless file, an image it does not fit
+                region = (o.crop_x, o.crop_y, o.crop_w, o.crop_h) != (0, 0, 0, 0)
+                no_region = region and (exc.code == EUNSUPPORTED and (four or info.sof_type == 3) or
+                                        exc.code == EINVAL and "exceeds the scaled image dimensions" in str(exc))
+                if not no_region and (exc.code != EUNSUPPORTED or not (info.sof_type == 3 or no_conversion)):
                     raise
                 res = [exc] * len(part)
             bad = [k for k, r in enumerate(res) if isinstance(r, MjhError)]
@@ -1156,6 +1190,20 @@ class Encoder:
         w, h, px, ms = C.c_int(), C.c_int(), C.c_int(), (C.c_float * 2)()
         _chk(lib().mjh_decode_stats(self._h, C.byref(w), C.byref(h), C.byref(px), ms))
         return dict(width=w.value, height=h.value, pixel_size=px.value, ms=dict(idct=float(ms[0]), upcolor=float(ms[1])))
+
+    def decode_region(self):
+        """(x, y, w, h) of the last decoded batch inside the scaled image (mjh_decode_region): x as jpeg_crop_scanline aligns it, w
+        grown by what x moved; without crop=, (0, 0, width, height)"""
+        v = [C.c_int() for _ in range(4)]
+        _chk(lib().mjh_decode_region(self._h, *[C.byref(a) for a in v]))
+        return tuple(a.value for a in v)
+
+    def decode_segments(self):
+        """(decoded, total) restart segments of the last decoded batch's files (mjh_decode_region_stats): decoded < total when a
+        region left segments of sequential Huffman files with restart markers out"""
+        a, b = C.c_longlong(), C.c_longlong()
+        _chk(lib().mjh_decode_region_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def get_pixels(self, i, out=None):
         """image i of the last decoded batch: uint8 [H, W, C], [H, W] for gray, uint16 [H, W] for RGB565, and for a lossless file its

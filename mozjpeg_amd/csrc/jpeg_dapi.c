@@ -104,6 +104,11 @@ typedef struct {
   mjh_encoder *enc;            /* leased only inside jpeg_start_decompress / jpeg_read_coefficients */
   jvirt_barray_ptr *coef_arrays;   /* jpeg_read_coefficients: one array per component (JPOOL_IMAGE: gone with jpeg_abort) */
   int latching;                /* jpeg_read_coefficients: every scan's components get their quant_table as the scan starts */
+  /* MOZJPEG_HIP_REGIONS=1: jpeg_start_decompress prepares the call and leaves it to the first jpeg_read_scanlines /
+   * jpeg_finish_decompress (decode_pending), so that a jpeg_crop_scanline in between can narrow its columns */
+  int pending, px;
+  mjh_decode_opts opts;
+  unsigned crop_x, crop_w;     /* jpeg_crop_scanline: the aligned columns (crop_w 0: none) */
 } d_master;
 
 #define DM(cinfo) ((d_master *)(cinfo)->master)
@@ -127,6 +132,7 @@ void mjh_dapi_drop(void *obj)
   for (ci = 0; ci < MAX_COMPONENTS; ci++) { free(m->planes[ci]); m->planes[ci] = NULL; }
   if (m->enc) { mjh_shim_cache_release(m->enc); m->enc = NULL; }
   m->coef_arrays = NULL; m->latching = 0;
+  m->pending = 0; m->crop_x = m->crop_w = 0;
 }
 
 /* =====================================================================================================================
@@ -1116,6 +1122,34 @@ static void decode_file(j_decompress_ptr cinfo, const mjh_decode_opts *opts)
   if (d_timing) { t1 = d_now(); d_acc(2, t1 - t0, 0); t0 = t1; }
 }
 
+static int regions_enabled(void)
+{
+  const char *v = getenv("MOZJPEG_HIP_REGIONS");
+  return v && v[0] == '1' && v[1] == 0;
+}
+
+/* The GPU call jpeg_start_decompress left open (MOZJPEG_HIP_REGIONS=1): the columns jpeg_crop_scanline named, at full height --
+ * jpeg_skip_scanlines only moves over rows of the image this makes. */
+static void decode_pending(j_decompress_ptr cinfo)
+{
+  d_master *m = DM(cinfo);
+  mjh_decode_opts o;
+  int rc;
+  if (!m->pending) return;
+  m->pending = 0;
+  o = m->opts;
+  if (m->crop_w) { o.crop_x = (int)m->crop_x; o.crop_w = (int)m->crop_w; }
+  decode_file(cinfo, &o);
+  m->row_bytes = (size_t)cinfo->output_width * (size_t)m->px;
+  m->pixels = (unsigned char *)malloc(m->row_bytes * cinfo->output_height);
+  if (m->pixels == NULL) { mjh_dapi_drop(cinfo); ERREXIT1(cinfo, JERR_OUT_OF_MEMORY, 10); }
+  rc = mjh_get_pixels(m->enc, 0, m->pixels, m->row_bytes);
+  if (rc != MJH_OK) decoder_failed(cinfo, rc, 0);
+  mjh_shim_cache_release(m->enc);
+  m->enc = NULL;
+  free(m->file); m->file = NULL; m->file_len = m->file_cap = 0;
+}
+
 boolean jpeg_start_decompress(j_decompress_ptr cinfo)
 {
   d_master *m = DM(cinfo);
@@ -1165,6 +1199,16 @@ boolean jpeg_start_decompress(j_decompress_ptr cinfo)
     o.rgb_offset[0] = off[0]; o.rgb_offset[1] = off[1]; o.rgb_offset[2] = off[2];
   } else
     ERREXIT(cinfo, JERR_CONVERSION_NOTIMPL);              /* JCS_YCbCr, JCS_YCCK */
+  /* MOZJPEG_HIP_REGIONS=1 (read here, per file): pixels of a one- or three-component file wait for the first row to be asked
+   * for; without the variable nothing moves and the decode stays inside this call */
+  if (regions_enabled() && !cinfo->raw_data_out && cinfo->num_components != 4) {
+    m->pending = 1; m->px = px; m->opts = o; m->crop_x = m->crop_w = 0;
+    (*cinfo->mem->realize_virt_arrays) ((j_common_ptr)cinfo);
+    cinfo->output_scanline = 0;
+    cinfo->output_scan_number = cinfo->input_scan_number;
+    cinfo->global_state = DSTATE_SCANNING;
+    return TRUE;
+  }
   decode_file(cinfo, &o);
   if (d_timing) t0 = d_now();
   if (cinfo->raw_data_out) {
@@ -1207,6 +1251,7 @@ JDIMENSION jpeg_read_scanlines(j_decompress_ptr cinfo, JSAMPARRAY scanlines, JDI
   }
   left = cinfo->output_height - cinfo->output_scanline;
   if (max_lines > left) max_lines = left;
+  decode_pending(cinfo);
   if (d_timing) {
     const double t0 = d_now();
     for (n = 0; n < max_lines; n++) memcpy(scanlines[n], m->pixels + (size_t)(cinfo->output_scanline + n) * m->row_bytes, m->row_bytes);
@@ -1308,6 +1353,7 @@ boolean jpeg_finish_decompress(j_decompress_ptr cinfo)
 { /* jdapimin.c:394-425: the datastream was read up to EOI by jpeg_start_decompress, so the source stands just behind it */
   if (cinfo->global_state == DSTATE_SCANNING || cinfo->global_state == DSTATE_RAW_OK) {
     if (cinfo->output_scanline < cinfo->output_height) ERREXIT(cinfo, JERR_TOO_LITTLE_DATA);
+    decode_pending(cinfo);                      /* (a client that skipped every row: the datastream is still read and decoded) */
     cinfo->global_state = DSTATE_STOPPING;
   } else if (cinfo->global_state != DSTATE_STOPPING)
     ERREXIT1(cinfo, JERR_BAD_STATE, cinfo->global_state);
@@ -1320,8 +1366,49 @@ boolean jpeg_finish_decompress(j_decompress_ptr cinfo)
  * entry points that exist because clients name them (djpeg is linked with immediate binding) and raise JERR_NOT_COMPILED
  * ===================================================================================================================== */
 #define NOT_BUILT(what) refuse(cinfo, what " is not built on the GPU path (no CPU fallback)")
-void jpeg_crop_scanline(j_decompress_ptr cinfo, JDIMENSION *xoffset, JDIMENSION *width) { (void)xoffset; (void)width; NOT_BUILT("jpeg_crop_scanline (djpeg -crop)"); }
-JDIMENSION jpeg_skip_scanlines(j_decompress_ptr cinfo, JDIMENSION num_lines) { (void)num_lines; NOT_BUILT("jpeg_skip_scanlines (djpeg -skip)"); return 0; }
+/* Partial decompression, with MOZJPEG_HIP_REGIONS=1 in the environment (without it both raise JERR_NOT_COMPILED as they always
+ * did: that refusal is part of the tested contract).
+ * jpeg_crop_scanline, jdapistd.c:185-300: its checks in its order, *xoffset moved left to a multiple of the iMCU column width,
+ * *width grown by as much, output_width set; a second call names new columns of the image (not of the first crop), checked
+ * against the width the first one left, as there. */
+void jpeg_crop_scanline(j_decompress_ptr cinfo, JDIMENSION *xoffset, JDIMENSION *width)
+{
+  d_master *m = DM(cinfo);
+  JDIMENSION input_xoffset;
+  int align;
+  if (!regions_enabled()) NOT_BUILT("jpeg_crop_scanline (djpeg -crop)");
+  if (cinfo->data_precision != 8) ERREXIT1(cinfo, JERR_BAD_PRECISION, cinfo->data_precision);
+  if (cinfo->master->lossless) ERREXIT(cinfo, JERR_NOTIMPL);
+  if ((cinfo->global_state != DSTATE_SCANNING && cinfo->global_state != DSTATE_BUFIMAGE) || cinfo->output_scanline != 0) ERREXIT1(cinfo, JERR_BAD_STATE, cinfo->global_state);
+  if (!xoffset || !width) ERREXIT(cinfo, JERR_BAD_CROP_SPEC);
+  if (*width == 0 || (unsigned long long)(*xoffset) + *width > cinfo->output_width) ERREXIT(cinfo, JERR_WIDTH_OVERFLOW);
+  if (*width == cinfo->output_width) return;
+  if (!m->pending) refuse(cinfo, "jpeg_crop_scanline on an image that was decoded whole (MOZJPEG_HIP_REGIONS was not set at jpeg_start_decompress, or the file has four components)");
+  align = (cinfo->comps_in_scan == 1 && cinfo->num_components == 1) ? cinfo->min_DCT_scaled_size : cinfo->min_DCT_scaled_size * cinfo->max_h_samp_factor;
+  input_xoffset = *xoffset;
+  *xoffset = (input_xoffset / (JDIMENSION)align) * (JDIMENSION)align;
+  *width = *width + input_xoffset - *xoffset;
+  cinfo->output_width = *width;
+  m->crop_x = *xoffset; m->crop_w = *width;
+}
+
+/* jpeg_skip_scanlines, jdapistd.c:470-660: its checks and return values; skipping changes no value, so it only moves over rows
+ * of the image the GPU call makes (the columns at full height) */
+JDIMENSION jpeg_skip_scanlines(j_decompress_ptr cinfo, JDIMENSION num_lines)
+{
+  if (!regions_enabled()) NOT_BUILT("jpeg_skip_scanlines (djpeg -skip)");
+  if (cinfo->data_precision != 8) ERREXIT1(cinfo, JERR_BAD_PRECISION, cinfo->data_precision);
+  if (cinfo->master->lossless) ERREXIT(cinfo, JERR_NOTIMPL);
+  if (cinfo->quantize_colors && cinfo->two_pass_quantize) ERREXIT(cinfo, JERR_NOTIMPL);
+  if (cinfo->global_state != DSTATE_SCANNING) ERREXIT1(cinfo, JERR_BAD_STATE, cinfo->global_state);
+  if ((unsigned long long)cinfo->output_scanline + num_lines >= cinfo->output_height) {
+    num_lines = cinfo->output_height - cinfo->output_scanline;
+    cinfo->output_scanline = cinfo->output_height;
+    return num_lines;
+  }
+  cinfo->output_scanline += num_lines;
+  return num_lines;
+}
 boolean jpeg_start_output(j_decompress_ptr cinfo, int scan_number) { (void)scan_number; NOT_BUILT("jpeg_start_output (buffered-image mode)"); return FALSE; }
 boolean jpeg_finish_output(j_decompress_ptr cinfo) { NOT_BUILT("jpeg_finish_output (buffered-image mode)"); return FALSE; }
 int jpeg_consume_input(j_decompress_ptr cinfo) { NOT_BUILT("jpeg_consume_input"); return 0; }

@@ -264,6 +264,17 @@ struct DecOut {
   int W = 0, H = 0;                       // of the (scaled) image
   int px_size = 0;                        // bytes per pixel
   long long row_pitch = 0, image_stride = 0;
+  // a region call (mjh_decode_opts.crop_*): W x H above is the region image, which lies at (rx, ry) of the scaled image; every
+  // other call: 0, 0.  segs / segs_kept: the restart segments of the call's files and those that were decoded (mjh_decode_region_stats)
+  int rx = 0, ry = 0;
+  long long segs = 0, segs_kept = 0;
+};
+
+// The block rows of every component that a region call reads (by0 .. by1; by1 < by0: the component is not read at all): what
+// decode_front may leave out of a sequential Huffman file with restart markers.  segs / kept: counted by dec_split_segments.
+struct DecKeep {
+  int by0[MJH_MAXC], by1[MJH_MAXC], v[MJH_MAXC];
+  long long segs = 0, kept = 0;
 };
 
 struct mjh_encoder {
@@ -473,6 +484,7 @@ struct mjh_encoder {
   // first such call, grown like d_pixout.  Every other call keeps its samples in d_planes.
   uint8_t *d_planes_big = nullptr; size_t planes_big_cap = 0;
   DecOut dp{};
+  long long dec_segs = 0;                 // the restart segments the last decode_front handed to the device
   unsigned *h_dstat = nullptr;
   hipEvent_t dp_ev[3] = { nullptr, nullptr, nullptr }, dp_done = nullptr; bool dp_timed = false;
   bool dp_waited = false;               // ... and has been waited for (the guard check runs once per batch)
@@ -3001,7 +3013,12 @@ struct DecDescSet {
 // The restart segments of the scan that is about to become D.scans[D.scans.size()]: bytes [a, b) of file d, which lies at file_off
 // in the batch buffer.  RSTn markers are the only 0xFF not followed by 0x00 inside the range (mjh_jpeg_probe counted nrst of them).
 // subs: the segments get subsequences of S bytes, padded to whole workgroups behind the scan's last.  nullptr, or why the file is refused.
-static const char *dec_split_segments(const uint8_t *d, size_t a, size_t b, unsigned nrst, const MjhDecScan &sc, size_t file_off, int S, bool subs, DecDescSet &D)
+// keep: a region call -- a segment whose MCUs all lie in block rows the region's inverse DCT does not read is counted and left
+// out: nothing downstream sees it, its blocks stay the zeros d_q was cleared to, and its bytes are never decoded, so damage
+// inside it goes unnoticed (the markers around it are still checked here).  Every segment stands alone: the DC prediction
+// starts again behind a restart marker, and k_dec_dc sums the (zero) differences of a segment that was left out to zeros.
+static const char *dec_split_segments(const uint8_t *d, size_t a, size_t b, unsigned nrst, const MjhDecScan &sc, size_t file_off, int S, bool subs, DecDescSet &D,
+                                      DecKeep *keep = nullptr)
 {
   const int nseg_expected = (sc.mcus + sc.ri - 1) / sc.ri;
   size_t seg_start = a, q = a;
@@ -3015,6 +3032,19 @@ static const char *dec_split_segments(const uint8_t *d, size_t a, size_t b, unsi
     sg.scan = (int)D.scans.size();
     sg.mcu0 = k_seg * sc.ri;
     sg.nmcu = sc.mcus - sg.mcu0 < sc.ri ? sc.mcus - sg.mcu0 : sc.ri;
+    if (keep) {
+      // MCU rows r0 .. r1 of the scan: block rows r0 v .. r1 v + v - 1 of every component of an interleaved scan, block rows
+      // r0 .. r1 of the one component of any other
+      const int r0 = sg.mcu0 / sc.mcus_per_row, r1 = (sg.mcu0 + sg.nmcu - 1) / sc.mcus_per_row;
+      bool read = false;
+      for (int j = 0; j < sc.ncomp; j++) {
+        const int ci = sc.comp[j], v = sc.ncomp == 1 ? 1 : keep->v[ci];
+        read = read || (r0 * v <= keep->by1[ci] && r1 * v + v - 1 >= keep->by0[ci]);
+      }
+      keep->segs++;
+      if (!read) { k_seg++; return; }
+      keep->kept++;
+    }
     if (subs) {
       sg.sub0 = (int)D.sub_seg.size();
       sg.nsub = S > 0 ? (int)((sg.len + (unsigned)S - 1) / (unsigned)S) : 1;
@@ -3130,7 +3160,8 @@ static int dec_sync_rounds(mjh_encoder *e, hipStream_t s, int max_nsub, Launch l
 // the K-D kernels.  It leaves the batch's coefficient planes in d_q and its per-image status in d_tstat, both queued on e->stream.
 // pixels: the caller is mjh_decode_host (no result arenas are made); *o_jfif_out: where the files' APP0 fields lie in d_tdesc
 // samples: the caller goes on to the inverse DCT (pixels or planes), where the reference would smooth the blocks of some progressive files
-static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t sizes[], int n, bool pixels, size_t *o_jfif_out, bool samples = false)
+// keep: a region call names the block rows it reads; the restart segments of sequential Huffman files outside them are left out (dec_split_segments)
+static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t sizes[], int n, bool pixels, size_t *o_jfif_out, bool samples = false, DecKeep *keep = nullptr)
 {
   if (e) { e->tc_n = 0; e->tc_code.clear(); e->tc_text.clear(); e->tc_queued = false; e->dp_queued = false; }   // a call refused as a whole leaves no per-file status, and none of an earlier batch
   if (!e || !jpegs || !sizes || n < 1 || n > e->max_batch) return fail(MJH_EINVAL, "bad arguments (n=%d, max_batch=%d)", n, e ? e->max_batch : 0);
@@ -3278,6 +3309,7 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
     for (const DecDescSet &t : sets) saved.push_back(std::array<size_t, 4>{ { t.scans.size(), t.segs.size(), t.sub_seg.size(), (size_t)t.max_nsub } });
     for (const DecDescSet &t : asets) saved_a.push_back(std::array<size_t, 4>{ { t.scans.size(), t.segs.size(), t.sub_seg.size(), (size_t)t.max_nsub } });
     const size_t tabs0 = tables.size();
+    const DecKeep keep0 = keep ? *keep : DecKeep();
     const char *why = nullptr;
     long long diff_off = 0;
     int level_of[MJH_MAX_SRC_SCANS];
@@ -3368,7 +3400,7 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
         if (diff_off > G.total_mcu_blocks) { why = "internal: DC difference array too small"; break; }
       }
       if (data_size >= ((size_t)1 << 28)) { why = "a scan of 256 MB or more (bit positions inside a restart segment are 32-bit)"; break; }
-      why = dec_split_segments(d, data_offset, data_offset + data_size, nrst, sc, file_off[(size_t)i], S, !arith && set_idx < 2, D);
+      why = dec_split_segments(d, data_offset, data_offset + data_size, nrst, sc, file_off[(size_t)i], S, !arith && set_idx < 2, D, !arith && !prog && nrst ? keep : nullptr);
       if (why) break;
       D.scans.push_back(sc);
       D.ps.push_back(pp);
@@ -3389,6 +3421,7 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
         asets[t].scans.resize(z[0]); asets[t].ps.resize(z[0]); asets[t].ar.resize(z[0]); asets[t].segs.resize(z[1]);
       }
       tables.resize(tabs0);
+      if (keep) *keep = keep0;
       e->tc_code[(size_t)i] = MJH_EINVAL; e->tc_text[(size_t)i] = why;
     } else if (file_levels > levels) levels = file_levels;
   }
@@ -3435,6 +3468,9 @@ static int decode_front(mjh_encoder *e, const void *const jpegs[], const size_t 
     if (e->tc_code[(size_t)i] != MJH_OK) return fail(e->tc_code[(size_t)i], "file %d: %s", i, e->tc_text[(size_t)i].c_str());
   const bool has_prog = levels > 0;
   e->pg_levels = levels;
+  e->dec_segs = 0;
+  for (const DecDescSet &D : sets) e->dec_segs += (long long)D.segs.size();
+  for (const DecDescSet &D : asets) e->dec_segs += (long long)D.segs.size();
   // ---- 3. staging: the files as they are + one descriptor block, two host->device copies
   int rc = pixels ? MJH_OK : host_buffers(e);
   if (rc) return rc;
@@ -3874,6 +3910,81 @@ static int plan_pixels(const mjh_encoder *e, const mjh_decode_opts *o, int k, De
   return MJH_OK;
 }
 
+static bool region_asked(const mjh_decode_opts &o) { return o.crop_x || o.crop_y || o.crop_w || o.crop_h; }
+
+// A region call (mjh_decode_opts.crop_*): the plan of the whole scaled image that plan_pixels made becomes the plan of the region.
+// Columns as jpeg_crop_scanline has them (jdapistd.c:237-299): the offset moves left to a multiple of the iMCU column width
+// k * max_h (k alone for a one-component file), the width grows by as much, every component keeps its blocks first_MCU_col ..
+// last_MCU_col and gets the cropped row's downsampled_width; the upsamplers stay the ones the uncropped width picked unless a
+// width that was at least 2 falls below 2, which makes the reference pick all of them again.  Rows as jpeg_skip_scanlines leaves
+// them: the values of the whole image, so every component keeps the block rows that hold the sample rows the region's output
+// rows are made of -- with fancy vertical upsampling one more sample row on either side.
+// R[c]: the blocks K-IR1 transforms; *y0: the region's first row; keep: the same block rows for decode_front.
+static int plan_region(const mjh_encoder *e, const mjh_decode_opts *o, int k, DecOut *out, MjhPixOut *P, MjhUpComp up[MJH_MAXC], int ncomp, const int ssize[MJH_MAXC],
+                       MjhRegComp R[MJH_MAXC], DecKeep *keep)
+{
+  const MjhConst &C = e->C;
+  const long long W = out->W, H = out->H;
+  if (o->crop_x < 0 || o->crop_y < 0 || o->crop_w < 0 || o->crop_h < 0)
+    return fail(MJH_EINVAL, "region %dx%d+%d+%d (no number may be negative)", o->crop_w, o->crop_h, o->crop_x, o->crop_y);
+  const long long x = o->crop_x, y = o->crop_y, w = o->crop_w ? o->crop_w : W - x, h = o->crop_h ? o->crop_h : H - y;
+  if (w < 1 || h < 1 || x + w > W || y + h > H)
+    return fail(MJH_EINVAL, "region %dx%d+%d+%d exceeds the scaled image dimensions %lld x %lld (JERR_WIDTH_OVERFLOW)", o->crop_w, o->crop_h, o->crop_x, o->crop_y, W, H);
+  const bool one = C.ncomp == 1;
+  const long long align = one ? k : (long long)k * C.maxh;
+  const long long xe = x / align * align, we = w + x - xe;
+  // downsampled_width of every component of the FILE under the crop, and whether the upsamplers are picked again
+  bool reinit = false;
+  long long dw_new[MJH_MAXC];
+  for (int c = 0; c < C.ncomp; c++) {
+    const MjhComp &cc = C.c[c];
+    const int ss = c < ncomp ? ssize[c] : mjh_scaled_size(k, cc.h, cc.v, C.maxh, C.maxv);
+    const long long dw_old = div_round_up((long)C.W * cc.h * ss, (long)C.maxh * 8);
+    dw_new[c] = div_round_up((long)(we * cc.h * ss), (long)C.maxh * k);
+    if (we != W && dw_new[c] < 2 && dw_old >= 2) reinit = true;
+  }
+  const bool fancy = o->fancy_upsampling != 0 && k > 1;
+  memset(keep, 0, sizeof(*keep));
+  for (int c = 0; c < MJH_MAXC; c++) { keep->by0[c] = 1; keep->by1[c] = 0; keep->v[c] = c < C.ncomp ? C.c[c].v : 1; }
+  for (int c = 0; c < ncomp; c++) {
+    const MjhComp &cc = C.c[c];
+    MjhUpComp &u = up[c];
+    const int ss = ssize[c];
+    const long long hsf = one ? 1 : cc.h;
+    long long first = xe * hsf / align, last = div_round_up((long)((xe + we) * hsf), (long)align) - 1;
+    if (last > cc.wib - 1) last = cc.wib - 1;
+    if (we != W) u.dw = (int)dw_new[c];
+    if (reinit) {
+      u.mode = MJH_UP_REPLICATE;
+      if (u.hexp == 2 && u.vexp == 1) { if (fancy && u.dw > 2) u.mode = MJH_UP_H2V1_FANCY; }
+      else if (u.hexp == 1 && u.vexp == 2) { if (fancy) u.mode = MJH_UP_H1V2_FANCY; }
+      else if (u.hexp == 2 && u.vexp == 2) { if (fancy && u.dw > 2) u.mode = MJH_UP_H2V2_FANCY; }
+    }
+    // the sample rows up_sample reads for output rows y .. y + h - 1
+    long long rs0, rs1;
+    if (u.mode == MJH_UP_H1V2_FANCY || u.mode == MJH_UP_H2V2_FANCY) { rs0 = (y >> 1) - 1; rs1 = ((y + h - 1) >> 1) + 1; }
+    else { rs0 = y / u.vexp; rs1 = (y + h - 1) / u.vexp; }
+    if (rs0 < 0) rs0 = 0;
+    if (rs1 > u.dh - 1) rs1 = u.dh - 1;
+    if (rs0 > rs1) rs0 = rs1;
+    long long by0 = rs0 / ss, by1 = rs1 / ss;
+    if (by1 > cc.hib - 1) by1 = cc.hib - 1;
+    if (by0 > by1) by0 = by1;
+    MjhRegComp &r = R[c];
+    r.bx0 = (int)first; r.nbx = (int)(last - first + 1); r.by0 = (int)by0; r.nby = (int)(by1 - by0 + 1);
+    r.pitch = ss == 8 ? r.nbx * 8 : (r.nbx * ss + 3) & ~3;
+    u.pw = r.pitch;
+    u.plane_off = cc.plane_off - (long long)r.by0 * ss * r.pitch;      // (row r of the image is row r - by0 * ss of the region plane)
+    keep->by0[c] = r.by0; keep->by1[c] = (int)by1;
+  }
+  out->W = (int)we; out->H = (int)h; out->rx = (int)xe; out->ry = (int)y;
+  out->row_pitch = (long long)up16((size_t)out->px_size * (((size_t)out->W + 3) & ~(size_t)3));
+  out->image_stride = out->row_pitch * out->H;
+  P->W = out->W; P->H = out->H; P->row_pitch = out->row_pitch; P->image_stride = out->image_stride;
+  for (int c = 0; c < ncomp; c++) P->c[c] = up[c];
+  return MJH_OK;
+}
+
 // the host-side pieces every mjh_decode_host batch needs: its status words and the events behind it (made by the first call)
 static int decode_host_state(mjh_encoder *e)
 {
@@ -4158,6 +4269,11 @@ extern "C" int mjh_decode_host(mjh_encoder *e, const void *const jpegs[], const 
   if (e->xf_on) return fail(MJH_EUNSUPPORTED, "a lossless transform (mjh_encoder_set_transform) together with decoding to pixels");
   mjh_decode_opts o;
   if (opts) o = *opts; else mjh_decode_opts_defaults(&o);
+  const bool region = region_asked(o);
+  if (region && e->lossless) return fail(MJH_EUNSUPPORTED, "a region (crop_x, crop_y, crop_w, crop_h) of a lossless file: the reference has none either (jpeg_crop_scanline, jpeg_skip_scanlines: JERR_NOTIMPL)");
+  if (region && o.raw_coefs) return fail(MJH_EUNSUPPORTED, "a region (crop_x, crop_y, crop_w, crop_h) together with raw_coefs: coefficients come for the whole image");
+  if (region && o.raw_planes) return fail(MJH_EUNSUPPORTED, "a region (crop_x, crop_y, crop_w, crop_h) together with raw_planes: sample planes come for the whole image");
+  if (region && e->four) return fail(MJH_EUNSUPPORTED, "a region (crop_x, crop_y, crop_w, crop_h) of a four-component file (CMYK, YCCK): regions are built for files of one and three components");
   if (e->lossless) return decode_lossless(e, jpegs, sizes, n, o);
   if (o.raw_coefs) return decode_coefs(e, jpegs, sizes, n);
   if (o.dct_method != 0 && o.dct_method != 1) return fail(MJH_EINVAL, "dct_method %d of a decode call (0 = JDCT_ISLOW, 1 = JDCT_IFAST)", o.dct_method);
@@ -4165,6 +4281,8 @@ extern "C" int mjh_decode_host(mjh_encoder *e, const void *const jpegs[], const 
   int k = 8, ssize[MJH_MAXC] = { 8, 8, 8, 8 }, ncomp = 0;
   int rc = resolve_scale(&o, &k);
   if (rc) return rc;
+  if (region && !mjh_scale_size_is_classic(k))
+    return fail(MJH_EUNSUPPORTED, "a region (crop_x, crop_y, crop_w, crop_h) at the %dx%d inverse DCT, a size of all_scales: regions are built for the sizes 1x1, 2x2, 4x4 and 8x8", k, k);
   DecOut out;
   MjhPixOut P;
   MjhPixOut4 P4;
@@ -4189,9 +4307,18 @@ extern "C" int mjh_decode_host(mjh_encoder *e, const void *const jpegs[], const 
     if (rc) return rc;
     P.bottom_up = P4.bottom_up = o.bottom_up != 0;
   }
+  MjhRegComp RC[MJH_MAXC];
+  DecKeep keep;
+  memset(RC, 0, sizeof(RC));
+  if (region) {
+    rc = plan_region(e, &o, k, &out, &P, up, ncomp, ssize, RC, &keep);
+    if (rc) return rc;
+  }
   size_t o_jfif = 0;
-  rc = decode_front(e, jpegs, sizes, n, true, &o_jfif, true);
+  rc = decode_front(e, jpegs, sizes, n, true, &o_jfif, true, region ? &keep : nullptr);
   if (rc) return rc;
+  out.segs_kept = e->dec_segs;
+  out.segs = e->dec_segs + (region ? keep.segs - keep.kept : 0);
   const MjhConst &C = e->C;
   const size_t need = raw ? 0 : (size_t)e->max_batch * (size_t)out.image_stride;
   if (need > e->pixout_cap) {
@@ -4237,6 +4364,23 @@ extern "C" int mjh_decode_host(mjh_encoder *e, const void *const jpegs[], const 
   e->dp = out; e->dp_n = n; e->dp_raw = raw; e->dp_coefs = false;
   e->last_n = n; e->compact_last = false; e->last = nullptr;      // (mjh_read_tap: d_q holds this batch's plain planes, d_planes its samples)
   if (timed) HIPCHK(hipEventRecord(e->dp_ev[0], s));
+  if (region) {
+    // K-IR1: the components at size 8 in one launch (they alone have a method to choose), the reduced ones one by one
+    MjhConst C8 = C;
+    MjhIdctQ Q8;
+    MjhIdctRegion R8;
+    memset(&Q8, 0, sizeof(Q8));
+    memset(&R8, 0, sizeof(R8));
+    int n8 = 0;
+    for (int c = 0; c < ncomp; c++) {
+      if (ssize[c] != 8) { mjh_launch_idct_region_scaled(C, Q, c, ssize[c], RC[c], e->d_q, e->d_planes, e->d_tstat, n, s); continue; }
+      C8.c[n8] = C.c[c];
+      R8.c[n8] = RC[c];
+      memcpy(Q8.q[n8], (ifast ? QF : Q).q[c], sizeof(Q8.q[n8]));
+      n8++;
+    }
+    if (n8) mjh_launch_idct_region(C8, Q8, R8, n8, ifast, e->d_q, e->d_planes, e->d_tstat, n, s);
+  } else
   if (k == 8) (ifast ? mjh_launch_idct_ifast : mjh_launch_idct)(C, ifast ? QF : Q, ncomp, e->d_q, e->d_planes, e->d_tstat, n, s);
   else {
     // a scaled call: the reduced transforms component by component; the components the ratios leave at size 8 (chroma of a
@@ -4275,6 +4419,8 @@ extern "C" int mjh_decode_host(mjh_encoder *e, const void *const jpegs[], const 
     for (int c = 0; c < ncomp; c++) { e->rp_w[c] = C.c[c].wib * k; e->rp_h[c] = C.c[c].hib * k; e->rp_pitch[c] = up[c].pw; e->rp_off[c] = plane_at[c]; }
     e->rp_base = planes; e->rp_stride = plane_stride;
   } else if (e->four) mjh_launch_upcolor4(P4, planes, e->d_pixout, e->d_tstat, n, s);
+  else if (region && out.px_size == 2) mjh_launch_upcolor_565_region(P, out.ry, o.no_dither == 0, planes, e->d_pixout, e->d_tstat, n, s);
+  else if (region) mjh_launch_upcolor_region(P, out.ry, planes, e->d_pixout, e->d_tstat, n, s);
   else if (out.px_size == 2) mjh_launch_upcolor_565(P, o.no_dither == 0, planes, e->d_pixout, e->d_tstat, n, s);
   else mjh_launch_upcolor(P, planes, e->d_pixout, e->d_tstat, n, s);
   if (timed) HIPCHK(hipEventRecord(e->dp_ev[2], s));
@@ -4424,6 +4570,26 @@ extern "C" int mjh_decode_stats(mjh_encoder *e, int *width, int *height, int *pi
       for (int k = 0; k < 2; k++) HIPCHK(hipEventElapsedTime(&ms[k], e->dp_ev[k], e->dp_ev[k + 1]));
     }
   }
+  return MJH_OK;
+}
+
+extern "C" int mjh_decode_region(mjh_encoder *e, int *x, int *y, int *w, int *h)
+{
+  if (!e) return fail(MJH_EINVAL, "null encoder");
+  if (!e->dp_queued) return fail(MJH_EINVAL, "the last batch was not decoded through mjh_decode_host");
+  if (x) *x = e->dp.rx;
+  if (y) *y = e->dp.ry;
+  if (w) *w = e->dp.W;
+  if (h) *h = e->dp.H;
+  return MJH_OK;
+}
+
+extern "C" int mjh_decode_region_stats(mjh_encoder *e, long long *segments_decoded, long long *segments)
+{
+  if (!e) return fail(MJH_EINVAL, "null encoder");
+  if (!e->dp_queued) return fail(MJH_EINVAL, "the last batch was not decoded through mjh_decode_host");
+  if (segments_decoded) *segments_decoded = e->dp.segs_kept;
+  if (segments) *segments = e->dp.segs;
   return MJH_OK;
 }
 

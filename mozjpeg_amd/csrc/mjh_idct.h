@@ -53,6 +53,12 @@ struct MjhPixOut4 {
   MjhUpComp c[4];
 };
 
+// the blocks of one component a region call (mjh_decode_opts.crop_*) transforms, and the compact plane they go to: nbx x nby
+// blocks from block (bx0, by0) of the component on; rows of the plane are `pitch` samples apart (a multiple of 4, at least
+// nbx * DCT_scaled_size), its row 0 is sample row by0 * DCT_scaled_size of the image, its column 0 sample bx0 * DCT_scaled_size
+struct MjhRegComp { int bx0, nbx, by0, nby, pitch; };
+struct MjhIdctRegion { MjhRegComp c[3]; };
+
 // K-I1: coefficient planes (what k_dec_store / k_dec_dc leave) -> 8-bit sample planes, real blocks only; comps: the first
 // `comps` components.  status != 0: that image is skipped.
 void mjh_launch_idct(const MjhConst &C, const MjhIdctQ &Q, int comps, const int16_t *coef_q, uint8_t *planes, const unsigned *status, int n, hipStream_t s);
@@ -76,4 +82,16 @@ void mjh_launch_upcolor(const MjhPixOut &P, const uint8_t *planes, uint8_t *pixe
 void mjh_launch_upcolor_565(const MjhPixOut &P, int dither, const uint8_t *planes, uint8_t *pixels, const unsigned *status, int n, hipStream_t s);
 // K-I2 for four components: the grid of mjh_launch_upcolor, 4 pixels = 16 bytes = one store per lane
 void mjh_launch_upcolor4(const MjhPixOut4 &P, const uint8_t *planes, uint8_t *pixels, const unsigned *status, int n, hipStream_t s);
+// K-IR1: the inverse DCT of a region.  The first `comps` components of C, all at DCT_scaled_size 8, each over the blocks R.c[]
+// names, into compact planes at the components' plane_off (a region plane is never larger than the full-size one it replaces);
+// ifast: the method, as mjh_launch_idct / mjh_launch_idct_ifast (Q: the multipliers of that method).
+void mjh_launch_idct_region(const MjhConst &C, const MjhIdctQ &Q, const MjhIdctRegion &R, int comps, bool ifast, const int16_t *coef_q, uint8_t *planes, const unsigned *status, int n, hipStream_t s);
+// ... component ci alone at DCT_scaled_size N of 1, 2 or 4 over the blocks rc names (rc.pitch: a multiple of 4 that holds
+// nbx * N samples rounded up to whole words)
+void mjh_launch_idct_region_scaled(const MjhConst &C, const MjhIdctQ &Q, int ci, int N, const MjhRegComp &rc, const int16_t *coef_q, uint8_t *planes, const unsigned *status, int n, hipStream_t s);
+// K-IR2: region planes -> the region's pixels.  P.W x P.H: the region image; P.c[].dw, pw: the region plane's; P.c[].dh: the
+// WHOLE image's; P.c[].plane_off: the plane's offset minus (its first sample row * pw), so that rows are addressed by their
+// number in the whole image; y0: the region's first row in the (scaled) image.
+void mjh_launch_upcolor_region(const MjhPixOut &P, int y0, const uint8_t *planes, uint8_t *pixels, const unsigned *status, int n, hipStream_t s);
+void mjh_launch_upcolor_565_region(const MjhPixOut &P, int y0, int dither, const uint8_t *planes, uint8_t *pixels, const unsigned *status, int n, hipStream_t s);
 #endif

@@ -31,6 +31,10 @@
 // K-I2' k_upcolor_565: the same lanes for JCS_RGB565 (djpeg -rgb565): 4 packed 16-bit pixels, one 8-byte store, with or without
 //   the reference's ordered dither; see the kernel.
 // K-I2'' k_upcolor4: the same lanes for the four-component files (CMYK, YCCK): 4 pixels of C, M, Y, K, one 16-byte store; see the kernel.
+// K-IR k_idct_region, k_idct_region_scaled<N>, k_upcolor_region, k_upcolor_565_region: the same for a region of the image
+//   (mjh_decode_opts.crop_*: jpeg_crop_scanline + jpeg_skip_scanlines): only the region's blocks are transformed, into compact
+//   planes, and only its pixels are made.  The bodies of K-I1, K-I1f, K-I2 and K-I2' are shared as text (mjh_idct8_body.inc,
+//   mjh_idct8_ifast_body.inc, mjh_upcolor_body.inc, mjh_upcolor565_body.inc); see the kernels.
 #include <hip/hip_runtime.h>
 #include "mjh_device.h"
 #include "mjh_idct.h"
@@ -92,36 +96,7 @@ k_idct(MjhConst C, MjhIdctQ Q, const int16_t *__restrict__ coef_q, uint8_t *__re
   if (status[img] != 0u) return;
   const int16_t *in = coef_q + (size_t)img * C.coefs_per_image + cc.coef_off + b;
   const int *q = Q.q[ci];
-  int ws[64];
-  // pass 1: columns, results scaled up by 2^PASS1_BITS (2)
-#pragma unroll
-  for (int c = 0; c < 8; c++) {
-    int x[8];
-#pragma unroll
-    for (int r = 0; r < 8; r++) x[r] = (int)in[(size_t)kZigOfNat[r * 8 + c] * cc.kstride] * q[r * 8 + c];
-    long long o[8];
-    idct8(x, o);
-#pragma unroll
-    for (int r = 0; r < 8; r++) ws[r * 8 + c] = (int)((o[r] + 1024) >> 11);
-  }
-  // pass 2: rows; descale by 2^(CONST_BITS + PASS1_BITS + 3), then the range limit with the sample's centre added
-  const int by = b / cc.wib, bx = b - by * cc.wib;
-  uint8_t *out = planes + (size_t)img * C.planes_per_image + cc.plane_off + (size_t)(by * 8) * cc.pw + (size_t)bx * 8;
-#pragma unroll
-  for (int r = 0; r < 8; r++) {
-    int x[8];
-#pragma unroll
-    for (int c = 0; c < 8; c++) x[c] = ws[r * 8 + c];
-    long long o[8];
-    idct8(x, o);
-    unsigned s[8];
-#pragma unroll
-    for (int c = 0; c < 8; c++) s[c] = idct_range_limit((int)((o[c] + (1 << 17)) >> 18));
-    uint2 v;
-    v.x = s[0] | (s[1] << 8) | (s[2] << 16) | (s[3] << 24);
-    v.y = s[4] | (s[5] << 8) | (s[6] << 16) | (s[7] << 24);
-    *reinterpret_cast<uint2 *>(out + (size_t)r * cc.pw) = v;
-  }
+#include "mjh_idct8_body.inc"
 }
 
 // ---- K-I1 with the fast integer method (djpeg -dct fast, JDCT_IFAST): jpeg_idct_ifast jidctfst.c:170-368 --------------------------
@@ -166,34 +141,7 @@ k_idct_ifast(MjhConst C, MjhIdctQ Q, const int16_t *__restrict__ coef_q, uint8_t
   if (status[img] != 0u) return;
   const int16_t *in = coef_q + (size_t)img * C.coefs_per_image + cc.coef_off + b;
   const int *q = Q.q[ci];
-  unsigned ws[64];
-  // pass 1: columns; the multipliers carry the 2^PASS1_BITS the workspace is scaled up by
-#pragma unroll
-  for (int c = 0; c < 8; c++) {
-    unsigned x[8], o[8];
-#pragma unroll
-    for (int r = 0; r < 8; r++) x[r] = (unsigned)(int)in[(size_t)kZigOfNat[r * 8 + c] * cc.kstride] * (unsigned)q[r * 8 + c];
-    idct8_ifast(x, o);
-#pragma unroll
-    for (int r = 0; r < 8; r++) ws[r * 8 + c] = o[r];
-  }
-  // pass 2: rows; a plain shift by PASS1_BITS + 3, then the range limit with the sample's centre added
-  const int by = b / cc.wib, bx = b - by * cc.wib;
-  uint8_t *out = planes + (size_t)img * C.planes_per_image + cc.plane_off + (size_t)(by * 8) * cc.pw + (size_t)bx * 8;
-#pragma unroll
-  for (int r = 0; r < 8; r++) {
-    unsigned x[8], o[8];
-#pragma unroll
-    for (int c = 0; c < 8; c++) x[c] = ws[r * 8 + c];
-    idct8_ifast(x, o);
-    unsigned s[8];
-#pragma unroll
-    for (int c = 0; c < 8; c++) s[c] = idct_range_limit((int)o[c] >> 5);
-    uint2 v;
-    v.x = s[0] | (s[1] << 8) | (s[2] << 16) | (s[3] << 24);
-    v.y = s[4] | (s[5] << 8) | (s[6] << 16) | (s[7] << 24);
-    *reinterpret_cast<uint2 *>(out + (size_t)r * cc.pw) = v;
-  }
+#include "mjh_idct8_ifast_body.inc"
 }
 
 // ---- K-I1 at a reduced size (djpeg -scale): the transforms of jidctred.c ------------------------------------------------------
@@ -289,6 +237,66 @@ k_idct_scaled(MjhConst C, MjhIdctQ Q, int ci, int pitch, const int16_t *__restri
   uint8_t *out = planes + (size_t)img * C.planes_per_image + cc.plane_off + (size_t)(by * N) * pitch + (size_t)gx * 4;
 #pragma unroll
   for (int r = 0; r < N; r++) *reinterpret_cast<unsigned *>(out + (size_t)r * pitch) = w[r];
+}
+
+// ---- K-IR1: the inverse DCT of a region (mjh_decode_opts.crop_*: jpeg_crop_scanline + jpeg_skip_scanlines) ----------------------
+// Only the blocks the region's pixels are made of are dequantized and transformed: of component ci the nbx x nby blocks from
+// (bx0, by0) on (MjhRegComp: MCU columns first_MCU_col .. last_MCU_col of jdapistd.c:288-292, and the block rows that hold the
+// region's sample rows and the one context row fancy vertical upsampling reads on either side).  They go to a compact plane at
+// the component's plane_off whose row 0 is sample row by0 * N of the image and whose column 0 is sample bx0 * N: what the
+// reference's coefficient controller leaves in its output buffer under a crop (output_col counts from first_MCU_col).
+// One lane per block, region block t = by * nbx + bx: the lanes of a wave hold horizontally adjacent blocks of the REGION, so a
+// store instruction writes runs of min(64, nbx) * 8 contiguous bytes -- one 512-byte run for a region 64 blocks wide or more,
+// 64 / nbx shorter runs one block row apart for a narrow one -- and plane k of coef_q is read in runs of the same blocks.
+// The bodies are k_idct's and k_idct_ifast's, given a component descriptor whose wib / pw are the region plane's.
+template <bool FAST>
+__global__ void __launch_bounds__(256)
+k_idct_region(MjhConst C, MjhIdctQ Q, MjhIdctRegion R, const int16_t *__restrict__ coef_q, uint8_t *__restrict__ planes, const unsigned *__restrict__ status)
+{
+  const int img = blockIdx.z, ci = blockIdx.y;
+  const MjhRegComp &rc = R.c[ci];
+  const int b = (int)(blockIdx.x * 256u + threadIdx.x);
+  if (b >= rc.nbx * rc.nby) return;
+  if (status[img] != 0u) return;
+  MjhComp cc = C.c[ci];
+  const int ry = b / rc.nbx, rx = b - ry * rc.nbx;
+  const int16_t *in = coef_q + (size_t)img * C.coefs_per_image + cc.coef_off + (size_t)(rc.by0 + ry) * cc.wib + (size_t)(rc.bx0 + rx);
+  const int *q = Q.q[ci];
+  cc.wib = rc.nbx; cc.pw = rc.pitch;                   // the body's b / wib, pw: the region plane's
+  if (FAST) {
+#include "mjh_idct8_ifast_body.inc"
+  } else {
+#include "mjh_idct8_body.inc"
+  }
+}
+
+// The same at DCT_scaled_size N = 1, 2, 4: the lanes of k_idct_scaled (G = 4 / N horizontally adjacent blocks each, N words
+// stored) over the region's blocks of component ci; rc.pitch: a multiple of 4 that holds ceil(nbx / G) words.
+template <int N>
+__global__ void __launch_bounds__(256)
+k_idct_region_scaled(MjhConst C, MjhIdctQ Q, int ci, MjhRegComp rc, const int16_t *__restrict__ coef_q, uint8_t *__restrict__ planes, const unsigned *__restrict__ status)
+{
+  constexpr int G = 4 / N;
+  const int img = blockIdx.z;
+  const MjhComp &cc = C.c[ci];
+  const int gpr = (rc.nbx + G - 1) / G;
+  const int t = (int)(blockIdx.x * 256u + threadIdx.x);
+  if (t >= gpr * rc.nby) return;
+  if (status[img] != 0u) return;
+  const int ry = t / gpr, gx = t - ry * gpr;
+  const int16_t *in = coef_q + (size_t)img * C.coefs_per_image + cc.coef_off + (size_t)(rc.by0 + ry) * cc.wib + (size_t)rc.bx0;
+  unsigned w[N];
+#pragma unroll
+  for (int r = 0; r < N; r++) w[r] = 0u;
+#pragma unroll
+  for (int j = 0; j < G; j++) {
+    const int rx = gx * G + j;
+    if (rx >= rc.nbx) continue;
+    idct_block<N>(in + rx, cc.kstride, Q.q[ci], w, j);
+  }
+  uint8_t *out = planes + (size_t)img * C.planes_per_image + cc.plane_off + (size_t)(ry * N) * rc.pitch + (size_t)gx * 4;
+#pragma unroll
+  for (int r = 0; r < N; r++) *reinterpret_cast<unsigned *>(out + (size_t)r * rc.pitch) = w[r];
 }
 
 // ---- K-I1n: every other size of jidctint.c, N = 3, 5, 6, 7 and 9 to 16 (djpeg -scale N/8, mjh_decode_opts.all_scales) -----------
@@ -804,48 +812,7 @@ k_upcolor(MjhPixOut P, const uint8_t *__restrict__ planes, uint8_t *__restrict__
   if (status[img] != 0u) return;
   const uint8_t *pl = planes + (size_t)img * P.planes_per_image;
   const int yo = P.bottom_up ? P.H - 1 - y : y;          // the output row image row y goes to
-  unsigned px[4][3];
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const int x = x0 + i < P.W ? x0 + i : P.W - 1;      // (the pad of the last group: an in-range position, its bytes mean nothing)
-    const int a = up_sample(P.c[0], pl + P.c[0].plane_off, x, y);
-    int r = a, g = a, b = a;
-    if (P.ncomp == 3) {
-      const int c1 = up_sample(P.c[1], pl + P.c[1].plane_off, x, y), c2 = up_sample(P.c[2], pl + P.c[2].plane_off, x, y);
-      if (P.conv == MJH_CC_YCC_RGB) {                  // ycc_rgb_convert with the tables of build_ycc_rgb_table (jdcolor.c:215-251), SCALEBITS 16
-        const int cb = c1 - 128, cr = c2 - 128;
-        r = clamp255(a + ((91881 * cr + 32768) >> 16));
-        g = clamp255(a + ((-22554 * cb + 32768 - 46802 * cr) >> 16));
-        b = clamp255(a + ((116130 * cb + 32768) >> 16));
-      } else if (P.conv == MJH_CC_RGB_GRAY) {           // rgb_gray_convert (build_rgb_y_table jdcolor.c:306-327)
-        r = g = b = (19595 * a + 38470 * c1 + 7471 * c2 + 32768) >> 16;
-      } else { g = c1; b = c2; }
-    }
-    px[i][0] = (unsigned)r; px[i][1] = (unsigned)g; px[i][2] = (unsigned)b;
-  }
-  uint8_t *out = pixels + (size_t)img * P.image_stride + (size_t)yo * P.row_pitch + (size_t)x0 * P.px_size;
-  if (P.px_size == 1) {
-    *reinterpret_cast<unsigned *>(out) = px[0][0] | (px[1][0] << 8) | (px[2][0] << 16) | (px[3][0] << 24);
-  } else if (P.px_size == 4) {
-    uint4 v;
-    unsigned w[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) w[i] = 0xFFFFFFFFu ^ ((0xFFu ^ px[i][0]) << (8 * P.off_r)) ^ ((0xFFu ^ px[i][1]) << (8 * P.off_g)) ^ ((0xFFu ^ px[i][2]) << (8 * P.off_b));
-    v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
-    *reinterpret_cast<uint4 *>(out) = v;
-  } else {
-    // twelve bytes: byte j of pixel i is the colour whose offset is j
-    unsigned w[3] = { 0u, 0u, 0u };
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const unsigned p24 = (px[i][0] << (8 * P.off_r)) | (px[i][1] << (8 * P.off_g)) | (px[i][2] << (8 * P.off_b));
-      const unsigned long long sh = (unsigned long long)p24 << (8 * (3 * i & 3));     // pixel i starts at byte 3 i: word 3 i / 4, byte 3 i % 4
-      w[(3 * i) >> 2] |= (unsigned)sh;
-      if (((3 * i) >> 2) + 1 < 3) w[((3 * i) >> 2) + 1] |= (unsigned)(sh >> 32);
-    }
-    unsigned *o32 = reinterpret_cast<unsigned *>(out);
-    o32[0] = w[0]; o32[1] = w[1]; o32[2] = w[2];
-  }
+#include "mjh_upcolor_body.inc"
 }
 
 // ---- K-I2 for JCS_RGB565 (djpeg -rgb565): jdcol565.c / jdmrg565.c, little-endian ------------------------------------------------
@@ -868,29 +835,42 @@ k_upcolor_565(MjhPixOut P, int dither, const uint8_t *__restrict__ planes, uint8
   if (status[img] != 0u) return;
   const uint8_t *pl = planes + (size_t)img * P.planes_per_image;
   const int yo = P.bottom_up ? P.H - 1 - y : y;
-  const unsigned dm = dither ? kDither565[y & 3] : 0u;
-  unsigned p16[4];
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const int x = x0 + i < P.W ? x0 + i : P.W - 1;      // (the pad of the last group, as in k_upcolor)
-    const int d = (int)((dm >> (8 * i)) & 0xFFu);       // x0 is a multiple of 4: x & 3 = i
-    const int a = up_sample(P.c[0], pl + P.c[0].plane_off, x, y);
-    int r, g, b;
-    if (P.ncomp == 3) {
-      const int c1 = up_sample(P.c[1], pl + P.c[1].plane_off, x, y), c2 = up_sample(P.c[2], pl + P.c[2].plane_off, x, y);
-      if (P.conv == MJH_CC_YCC_RGB) {                  // the tables of build_ycc_rgb_table, as k_upcolor
-        const int cb = c1 - 128, cr = c2 - 128;
-        r = a + ((91881 * cr + 32768) >> 16);
-        g = a + ((-22554 * cb + 32768 - 46802 * cr) >> 16);
-        b = a + ((116130 * cb + 32768) >> 16);
-      } else { r = a; g = c1; b = c2; }                // rgb_rgb565(D)_convert
-      r = clamp255(r + d); g = clamp255(g + (d >> 1)); b = clamp255(b + d);
-    } else r = g = b = clamp255(a + d);                // gray_rgb565(D)_convert
-    p16[i] = (((unsigned)r << 8) & 0xF800u) | (((unsigned)g << 3) & 0x7E0u) | ((unsigned)b >> 3);      // PACK_SHORT_565_LE
-  }
-  uint2 v;
-  v.x = p16[0] | (p16[1] << 16); v.y = p16[2] | (p16[3] << 16);
-  *reinterpret_cast<uint2 *>(pixels + (size_t)img * P.image_stride + (size_t)yo * P.row_pitch + (size_t)x0 * 2) = v;
+#include "mjh_upcolor565_body.inc"
+}
+
+// ---- K-IR2: upsampling and colour conversion of a region ---------------------------------------------------------------------------
+// The lanes, the conversions and the stores of k_upcolor / k_upcolor_565 over the region image P.W x P.H (the aligned width, the
+// rows asked for); row y of the region is row y0 + y of the whole image.
+// Across, everything is the region's: P.c[].dw is the cropped downsampled_width (jdapistd.c:276-281) and column 0 of a region
+// plane is the region's first sample, so the clamps of up_sample give the crop edges the image-edge formulas, as the reference's
+// fancy upsamplers do when they are handed the cropped rows, and the 565 dither counts columns from the region's left edge.
+// Down, everything is the whole image's: P.c[].dh is the image's downsampled_height and up_sample is asked for image row
+// y0 + y, so only rows at the image's top or bottom get the edge formula, every other row its real neighbours (which K-IR1
+// transformed: MjhRegComp.by0 / nby), and the dither row is the image's.  P.c[].plane_off points by0 * N rows ABOVE the region
+// plane (the host subtracts them), so image row r of a component is at plane_off + r * pw although the plane starts at row
+// by0 * N; rows outside [by0 * N, (by0 + nby) * N) are never asked for.
+__global__ void __launch_bounds__(256)
+k_upcolor_region(MjhPixOut P, int y0, const uint8_t *__restrict__ planes, uint8_t *__restrict__ pixels, const unsigned *__restrict__ status)
+{
+  const int img = blockIdx.z, ry = blockIdx.y, y = y0 + ry;
+  const int x0 = (int)(blockIdx.x * 256u + threadIdx.x) * 4;
+  if (x0 >= P.W) return;
+  if (status[img] != 0u) return;
+  const uint8_t *pl = planes + (size_t)img * P.planes_per_image;
+  const int yo = P.bottom_up ? P.H - 1 - ry : ry;        // the flip is inside the region
+#include "mjh_upcolor_body.inc"
+}
+
+__global__ void __launch_bounds__(256)
+k_upcolor_565_region(MjhPixOut P, int y0, int dither, const uint8_t *__restrict__ planes, uint8_t *__restrict__ pixels, const unsigned *__restrict__ status)
+{
+  const int img = blockIdx.z, ry = blockIdx.y, y = y0 + ry;
+  const int x0 = (int)(blockIdx.x * 256u + threadIdx.x) * 4;
+  if (x0 >= P.W) return;
+  if (status[img] != 0u) return;
+  const uint8_t *pl = planes + (size_t)img * P.planes_per_image;
+  const int yo = P.bottom_up ? P.H - 1 - ry : ry;
+#include "mjh_upcolor565_body.inc"
 }
 
 // ---- K-I2 for four components (Adobe-style CMYK and YCCK files): pixels of four bytes C, M, Y, K ---------------------------------
@@ -983,4 +963,35 @@ void mjh_launch_idct_sized(const MjhConst &C, const MjhIdctQ &Q, int ci, int N, 
     MJH_SIZED(12); MJH_SIZED(13); MJH_SIZED(14); MJH_SIZED(15); MJH_SIZED(16);
   }
 #undef MJH_SIZED
+}
+
+void mjh_launch_idct_region(const MjhConst &C, const MjhIdctQ &Q, const MjhIdctRegion &R, int comps, bool ifast, const int16_t *coef_q, uint8_t *planes, const unsigned *status, int n, hipStream_t s)
+{
+  int nblk = 1;
+  for (int c = 0; c < comps; c++) if (R.c[c].nbx * R.c[c].nby > nblk) nblk = R.c[c].nbx * R.c[c].nby;
+  const dim3 grid((nblk + 255) / 256, comps, n);
+  if (ifast) hipLaunchKernelGGL((k_idct_region<true>), grid, dim3(256), 0, s, C, Q, R, coef_q, planes, status);
+  else hipLaunchKernelGGL((k_idct_region<false>), grid, dim3(256), 0, s, C, Q, R, coef_q, planes, status);
+}
+
+void mjh_launch_idct_region_scaled(const MjhConst &C, const MjhIdctQ &Q, int ci, int N, const MjhRegComp &rc, const int16_t *coef_q, uint8_t *planes, const unsigned *status, int n, hipStream_t s)
+{
+  const int G = 4 / N;
+  const int lanes = (rc.nbx + G - 1) / G * rc.nby;
+  const dim3 grid((lanes + 255) / 256, 1, n);
+  if (N == 4) hipLaunchKernelGGL((k_idct_region_scaled<4>), grid, dim3(256), 0, s, C, Q, ci, rc, coef_q, planes, status);
+  else if (N == 2) hipLaunchKernelGGL((k_idct_region_scaled<2>), grid, dim3(256), 0, s, C, Q, ci, rc, coef_q, planes, status);
+  else hipLaunchKernelGGL((k_idct_region_scaled<1>), grid, dim3(256), 0, s, C, Q, ci, rc, coef_q, planes, status);
+}
+
+void mjh_launch_upcolor_region(const MjhPixOut &P, int y0, const uint8_t *planes, uint8_t *pixels, const unsigned *status, int n, hipStream_t s)
+{
+  const int groups = (P.W + 3) / 4;
+  hipLaunchKernelGGL(k_upcolor_region, dim3((groups + 255) / 256, P.H, n), dim3(256), 0, s, P, y0, planes, pixels, status);
+}
+
+void mjh_launch_upcolor_565_region(const MjhPixOut &P, int y0, int dither, const uint8_t *planes, uint8_t *pixels, const unsigned *status, int n, hipStream_t s)
+{
+  const int groups = (P.W + 3) / 4;
+  hipLaunchKernelGGL(k_upcolor_565_region, dim3((groups + 255) / 256, P.H, n), dim3(256), 0, s, P, y0, dither, planes, pixels, status);
 }

@@ -45,6 +45,7 @@ typedef struct tjs {
   /* decompress instances: TJPARAM_FASTUPSAMPLE / SCANLIMIT / MAXMEMORY / MAXPIXELS and tj3SetScalingFactor */
   int decompress, fast_upsample, scan_limit, max_memory, max_pixels;
   tjscalingfactor sf;
+  tjregion crop;             /* tj3SetCroppingRegion with MOZJPEG_HIP_REGIONS=1; all 0: TJUNCROPPED */
   /* one cached encoder (a handle is used by one thread at a time, like a tjinstance) */
   mjh_encoder *enc;
   mjh_params enc_params;
@@ -93,6 +94,14 @@ static int serve_decompress(void)
 static int all_scales(void)
 {
   const char *v = getenv("MOZJPEG_HIP_ALL_SCALES");
+  return v && v[0] == '1' && v[1] == 0;
+}
+
+/* MOZJPEG_HIP_REGIONS=1: tj3SetCroppingRegion takes regions and tj3Decompress8 decodes them (mjh_decode_opts.crop_*).  Read per
+ * call; without it a region other than TJUNCROPPED is refused as it always was (the refusal is part of the tested contract). */
+static int regions(void)
+{
+  const char *v = getenv("MOZJPEG_HIP_REGIONS");
   return v && v[0] == '1' && v[1] == 0;
 }
 
@@ -645,7 +654,8 @@ DLLEXPORT int tjCompressFromYUV(tjhandle handle, const unsigned char *srcBuf, in
  * - All 16 scaling factors of the reference are accepted and chosen (tjDecompress2) as there; a decompress call at a factor other
  *   than 1/1, 1/2, 1/4, 1/8 fails with a text naming the factor.
  * - Damaged entropy-coded data is a FATAL error and the destination is left untouched (the reference: a warning and a partial
- *   image).  Cropping regions other than TJUNCROPPED and 12- / 16-bit output are refused.
+ *   image).  12- / 16-bit output is refused, and so are cropping regions other than TJUNCROPPED unless MOZJPEG_HIP_REGIONS=1
+ *   is set when tj3SetCroppingRegion is called (regions(): then tj3Decompress8 decodes the region, mjh_decode_opts.crop_*).
  * A handle keeps one mjh_encoder made from mjh_params_from_jpeg (the 'revert' profile, one file per call) and remakes it when
  * a file's parameters differ, as the compress half does. */
 #define NUMSF 16
@@ -691,8 +701,28 @@ DLLEXPORT int tj3SetCroppingRegion(tjhandle handle, tjregion croppingRegion)
   void *f;
   tjs *t = dinstance(handle, "tj3SetCroppingRegion", &f);
   if (!t) return f ? ((int (*)(tjhandle, tjregion))f)(handle, croppingRegion) : -1;
-  if (croppingRegion.x == 0 && croppingRegion.y == 0 && croppingRegion.w == 0 && croppingRegion.h == 0) return 0;
-  return fail(t, "tj3SetCroppingRegion", "partial decompression (a cropping region other than TJUNCROPPED) is not built on the GPU path");
+  if (croppingRegion.x == 0 && croppingRegion.y == 0 && croppingRegion.w == 0 && croppingRegion.h == 0) { t->crop = croppingRegion; return 0; }
+  if (!regions()) return fail(t, "tj3SetCroppingRegion", "partial decompression (a cropping region other than TJUNCROPPED) is not built on the GPU path");
+  { /* turbojpeg.c:1931-1959, its checks in its order and its texts */
+    char msg[160];
+    int sw, sh, mw;
+    if (croppingRegion.x < 0 || croppingRegion.y < 0 || croppingRegion.w < 0 || croppingRegion.h < 0) return fail(t, "tj3SetCroppingRegion", "Invalid cropping region");
+    if (t->jpeg_width < 0 || t->jpeg_height < 0) return fail(t, "tj3SetCroppingRegion", "JPEG header has not yet been read");
+    if (t->precision == 16 || t->lossless) return fail(t, "tj3SetCroppingRegion", "Cannot partially decompress lossless JPEG images");
+    if (t->subsamp == TJSAMP_UNKNOWN) return fail(t, "tj3SetCroppingRegion", "Could not determine subsampling level of JPEG image");
+    sw = TJSCALED(t->jpeg_width, t->sf); sh = TJSCALED(t->jpeg_height, t->sf);
+    mw = TJSCALED(kMcuW[t->subsamp], t->sf);
+    if (croppingRegion.x % mw != 0) {
+      snprintf(msg, sizeof(msg), "The left boundary of the cropping region (%d) is not\ndivisible by the scaled iMCU width (%d)", croppingRegion.x, mw);
+      return fail(t, "tj3SetCroppingRegion", msg);
+    }
+    if (croppingRegion.w == 0) croppingRegion.w = sw - croppingRegion.x;
+    if (croppingRegion.h == 0) croppingRegion.h = sh - croppingRegion.y;
+    if (croppingRegion.w <= 0 || croppingRegion.h <= 0 || croppingRegion.x + croppingRegion.w > sw || croppingRegion.y + croppingRegion.h > sh)
+      return fail(t, "tj3SetCroppingRegion", "The cropping region exceeds the scaled image dimensions");
+    t->crop = croppingRegion;
+  }
+  return 0;
 }
 
 /* getSubsamp turbojpeg.c:400-478 for the files that get this far (one, three or four components).  In a CMYK / YCCK file the
@@ -817,6 +847,10 @@ static int decompress_pixels(tjs *t, const char *fn, const unsigned char *jpegBu
     o.rgb_offset[0] = kRed[pixelFormat]; o.rgb_offset[1] = kGreen[pixelFormat]; o.rgb_offset[2] = kBlue[pixelFormat];
   }
   o.bottom_up = t->bottom_up;
+  /* a region that was set (turbojpeg-mp.c:199-222): the columns when they are not the whole width, the rows whenever one was
+   * named; the buffer then holds crop.w x crop.h pixels and bottom-up rows are flipped inside it */
+  if (t->crop.x != 0 || (t->crop.w != 0 && t->crop.w != W)) { o.crop_x = t->crop.x; o.crop_w = t->crop.w; W = t->crop.w; }
+  if (t->crop.y != 0 || t->crop.h != 0) { o.crop_y = t->crop.y; o.crop_h = t->crop.h; }
   files[0] = jpegBuf;
   if (mjh_decode_host(t->enc, files, &jpegSize, 1, &o) != MJH_OK) return fail(t, fn, mjh_last_error());
   /* (waits, and fails on damaged data before a byte of dstBuf is written; only the pixels' bytes of every row are written) */
